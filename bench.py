@@ -11,6 +11,9 @@ State is resident in HBM before the timed region.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     ... --online     harvest (state, TD-target) tuples at every garbage collection and all-gather them over the ranks
                      after every move inside the timed region (BASELINE configs[3]: RCCL used for exactly that)
+    ... --full       everything else the line can carry: the steady-state window (moves 76-95), the other BASELINE configs,
+                     the headline's windows under the committed trained net, the CPU baselines
+    ... --dump-outputs DIR   after the timed window, what its last step handed the caller as DIR/<name>.npy (rank 0's games)
 """
 import argparse
 import json
@@ -74,10 +77,36 @@ AGENTS = {"ValueSim": 1, "ValueSimLP": 2, "DistValueSim": 4, "Vanilla": 0}     #
 TRAINED_CHECKPOINT = os.path.join("tetris_mcts_amd", "checkpoints", "value_net_online_r05.pt")     # scripts/gpu_r05_train.sh
 
 
-def run_agent(args, name, sims, warmup, steps, steady_warmup, steady_steps, ctx, checkpoint=None):
+DUMP_LIMIT_BYTES = 64 << 20         # --dump-outputs: at most this much in all (a fixed sample of the games beyond it)
+
+
+def dump_outputs(out_dir, action, stats, game):
+    """What the timed path's last step handed its caller, one float64/float32 .npy per array: the actions agent.play()
+    returned, the root statistics behind them (agent.get_stats(), [G, 3 x 7]) and every game after game.play + update_root
+    (score, lines cleared, the packed 16-word state).  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of the games is written
+    (`game_index` names them)."""
+    import numpy as np
+    G = game.n_games
+    arrays = {"action": np.asarray(action, np.float64).reshape(G),
+              "root_stats": np.asarray(stats, np.float32).reshape(G, -1),
+              "score": np.asarray(game.score, np.float64).reshape(G),
+              "line_clears": np.asarray(game.line_clears, np.float64).reshape(G),
+              "game_state": game.packed().astype(np.float64).reshape(G, -1)}
+    per_game = sum(a.nbytes for a in arrays.values()) / G + 8
+    idx = np.arange(G)
+    if per_game * G > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(G, int(DUMP_LIMIT_BYTES // per_game), replace=False))
+    arrays = {k: v[idx] for k, v in arrays.items()}
+    arrays["game_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def run_agent(args, name, sims, warmup, steps, steady_warmup, steady_steps, ctx, checkpoint=None, dump_dir=None):
     """One agent's windows on this rank's games: `warmup` untimed moves, `steps` timed ones (barrier + synchronize on both
     sides, max over ranks, counters summed over ranks), optionally a second window later in the same games.  Returns the fields
-    of a bench line (rank 0; None elsewhere) and the model."""
+    of a bench line (rank 0; None elsewhere) and the model.  dump_dir: rank 0 writes what the last timed step returned."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -124,9 +153,11 @@ def run_agent(args, name, sims, warmup, steps, steady_warmup, steady_steps, ctx,
     tally = dict(episodes=0, lines=0, lines_all=0, game_moves=0, ended_lines=[])
     prev_lines = np.zeros(G, np.int64)      # every game's line count so far in its episode under way
     gather = dict(ms=0.0, tuples=0, bytes=0, calls=0, checksum_ok=True)
+    last = {}
 
     def one_step(timed):
         action = agent.play()      # mcts(sims) + get_action (games whose reachable tree outgrew the pool restart with an empty tree)
+        last["action"] = action
         game.play(action)
         agent.update_root(game)   # reads game.end: one small host sync per move, as the reference's loop has
         ended = np.atleast_1d(game.end)
@@ -236,6 +267,8 @@ def run_agent(args, name, sims, warmup, steps, steady_warmup, steady_steps, ctx,
     for _ in range(warmup):
         one_step(False)
     head = measure(steps)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, last["action"], agent.get_stats(), game)
     max_trace = int(S.t["gs"][:, st.GS["MAX_TRACE"]].max().item())
     phase_kcycles = {k: float(S.t["gs"][:, st.GS[k]].float().mean().item()) / 1e3
                      for k in ("CYC_BACK", "CYC_SELECT", "CYC_VERIFY", "CYC_EXPAND", "FIRST_MISS", "TRACE_LEN")}
@@ -443,18 +476,26 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="value-net checkpoint for the measured agent (default: random init under manual_seed(0))")
     ap.add_argument("--online", action="store_true", help="harvest training tuples at GC and all-gather them every move")
     ap.add_argument("--steady-warmup", type=int, default=75, help="the steady-state window starts after this many moves")
-    ap.add_argument("--steady-steps", type=int, default=20, help="moves of the second, steady-state window (0: none)")
+    ap.add_argument("--steady-steps", type=int, default=20, help="moves of the second, steady-state window (0: none; --full only)")
     ap.add_argument("--steady-multi", action="store_true", help="measure the steady-state window in multi-GPU runs too")
     ap.add_argument("--others", default="auto", choices=["auto", "none", "all"],
                     help="short lines of the other BASELINE configs (ValueSimLP, DistValueSim at 1000 sims, Vanilla at 100 sims) "
-                    "inside the headline's; auto = when this is the default single-GPU ValueSim run")
+                    "inside the headline's, and the headline's windows under the trained net; auto = when this is the default "
+                    "single-GPU ValueSim run (--full only)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="all ranks on cuda:0 with the gloo backend (payloads staged through host memory): exercises the multi-rank "
                     "code path on a one-GPU box; size --games so that all ranks' stores fit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full only: a plain run has no CPU baseline)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes of the N-process CPU baseline (0: all host cores, at most 128)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline window: the steady-state window, the other configs, the trained net's windows and "
+                    "the CPU baselines (a plain run sets up, warms up, times --steps moves and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (actions, root statistics, games) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -505,10 +546,11 @@ def main():
         ckpt = next((c for c in (os.path.abspath(args.checkpoint), os.path.join(ROOT, args.checkpoint)) if os.path.isfile(c)), None)
         if ckpt is None:
             sys.exit("bench.py: checkpoint %s not found" % args.checkpoint)
-    out, model = run_agent(args, args.agent, sims, args.warmup, args.steps, args.steady_warmup, args.steady_steps, ctx, checkpoint=ckpt)
+    out, model = run_agent(args, args.agent, sims, args.warmup, args.steps, args.steady_warmup, args.steady_steps if args.full else 0, ctx,
+                           checkpoint=ckpt, dump_dir=args.dump_outputs)
     others = {}
-    want_others = args.others == "all" or (args.others == "auto" and world == 1 and args.agent == "ValueSim" and not args.online
-                                           and args.backend == "hip" and args.split == 1 and not args.checkpoint)
+    want_others = args.full and (args.others == "all" or (args.others == "auto" and world == 1 and args.agent == "ValueSim" and not args.online
+                                                          and args.backend == "hip" and args.split == 1 and not args.checkpoint))
     if want_others:
         # the other configurations of BASELINE.json, short windows, so that the driver's one command line shows them all
         for name, osims, w, k in (("ValueSimLP", 500, 5, 20), ("DistValueSim", 1000, 2, 5), ("Vanilla", 100, 5, 20)):
@@ -565,7 +607,7 @@ def main():
                 out["trained_steady_mean_lines_all_episodes_under_way"] = trained["steady_state"]["mean_lines_all_episodes_under_way"]
         if others:
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if args.agent == "DistValueSim":
                 out["cpu_baseline"] = {"value": None, "unit": "node-expansions/s", "cores": 0, "kind": "port",
                                        "sample": "none: the reference has no distributional agent that runs (agents/DistValueSimOnline.py does "

@@ -90,7 +90,7 @@ tune)
     line $OUT/r06.tune_$1_$2.json
   done ;;
 bench)
-  ( time timeout 900 python bench.py > $OUT/r06.bench.json 2> $OUT/r06.bench.err ) 2>&1 | grep real
+  ( time timeout 900 python bench.py --full > $OUT/r06.bench.json 2> $OUT/r06.bench.err ) 2>&1 | grep real
   line $OUT/r06.bench.json
   python -c "import json;d=json.load(open('$OUT/r06.bench.json'));print({k:v for k,v in d.items() if not isinstance(v,(dict,list))})" ;;
 prof)

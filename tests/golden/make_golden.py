@@ -105,6 +105,34 @@ def gen_uct():
     print("ref_uct.npz:", len(cases), "cases")
 
 
+def gen_uct_live():
+    """ref_uct_live.npz: select_trace_obs / backup_trace_obs of the reference's core on 6 DAGs x 20 steps, each step
+    backing up the trace it selected; the inputs come from default_rng(5) in the order tests/test_oracle_uct.py draws them."""
+    ref_shims.install()
+    core = sys.modules["agents.cppmodule.core"]
+    rng = np.random.default_rng(5)
+    out = {}
+    for ci in range(6):
+        child, n_to_o, score, visit, value, variance = random_dag(rng, 300, 120)
+        ref_shims.srand(1)
+        v1, a1, r1 = visit.copy(), value.copy(), variance.copy()
+        traces, visits, values, variances = [], [], [], []
+        for rep in range(20):
+            root = int(rng.integers(1, 40))
+            t_ref = np.asarray(core.select_trace_obs(root, child, v1, a1, r1, score, n_to_o, 1), np.int32)
+            val, var_ = float(rng.random() * 100), float(rng.random() * 300)
+            core.backup_trace_obs(t_ref, v1, a1, r1, n_to_o, score, val, var_, 0.99)
+            traces.append(t_ref)
+            visits.append(v1.copy()); values.append(a1.copy()); variances.append(r1.copy())
+        out["c%d_tracecat" % ci] = np.concatenate(traces)
+        out["c%d_tracelen" % ci] = np.array([len(t) for t in traces], np.int32)
+        out["c%d_visit" % ci] = np.stack(visits)
+        out["c%d_value" % ci] = np.stack(values)
+        out["c%d_variance" % ci] = np.stack(variances)
+    np.savez_compressed(os.path.join(OUT, "ref_uct_live.npz"), **out)
+    print("ref_uct_live.npz: 6 cases x 20 steps")
+
+
 def gen_vanilla():
     """The reference's Vanilla agent (agents/Vanilla.py, random rollouts with random.randint) - BASELINE configs[0]."""
     import random
@@ -739,10 +767,12 @@ def gen_training():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["uct", "valuenet", "agents", "cppagent", "mixture", "vanilla", "online", "online_py", "agents_env", "training", "vanillac", "dist", "distnet", "treeagent", "distpy"]
+    which = sys.argv[1:] or ["uct", "uct_live", "valuenet", "agents", "cppagent", "mixture", "vanilla", "online", "online_py", "agents_env", "training", "vanillac", "dist", "distnet", "treeagent", "distpy"]
     params = None
     if "uct" in which:
         gen_uct()
+    if "uct_live" in which:
+        gen_uct_live()
     if "valuenet" in which:
         params = gen_valuenet()
     if "cppagent" in which:
