@@ -41,6 +41,11 @@ extern "C" {
                                           kernels keep a counter per tile of 32 or 64 states in the rows' padding: every evaluation
                                           clears them first) */
 #define TM_VALUENET_PREPARED 477184    /* floats: conv2 + conv3 + fc1 operand streams */
+#define TM_VALUENET_PREPARED_X3 27648  /* floats (55 296 bf16): conv2 + conv3 weights as bf16 hi / mid / lo planes, tm_valuenet_prepare_x3;
+                                          the _x3 forwards take TM_VALUENET_SCRATCH_MFMA floats of scratch per state, as the fp32 ones */
+/* evaluator backends of the native search loop (tm_search_set_valuenet) */
+#define TM_VALUENET_FP32 0             /* tm_valuenet_forward_requests: fp32 matrix cores, the oracle's bits (the default) */
+#define TM_VALUENET_BF16X3 1           /* tm_valuenet_forward_requests_x3: conv2 / conv3 as three-way bf16 splits, fp32 accumulation */
 #define TM_DISTNET_PARAMS(atoms) (279232 + 129 * (atoms))  /* floats: conv1.w[32][1][4][4] conv1.b[32] conv2.w[32][32][4][4] conv2.b[32]
                                           fc1.w[128][2048] fc1.b[128] fc_v.w[atoms][128] fc_v.b[atoms] (model/model_distributional.py:33-42) */
 #define TM_DISTNET_PARAMS_50 285682    /* TM_DISTNET_PARAMS(50) */
@@ -299,6 +304,12 @@ int tm_search_stats(tm_search *h, double *out, int n, int reset);
 /* the evaluator's weights changed: s->eval_epoch of the handle's copy of the store (outputs filed in obs_eval under another
  * epoch are not used; epochs are >= 1 and never reused for other weights) */
 int tm_search_set_epoch(tm_search *h, int epoch);
+/* the evaluator backend of tm_search_run's value net: TM_VALUENET_FP32 (the default) or TM_VALUENET_BF16X3.  Under
+ * TM_VALUENET_BF16X3, vn_prepared points at TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3 floats: the fp32 operand streams of
+ * tm_valuenet_prepare (fc1 stays on them) followed by the planes of tm_valuenet_prepare_x3.  hipErrorInvalidValue for any
+ * other value, and for TM_VALUENET_BF16X3 on a TM_KIND_DIST store (its head has no such backend).  The caller gives the
+ * backend's outputs an epoch of their own (tm_search_set_epoch): obs_eval must not mix the two. */
+int tm_search_set_valuenet(tm_search *h, int backend);
 int tm_root_stats(const tm_store *s, float *stats /* [G][3][7] */, int32_t *action /* [G] */, void *stream);
 /* one game's tree in the reference's array layout (agents/agent.py:58-88), for inspection and tests */
 int tm_export_game(const tm_store *s, int game, int32_t *child /* [N][7] */, float *score, int32_t *n_to_o,
@@ -378,6 +389,17 @@ int tm_valuenet_forward_requests(const float *params, const float *prepared, con
                                  void *stream);
 int tm_valuenet_forward_plain(const float *params, const int8_t *states, int n, float *v, float *var, float *scratch,
                               void *stream);
+/* The split-precision backend (valuenet_x3.inc; numerics contract in DESIGN.md section 3.3): conv2 and conv3 on the bf16 matrix
+ * cores, every operand split into three bf16 planes, six plane products per fp32 product, fp32 accumulation; conv1, fc1 and
+ * the output layer as in tm_valuenet_forward.  Within 1e-4 of the reference, not bit-equal to the fp32 path; a state's outputs
+ * depend on that state only.  tm_valuenet_prepare_x3 writes the planes (TM_VALUENET_PREPARED_X3 floats, after every weight
+ * change); the forwards take both prepared buffers (fc1 reads tm_valuenet_prepare's) and TM_VALUENET_SCRATCH_MFMA floats of
+ * scratch per state.  prepared_x3 == NULL: hipErrorInvalidValue. */
+int tm_valuenet_prepare_x3(const float *params, float *prepared_x3, void *stream);
+int tm_valuenet_forward_x3(const float *params, const float *prepared, const float *prepared_x3, const int8_t *states, int n,
+                           float *v, float *var, float *scratch, void *stream);
+int tm_valuenet_forward_requests_x3(const float *params, const float *prepared, const float *prepared_x3, const tm_store *s,
+                                    float *scratch, void *stream);
 
 /* distributional value head (model/model_distributional.py:18-57 `Net`, Model_Dist.inference :100-107), the leaf evaluator
  * of TM_KIND_DIST: states int8 [n][200] (the 20 visible rows; the net's two extra rows on top are empty) -> softmax over

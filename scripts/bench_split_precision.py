@@ -1,0 +1,152 @@
+#!/usr/bin/env python
+"""The split-precision value-net backend ("hip_bf16x3") against the fp32 one ("hip"), on one GPU.  Two modes, one JSON line each:
+
+  kernels  per-launch time of the value net (dense states, k_vn_conv[_x3] + k_vn_fc1) at the headline's and ValueSimLP's mean
+           requests per launch (1 867 and 7 169 states), both backends, with TFLOP/s against each backend's own peak (fp32
+           matrix 157.3 TF; bf16x3 = the bf16 matrix peak / 6 products); and max |dv|, |dvar| of bf16x3 against fp32 over the
+           states a short real search asked for (render_eval), with the r06 checkpoint;
+  search   ms per move of the native search loop, moves warmup+1 .. warmup+steps, for ONE agent and ONE backend (two stores of
+           4096 x 100 000 nodes do not fit one GPU: one process per backend).
+
+    python scripts/bench_split_precision.py kernels [--out profiles/FILE.json]
+    python scripts/bench_split_precision.py search --agent ValueSim --backend hip_bf16x3 [--out ...]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CKPT = os.path.join(ROOT, "tetris_mcts_amd", "checkpoints", "value_net_online_r06.pt")
+# useful FLOP per state: conv1 144x32x9, conv2 96x32x288, conv3 56x32x288, fc1 1792x256, out 256x2 multiply-adds
+FLOP_STATE = 2 * (144 * 32 * 9 + 96 * 32 * 288 + 56 * 32 * 288 + 1792 * 256 + 256 * 2)
+PEAK_TF = {"hip": 157.3, "hip_bf16x3": 2516.6 / 6}      # MI355X: fp32 matrix = fp32 vector rate; bf16 matrix dense
+
+
+def _model(backend):
+    from tetris_mcts_amd.model import Model_VV
+    m = Model_VV(backend=backend)
+    m.load(CKPT, verbose=False)
+    return m
+
+
+def _searched_states(n_games=512, sims=16, moves=6):
+    """int8 [n, 200]: every leaf state a ValueSimLP search with the fp32 net asked for (render_eval of every launch)"""
+    import torch
+    from tetris_mcts_amd import agents
+    from tetris_mcts_amd.pyTetris import Tetris
+    m = _model("hip")
+    seen = []
+
+    def ev(states):
+        seen.append(states.clone())
+        return m.inference_device(states)
+    env_args = ((20, 10), 1, 0, 0)
+    game = Tetris(*env_args, seed=20261016, n_games=n_games)
+    agent = agents.ValueSimLP(sims=sims, env=Tetris, env_args=env_args, n_games=n_games, max_nodes=20000, evaluator=ev,
+                              online=False)
+    agent.update_root(game)
+    for _ in range(moves):
+        act = agent.play()
+        game.play(act)
+        agent.update_root(game)
+    s = torch.cat(seen)
+    return s[(s != 0).any(dim=1)].contiguous()
+
+
+def kernels(args):
+    import torch
+    states = _searched_states()
+    models = {b: _model(b) for b in ("hip", "hip_bf16x3")}
+    out = dict(mode="kernels", searched_states=int(states.shape[0]), flop_per_state=FLOP_STATE, launches={})
+    v32, r32 = [t.clone() for t in models["hip"].inference_device(states)]
+    vx, rx = [t.clone() for t in models["hip_bf16x3"].inference_device(states)]
+    out["max_abs_dv"] = float((vx - v32).abs().max().item())
+    out["max_abs_dvar"] = float((rx - r32).abs().max().item())
+    out["max_abs_v"], out["max_abs_var"] = float(v32.abs().max().item()), float(r32.abs().max().item())
+    for n in (1867, 7169):
+        batch = states[torch.arange(n, device=states.device) % states.shape[0]].contiguous()
+        row = {}
+        for b, m in models.items():
+            v, r = torch.empty(n, device="cuda"), torch.empty(n, device="cuda")
+            for _ in range(20):
+                m.inference_device(batch, v, r)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.launches):
+                m.inference_device(batch, v, r)
+            e1.record()
+            torch.cuda.synchronize()
+            us = 1e3 * e0.elapsed_time(e1) / args.launches
+            tf = FLOP_STATE * n / (us * 1e-6) / 1e12
+            row[b] = dict(us_per_launch=round(us, 2), tflops=round(tf, 2), peak_tflops=round(PEAK_TF[b], 1),
+                          of_peak=round(tf / PEAK_TF[b], 4))
+        row["speedup"] = round(row["hip"]["us_per_launch"] / row["hip_bf16x3"]["us_per_launch"], 3)
+        out["launches"][str(n)] = row
+    return out
+
+
+def search(args):
+    import numpy as np
+    import torch
+    from tetris_mcts_amd import agents
+    from tetris_mcts_amd.pyTetris import Tetris
+    model = _model(args.backend)
+    env_args = ((20, 10), 1, 0, 0)
+    G = args.games
+    game = Tetris(*env_args, seed=20260925, n_games=G)
+    agent = getattr(agents, args.agent)(sims=args.sims, env=Tetris, env_args=env_args, n_games=G, max_nodes=args.max_nodes,
+                                        model=model, online=False, ev_every=16)
+    assert agent.search_model() is model
+    agent.update_root(game)
+    torch.cuda.synchronize()
+
+    def move():
+        act = agent.play()
+        game.play(act)
+        agent.update_root(game)
+        ended = np.atleast_1d(game.end)
+        if ended.any():
+            game.reset("ended")
+            agent.update_root(game)
+    for _ in range(args.warmup):
+        move()
+    torch.cuda.synchronize()
+    agent.store.search_stats(agent.n_sub, agent.ev_every, reset=True)
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        move()
+    torch.cuda.synchronize()
+    ms = 1e3 * (time.perf_counter() - t0) / args.steps
+    st = agent.store.search_stats(agent.n_sub, agent.ev_every, reset=True) or {}
+    return dict(mode="search", agent=args.agent, backend=args.backend, games=G, sims=args.sims, max_nodes=args.max_nodes,
+                moves="%d-%d" % (args.warmup + 1, args.warmup + args.steps), ms_per_move=round(ms, 2), search_stats=st)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("mode", choices=("kernels", "search"))
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--agent", default="ValueSim", choices=("ValueSim", "ValueSimLP"))
+    ap.add_argument("--backend", default="hip", choices=("hip", "hip_bf16x3"))
+    ap.add_argument("--games", type=int, default=4096)
+    ap.add_argument("--sims", type=int, default=500)
+    ap.add_argument("--max-nodes", type=int, default=100000)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    args = ap.parse_args()
+    res = kernels(args) if args.mode == "kernels" else search(args)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -60,6 +60,9 @@ SYMBOLS = {
     "tm_valuenet_forward": [vp, vp, vp, i32, vp, vp, vp, vp],
     "tm_valuenet_forward_plain": [vp, vp, i32, vp, vp, vp, vp],
     "tm_valuenet_forward_requests": [vp, vp, C.POINTER(TmStore), vp, vp],
+    "tm_valuenet_prepare_x3": [vp, vp, vp],
+    "tm_valuenet_forward_x3": [vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "tm_valuenet_forward_requests_x3": [vp, vp, vp, C.POINTER(TmStore), vp, vp],
     "tm_distnet_prepare": [vp, vp, vp],
     "tm_distnet_forward": [vp, vp, vp, i32, i32, vp, i32, vp, vp],
     "tm_distnet_forward_requests": [vp, vp, C.POINTER(TmStore), vp, vp],
@@ -73,6 +76,7 @@ SYMBOLS = {
     "tm_search_run": [vp, i32, vp, vp, vp, vp],
     "tm_search_stats": [vp, vp, i32, i32],
     "tm_search_set_epoch": [vp, i32],
+    "tm_search_set_valuenet": [vp, i32],
 }
 
 _lib = None

@@ -3,7 +3,7 @@ select -> evaluate the leaf with the value net -> expand -> backup (gamma 0.999,
 pool of 100000 nodes per game).  The tree loop runs in tree.hip; leaf states of all games are evaluated
 as one batch."""
 from .. import store as st
-from ..model import Model_VV as Model
+from ..model import HIP_BACKENDS, Model_VV as Model
 from .agent import TreeAgent
 
 
@@ -12,7 +12,9 @@ class ValueSim(TreeAgent):
     low = 1
 
     def __init__(self, online=True, memory_size=500000, min_visits_to_store=10, gamma=0.999, memory_growth_rate=5000,
-                 max_nodes=100000, model=None, evaluator=None, **kwargs):
+                 max_nodes=100000, model=None, evaluator=None, valuenet_backend="hip", **kwargs):
+        """`valuenet_backend`: the Model_VV backend of the model the agent builds when `model` is None ("hip", the default;
+        "hip_bf16x3", the split-precision kernels; "torch")."""
         kwargs.pop("min_visit", None)  # play.py:89 forwards it; the reference ValueSim ignores it too
         benchmark = kwargs.get("benchmark", False)
         # device-side harvest buffer per game (64 B per tuple); a GC at a 100 000-entry pool frees a few thousand
@@ -28,7 +30,7 @@ class ValueSim(TreeAgent):
         self.min_visits_to_store = min_visits_to_store
         self.evaluator = evaluator
         if evaluator is None:
-            self.model = model if model is not None else Model()
+            self.model = model if model is not None else Model(backend=valuenet_backend)
             if model is None:
                 self.model.load()
             self.model.training(False)
@@ -42,10 +44,10 @@ class ValueSim(TreeAgent):
             self.model.inference_device(states, v_out, var_out)
 
     def search_model(self):
-        return self.model if (self.evaluator is None and self.model.backend == "hip") else False
+        return self.model if (self.evaluator is None and self.model.backend in HIP_BACKENDS) else False
 
     def evaluate_requests(self):
-        if self.evaluator is None and self.model.backend == "hip":
+        if self.evaluator is None and self.model.backend in HIP_BACKENDS:
             self.model.inference_requests(self.store)   # observations rendered inside the conv kernel
         else:
             super().evaluate_requests()

@@ -43,6 +43,7 @@ struct tm_search {
     int ev_used;
     double tree_ms, nn_ms;
     long long n_timed, n_runs, extra_launches, launches, gc_launches;
+    int vn_backend = TM_VALUENET_FP32;   // tm_search_set_valuenet
 };
 
 #define TM_TRY(x) do { int e_ = (int)(x); if (e_ != 0) return e_; } while (0)
@@ -191,6 +192,8 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
             return tm_distnet_forward_requests(vn_params, vn_prepared, &h->sub[k],
                                                vn_scratch + (size_t)h->first[k] * TM_DISTNET_SCRATCH, st[k]);
         float* scr = vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA;
+        if (h->vn_backend == TM_VALUENET_BF16X3)      // vn_prepared: the fp32 operand streams, then the planes (tm_search_set_valuenet)
+            return tm_valuenet_forward_requests_x3(vn_params, vn_prepared, vn_prepared + TM_VALUENET_PREPARED, &h->sub[k], scr, st[k]);
         return tm_valuenet_forward_requests(vn_params, vn_prepared, &h->sub[k], scr, st[k]);
     };
     h->ev_used = 0;
@@ -271,6 +274,14 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
 int tm_search_set_epoch(tm_search* h, int epoch) {
     h->full.eval_epoch = epoch;
     for (auto& t : h->sub) t.eval_epoch = epoch;
+    return 0;
+}
+
+// The value net's backend for the runs that follow (include/tetris_mcts_hip.h: TM_VALUENET_FP32 / TM_VALUENET_BF16X3).
+int tm_search_set_valuenet(tm_search* h, int backend) {
+    if (backend != TM_VALUENET_FP32 && backend != TM_VALUENET_BF16X3) return (int)hipErrorInvalidValue;
+    if (backend == TM_VALUENET_BF16X3 && h->full.kind == TM_KIND_DIST) return (int)hipErrorInvalidValue;
+    h->vn_backend = backend;
     return 0;
 }
 

@@ -221,6 +221,30 @@ __device__ __forceinline__ int req_at(const ReqList& rq, int incl, int p, int la
     const int d = p - (sg > 0 ? before : 0);
     return (sg + rq.segs * (d / rq.slots)) * rq.slots + d % rq.slots;
 }
+// The request-list render as functions, for k_vn_conv_x3 (valuenet_x3.inc).  k_vn_conv keeps its own inline copy of the same
+// statements: calling these from it changes its machine code (measured on the code object), and the fp32 kernel stays as it is.
+// lane < 12: word `lane` of the packed observation of dense request p (0 past the end; every lane of the wave calls it)
+__device__ __forceinline__ uint32_t req_obs_word(const ReqList& rq, int incl, const uint32_t* __restrict__ obs_key, int max_nodes,
+                                                 int n, int p, int lane) {
+    if (p >= n) return 0u;
+    const int2 e = rq.list[req_at(rq, incl, p, lane)];
+    return lane < 12 ? obs_key[((size_t)(e.x / rq.slots) * max_nodes + e.y) * 12 + lane] : 0u;
+}
+// the packed observation held in lanes 0..11 of kw, rendered into x0[0..200): 0 empty, 1 locked, -1 falling piece
+__device__ __forceinline__ void render_obs(uint32_t kw, int lane, float* x0) {
+    const uint32_t cells = __shfl((int)kw, 10, 64), endw = __shfl((int)kw, 11, 64);
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {   // uniform trip count: the shuffles below need every lane active
+        const int i = lane + 64 * it, ic = min(i, 199);
+        int r = ic / 10, c = ic - 10 * r;
+        uint32_t w2 = (uint32_t)__shfl((int)kw, r >> 1, 64);
+        float v = (float)((w2 >> (16 * (r & 1) + c)) & 1u);
+        bool pc = ((cells & 0xFF) == (uint32_t)ic) | (((cells >> 8) & 0xFF) == (uint32_t)ic) |
+                  (((cells >> 16) & 0xFF) == (uint32_t)ic) | ((cells >> 24) == (uint32_t)ic);
+        if (!(endw & 0xFFu) && pc) v = -1.0f;
+        if (i < 200) x0[i] = v;
+    }
+}
 #include "valuenet_conv.inc"
 
 // fc1 (1792 -> 256) + ReLU on v_mfma_f32_16x16x4_f32 (D[16x16] += A[16x4] B[4x16]; lane l: A[i=l&15][k=l>>4],
@@ -475,6 +499,8 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
     FC1_STAMP(7);
 }
 
+#include "valuenet_x3.inc"
+
 }  // namespace tmcts_vn
 
 using namespace tmcts_vn;
@@ -507,24 +533,39 @@ int tm_valuenet_forward_plain(const float* P, const int8_t* states, int n, float
     return (int)hipGetLastError();
 }
 
-static int vn_forward_impl(const float* P, const float* prepared, const int8_t* states, const uint32_t* obs_key,
-                           const ReqList& rq, int max_nodes, int n, float* v, float* var,
+// planes != nullptr: the convolutions of the split-precision backend (k_vn_conv_x3), fc1 and the output layer as always
+static int vn_forward_impl(const float* P, const float* prepared, const __bf16* planes, const int8_t* states,
+                           const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n, float* v, float* var,
                            float* scratch, hipStream_t stream) {
     if (n <= 0) return 0;
     constexpr int SS = TM_VALUENET_SCRATCH_MFMA;   // a3 (1792) + hidden (256) + 16 pad words (word 0 of a tile's first row: its arrival counter)
     static_assert(SS >= A3 + HID + 1 && SS % 4 == 0, "scratch row");
-    const int lds = 4 * WAVE_LDS * (int)sizeof(float);
-    static std::once_flag attr_once;
-    static int attr_err = 0;
-    std::call_once(attr_once, [&] {
-        attr_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vn_conv),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
-    if (attr_err) return attr_err;
-    int blocks = (n + 3) / 4;
-    if (blocks > 256 * CONV_WG_PER_CU) blocks = 256 * CONV_WG_PER_CU;   // resident workgroups, waves stride over the states
-    hipLaunchKernelGGL(k_vn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, obs_key, rq,
-                       max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
+    if (planes) {
+        const int lds = 4 * X3_WAVE_BYTES;
+        static std::once_flag x3_once;
+        static int x3_err = 0;
+        std::call_once(x3_once, [&] {
+            x3_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vn_conv_x3),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        });
+        if (x3_err) return x3_err;
+        const int blocks = (n + 3) / 4 < 256 ? (n + 3) / 4 : 256;     // one workgroup per CU, waves stride over the states
+        hipLaunchKernelGGL(k_vn_conv_x3, dim3(blocks), dim3(256), lds, stream, P, planes, states, obs_key, rq,
+                           max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
+    } else {
+        const int lds = 4 * WAVE_LDS * (int)sizeof(float);
+        static std::once_flag attr_once;
+        static int attr_err = 0;
+        std::call_once(attr_once, [&] {
+            attr_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vn_conv),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        });
+        if (attr_err) return attr_err;
+        int blocks = (n + 3) / 4;
+        if (blocks > 256 * CONV_WG_PER_CU) blocks = 256 * CONV_WG_PER_CU;   // resident workgroups, waves stride over the states
+        hipLaunchKernelGGL(k_vn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, obs_key, rq,
+                           max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
+    }
     if (n >= 8192)      // (request slots: the leaf-parallel kinds' seven per game)
         hipLaunchKernelGGL((k_vn_fc1<4, 4, 128, 3, 2>), dim3((n + 63) / 64, 4), dim3(512), 0, stream, P, prepared, scratch, SS, n,
                            scratch + A3, SS, rq, reinterpret_cast<int32_t*>(scratch + A3 + HID), 64 * SS, v, var);
@@ -537,14 +578,38 @@ static int vn_forward_impl(const float* P, const float* prepared, const int8_t* 
 // matrix-core path; prepared: tm_valuenet_prepare output; scratch: n x TM_VALUENET_SCRATCH_MFMA floats
 int tm_valuenet_forward(const float* P, const float* prepared, const int8_t* states, int n, float* v, float* var,
                         float* scratch, void* stream_) {
-    return vn_forward_impl(P, prepared, states, nullptr, ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch, (hipStream_t)stream_);
+    return vn_forward_impl(P, prepared, nullptr, states, nullptr, ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch,
+                           (hipStream_t)stream_);
 }
 
 // the tree engine's evaluation requests, rendered inside the first kernel: v/var -> s->eval_v / s->eval_var
 int tm_valuenet_forward_requests(const float* P, const float* prepared, const tm_store* s, float* scratch, void* stream_) {
     // the requests of the last tm_sim_step launch, drawn from its dense list (s->eval_parity = that launch's)
     const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
-    return vn_forward_impl(P, prepared, nullptr, s->obs_key, rq, s->max_nodes,
+    return vn_forward_impl(P, prepared, nullptr, nullptr, s->obs_key, rq, s->max_nodes,
+                           s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
+}
+
+// ---- the split-precision backend (valuenet_x3.inc) ----
+int tm_valuenet_prepare_x3(const float* P, float* prepared_x3, void* stream_) {
+    if (!prepared_x3) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_vn_prepare_x3, dim3((2 * 18 * 64 * 8 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
+                       reinterpret_cast<__bf16*>(prepared_x3));
+    return (int)hipGetLastError();
+}
+
+int tm_valuenet_forward_x3(const float* P, const float* prepared, const float* prepared_x3, const int8_t* states, int n, float* v,
+                           float* var, float* scratch, void* stream_) {
+    if (!prepared_x3) return (int)hipErrorInvalidValue;
+    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), states, nullptr,
+                           ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch, (hipStream_t)stream_);
+}
+
+int tm_valuenet_forward_requests_x3(const float* P, const float* prepared, const float* prepared_x3, const tm_store* s,
+                                    float* scratch, void* stream_) {
+    if (!prepared_x3) return (int)hipErrorInvalidValue;
+    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
+    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->obs_key, rq, s->max_nodes,
                            s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
 }
 

@@ -3,10 +3,13 @@
 Same architecture, same state_dict keys (`head.conv1.weight` ... `head.fc_out.bias`, `out_ubound`,
 `out_lbound`) and the same checkpoint dict format (`model_state_dict`, model/model.py:152-160), so the
 reference's checkpoints load unchanged.  fp32 end to end (outputs must stay within 1e-4 of the
-reference's CPU result).  Two back ends:
-  * "hip"   — tm_valuenet_forward: hand-written gfx950 kernels (fp32 MFMA), bit-identical to
-              oracle/valuenet_oracle.c's fma chains;
-  * "torch" — PyTorch-ROCm ops (MIOpen / rocBLAS), used for training and as a cross-check.
+reference's CPU result).  Back ends:
+  * "hip"        — tm_valuenet_forward: hand-written gfx950 kernels (fp32 MFMA), bit-identical to
+                   oracle/valuenet_oracle.c's fma chains;
+  * "hip_bf16x3" — tm_valuenet_forward_x3: conv2 / conv3 on the bf16 matrix cores with every operand split into
+                   three bf16 planes (six plane products, fp32 accumulation), the rest as
+                   "hip": within 1e-4 of the reference, not bit-equal to "hip" (opt-in);
+  * "torch"      — PyTorch-ROCm ops (MIOpen / rocBLAS), used for training and as a cross-check.
 """
 import ctypes as C
 import os
@@ -19,6 +22,10 @@ from . import _lib
 from .store import _p, _stream
 
 SCRATCH_MFMA = 2064     # TM_VALUENET_SCRATCH_MFMA (include/tetris_mcts_hip.h): floats of scratch per state (no initial contents required)
+PREPARED = 477184       # TM_VALUENET_PREPARED: floats of tm_valuenet_prepare's operand streams
+PREPARED_X3 = 27648     # TM_VALUENET_PREPARED_X3: floats of tm_valuenet_prepare_x3's bf16 planes
+HIP_BACKENDS = ("hip", "hip_bf16x3")    # the backends the native search loop (search.hip) runs
+VALUENET_BACKEND = {"hip": 0, "hip_bf16x3": 1}      # TM_VALUENET_FP32 / TM_VALUENET_BF16X3 (tm_search_set_valuenet)
 PARAM_ORDER = ["head.conv1.weight", "head.conv1.bias", "head.conv2.weight", "head.conv2.bias", "head.conv3.weight",
                "head.conv3.bias", "head.fc1.weight", "head.fc1.bias", "head.fc_out.weight", "head.fc_out.bias",
                "out_ubound", "out_lbound"]
@@ -166,6 +173,12 @@ class Model_VV:
                 _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(self._prepared), _stream()), "tm_valuenet_prepare")
             _lib.check(_lib.lib().tm_valuenet_forward(_p(P), _p(self._prepared), _p(states), B, _p(v_out), _p(var_out),
                                                       _p(self._scratch), _stream()), "tm_valuenet_forward")
+        elif self.backend == "hip_bf16x3":
+            if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[1] < SCRATCH_MFMA:
+                self._scratch = torch.zeros(B, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
+            P, prep = self.flat_params(), self._prepared_x3()
+            _lib.check(_lib.lib().tm_valuenet_forward_x3(_p(P), _p(prep), _p(prep[PREPARED:]), _p(states), B, _p(v_out),
+                                                         _p(var_out), _p(self._scratch), _stream()), "tm_valuenet_forward_x3")
         elif self.backend == "hip_plain":
             if self._scratch_plain is None or self._scratch_plain.shape[0] < B:
                 self._scratch_plain = torch.empty(B, 9728, dtype=torch.float32, device=self.device)
@@ -177,12 +190,27 @@ class Model_VV:
             var_out.copy_(out[:, 1])
         return v_out, var_out
 
+    def _prepared_x3(self):
+        """"hip_bf16x3": one buffer of PREPARED + PREPARED_X3 floats, tm_valuenet_prepare's operand streams (fc1 runs on them)
+        followed by tm_valuenet_prepare_x3's planes - the layout tm_search_run takes under TM_VALUENET_BF16X3.  It lives in
+        _prepared, so everything that invalidates the fp32 streams (set_flat_params, load, train_data) invalidates the planes."""
+        if self._prepared is None:
+            P = self.flat_params()
+            prep = torch.empty(PREPARED + PREPARED_X3, dtype=torch.float32, device=self.device)
+            _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(prep), _stream()), "tm_valuenet_prepare")
+            _lib.check(_lib.lib().tm_valuenet_prepare_x3(_p(P), _p(prep[PREPARED:]), _stream()), "tm_valuenet_prepare_x3")
+            self._prepared = prep
+        return self._prepared
+
     @torch.no_grad()
     def hip_buffers(self, n_states):
-        """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip)."""
+        """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip); for
+        "hip_bf16x3" the prepared buffer holds the planes behind the streams (tm_search_set_valuenet)."""
         if self._scratch is None or self._scratch.shape[0] < n_states or self._scratch.shape[1] < SCRATCH_MFMA:
             self._scratch = torch.zeros(n_states, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
         P = self.flat_params()
+        if self.backend == "hip_bf16x3":
+            return _p(P), _p(self._prepared_x3()), _p(self._scratch)
         if self._prepared is None:
             self._prepared = torch.empty(477184, dtype=torch.float32, device=self.device)
             _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(self._prepared), _stream()), "tm_valuenet_prepare")
@@ -196,6 +224,11 @@ class Model_VV:
         if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[1] < SCRATCH_MFMA:
             self._scratch = torch.zeros(B, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
         P = self.flat_params()
+        if self.backend == "hip_bf16x3":
+            prep = self._prepared_x3()
+            _lib.check(_lib.lib().tm_valuenet_forward_requests_x3(_p(P), _p(prep), _p(prep[PREPARED:]), C.byref(store.s),
+                                                                  _p(self._scratch), _stream()), "tm_valuenet_forward_requests_x3")
+            return
         if self._prepared is None:
             self._prepared = torch.empty(477184, dtype=torch.float32, device=self.device)
             _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(self._prepared), _stream()), "tm_valuenet_prepare")
