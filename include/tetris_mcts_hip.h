@@ -45,11 +45,13 @@ extern "C" {
                                           the _x3 forwards take TM_VALUENET_SCRATCH_MFMA floats of scratch per state, as the fp32 ones */
 /* evaluator backends of the native search loop (tm_search_set_valuenet) */
 #define TM_VALUENET_FP32 0             /* tm_valuenet_forward_requests: fp32 matrix cores, the oracle's bits (the default) */
-#define TM_VALUENET_BF16X3 1           /* tm_valuenet_forward_requests_x3: conv2 / conv3 as three-way bf16 splits, fp32 accumulation */
+#define TM_VALUENET_BF16X3 1           /* tm_valuenet_forward_requests_x3 (TM_KIND_DIST: tm_distnet_forward_requests_x3): the
+                                          convolutions after the first as three-way bf16 splits, fp32 accumulation */
 #define TM_DISTNET_PARAMS(atoms) (279232 + 129 * (atoms))  /* floats: conv1.w[32][1][4][4] conv1.b[32] conv2.w[32][32][4][4] conv2.b[32]
                                           fc1.w[128][2048] fc1.b[128] fc_v.w[atoms][128] fc_v.b[atoms] (model/model_distributional.py:33-42) */
 #define TM_DISTNET_PARAMS_50 285682    /* TM_DISTNET_PARAMS(50) */
 #define TM_DISTNET_PREPARED 278528     /* floats: conv2 + fc1 operand streams */
+#define TM_DISTNET_PREPARED_X3 24576   /* floats (49 152 bf16): conv2's weights as bf16 hi / mid / lo planes, tm_distnet_prepare_x3 */
 #define TM_DISTNET_SCRATCH 2048        /* floats of scratch per state (conv2's output), tm_distnet_forward / _requests */
 
 /* per-game control block (int32 words) */
@@ -292,7 +294,8 @@ int tm_store_slice(const tm_store *s, int first, int n, tm_store *out);
  * catch-up launches of games that collected garbage, tm_sims_remaining).  vn_params == NULL: no evaluator launches
  * (TM_KIND_VANILLA).  The evaluator follows the store's kind: the value net (tm_valuenet_forward_requests; vn_scratch:
  * n_games * eval_slots * TM_VALUENET_SCRATCH_MFMA floats, no initial contents required) or, for TM_KIND_DIST, the distributional head
- * (tm_distnet_forward_requests; vn_params / vn_prepared = its blobs, vn_scratch: n_games * TM_DISTNET_SCRATCH floats).  ev_every > 0: HIP events
+ * (tm_distnet_forward_requests, or _x3 under tm_search_set_valuenet; vn_params / vn_prepared = its blobs, vn_scratch:
+ * n_games * TM_DISTNET_SCRATCH floats).  ev_every > 0: HIP events
  * around every ev_every-th simulation of sub-batch 0 (on the stream it runs on), read back by tm_search_stats:
  * out = {runs, tree launches, catch-up launches, timed samples, sum tree-kernel ms, sum value-net ms, n_sub}. */
 typedef struct tm_search tm_search;
@@ -307,8 +310,11 @@ int tm_search_set_epoch(tm_search *h, int epoch);
 /* the evaluator backend of tm_search_run's value net: TM_VALUENET_FP32 (the default) or TM_VALUENET_BF16X3.  Under
  * TM_VALUENET_BF16X3, vn_prepared points at TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3 floats: the fp32 operand streams of
  * tm_valuenet_prepare (fc1 stays on them) followed by the planes of tm_valuenet_prepare_x3.  hipErrorInvalidValue for any
- * other value, and for TM_VALUENET_BF16X3 on a TM_KIND_DIST store (its head has no such backend).  The caller gives the
- * backend's outputs an epoch of their own (tm_search_set_epoch): obs_eval must not mix the two. */
+ * other value.  On a TM_KIND_DIST store TM_VALUENET_BF16X3 selects the distributional head's split-precision backend
+ * (tm_distnet_forward_requests_x3): vn_prepared then points at TM_DISTNET_PREPARED + TM_DISTNET_PREPARED_X3 floats, the
+ * streams of tm_distnet_prepare (fc1 stays on them) followed by the planes of tm_distnet_prepare_x3.  The caller gives the
+ * backend's outputs an epoch of their own (tm_search_set_epoch): obs_eval must not mix the two (TM_KIND_DIST keeps no
+ * obs_eval). */
 int tm_search_set_valuenet(tm_search *h, int backend);
 int tm_root_stats(const tm_store *s, float *stats /* [G][3][7] */, int32_t *action /* [G] */, void *stream);
 /* one game's tree in the reference's array layout (agents/agent.py:58-88), for inspection and tests */
@@ -413,6 +419,17 @@ int tm_distnet_forward(const float *params, const float *prepared, const int8_t 
 /* the tree engine's pending requests (TM_KIND_DIST: s->eval_obs[g] = the leaf NODE of game g, rendered from its packed game
  * inside the first kernel) -> s->eval_dist[g][0 .. dist_bins); scratch: n_games x TM_DISTNET_SCRATCH floats */
 int tm_distnet_forward_requests(const float *params, const float *prepared, const tm_store *s, float *scratch, void *stream);
+/* The split-precision backend (distnet_x3.inc; numerics contract in DESIGN.md section 3.8): conv2 on the bf16 matrix cores,
+ * every operand split into three bf16 planes, six plane products per fp32 product, fp32 accumulation; conv1, fc1, fc_v and
+ * the softmax as in tm_distnet_forward.  Within 1e-6 relative of the reference's Net, not bit-equal to the fp32 path; a
+ * state's outputs depend on that state only.  tm_distnet_prepare_x3 writes the planes (TM_DISTNET_PREPARED_X3 floats, after
+ * every weight change); the forwards take both prepared buffers (fc1 reads tm_distnet_prepare's) and TM_DISTNET_SCRATCH
+ * floats of scratch per state.  prepared_x3 == NULL, or arguments the fp32 calls refuse: hipErrorInvalidValue. */
+int tm_distnet_prepare_x3(const float *params, float *prepared_x3, void *stream);
+int tm_distnet_forward_x3(const float *params, const float *prepared, const float *prepared_x3, const int8_t *states,
+                          int n, int atoms, float *dist, int dist_stride, float *scratch, void *stream);
+int tm_distnet_forward_requests_x3(const float *params, const float *prepared, const float *prepared_x3,
+                                   const tm_store *s, float *scratch, void *stream);
 
 const char *tm_version(void);
 /* sizeof(tm_store) and a few offsets, so a host mirror of the struct can be checked without a GPU */

@@ -46,7 +46,8 @@ def build_parser():
     add('--train_min_tuples', default=0, type=int, help='[new] online mode: fit only once this many fresh tuples are held over '
         'all ranks (0: 1 with one game, 1024 = one training batch with more)')
     add('--valuenet_backend', default='hip', choices=('hip', 'hip_bf16x3', 'torch'), help='[new] value net of ValueSim, '
-        'ValueSimLP and ValueSimC: hip (fp32 matrix cores), hip_bf16x3 (split-precision bf16 matrix cores) or torch')
+        'ValueSimLP and ValueSimC, distributional head of DistValueSim: hip (fp32 matrix cores), hip_bf16x3 (split-precision '
+        'bf16 matrix cores) or torch')
     return p
 
 
@@ -82,10 +83,10 @@ def main(argv=None):
     G = args.n_games
     game = Tetris(*env_args, seed=args.seed, n_games=G)
     extra = {}
-    if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC'):
+    if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim'):
         extra['valuenet_backend'] = args.valuenet_backend
     elif args.valuenet_backend != 'hip':
-        sys.exit('--valuenet_backend applies to ValueSim, ValueSimLP and ValueSimC only')
+        sys.exit('--valuenet_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     agent.update_root(game)

@@ -5,11 +5,17 @@
            requests per launch (1 867 and 7 169 states), both backends, with TFLOP/s against each backend's own peak (fp32
            matrix 157.3 TF; bf16x3 = the bf16 matrix peak / 6 products); and max |dv|, |dvar| of bf16x3 against fp32 over the
            states a short real search asked for (render_eval), with the r06 checkpoint;
+  head     the distributional head (DistValueSim's leaf evaluator, Model_Dist(seed 0) as bench.py runs it): per-launch time on
+           4096 dense states (k_dn_conv[_x3] + k_dn_fc), both backends alternated in blocks of 20 launches after 20 warm-up
+           launches each, with TFLOP/s against each backend's own peak; and max |dp| of bf16x3 against fp32 over the leaves a
+           short real DistValueSim search asked for (render_eval);
   search   ms per move of the native search loop, moves warmup+1 .. warmup+steps, for ONE agent and ONE backend (two stores of
            4096 x 100 000 nodes do not fit one GPU: one process per backend).
 
     python scripts/bench_split_precision.py kernels [--out profiles/FILE.json]
+    python scripts/bench_split_precision.py head [--out ...]
     python scripts/bench_split_precision.py search --agent ValueSim --backend hip_bf16x3 [--out ...]
+    python scripts/bench_split_precision.py search --agent DistValueSim --sims 1000 --warmup 5 --steps 5 --backend hip_bf16x3
 """
 import argparse
 import json
@@ -23,6 +29,8 @@ CKPT = os.path.join(ROOT, "tetris_mcts_amd", "checkpoints", "value_net_online_r0
 # useful FLOP per state: conv1 144x32x9, conv2 96x32x288, conv3 56x32x288, fc1 1792x256, out 256x2 multiply-adds
 FLOP_STATE = 2 * (144 * 32 * 9 + 96 * 32 * 288 + 56 * 32 * 288 + 1792 * 256 + 256 * 2)
 PEAK_TF = {"hip": 157.3, "hip_bf16x3": 2516.6 / 6}      # MI355X: fp32 matrix = fp32 vector rate; bf16 matrix dense
+# the distributional head: conv1 133x32x16, conv2 64x32x512, fc1 2048x128, fc_v 128x50 multiply-adds per state
+FLOP_STATE_DIST = 2 * (133 * 32 * 16 + 64 * 32 * 512 + 2048 * 128 + 128 * 50)
 
 
 def _model(backend):
@@ -89,12 +97,78 @@ def kernels(args):
     return out
 
 
+def _dist_model(backend):
+    from tetris_mcts_amd.model_distributional import Model_Dist
+    return Model_Dist(atoms=50, seed=0, backend=backend)       # bench.py's DistValueSim head
+
+
+def _dist_searched_states(n_games=512, sims=32, moves=6):
+    """int8 [n, 200]: every leaf state a DistValueSim search with the fp32 head asked for (render_eval of every launch)"""
+    import torch
+    from tetris_mcts_amd import agents
+    from tetris_mcts_amd.pyTetris import Tetris
+    m = _dist_model("hip")
+    seen = []
+
+    def ev(states):
+        st = torch.from_numpy(states.reshape(-1, 200)).cuda()
+        seen.append(st)
+        return m.inference_device(st)[:, :50].cpu().numpy()
+    env_args = ((20, 10), 1, 0, 0)
+    game = Tetris(*env_args, seed=20261016, n_games=n_games)
+    agent = agents.DistValueSim(sims=sims, env=Tetris, env_args=env_args, n_games=n_games, max_nodes=20000, evaluator=ev)
+    agent.update_root(game)
+    for _ in range(moves):
+        act = agent.play()
+        game.play(act)
+        agent.update_root(game)
+    s = torch.cat(seen)
+    return s[(s != 0).any(dim=1)].contiguous()
+
+
+def head(args):
+    import torch
+    states = _dist_searched_states()
+    models = {b: _dist_model(b) for b in ("hip", "hip_bf16x3")}
+    p32 = models["hip"].inference_device(states)[:, :50].clone()
+    px3 = models["hip_bf16x3"].inference_device(states)[:, :50].clone()
+    out = dict(mode="head", searched_states=int(states.shape[0]), flop_per_state=FLOP_STATE_DIST,
+               max_abs_dp=float((px3 - p32).abs().max().item()), max_rel_dp=float(((px3 - p32).abs() / p32).max().item()))
+    n = args.states
+    batch = states[torch.arange(n, device=states.device) % states.shape[0]].contiguous()
+    dist = {b: torch.empty(n, 64, device="cuda") for b in models}
+    for b, m in models.items():
+        for _ in range(20):
+            m.inference_device(batch, dist[b])
+    torch.cuda.synchronize()
+    ms = {b: 0.0 for b in models}
+    block = 20
+    for _ in range(args.launches // block):
+        for b, m in models.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(block):
+                m.inference_device(batch, dist[b])
+            e1.record()
+            torch.cuda.synchronize()
+            ms[b] += e0.elapsed_time(e1)
+    row = {}
+    for b in models:
+        us = 1e3 * ms[b] / (block * (args.launches // block))
+        tf = FLOP_STATE_DIST * n / (us * 1e-6) / 1e12
+        row[b] = dict(us_per_launch=round(us, 2), tflops=round(tf, 2), peak_tflops=round(PEAK_TF[b], 1),
+                      of_peak=round(tf / PEAK_TF[b], 4))
+    row["speedup"] = round(row["hip"]["us_per_launch"] / row["hip_bf16x3"]["us_per_launch"], 3)
+    out["launches"] = {str(n): row}
+    return out
+
+
 def search(args):
     import numpy as np
     import torch
     from tetris_mcts_amd import agents
     from tetris_mcts_amd.pyTetris import Tetris
-    model = _model(args.backend)
+    model = _dist_model(args.backend) if args.agent == "DistValueSim" else _model(args.backend)
     env_args = ((20, 10), 1, 0, 0)
     G = args.games
     game = Tetris(*env_args, seed=20260925, n_games=G)
@@ -128,9 +202,10 @@ def search(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=("kernels", "search"))
+    ap.add_argument("mode", choices=("kernels", "head", "search"))
     ap.add_argument("--launches", type=int, default=200)
-    ap.add_argument("--agent", default="ValueSim", choices=("ValueSim", "ValueSimLP"))
+    ap.add_argument("--states", type=int, default=4096, help="head: states per launch")
+    ap.add_argument("--agent", default="ValueSim", choices=("ValueSim", "ValueSimLP", "DistValueSim"))
     ap.add_argument("--backend", default="hip", choices=("hip", "hip_bf16x3"))
     ap.add_argument("--games", type=int, default=4096)
     ap.add_argument("--sims", type=int, default=500)
@@ -139,7 +214,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
-    res = kernels(args) if args.mode == "kernels" else search(args)
+    res = {"kernels": kernels, "head": head, "search": search}[args.mode](args)
     line = json.dumps(res)
     print(line, flush=True)
     if args.out:

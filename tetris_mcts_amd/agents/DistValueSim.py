@@ -25,8 +25,10 @@ class DistValueSim(TreeAgent):
     low = 5
 
     def __init__(self, atoms=50, vmin=0, vmax=5000, max_nodes=100000, model=None, evaluator=None, online=False,
-                 min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, **kwargs):
-        """online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
+                 min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, valuenet_backend=None, **kwargs):
+        """valuenet_backend: the Model_Dist backend of the model the agent builds when `model` is None (None: Model_Dist's
+        default; "hip", "hip_bf16x3" - the split-precision kernels - or "torch").
+        online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
         least `min_visits_to_store` visits whose seven children have all been visited (its commented store_nodes, default 50)
         as (board, distribution, visits) tuples, train_nodes fits the head on them (memory_size / memory_growth_rate as
         ValueSim's)."""
@@ -41,7 +43,7 @@ class DistValueSim(TreeAgent):
         super().__init__(max_nodes=max_nodes, online=self.online, min_visits_to_store=min_visits_to_store, **kwargs)
         if evaluator is None:
             from ..model_distributional import Model_Dist
-            self.model = model if model is not None else Model_Dist(atoms=self.atoms)
+            self.model = model if model is not None else Model_Dist(atoms=self.atoms, backend=valuenet_backend)
             if int(getattr(self.model, "atoms", self.atoms)) != self.atoms:
                 # the head's parameter blob is indexed with the store's atom count (tm_distnet_forward_requests): another
                 # count reads fc_v out of bounds
@@ -57,15 +59,17 @@ class DistValueSim(TreeAgent):
         self.store = st.TreeStore(self.n_games, self.max_nodes, **kw)
 
     def search_model(self):
-        """the HIP head is driven by the native launch loop (search.hip); a Python callable or the torch back end by
-        TreeAgent.mcts"""
-        return self.model if (self.evaluator is None and self.model.backend == "hip") else False
+        """the HIP head (either HIP backend) is driven by the native launch loop (search.hip); a Python callable or the
+        torch back end by TreeAgent.mcts"""
+        from ..model_distributional import HIP_BACKENDS
+        return self.model if (self.evaluator is None and self.model.backend in HIP_BACKENDS) else False
 
     @torch.no_grad()
     def evaluate_requests(self):
         """The pending leaves' observations -> distributions over the atoms, into the store's eval_dist."""
+        from ..model_distributional import HIP_BACKENDS
         s = self.store
-        if self.evaluator is None and self.model.backend == "hip":
+        if self.evaluator is None and self.model.backend in HIP_BACKENDS:
             self.model.inference_requests(s)                              # nodes rendered inside the convolution kernel
             return
         states = s.render_eval()                                          # int8 [G, 200]; all zero where nothing is asked

@@ -12,6 +12,7 @@
 // Two kernels per evaluation of all pending leaves:
 //   k_dn_conv : one wave per state (render + conv1 + conv2, activations in LDS, conv2 = 2 position tiles x 256 MFMA steps),
 //               two workgroups of four waves per CU; 4096 states = exactly four per SIMD
+//               (or k_dn_conv_x3, distnet_x3.inc: the opt-in split-precision backend, conv2 on the bf16 matrix cores)
 //   k_dn_fc   : 16 states x all 128 hidden units per workgroup (8 waves, one 16 x 16 tile each, K = 2048 staged through LDS),
 //               then FC atoms on the matrix cores and the softmax in the same workgroup - no hand-off between workgroups
 #include <hip/hip_runtime.h>
@@ -134,6 +135,89 @@ __device__ __forceinline__ void conv2_mfma(const float* __restrict__ in, const i
     }
 }
 
+// ---- the pieces of the state loop that k_dn_conv and k_dn_conv_x3 (distnet_x3.inc) share ----
+// lanes 0..15: word `lane` of the packed game of node o of game s (0 past the end and on the other lanes)
+__device__ __forceinline__ uint32_t game_word(const uint32_t* __restrict__ node_game, int max_nodes, int n, int s, int o,
+                                              int lane) {
+    return (s < n && lane < 16) ? node_game[((size_t)s * max_nodes + o) * tmcts::GAME_DW + lane] : 0u;
+}
+
+// The input of state s into rows 2..21 of x0 (x0[20 ..]): a dense int8 state, or the packed game held in lanes 0..15 of
+// gw_next (the request's node o_next), rendered.  The request path fetches the next state's (sn's) node and packed game
+// here, one state ahead.  false: slot s carries no request (request 0) and is skipped.
+__device__ __forceinline__ bool load_input(const int8_t* __restrict__ states, const uint32_t* __restrict__ node_game,
+                                           const int32_t* __restrict__ eval_obs, int max_nodes, int n, int s, int sn,
+                                           int lane, int& o_next, uint32_t& gw_next, float* x0) {
+    if (states) {
+        for (int i = lane; i < 200; i += 64) x0[20 + i] = (float)states[(size_t)s * 200 + i];
+        return true;
+    }
+    const int o = o_next;
+    const uint32_t gw = gw_next;
+    o_next = (sn < n) ? eval_obs[sn] : 0;
+    if (o == 0) {
+        gw_next = game_word(node_game, max_nodes, n, sn, o_next, lane);
+        return false;
+    }
+    const uint32_t pa = (uint32_t)__shfl((int)gw, 10, 64), pb = (uint32_t)__shfl((int)gw, 11, 64);
+    const bool ended = (pb >> 8) & 1u;
+    const int piece = pa & 0xFF, rot = (pa >> 8) & 0xFF;
+    const int px = (int)(int8_t)((pa >> 16) & 0xFF), py = (int)(int8_t)((pa >> 24) & 0xFF);
+    const uint32_t mask = (piece < 7 && rot < 4) ? tmcts::PIECE_MASK[piece][rot] : 0u;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {   // uniform trip count: the shuffles need every lane active
+        const int i = lane + 64 * it, ic = min(i, 199);
+        const int r = ic / 10, c = ic - 10 * r;
+        const uint32_t w2 = (uint32_t)__shfl((int)gw, r >> 1, 64);
+        float v = (float)((w2 >> (16 * (r & 1) + c)) & 1u);
+        const int dr = r - py, dc = c - px;
+        const bool pc = dr >= 0 && dr < 4 && dc >= 0 && dc < 4 && ((mask >> (4 * dr + dc)) & 1u);
+        if (!ended && pc) v = -1.0f;
+        if (i < 200) x0[20 + i] = v;
+    }
+    gw_next = game_word(node_game, max_nodes, n, sn, o_next, lane);
+    return true;
+}
+
+// conv1's per-lane constants: bias1[r] = the bias of the accumulator's channel (r & 3) + 8 (r >> 2) + 4 half; the A operand
+// of step st = W1[co = l31][k = 2 st + half] and the x0 offset of its tap
+__device__ __forceinline__ void conv1_setup(const float* __restrict__ P, int l31, int half, float (&bias1)[16], float (&w1)[8],
+                                            int (&koff1)[8]) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bias1[r] = P[OFF_C1B + (r & 3) + 8 * (r >> 2) + 4 * half];
+#pragma unroll
+    for (int st = 0; st < 8; ++st) {
+        const int k = 2 * st + half;
+        w1[st] = P[OFF_C1W + l31 * 16 + k];
+        koff1[st] = (k >> 2) * 10 + (k & 3);
+    }
+}
+
+// conv1 (K = 16 = 8 steps of two taps) of position tile t (positions 32 t + l31; 133 positions = 5 tiles, the last one 5
+// positions), before the activation
+__device__ __forceinline__ f32x16 conv1_tile(const float* x0, int t, int l31, const float (&bias1)[16], const float (&w1)[8],
+                                             const int (&koff1)[8]) {
+    const int p = 32 * t + l31, pc = min(p, C1P - 1), y = pc / 7, base = y * 10 + (pc - 7 * y);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = bias1[r];
+#pragma unroll
+    for (int st = 0; st < 8; ++st)
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], x0[base + koff1[st]], acc, 0, 0, 0);
+    return acc;
+}
+
+// conv2's two accumulator tiles, LeakyReLU'd, into the state's scratch row (flatten order co*64 + y*4 + x)
+__device__ __forceinline__ void store_a2(float* dst, const f32x16 (&acc)[2], int half, int l31) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
+            dst[i * C2P + 32 * t + l31] = leaky(acc[t][r]);
+        }
+}
+
 // Input: either int8 states [n][200] (0 empty, 1 locked, -1 falling piece), or (states == nullptr) the tree engine's
 // evaluation requests: request s names NODE eval_obs[s] of game s (TM_KIND_DIST: no observation projection), rendered here
 // from the node's packed game (ENGINE_SPEC.md section 2; the rendering of tree.hip k_eval_render: pack_obs + obs_cell).
@@ -157,85 +241,36 @@ __global__ __launch_bounds__(256, 2) void k_dn_conv(const float* __restrict__ P,
             boff2[t][j] = (y + (k >> 2)) * 7 + x + (k & 3);
         }
     }
-    float bias2[16], bias1[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-        bias2[r] = P[OFF_C2B + i];
-        bias1[r] = P[OFF_C1B + i];
-    }
-    float w1[8];      // conv1 weights: A operand of step st = W1[co = l31][k = 2 st + half]
+    float bias2[16], bias1[16], w1[8];
     int koff1[8];
 #pragma unroll
-    for (int st = 0; st < 8; ++st) {
-        const int k = 2 * st + half;
-        w1[st] = P[OFF_C1W + l31 * 16 + k];
-        koff1[st] = (k >> 2) * 10 + (k & 3);
-    }
+    for (int r = 0; r < 16; ++r) bias2[r] = P[OFF_C2B + (r & 3) + 8 * (r >> 2) + 4 * half];
+    conv1_setup(P, l31, half, bias1, w1, koff1);
     const float4* W2 = reinterpret_cast<const float4*>(prep + PREP_W2) + lane;
 
     // the two dependent global reads per request (request -> packed game) are issued one state ahead
     const int stride = gridDim.x * 4;
     int s = blockIdx.x * 4 + w;
     int o_next = (!states && s < n) ? eval_obs[s] : 0;
-    uint32_t gw_next = 0;
-    if (!states && s < n && lane < 16) gw_next = node_game[((size_t)s * max_nodes + o_next) * tmcts::GAME_DW + lane];
+    uint32_t gw_next = states ? 0u : game_word(node_game, max_nodes, n, s, o_next, lane);
     // the two hidden rows never change
     if (lane < 20) x0[lane] = 0.0f;
     for (; s < n; s += stride) {
         int zoff = 0;                        // weight stream re-read per state (keeps it out of ~130 hoisted registers)
         asm volatile("" : "+s"(zoff));
         const float4* W2s = W2 + zoff;
-        const int o = o_next;
-        const uint32_t gw = gw_next;
-        const int sn = s + stride;
-        if (!states) {
-            o_next = (sn < n) ? eval_obs[sn] : 0;
-            if (o == 0) {
-                gw_next = (sn < n && lane < 16) ? node_game[((size_t)sn * max_nodes + o_next) * tmcts::GAME_DW + lane] : 0u;
-                continue;
-            }
-        }
-        // ---- input: rows 2..21 of x0 ----
-        if (states) {
-            for (int i = lane; i < 200; i += 64) x0[20 + i] = (float)states[(size_t)s * 200 + i];
-        } else {
-            const uint32_t pa = (uint32_t)__shfl((int)gw, 10, 64), pb = (uint32_t)__shfl((int)gw, 11, 64);
-            const bool ended = (pb >> 8) & 1u;
-            const int piece = pa & 0xFF, rot = (pa >> 8) & 0xFF;
-            const int px = (int)(int8_t)((pa >> 16) & 0xFF), py = (int)(int8_t)((pa >> 24) & 0xFF);
-            const uint32_t mask = (piece < 7 && rot < 4) ? tmcts::PIECE_MASK[piece][rot] : 0u;
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {   // uniform trip count: the shuffles need every lane active
-                const int i = lane + 64 * it, ic = min(i, 199);
-                const int r = ic / 10, c = ic - 10 * r;
-                const uint32_t w2 = (uint32_t)__shfl((int)gw, r >> 1, 64);
-                float v = (float)((w2 >> (16 * (r & 1) + c)) & 1u);
-                const int dr = r - py, dc = c - px;
-                const bool pc = dr >= 0 && dr < 4 && dc >= 0 && dc < 4 && ((mask >> (4 * dr + dc)) & 1u);
-                if (!ended && pc) v = -1.0f;
-                if (i < 200) x0[20 + i] = v;
-            }
-            gw_next = (sn < n && lane < 16) ? node_game[((size_t)sn * max_nodes + o_next) * tmcts::GAME_DW + lane] : 0u;
-        }
+        if (!load_input(states, node_game, eval_obs, max_nodes, n, s, s + stride, lane, o_next, gw_next, x0)) continue;
         lds_fence();
-        // ---- conv1 (K = 16 = 8 steps of two taps): 133 positions = 5 tiles (the last one 5 positions) ----
-        {
+        // ---- conv1: 133 positions = 5 tiles ----
 #pragma unroll 1
-            for (int t = 0; t < 5; ++t) {
-                const int p = 32 * t + l31, pc = min(p, C1P - 1), y = pc / 7, base = y * 10 + (pc - 7 * y);
-                f32x16 acc;
+        for (int t = 0; t < 5; ++t) {
+            const f32x16 acc = conv1_tile(x0, t, l31, bias1, w1, koff1);
+            const int p = 32 * t + l31;
+            if (p < C1P) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = bias1[r];
-#pragma unroll
-                for (int st = 0; st < 8; ++st)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], x0[base + koff1[st]], acc, 0, 0, 0);
-                if (p < C1P) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-                        a1[i * A1CS + p] = leaky(acc[r]);
-                    }
+                for (int r = 0; r < 16; ++r) {
+                    const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    a1[i * A1CS + p] = leaky(acc[r]);
                 }
             }
         }
@@ -248,14 +283,7 @@ __global__ __launch_bounds__(256, 2) void k_dn_conv(const float* __restrict__ P,
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[t][r] = bias2[r];
             conv2_mfma(a1, boff2, W2s, acc);
-            float* dst = a2out + (size_t)s * a2stride;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-                    dst[i * C2P + 32 * t + l31] = leaky(acc[t][r]);
-                }
+            store_a2(a2out + (size_t)s * a2stride, acc, half, l31);
         }
         lds_fence();
     }
@@ -404,24 +432,41 @@ __global__ __launch_bounds__(512) void k_dn_fc(const float* __restrict__ P, cons
     }
 }
 
+#include "distnet_x3.inc"
+
 static std::once_flag g_attr_once;
 static int g_attr_err = 0;
 
-static int dn_forward_impl(const float* P, const float* prepared, const int8_t* states, const uint32_t* node_game,
-                           const int32_t* eval_obs, int max_nodes, int n, int atoms, float* out, int out_stride,
-                           float* scratch, hipStream_t stream) {
+// planes != nullptr: conv1 + conv2 of the split-precision backend (k_dn_conv_x3), k_dn_fc as always
+static int dn_forward_impl(const float* P, const float* prepared, const __bf16* planes, const int8_t* states,
+                           const uint32_t* node_game, const int32_t* eval_obs, int max_nodes, int n, int atoms, float* out,
+                           int out_stride, float* scratch, hipStream_t stream) {
     if (n <= 0) return 0;
     if (atoms < 1 || atoms > 64) return (int)hipErrorInvalidValue;
-    const int lds = 4 * WAVE_LDS * (int)sizeof(float);
-    std::call_once(g_attr_once, [&] {
-        g_attr_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_dn_conv),
+    if (planes) {
+        const int lds = 4 * X3_WAVE_BYTES;
+        static std::once_flag x3_once;
+        static int x3_err = 0;
+        std::call_once(x3_once, [&] {
+            x3_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_dn_conv_x3),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    });
-    if (g_attr_err) return g_attr_err;
-    int blocks = (n + 3) / 4;
-    if (blocks > 512) blocks = 512;      // two resident workgroups per CU, waves stride over the states
-    hipLaunchKernelGGL(k_dn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, node_game, eval_obs, max_nodes,
-                       n, scratch, TM_DISTNET_SCRATCH);
+        });
+        if (x3_err) return x3_err;
+        const int blocks = (n + 3) / 4 < 256 ? (n + 3) / 4 : 256;     // one workgroup per CU, waves stride over the states
+        hipLaunchKernelGGL(k_dn_conv_x3, dim3(blocks), dim3(256), lds, stream, P, planes, states, node_game, eval_obs,
+                           max_nodes, n, scratch, TM_DISTNET_SCRATCH);
+    } else {
+        const int lds = 4 * WAVE_LDS * (int)sizeof(float);
+        std::call_once(g_attr_once, [&] {
+            g_attr_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_dn_conv),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        });
+        if (g_attr_err) return g_attr_err;
+        int blocks = (n + 3) / 4;
+        if (blocks > 512) blocks = 512;      // two resident workgroups per CU, waves stride over the states
+        hipLaunchKernelGGL(k_dn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, node_game, eval_obs,
+                           max_nodes, n, scratch, TM_DISTNET_SCRATCH);
+    }
     hipLaunchKernelGGL(k_dn_fc, dim3((n + FC_ST - 1) / FC_ST), dim3(512), 0, stream, P, prepared, scratch, TM_DISTNET_SCRATCH,
                        n, atoms, eval_obs, out, out_stride);
     return (int)hipGetLastError();
@@ -441,13 +486,36 @@ int tm_distnet_prepare(const float* P, float* prepared, void* stream_) {
 int tm_distnet_forward(const float* P, const float* prepared, const int8_t* states, int n, int atoms, float* dist,
                        int dist_stride, float* scratch, void* stream_) {
     if (dist_stride < atoms) return (int)hipErrorInvalidValue;
-    return dn_forward_impl(P, prepared, states, nullptr, nullptr, 0, n, atoms, dist, dist_stride, scratch, (hipStream_t)stream_);
+    return dn_forward_impl(P, prepared, nullptr, states, nullptr, nullptr, 0, n, atoms, dist, dist_stride, scratch,
+                           (hipStream_t)stream_);
 }
 
 int tm_distnet_forward_requests(const float* P, const float* prepared, const tm_store* s, float* scratch, void* stream_) {
     if (s->kind != TM_KIND_DIST || s->eval_slots != 1) return (int)hipErrorInvalidValue;
-    return dn_forward_impl(P, prepared, nullptr, s->node_game, s->eval_obs, s->max_nodes, s->n_games, s->dist_bins,
+    return dn_forward_impl(P, prepared, nullptr, nullptr, s->node_game, s->eval_obs, s->max_nodes, s->n_games, s->dist_bins,
                            s->eval_dist, TM_DIST_ROW, scratch, (hipStream_t)stream_);
+}
+
+// ---- the split-precision backend (distnet_x3.inc) ----
+int tm_distnet_prepare_x3(const float* P, float* prepared_x3, void* stream_) {
+    if (!prepared_x3) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dn_prepare_x3, dim3((X3_STEPS * 64 * 8 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
+                       reinterpret_cast<__bf16*>(prepared_x3));
+    return (int)hipGetLastError();
+}
+
+int tm_distnet_forward_x3(const float* P, const float* prepared, const float* prepared_x3, const int8_t* states, int n,
+                          int atoms, float* dist, int dist_stride, float* scratch, void* stream_) {
+    if (!prepared_x3 || dist_stride < atoms) return (int)hipErrorInvalidValue;
+    return dn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), states, nullptr, nullptr, 0, n, atoms,
+                           dist, dist_stride, scratch, (hipStream_t)stream_);
+}
+
+int tm_distnet_forward_requests_x3(const float* P, const float* prepared, const float* prepared_x3, const tm_store* s,
+                                   float* scratch, void* stream_) {
+    if (!prepared_x3 || s->kind != TM_KIND_DIST || s->eval_slots != 1) return (int)hipErrorInvalidValue;
+    return dn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->node_game, s->eval_obs,
+                           s->max_nodes, s->n_games, s->dist_bins, s->eval_dist, TM_DIST_ROW, scratch, (hipStream_t)stream_);
 }
 
 }  // extern "C"

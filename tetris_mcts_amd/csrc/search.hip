@@ -188,9 +188,13 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
     };
     auto nn = [&](int k) -> int {
         if (!vn_params || h->sub[k].n_games == 0) return 0;
-        if (h->full.kind == TM_KIND_DIST)      // the distributional head (distnet.hip): eval_obs names the leaf node
-            return tm_distnet_forward_requests(vn_params, vn_prepared, &h->sub[k],
-                                               vn_scratch + (size_t)h->first[k] * TM_DISTNET_SCRATCH, st[k]);
+        if (h->full.kind == TM_KIND_DIST) {    // the distributional head (distnet.hip): eval_obs names the leaf node
+            float* scr = vn_scratch + (size_t)h->first[k] * TM_DISTNET_SCRATCH;
+            if (h->vn_backend == TM_VALUENET_BF16X3)  // vn_prepared: the fp32 operand streams, then the planes
+                return tm_distnet_forward_requests_x3(vn_params, vn_prepared, vn_prepared + TM_DISTNET_PREPARED, &h->sub[k], scr,
+                                                      st[k]);
+            return tm_distnet_forward_requests(vn_params, vn_prepared, &h->sub[k], scr, st[k]);
+        }
         float* scr = vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA;
         if (h->vn_backend == TM_VALUENET_BF16X3)      // vn_prepared: the fp32 operand streams, then the planes (tm_search_set_valuenet)
             return tm_valuenet_forward_requests_x3(vn_params, vn_prepared, vn_prepared + TM_VALUENET_PREPARED, &h->sub[k], scr, st[k]);
@@ -277,10 +281,10 @@ int tm_search_set_epoch(tm_search* h, int epoch) {
     return 0;
 }
 
-// The value net's backend for the runs that follow (include/tetris_mcts_hip.h: TM_VALUENET_FP32 / TM_VALUENET_BF16X3).
+// The evaluator's backend for the runs that follow (include/tetris_mcts_hip.h: TM_VALUENET_FP32 / TM_VALUENET_BF16X3), the
+// value net's or, on a TM_KIND_DIST store, the distributional head's.
 int tm_search_set_valuenet(tm_search* h, int backend) {
     if (backend != TM_VALUENET_FP32 && backend != TM_VALUENET_BF16X3) return (int)hipErrorInvalidValue;
-    if (backend == TM_VALUENET_BF16X3 && h->full.kind == TM_KIND_DIST) return (int)hipErrorInvalidValue;
     h->vn_backend = backend;
     return 0;
 }

@@ -16,8 +16,7 @@
 //   * one wave computes one state from its own inputs, with the same instructions whatever the batch: a state's outputs depend
 //     on that state only, not on the batch size, its position in it or its neighbours, and are the same bits from launch to
 //     launch.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+#include "bf16x3.h"     // split3, bf16x8, bf16x4
 
 // Activations in LDS: a row of X3_ROW bf16 per position = the hi, mid and lo planes of its 32 channels (channel innermost: a
 // lane's eight consecutive k of one MFMA step are eight channels at one tap, one 16-byte read per plane) and 8 bf16 of
@@ -28,13 +27,6 @@ static_assert((144 * X3_ROW * 2) % 16 == 0, "input board aligned");
 // one workgroup of four waves per CU: 123 KB of the 160 KB
 constexpr int X3_PLANES = 18 * 3 * 64 * 8;                   // bf16 per convolution in the prepared planes: [step][plane][lane][8]
 static_assert(2 * X3_PLANES / 2 == TM_VALUENET_PREPARED_X3, "planes buffer");
-
-__device__ __forceinline__ void split3(float x, __bf16& hi, __bf16& mid, __bf16& lo) {
-    hi = (__bf16)x;
-    const float r1 = x - (float)hi;
-    mid = (__bf16)r1;
-    lo = (__bf16)(r1 - (float)mid);
-}
 
 // conv2 / conv3 weights as bf16 planes in the A-operand order of v_mfma_f32_32x32x16_bf16: for step s of the 18 (16 k each,
 // k = tap * 32 + ci, so tap = s / 2 and ci = 16 (s % 2) + 8 (l >> 5) + j) lane l holds W[co = l & 31][ci][tap] in element

@@ -2,11 +2,14 @@
 BASELINE configs[4]): conv4x4(1->32) -> LeakyReLU -> conv4x4(32->32) -> LeakyReLU -> flatten -> FC 128 -> LeakyReLU ->
 FC `atoms` -> softmax, on the reference's 22 x 10 input (the two rows that are hidden today included: the reference's
 network was never moved to the 20-row engine, `convOutShape((22, 10), ...)` is hard-coded at
-model_distributional.py:27).  Same module names, so `state_dict`s are interchangeable.  Two back ends, as model.Model_VV:
-  * "hip"   - csrc/distnet.hip: hand-written gfx950 kernels on the fp32 matrix cores (wave-per-state convolutions, a batched
-              FC + softmax kernel), bit-identical to oracle/distnet_oracle.c's fma chains, driven by the native launch loop
-              (csrc/search.hip) when it is the leaf evaluator of DistValueSim;
-  * "torch" - PyTorch-ROCm ops (MIOpen / rocBLAS): training (`loss`) and a cross-check.
+model_distributional.py:27).  Same module names, so `state_dict`s are interchangeable.  Back ends, as model.Model_VV:
+  * "hip"        - csrc/distnet.hip: hand-written gfx950 kernels on the fp32 matrix cores (wave-per-state convolutions, a
+                   batched FC + softmax kernel), bit-identical to oracle/distnet_oracle.c's fma chains, driven by the native
+                   launch loop (csrc/search.hip) when it is the leaf evaluator of DistValueSim;
+  * "hip_bf16x3" - csrc/distnet_x3.inc: conv2 on the bf16 matrix cores with every operand split into three bf16 planes (six
+                   plane products, fp32 accumulation), the rest as "hip": within 1e-6 relative of the
+                   reference, not bit-equal to "hip" (opt-in);
+  * "torch"      - PyTorch-ROCm ops (MIOpen / rocBLAS): training (`loss`) and a cross-check.
 The distribution arithmetic around it is in csrc/tree.hip (wave_dist_front / wave_dist_back)."""
 from collections import OrderedDict
 
@@ -17,6 +20,8 @@ import torch.nn.functional as F
 PARAM_ORDER = ["seq.conv1.weight", "seq.conv1.bias", "seq.conv2.weight", "seq.conv2.bias", "seq.fc1.weight", "seq.fc1.bias",
                "seq.fc_v.weight", "seq.fc_v.bias"]
 PREPARED = 278528       # TM_DISTNET_PREPARED
+PREPARED_X3 = 24576     # TM_DISTNET_PREPARED_X3: floats of tm_distnet_prepare_x3's bf16 planes
+HIP_BACKENDS = ("hip", "hip_bf16x3")    # the backends the native search loop (search.hip) runs
 SCRATCH = 2048          # TM_DISTNET_SCRATCH
 ROW = 64                # TM_DIST_ROW
 
@@ -57,7 +62,7 @@ class Model_Dist:
         self.atoms = int(atoms)
         self.model = Net(atoms=atoms).to(self.device).eval()
         self.backend = backend or ("hip" if self.device.type == "cuda" else "torch")
-        if self.backend == "hip" and not (0 < self.atoms <= ROW):
+        if self.backend in HIP_BACKENDS and not (0 < self.atoms <= ROW):
             raise ValueError("the HIP head holds 1..64 atoms")
         self._flat = self._prepared = self._scratch = None
 
@@ -65,7 +70,8 @@ class Model_Dist:
         self.model.train(mode)
 
     def weights_changed(self):
-        """call after the parameters were written (an optimiser step, load_state_dict): the HIP operand streams are rebuilt"""
+        """call after the parameters were written (an optimiser step, load_state_dict): the HIP operand streams (and the
+        "hip_bf16x3" planes, which live in the same buffer) are rebuilt"""
         self._flat = self._prepared = None
 
     def flat_params(self):
@@ -86,14 +92,31 @@ class Model_Dist:
         assert off == flat.numel()
         self.weights_changed()
 
+    def _prepared_x3(self):
+        """"hip_bf16x3": one buffer of PREPARED + PREPARED_X3 floats, tm_distnet_prepare's operand streams (fc1 runs on them)
+        followed by tm_distnet_prepare_x3's planes - the layout tm_search_run takes under TM_VALUENET_BF16X3.  It lives in
+        _prepared, so everything that invalidates the fp32 streams (weights_changed) invalidates the planes."""
+        from . import _lib
+        from .store import _p, _stream
+        if self._prepared is None or self._prepared.numel() < PREPARED + PREPARED_X3:
+            P = self.flat_params()
+            prep = torch.empty(PREPARED + PREPARED_X3, dtype=torch.float32, device=self.device)
+            _lib.check(_lib.lib().tm_distnet_prepare(_p(P), _p(prep), _stream()), "tm_distnet_prepare")
+            _lib.check(_lib.lib().tm_distnet_prepare_x3(_p(P), _p(prep[PREPARED:]), _stream()), "tm_distnet_prepare_x3")
+            self._prepared = prep
+        return self._prepared
+
     @torch.no_grad()
     def hip_buffers(self, n_states):
-        """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip)."""
+        """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip); for
+        "hip_bf16x3" the prepared buffer holds the planes behind the streams (tm_search_set_valuenet)."""
         from . import _lib
         from .store import _p, _stream
         if self._scratch is None or self._scratch.shape[0] < n_states:
             self._scratch = torch.empty(n_states, SCRATCH, dtype=torch.float32, device=self.device)
         P = self.flat_params()
+        if self.backend == "hip_bf16x3":
+            return _p(P), _p(self._prepared_x3()), _p(self._scratch)
         if self._prepared is None:
             self._prepared = torch.empty(PREPARED, dtype=torch.float32, device=self.device)
             _lib.check(_lib.lib().tm_distnet_prepare(_p(P), _p(self._prepared), _stream()), "tm_distnet_prepare")
@@ -113,6 +136,12 @@ class Model_Dist:
             st = states.reshape(B, 200).to(torch.int8).contiguous()
             _lib.check(_lib.lib().tm_distnet_forward(P, prep, _p(st), B, self.atoms, _p(out), out.stride(0), scr, _stream()),
                        "tm_distnet_forward")
+        elif self.backend == "hip_bf16x3":
+            P, _, scr = self.hip_buffers(B)
+            prep = self._prepared_x3()
+            st = states.reshape(B, 200).to(torch.int8).contiguous()
+            _lib.check(_lib.lib().tm_distnet_forward_x3(P, _p(prep), _p(prep[PREPARED:]), _p(st), B, self.atoms, _p(out),
+                                                        out.stride(0), scr, _stream()), "tm_distnet_forward_x3")
         else:
             x = torch.zeros(B, 1, 22, 10, dtype=torch.float32, device=self.device)
             x[:, 0, 2:, :] = states.reshape(B, 20, 10).float()   # the reference's net sees 22 rows (model_distributional.py:27)
@@ -121,18 +150,23 @@ class Model_Dist:
 
     @torch.no_grad()
     def inference_requests(self, store):
-        """Evaluate a TreeStore's pending leaf requests into its eval_dist (fused render + forward, HIP back end only)."""
+        """Evaluate a TreeStore's pending leaf requests into its eval_dist (fused render + forward, HIP back ends only)."""
         import ctypes as C
         from . import _lib
-        from .store import _stream
+        from .store import _p, _stream
         P, prep, scr = self.hip_buffers(store.n_games)
+        if self.backend == "hip_bf16x3":
+            prep = self._prepared_x3()
+            _lib.check(_lib.lib().tm_distnet_forward_requests_x3(P, _p(prep), _p(prep[PREPARED:]), C.byref(store.s), scr,
+                                                                 _stream()), "tm_distnet_forward_requests_x3")
+            return
         _lib.check(_lib.lib().tm_distnet_forward_requests(P, prep, C.byref(store.s), scr, _stream()), "tm_distnet_forward_requests")
 
     @torch.no_grad()
     def inference(self, batch):
         """Reference signature (model_distributional.py:100-107): float array [B,1,22,10] -> [dist [B, atoms]] numpy."""
         b = torch.as_tensor(batch, dtype=torch.float32, device=self.device)
-        if self.backend == "hip" and bool((b[:, 0, :2] == 0).all().item()):
+        if self.backend in HIP_BACKENDS and bool((b[:, 0, :2] == 0).all().item()):
             out = self.inference_device(b[:, 0, 2:, :].reshape(b.shape[0], 200).to(torch.int8))
             return [out[:, :self.atoms].cpu().numpy()]
         return [self.model(b).cpu().numpy()]     # something in the two hidden rows: only the torch ops take 22 rows

@@ -198,7 +198,7 @@ class TreeStore:
             P, prep, scr = model.hip_buffers(self.n_games * self.eval_slots)
             # the version of the weights the evaluator runs on: what was filed per observation under another one is not used
             self.L.tm_search_set_epoch(h, int(getattr(model, "weights_epoch", 0)))
-            # the value net's backend (TM_VALUENET_FP32 / TM_VALUENET_BF16X3; the distributional head has only the first)
+            # the evaluator's backend, the value net's or the distributional head's (TM_VALUENET_FP32 / TM_VALUENET_BF16X3)
             _lib.check(self.L.tm_search_set_valuenet(h, 1 if getattr(model, "backend", "hip") == "hip_bf16x3" else 0),
                        "tm_search_set_valuenet")
         _lib.check(self.L.tm_search_run(h, int(sims), P, prep, scr, _stream()), "tm_search_run")
