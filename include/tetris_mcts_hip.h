@@ -395,6 +395,12 @@ int tm_valuenet_forward_requests(const float *params, const float *prepared, con
                                  void *stream);
 int tm_valuenet_forward_plain(const float *params, const int8_t *states, int n, float *v, float *var, float *scratch,
                               void *stream);
+/* How the matrix-core path's fc1 kernel deals its work (host arithmetic only, callable without a GPU; the kernel and its
+ * launch use the same formula): `requests` states make ceil(requests / rows) tiles of `parts` parts each; the items (tile,
+ * part) are numbered tiles fastest, a tile's parts a multiple of eight apart (valuenet.hip fc1_item: workgroups go to the XCDs
+ * round robin); workgroup b of `grid` takes items b, b + grid, ...  Writes the workgroup's (tile, part) pairs to
+ * items[0 .. 2 * cap) and returns how many it takes (possibly more than cap); -1 on arguments that make no grid. */
+int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t *items, int cap);
 /* The split-precision backend (valuenet_x3.inc; numerics contract in DESIGN.md section 3.3): conv2 and conv3 on the bf16 matrix
  * cores, every operand split into three bf16 planes, six plane products per fp32 product, fp32 accumulation; conv1, fc1 and
  * the output layer as in tm_valuenet_forward.  Within 1e-4 of the reference, not bit-equal to the fp32 path; a state's outputs

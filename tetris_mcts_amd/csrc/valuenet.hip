@@ -254,7 +254,7 @@ __device__ __forceinline__ void render_obs(uint32_t kw, int lane, float* x0) {
 // Activations are staged through LDS in KC-wide K chunks (requested two chunks ahead), the B operands read from LDS a group
 // of steps ahead, the weights held in a ring of WRING groups.  Two shapes, the same arithmetic and the same bits (every
 // output element is its own k-ordered chain whatever the tiling):
-//   <2, 4, 256, 6>  32-state tiles, four workgroups of 64 units each, 152 registers, one workgroup per CU: the single-leaf
+//   <2, 4, 256, 6>  32-state tiles, four workgroups of 64 units each, 172 registers, one workgroup per CU: the single-leaf
 //                   kinds, whose dense request list leaves 60-100 tiles a launch - a latency problem (r03 gave a tile two
 //                   workgroups of 128 units: half of the CUs without a workgroup, 40 us whatever the number of tiles; r04 calls
 //                   B-G: 51 -> 33 us);
@@ -270,14 +270,46 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // anybody.  `cnt`: one int per tile (the first pad word of the scratch row of the tile's first state), zeroed by k_vn_conv at
 // the start of every evaluation (the kernel also leaves it zero).
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+// The grid is one of work ITEMS, not of tiles: an item = (tile, part) of the tiles that exist, `tiles` = ceil(requests / ROWS).
+// Workgroup b of a grid of `grid` takes items b, b + grid, ...: any two workgroups' shares differ by at most one item, and the
+// launch never holds more workgroups than the chip keeps resident (vn_fc1_launch), so nothing queues behind a workgroup that only
+// finds out it has no work.  (Until this the grid was the request SLOTS' tiles x NY: 512 workgroups for the headline's 4096 slots,
+// 236 of them with work at its 1 867 requests a launch, the other 276 dispatched in between to read the list's counters and leave.)
+// The numbering of the items decides where a tile's parts run, and that is worth more than the dead workgroups (measured: parts
+// 59 workgroups apart, on four different XCDs, lost 1.2 us a launch where the dead workgroups were to win one): workgroups go to the
+// XCDs round robin, and a tile's NY parts read the same ROWS rows of activations - on ONE XCD they come from memory once and from
+// that XCD's L2 three times.  So tiles run fastest, over the whole multiples of FC1_XCDS tiles (item i = part * t8 + tile: a tile's
+// parts are t8 = 0 (mod 8) workgroups apart - one XCD, and not on neighbouring CUs at the same moment, which measured + 0.9 us),
+// and the up to seven tiles left over follow, tiles fastest again.  The one formula, host and device (tm_fc1_deal exports it for
+// tests/test_fc1_items.py):
+constexpr int FC1_XCDS = 8;
+struct Fc1Item { int tile, part; };
+__host__ __device__ constexpr int fc1_item_count(int requests, int rows, int parts) {
+    return requests > 0 ? (requests + rows - 1) / rows * parts : 0;
+}
+// k-th item of workgroup b (valid while fc1_item_index(...) < fc1_item_count(...))
+__host__ __device__ constexpr int fc1_item_index(int b, int grid, int k) { return b + k * grid; }
+__host__ __device__ constexpr Fc1Item fc1_item(int index, int requests, int rows, int parts) {
+    const int tiles = (requests + rows - 1) / rows, t8 = tiles / FC1_XCDS * FC1_XCDS, bulk = t8 * parts;
+    if (index < bulk) return Fc1Item{index % t8, index / t8};
+    const int rest = tiles - t8, j = index - bulk;
+    return Fc1Item{t8 + j % rest, j / rest};
+}
 #ifdef TM_FC1_TIMELINE   // (measurement builds, scripts/fc1_timeline.py: thread 0's s_memrealtime at the kernel's stations, in the pad words of
-                         //  scratch row s0 + blockIdx.y)
-#define FC1_STAMP(i) do { if (threadIdx.x == 0 && s0 + (int)blockIdx.y < n) reinterpret_cast<int*>(hout)[(size_t)(s0 + blockIdx.y) * hstride + HID + 1 + (i)] = (int)__builtin_amdgcn_s_memrealtime(); } while (0)
+                         //  scratch row s0 + part)
+#define FC1_STAMP(i) do { if (tid == 0 && s0 + part < n) reinterpret_cast<int*>(hout)[(size_t)(s0 + part) * hstride + HID + 1 + (i)] = (int)__builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define FC1_STAMP(i) do { } while (0)
 #endif
+// (a call, not inline: inside k_vn_fc1's item loop the compiler otherwise hoists tm_exp's twenty-odd 64-bit constants out of the loop
+//  and keeps them in registers through the K loop - the 64-state shape then no longer fits the 128 registers of two workgroups a CU)
+__device__ __noinline__ float fc1_sigmoid(float a) {
+    const double e = tm_exp(-(double)a);
+    return (float)(1.0 / (1.0 + e));
+}
+// (waves per SIMD: four for the 64-state shape - two workgroups a CU, at most 128 registers - two for the other)
 template <int RT, int NY, int KC, int WRING, int PF>
-__global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, const float* __restrict__ prep,
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 4 : 2))) void k_vn_fc1(const float* __restrict__ P, const float* __restrict__ prep,
                                                 const float* __restrict__ a3, int a3stride, int n,
                                                 float* __restrict__ hout, int hstride,
                                                 ReqList rq, int32_t* __restrict__ cnt, int cnt_stride,
@@ -289,15 +321,32 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
     __shared__ __attribute__((aligned(16))) float bt[2][BT];
     __shared__ int row_slot[ROWS];        // request mode: where row j of the tile delivers its outputs
     __shared__ int last_flag;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, kk = lane >> 4, l15 = lane & 15;
-    const int s0 = blockIdx.x * ROWS;
+    // the output layer's operands - its 2 x 256 weights, two biases and the four affine constants, 518 consecutive parameters -
+    // fetched by every workgroup under the K loop's last chunk, so that the tile's last workgroup runs its chains on LDS alone
+    constexpr int WO = 2 * HID + 6;
+    static_assert(OFF_FOB == OFF_FOW + 2 * HID && OFF_UB == OFF_FOB + 2 && OFF_LB == OFF_UB + 2, "the output layer's parameters are consecutive");
+    __shared__ __attribute__((aligned(16))) float wo[(WO + 3) / 4 * 4];
+    const int lane = threadIdx.x & 63;
+    // rows = dense positions of the request list: its length decides how many items there are (a fixed trip count from here on; a
+    // workgroup past the last item leaves before it has asked the memory system for anything else)
+    int incl = 0;
+    if (rq.list) {
+        incl = req_prefix(rq, lane, n);
+        n = __builtin_amdgcn_readfirstlane(n);      // (the same in every lane: say so, or the items' tile, part and s0 are vector arithmetic)
+    }
+    const int n_items = fc1_item_count(n, ROWS, NY);
+    for (int item = fc1_item_index(blockIdx.x, gridDim.x, 0), kth = 0; item < n_items; item = fc1_item_index(blockIdx.x, gridDim.x, ++kth)) {
+    // (the thread's index behind an empty asm: nothing derived from it is loop-invariant for the compiler, which otherwise keeps
+    //  some seventy registers of hoisted addresses alive across the items - 233 registers against 163 for the single-leaf shape,
+    //  172 against 106 for the other, which then no longer fits two workgroups a CU)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int w = tid >> 6, lane = tid & 63, kk = lane >> 4, l15 = lane & 15;     // (`lane` shadows the one above on purpose)
+    const Fc1Item it = fc1_item(item, n, ROWS, NY);
+    const int tile = it.tile, part = it.part, s0 = tile * ROWS;
     int my_slot = 0;
     FC1_STAMP(0);
     if (rq.list) {
-        // rows = dense positions of the request list; a tile past its end has nothing to do (all of its workgroups leave,
-        // before they have asked the memory system for anything else)
-        const int incl = req_prefix(rq, lane, n);
-        if (s0 >= n) return;
         if (w == 0) {
             // lane j resolves row j (all list entries in flight together; the slot is needed after the K loop only)
             const int p = min(s0 + (lane & (ROWS - 1)), n - 1);
@@ -308,7 +357,7 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
             my_slot = rq.list[(sg + rq.segs * (d / rq.slots)) * rq.slots + d % rq.slots].x;
         }
     }
-    const int ht = blockIdx.y * HT + (w % HT);       // 16-row hidden tile 0..15
+    const int ht = part * HT + (w % HT);             // 16-row hidden tile 0..15
     const int st0 = (w / HT) * NST;                   // this wave's first 16-state tile
     const float4* W = reinterpret_cast<const float4*>(prep + PREP_W1) + (size_t)ht * 112 * 64 + lane;
     f32x4 acc[NST];
@@ -329,12 +378,14 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
         for (int q = 0; q < QPG; ++q) wring[G % WRING][q] = W[((size_t)G * QPG + q) * 64];
     };
     // The first weights (and the biases above) are requested BEFORE the activations: a wave's loads return in order, and the first
-    // MFMA needs both.  (Requested before the request list's counters are read, by every workgroup of the grid: 34.4 us against 31.5.)
+    // MFMA needs both.  (Which weights is a matter of the item's part, and the item numbering needs the number of tiles: they
+    // cannot go out before the request list's counters are back.  On the former grid of slots, where blockIdx.y was the part,
+    // every workgroup asking before it read the counters measured 34.4 us against 31.5.)
 #pragma unroll
     for (int G0 = 0; G0 < WRING - 1; ++G0) wload(G0);
     // staging: ROWS rows x KC floats per chunk, KC/4 threads per row, 16-byte pieces
     constexpr int TPR = KC / 4, RPP = 512 / TPR, NPASS = ROWS / RPP;
-    const int row0 = threadIdx.x / TPR, c4 = (threadIdx.x % TPR) * 4;
+    const int row0 = tid / TPR, c4 = (tid % TPR) * 4;
     // The activations of chunk c + 2 are requested while chunk c is multiplied (two register sets): a tile's rows were written
     // by convolution waves all over the chip, so they come from beyond this XCD's L2, and one chunk of MFMAs (under 2 us) does
     // not cover that round trip.  (Kept as a select: a plain 16-byte copy into the array sent the whole array to scratch
@@ -359,6 +410,7 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
             *reinterpret_cast<float4*>(&bt[chunk & 1][(row0 + RPP * i) * PITCH + c4]) = st[chunk % PF][i];
     };
     static_assert(PF >= 2 && PF <= A3 / KC, "chunks in flight");
+    float wo_r[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < PF; ++c) gload(c);
     FC1_STAMP(1);
@@ -368,6 +420,11 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
         if (c + PF < NCH) gload(c + PF);         // into the register set chunk c's staging has left (lstore(c): before the last barrier)
+        if (c == NCH - 1 && tid < (WO + 3) / 4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (4 * tid + r < WO) wo_r[r] = P[OFF_FOW + 4 * tid + r];
+        }
         const float* b0 = &bt[c & 1][(16 * st0 + l15) * PITCH + kk];
         // The B operands (LDS) of the next group of MFMA steps are requested while this group's MFMAs issue (r03 - r04 call C:
         // the compiler's own order was read, wait for it, two MFMAs, read ...: an LDS round trip per pair of MFMAs, 45 us per
@@ -424,21 +481,22 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
         *reinterpret_cast<f32x4v*>(&hs[row * HS_PITCH + i0]) = o0;
     }
     if (rq.list && w == 0 && lane < ROWS) row_slot[lane] = my_slot;      // (the list entry has had the whole K loop to arrive)
+    if (tid < (WO + 3) / 4) *reinterpret_cast<float4*>(&wo[4 * tid]) = make_float4(wo_r[0], wo_r[1], wo_r[2], wo_r[3]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     FC1_STAMP(4);
-    if (threadIdx.x == 0) {
+    if (tid == 0) {
         // (relaxed on purpose: the hand-off is carried by the write-through sc1 stores + s_waitcnt before the arrival and the sc1
         // loads after it - MI355X_MICROARCH.md's measured form.  With __ATOMIC_ACQ_REL here the compiler adds buffer_wbl2 sc1 /
         // buffer_inv sc1 around the atomic: 33.4 -> 35.8 us per launch, r04; tests/test_gpu_valuenet.py holds the folded output
         // layer to the oracle's bits on every run)
-        const int old = __hip_atomic_fetch_add(&cnt[(size_t)blockIdx.x * cnt_stride], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int old = __hip_atomic_fetch_add(&cnt[(size_t)tile * cnt_stride], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         last_flag = old;
-        if (old == NY - 1) __hip_atomic_store(&cnt[(size_t)blockIdx.x * cnt_stride], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next launch
+        if (old == NY - 1) __hip_atomic_store(&cnt[(size_t)tile * cnt_stride], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next launch
     }
     __syncthreads();
     FC1_STAMP(5);
-    if (last_flag != NY - 1) return;
+    if (last_flag == NY - 1) {
     // ---- this workgroup arrived last: the other parts of h past the caches (ROWS states x (256 - UNITS) units) ----
     {
         // all of a thread's 16-byte loads in flight together, one wait (the memory clobbers keep the LDS stores behind it)
@@ -447,16 +505,16 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
         f32x4v wv[CNT];
 #pragma unroll
         for (int i = 0; i < CNT; ++i) {
-            const int e = i * 512 + threadIdx.x, row = e / OQ, c = (e % OQ) * 4;
-            const int col = c < (int)blockIdx.y * UNITS ? c : c + UNITS;      // skipping this workgroup's own units
+            const int e = i * 512 + tid, row = e / OQ, c = (e % OQ) * 4;
+            const int col = c < part * UNITS ? c : c + UNITS;      // skipping this workgroup's own units
             const float* src = hout + (size_t)(s0 + (s0 + row < n ? row : 0)) * hstride + col;
             asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(wv[i]) : "v"(src) : "memory");
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
         for (int i = 0; i < CNT; ++i) {
-            const int e = i * 512 + threadIdx.x, row = e / OQ, c = (e % OQ) * 4;
-            const int col = c < (int)blockIdx.y * UNITS ? c : c + UNITS;
+            const int e = i * 512 + tid, row = e / OQ, c = (e % OQ) * 4;
+            const int col = c < part * UNITS ? c : c + UNITS;
             f32x4v t = wv[i];
             asm volatile("" : "+v"(t));          // (a use the compiler cannot hoist above the wait)
             if (s0 + row < n) *reinterpret_cast<f32x4v*>(&hs[row * HS_PITCH + col]) = t;
@@ -464,39 +522,35 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
     }
     __syncthreads();
     FC1_STAMP(6);
-    if (threadIdx.x < 2 * ROWS) {
+    if (tid < 2 * ROWS) {
         // one chain per lane: state j = t >> 1, output o = t & 1 (k_fc_out's thread t = 2 s + o); fma over the 256 hidden units
         // in order
-        const int j = threadIdx.x >> 1, o = threadIdx.x & 1;
+        const int j = tid >> 1, o = tid & 1;
         int sidx = s0 + j;
         const bool live = sidx < n;
         if (rq.list) sidx = row_slot[j];          // (written by wave 0 before the barrier above)
         if (live) {
-            float a = P[OFF_FOB + o];
-            const float* x = &hs[j * HS_PITCH];
-            const float* wr = P + OFF_FOW + o * HID;
+            float a = wo[2 * HID + o];
             // the same chain in the same order, its operands fetched four at a time (r06, scripts/fc1_timeline.py: this loop was
             // 4.5 us of the tile's last workgroup - a scalar LDS read and a scalar global read in front of every fma)
-            if ((reinterpret_cast<uintptr_t>(wr) & 15) == 0) {
-                const float4* x4 = reinterpret_cast<const float4*>(x);
-                const float4* w4 = reinterpret_cast<const float4*>(wr);
+            const float4* x4 = reinterpret_cast<const float4*>(&hs[j * HS_PITCH]);
+            const float4* w4 = reinterpret_cast<const float4*>(&wo[o * HID]);
 #pragma unroll 8
-                for (int i = 0; i < HID / 4; ++i) {
-                    const float4 xv = x4[i], wv = w4[i];
-                    a = fmaf(xv.x, wv.x, a); a = fmaf(xv.y, wv.y, a); a = fmaf(xv.z, wv.z, a); a = fmaf(xv.w, wv.w, a);
-                }
-            } else {
-#pragma unroll 8
-                for (int i = 0; i < HID; ++i) a = fmaf(x[i], wr[i], a);
+            for (int i = 0; i < HID / 4; ++i) {
+                const float4 xv = x4[i], wv = w4[i];
+                a = fmaf(xv.x, wv.x, a); a = fmaf(xv.y, wv.y, a); a = fmaf(xv.z, wv.z, a); a = fmaf(xv.w, wv.w, a);
             }
-            const double e = tm_exp(-(double)a);
-            const float sg = (float)(1.0 / (1.0 + e));
-            const float tt = sg * P[OFF_UB + o];
-            const float res = tt + P[OFF_LB + o];
+            const float sg = fc1_sigmoid(a);
+            const float tt = sg * wo[2 * HID + 2 + o];
+            const float res = tt + wo[2 * HID + 4 + o];
             if (o == 0) v_out[sidx] = res; else var_out[sidx] = res;
         }
     }
     FC1_STAMP(7);
+    }   // (arrived last)
+    // a further item stages into bt[] and resolves into row_slot[]: not before the output layer above has read them
+    if (fc1_item_index(blockIdx.x, gridDim.x, kth + 1) < n_items) __syncthreads();
+    }   // (items)
 }
 
 #include "valuenet_x3.inc"
@@ -504,6 +558,39 @@ __global__ __launch_bounds__(512) void k_vn_fc1(const float* __restrict__ P, con
 }  // namespace tmcts_vn
 
 using namespace tmcts_vn;
+
+// compute units of the current device (asked once: every device of a process is the same part)
+static int vn_compute_units() {
+    static std::once_flag once;
+    static int cus = 0;
+    std::call_once(once, [&] {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
+    });
+    return cus;
+}
+
+// k_vn_fc1 over rows [0, n) of the scratch (request mode: n = the request slots, the kernel reads the list's length itself).
+// The grid: the items there can be, and no more workgroups than stay resident at once - one a CU for the 152-register shape,
+// two for the other (116 registers).
+template <int RT, int NY, int KC, int WRING, int PF, int WG_PER_CU>
+static int vn_fc1_launch_shape(const float* P, const float* prepared, const ReqList& rq, int n, float* v, float* var,
+                               float* scratch, hipStream_t stream) {
+    constexpr int SS = TM_VALUENET_SCRATCH_MFMA, ROWS = 16 * RT;
+    const int cus = vn_compute_units();
+    if (cus <= 0) return (int)hipErrorInvalidDevice;
+    const int items = fc1_item_count(n, ROWS, NY), resident = cus * WG_PER_CU;
+    hipLaunchKernelGGL((k_vn_fc1<RT, NY, KC, WRING, PF>), dim3(items < resident ? items : resident), dim3(512), 0, stream, P,
+                       prepared, scratch, SS, n, scratch + A3, SS, rq, reinterpret_cast<int32_t*>(scratch + A3 + HID), ROWS * SS,
+                       v, var);
+    return (int)hipGetLastError();
+}
+static int vn_fc1_launch(const float* P, const float* prepared, const ReqList& rq, int n, float* v, float* var, float* scratch,
+                         hipStream_t stream) {
+    if (n >= 8192)      // (request slots: the leaf-parallel kinds' seven per game)
+        return vn_fc1_launch_shape<4, 4, 128, 3, 2, 2>(P, prepared, rq, n, v, var, scratch, stream);
+    return vn_fc1_launch_shape<2, 4, 256, 6, 2, 1>(P, prepared, rq, n, v, var, scratch, stream);
+}
 
 extern "C" {
 
@@ -566,13 +653,7 @@ static int vn_forward_impl(const float* P, const float* prepared, const __bf16* 
         hipLaunchKernelGGL(k_vn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, obs_key, rq,
                            max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
     }
-    if (n >= 8192)      // (request slots: the leaf-parallel kinds' seven per game)
-        hipLaunchKernelGGL((k_vn_fc1<4, 4, 128, 3, 2>), dim3((n + 63) / 64, 4), dim3(512), 0, stream, P, prepared, scratch, SS, n,
-                           scratch + A3, SS, rq, reinterpret_cast<int32_t*>(scratch + A3 + HID), 64 * SS, v, var);
-    else
-        hipLaunchKernelGGL((k_vn_fc1<2, 4, 256, 6, 2>), dim3((n + 31) / 32, 4), dim3(512), 0, stream, P, prepared, scratch, SS, n,
-                           scratch + A3, SS, rq, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS, v, var);
-    return (int)hipGetLastError();
+    return vn_fc1_launch(P, prepared, rq, n, v, var, scratch, stream);
 }
 
 // matrix-core path; prepared: tm_valuenet_prepare output; scratch: n x TM_VALUENET_SCRATCH_MFMA floats
@@ -588,6 +669,20 @@ int tm_valuenet_forward_requests(const float* P, const float* prepared, const tm
     const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
     return vn_forward_impl(P, prepared, nullptr, nullptr, s->obs_key, rq, s->max_nodes,
                            s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
+}
+
+// k_vn_fc1's item dealing (host arithmetic only: callable without a GPU): the items of workgroup b of a grid of `grid` workgroups
+// at `requests` requests, tiles of `rows` states in `parts` parts - (tile, part) pairs into items[0 .. 2 * cap); returns how many
+// the workgroup takes (they may be more than cap), -1 on arguments that make no grid
+int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t* items, int cap) {
+    if (requests < 0 || rows <= 0 || parts <= 0 || grid <= 0 || b < 0 || b >= grid) return -1;
+    const int n_items = fc1_item_count(requests, rows, parts);
+    int k = 0;
+    for (int i = fc1_item_index(b, grid, 0); i < n_items; i = fc1_item_index(b, grid, ++k)) {
+        const Fc1Item it = fc1_item(i, requests, rows, parts);
+        if (items && k < cap) { items[2 * k] = it.tile; items[2 * k + 1] = it.part; }
+    }
+    return k;
 }
 
 // ---- the split-precision backend (valuenet_x3.inc) ----
