@@ -766,8 +766,68 @@ def gen_training():
     print("ref_training.npz: losses", losses, "grad norms", gnorms, "val", val)
 
 
+def gen_heads_trained():
+    """ref_heads_trained.npz: the reference's own Nets at trained-scale weights, CPU, one thread (tests/heads_numerics.py builds
+    the boards; tests/test_heads_accuracy.py holds the helper's torch forwards to these once).
+      * model/model_vv.py `Net` under the committed r06 checkpoint on ~300 boards of every family: fp32 output and the output
+        of `.double()` (the weights themselves stay in the checkpoint);
+      * model/model_distributional.py `Net` at 50 atoms after a short fit by `Model_Dist.train` (its own loss, :81-93, its own
+        Adam with the step size raised to 1e-3 so that 400 steps are enough) towards peaked targets - 0.97 on one atom chosen by
+        the board's filled cells, the rest spread evenly - so that the logit spread comes from every layer: the fitted
+        state_dict (fc1.weight rounded to 12 significant bits to keep the file under 1 MiB), fp32 and fp64 log_prob on the same
+        boards."""
+    ref_shims.install()
+    _legacy_torch_overloads()
+    import torch
+    torch.set_num_threads(1)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import heads_numerics as H
+    from model.model_vv import Net as VNet
+    from model.model_distributional import Model_Dist
+    boards = H.golden_boards()
+    out = {"boards": boards, "torch_version": np.array(torch.__version__)}
+    net = VNet().eval()
+    ck = torch.load(os.path.join(H.CHECKPOINTS, "value_net_online_r06.pt"), map_location="cpu")
+    net.load_state_dict(ck["model_state_dict"])
+    x = H.vn_input(boards)
+    with torch.no_grad():
+        out["vn_out32"] = net(x).numpy()
+        out["vn_out64"] = net.double()(x.double()).numpy()
+    torch.manual_seed(0)
+    m = Model_Dist(atoms=50, use_cuda=False)
+    for g in m.optimizer.param_groups:
+        g["lr"] = 1e-3
+    m.training(True)
+    train_boards = np.concatenate([boards, H.ternary_boards(212, 7)])
+    tx = H.dn_input(train_boards).numpy()
+    n = tx.shape[0]
+    peak = ((train_boards != 0).reshape(n, -1).sum(1) * 7 + (train_boards == -1).reshape(n, -1).sum(1)) % 50
+    target = np.full((n, 50), 0.03 / 49, np.float32)
+    target[np.arange(n), peak] = 0.97
+    rng = np.random.default_rng(13)
+    for it in range(400):
+        idx = rng.choice(n, 64, replace=False)
+        r = m.train([tx[idx], target[idx], np.ones((64, 1), np.float32)], g_norm_warn=1e30)
+    m.training(False)
+    x = H.dn_input(boards)
+    with torch.no_grad():
+        # the file's size: fc1.weight (1 MB of the 1.1 MB of weights; an fp32 layer in every backend) is rounded to 12
+        # significant bits BEFORE the outputs are taken, so that it compresses; the split-precision layer keeps every bit
+        w = m.model.state_dict()["seq.fc1.weight"]
+        w.copy_(((w.view(torch.int32) + 0x800) & ~0xFFF).view(torch.float32))
+        out["dn_lp32"] = m.model.log_prob(x).numpy()
+        sd = {"dn_" + k.replace(".", "__"): v.numpy().copy() for k, v in m.model.state_dict().items()}
+        m.model.double()
+        out["dn_lp64"] = m.model.log_prob(x.double()).numpy()
+    out.update(sd)
+    np.savez_compressed(os.path.join(OUT, "ref_heads_trained.npz"), **out)
+    lg = out["dn_lp64"]
+    print("ref_heads_trained.npz: %d boards, last loss %.4f, mean log p spread %.1f, size %d" % (
+        len(boards), r["loss"], float((lg.max(1) - lg.min(1)).mean()), os.path.getsize(os.path.join(OUT, "ref_heads_trained.npz"))))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["uct", "uct_live", "valuenet", "agents", "cppagent", "mixture", "vanilla", "online", "online_py", "agents_env", "training", "vanillac", "dist", "distnet", "treeagent", "distpy"]
+    which = sys.argv[1:] or ["uct", "uct_live", "valuenet", "agents", "cppagent", "mixture", "vanilla", "online", "online_py", "agents_env", "training", "vanillac", "dist", "distnet", "treeagent", "distpy", "heads_trained"]
     params = None
     if "uct" in which:
         gen_uct()
@@ -799,6 +859,8 @@ if __name__ == "__main__":
         gen_dist()
     if "distnet" in which:
         gen_distnet()
+    if "heads_trained" in which:
+        gen_heads_trained()
     if "agents" in which:
         if params is None:
             params = np.load(os.path.join(OUT, "ref_valuenet.npz"))["params"]

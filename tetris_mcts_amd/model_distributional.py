@@ -8,7 +8,8 @@ model_distributional.py:27).  Same module names, so `state_dict`s are interchang
                    launch loop (csrc/search.hip) when it is the leaf evaluator of DistValueSim;
   * "hip_bf16x3" - csrc/distnet_x3.inc: conv2 on the bf16 matrix cores with every operand split into three bf16 planes (six
                    plane products, fp32 accumulation), the rest as "hip": within 1e-6 relative of the
-                   reference, not bit-equal to "hip" (opt-in);
+                   reference at the fixture's weights (logit spread 0.3), in general log p within 8x the reference's own
+                   fp32 error against an fp64 forward (DESIGN.md section 6), not bit-equal to "hip" (opt-in);
   * "torch"      - PyTorch-ROCm ops (MIOpen / rocBLAS): training (`loss`) and a cross-check.
 The distribution arithmetic around it is in csrc/tree.hip (wave_dist_front / wave_dist_back)."""
 from collections import OrderedDict
