@@ -386,6 +386,20 @@ int tm_distpy_backup(int n_trees, int n_nodes, int bins, const int32_t *trace, c
  * Yogi.step (12 parameters x 8 launches). */
 int tm_yogi_step(float *p, const float *g, float *m, float *v, double *state, int n, double lr, double beta1, double beta2,
                  double eps, double weight_decay, void *stream);
+/* The gradient step of the value net's online fit (csrc/valuenet_fit.hip): forward of model.Net, train.batch_loss and the gradient
+ * of its MEAN with respect to the ten learnable tensors, for the minibatch rows idx[0 .. batch) of the training set (idx NULL: rows
+ * 0 .. batch-1; repeats allowed; every entry must be a valid row - the caller checks).  params / grad: 478338 floats in
+ * model.PARAM_ORDER (Yogi's flat p / g buffers as they stand); out_bounds: out_ubound[2], out_lbound[2]; states int8 [rows][200];
+ * value / variance / weight fp32 [rows] (weight read only when weighted != 0).  grad is OVERWRITTEN; loss = {mean, population std} of
+ * the per-sample losses.  workspace: tm_valuenet_fit_workspace(batch) floats, 16-byte aligned, no initial contents required.
+ * Everything is enqueued on `stream` in a sequence of launches whose shapes depend on `batch` alone: no allocation, no host
+ * synchronisation, nothing read back - capturable in a HIP graph.  Deterministic (no atomics; fixed-order partial sums).
+ * hipErrorInvalidValue, and nothing launched, for a NULL pointer (idx excepted), batch < 1 or batch > 2^20.
+ * tm_valuenet_fit_workspace is host arithmetic only (callable without a GPU): -1 for a batch that is refused. */
+long long tm_valuenet_fit_workspace(int batch);
+int tm_valuenet_fit_grad(const float *params, const float *out_bounds, const int8_t *states, const float *value,
+                         const float *variance, const float *weight, const int64_t *idx, int batch, int weighted,
+                         float variance_clip, float *grad, float *loss, float *workspace, void *stream);
 int tm_valuenet_prepare(const float *params, float *prepared, void *stream);
 int tm_valuenet_forward(const float *params, const float *prepared, const int8_t *states, int n, float *v, float *var,
                         float *scratch, void *stream);

@@ -48,6 +48,9 @@ def build_parser():
     add('--valuenet_backend', default='hip', choices=('hip', 'hip_bf16x3', 'torch'), help='[new] value net of ValueSim, '
         'ValueSimLP and ValueSimC, distributional head of DistValueSim: hip (fp32 matrix cores), hip_bf16x3 (split-precision '
         'bf16 matrix cores) or torch')
+    add('--fit_backend', default='torch', choices=('torch', 'hip'), help='[new] online mode: gradients of the value net\'s fits '
+        'through PyTorch autograd (torch) or the hand-written gfx950 forward / loss / backward kernels (hip); ValueSim, '
+        'ValueSimLP and ValueSimC (DistValueSim fits through torch only)')
     return p
 
 
@@ -87,6 +90,10 @@ def main(argv=None):
         extra['valuenet_backend'] = args.valuenet_backend
     elif args.valuenet_backend != 'hip':
         sys.exit('--valuenet_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
+    if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim'):
+        extra['fit_backend'] = args.fit_backend      # (DistValueSim refuses 'hip' itself)
+    elif args.fit_backend != 'torch':
+        sys.exit('--fit_backend applies to ValueSim, ValueSimLP and ValueSimC only')
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     agent.update_root(game)

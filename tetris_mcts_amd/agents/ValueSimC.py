@@ -71,7 +71,8 @@ class ValueSimC(ValueSim):
         """ValueSimC.py:6-14: dump the training set in the reference's np.savez layout, fit, back to inference mode."""
         if self.dump_path:
             self.dump_training_set(self.dump_path, state[:d_size], value[:d_size], variance[:d_size], visit[:d_size])
-        opts = dict(iters_per_val=100, batch_size=512, max_iters=50000, sample_replacement=True, oversampling=False)
+        opts = dict(iters_per_val=100, batch_size=512, max_iters=50000, sample_replacement=True, oversampling=False,
+                    fit_backend=self.fit_backend)
         opts.update(train_kwargs)
         res = self.model.train_data([state[:d_size], value[:d_size], variance[:d_size], visit[:d_size]], **opts)
         self.model.training(False)

@@ -204,10 +204,88 @@ def check_data_parallel_batch(batch_size, world):
                          % (batch_size, world))
 
 
+def flat_order_is_param_order(net, optimizer):
+    """Whether Yogi's flat buffers hold exactly the ten learnable tensors of model.Net in model.PARAM_ORDER - the layout
+    tm_valuenet_fit_grad reads its parameters in and writes its gradient in."""
+    from .model import PARAM_ORDER
+    named = dict(net.named_parameters())
+    want = [named.get(k) for k in PARAM_ORDER[:10]]
+    got = optimizer.flatten()["params"]
+    return (all(w is not None for w in want) and len(got) == len(want) and all(a is b for a, b in zip(got, want))
+            and not any(named[k].requires_grad for k in PARAM_ORDER[10:] if k in named))
+
+
+class HipFit:
+    """The per-fit state of fit_backend="hip": the checks (once per fit), the int8 copy of the training states, the flattened
+    targets, the output bounds and the workspace; grad(idx) is one call of tm_valuenet_fit_grad on the current stream."""
+    N_PARAMS = 478338
+
+    def __init__(self, net, optimizer, train, batch):
+        from . import _lib
+        from .model import Net
+        if len(train) != 4:
+            raise ValueError("fit_backend='hip' needs data = [states, values, variances, weights]")
+        states = train[0]
+        rows = states.shape[0]
+        if rows < 1 or states.numel() != rows * 200:
+            raise ValueError("fit_backend='hip' needs states of 20 x 10 cells a row, got shape %s" % (tuple(states.shape),))
+        if not bool(((states == states.round()) & (states.abs() <= 127)).all()):
+            raise ValueError("fit_backend='hip' reads the states as int8: they must be integers in [-127, 127]")
+        if not all(d.is_cuda and d.dtype == torch.float32 for d in train):
+            raise ValueError("fit_backend='hip' needs float32 CUDA tensors (the data is on %s)" % (states.device,))
+        if not isinstance(net, Net):
+            raise ValueError("fit_backend='hip' computes model.Net, not %s" % type(net).__name__)
+        if not (hasattr(optimizer, "fused") and optimizer.fused()):
+            raise ValueError("fit_backend='hip' writes the fused Yogi's flat gradient buffer: the optimizer must be a Yogi "
+                             "whose fused() holds (float32 parameters on one GPU in a single group)")
+        if any(t.shape[0] != rows for t in train[1:]) or any(t.numel() != rows for t in train[1:]):
+            raise ValueError("fit_backend='hip' needs one value, variance and weight a row")
+        F = optimizer.flatten()
+        if F["n"] != self.N_PARAMS or not flat_order_is_param_order(net, optimizer):
+            raise ValueError("fit_backend='hip': the optimizer's flat buffers are not the net's learnable tensors in "
+                             "model.PARAM_ORDER")
+        if batch < 1:
+            raise ValueError("fit_backend='hip' needs a batch of at least one row per rank")
+        self._lib, self.F, self.batch, self.rows, self.dev = _lib, F, batch, rows, states.device
+        self.states = states.reshape(rows, 200).to(torch.int8).contiguous()
+        self.value, self.variance, self.weight = (t.reshape(rows).contiguous() for t in train[1:])
+        self.bounds = torch.cat([net.out_ubound.detach().reshape(2), net.out_lbound.detach().reshape(2)]).float().contiguous()
+        n_ws = _lib.lib().tm_valuenet_fit_workspace(batch)
+        if n_ws < 0:
+            raise ValueError("fit_backend='hip': a batch of %d rows is refused" % batch)
+        self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
+        self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
+        self._idx_checked = False
+
+    def check_idx(self, idx):
+        """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= self.rows:
+            raise ValueError("fit_backend='hip': indices in [%d, %d] do not all name one of the %d training rows" % (lo, hi, self.rows))
+
+    def grad(self, idx, weighted):
+        """loss (a 0-d device tensor) of the rows idx (int64, every value in [0, rows)); the gradient of its mean lands in the
+        optimiser's flat buffer.  The kernels read the rows idx names without a bounds check of their own: the first call of a
+        fit that is not being captured checks the range here (one host synchronisation), and train_data's draws are indices
+        into [0, rows) by construction; a caller who changes where idx comes from between calls calls check_idx itself."""
+        if idx.dtype != torch.int64 or idx.numel() != self.batch:
+            raise ValueError("fit_backend='hip': expected %d int64 indices, got %d %s" % (self.batch, idx.numel(), idx.dtype))
+        if not self._idx_checked and not torch.cuda.is_current_stream_capturing():
+            self.check_idx(idx)
+            self._idx_checked = True
+        idx = idx.contiguous()
+        F = self.F
+        self._lib.check(self._lib.lib().tm_valuenet_fit_grad(
+            F["p"].data_ptr(), self.bounds.data_ptr(), self.states.data_ptr(), self.value.data_ptr(), self.variance.data_ptr(),
+            self.weight.data_ptr(), idx.data_ptr(), self.batch, int(bool(weighted)), float(variance_bound), F["g"].data_ptr(),
+            self.loss.data_ptr(), self.ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream), "tm_valuenet_fit_grad")
+        return self.loss[0]
+
+
 def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validation_fraction=0.1,
                sample_replacement=True, oversampling=False, weighted=True, early_stopping=True, early_stopping_patience=10,
                early_stopping_threshold=1.0, shuffle=False, max_iters=100000, grad_clip=0.0, save=None, load=None,
-               generator=None, log=True, data_parallel=True, group=None, loss_fn=None):
+               generator=None, log=True, data_parallel=True, group=None, loss_fn=None, fit_backend="torch"):
     """data = [states f32 [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (device tensors); with `loss_fn`
     (net, batch, weighted) -> (mean, std) any list of arrays whose LAST one holds the sample weights (Model.train_data is
     generic in the reference too, model/model.py:176-249: the model class supplies `_loss`).
@@ -218,8 +296,22 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     sampling stream shared by the ranks: `generator`, or one seeded by a number rank 0 broadcasts) and takes every
     world-th of them, the flattened gradients (1.9 MB) are averaged with one all-reduce per iteration, and every rank takes
     the same optimizer step - the replicas stay bit-identical and one iteration sees batch_size distinct draws, as in a
-    single process.  Validation runs on every rank (same numbers, same stopping)."""
+    single process.  Validation runs on every rank (same numbers, same stopping).
+
+    `fit_backend`: "torch" (the default) takes the gradient of an iteration through autograd (MIOpen / rocBLAS); "hip" takes
+    it with ONE call of tm_valuenet_fit_grad (csrc/valuenet_fit.hip: forward, loss and backward as hand-written gfx950 kernels,
+    writing the loss and Yogi's flat gradient buffer; the minibatch is gathered inside the kernels from an int8 copy of the
+    states).  The index draws, the all-reduce, the gradient norm, clipping, the optimiser step, validation, early stopping and
+    the best-weights reload are the same code for both.  "hip" is for Net + batch_loss on the GPU with the fused Yogi and
+    refuses anything else with a ValueError (HipFit)."""
     import torch.distributed as tdist
+    if fit_backend not in ("torch", "hip"):
+        raise ValueError("fit_backend must be 'torch' or 'hip', not %r" % (fit_backend,))
+    if fit_backend == "hip":
+        if loss_fn is not None:
+            raise ValueError("fit_backend='hip' computes train.batch_loss: a custom loss_fn needs fit_backend='torch'")
+        if oversampling:
+            raise ValueError("fit_backend='hip' does not sample by the visit weights: oversampling needs fit_backend='torch'")
     world = tdist.get_world_size(group) if (data_parallel and tdist.is_available() and tdist.is_initialized()) else 1
     my_rank = tdist.get_rank(group) if world > 1 else 0
     check_data_parallel_batch(batch_size, world)
@@ -245,6 +337,9 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     iters_done = 0
     net.train()
     # the one-kernel optimiser step (Yogi on the GPU): parameters and gradients are views of flat buffers from here on
+    hip = HipFit(net, optimizer, train, batch_size // world) if fit_backend == "hip" else None
+    if hip is not None and hip.rows != n - n_val:      # every draw below is an index into [0, n - n_val): the rows the kernels hold
+        raise ValueError("fit_backend='hip': %d training rows, but the index draws cover %d" % (hip.rows, n - n_val))
     flat_g = optimizer.flat_grad() if hasattr(optimizer, "flat_grad") else None
 
     def one_iteration():
@@ -256,9 +351,12 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
             idx = torch.randperm(n - n_val, device=data[0].device, generator=generator)[:batch_size]
         if world > 1:
             idx = idx[my_rank::world]
-        optimizer.zero_grad(set_to_none=True)
-        loss, _ = loss_fn(net, [d[idx] for d in train], weighted)
-        loss.backward()
+        if hip is not None:
+            loss = hip.grad(idx, weighted)           # (overwrites the flat gradient: no zero_grad)
+        else:
+            optimizer.zero_grad(set_to_none=True)
+            loss, _ = loss_fn(net, [d[idx] for d in train], weighted)
+            loss.backward()
         if world > 1:
             if flat_g is not None:
                 tdist.all_reduce(flat_g, group=group)
@@ -293,15 +391,16 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     it = 0
     while it < max_iters:
         if want_graph and graph is None and it == n_warm:
+            t_before = optimizer._flat["t"]
             try:
                 torch.cuda.synchronize()
                 graph = torch.cuda.CUDAGraph()
-                t_before = optimizer._flat["t"]
                 with torch.cuda.graph(graph):
                     one_iteration()
                 optimizer._flat["t"] = t_before          # (captured, not run)
             except Exception as e:                        # noqa: BLE001 - whatever the runtime refuses: the eager loop is the same fit
                 graph, want_graph = None, False
+                optimizer._flat["t"] = t_before          # (a capture that failed after the step was recorded ran no step either)
                 torch.cuda.synchronize()
                 if log:
                     print("train_data: no graph replay (%s: %s)" % (type(e).__name__, str(e).splitlines()[0][:120]), file=stderr, flush=True)
