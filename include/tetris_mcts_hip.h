@@ -386,6 +386,13 @@ int tm_distpy_backup(int n_trees, int n_nodes, int bins, const int32_t *trace, c
  * Yogi.step (12 parameters x 8 launches). */
 int tm_yogi_step(float *p, const float *g, float *m, float *v, double *state, int n, double lr, double beta1, double beta2,
                  double eps, double weight_decay, void *stream);
+/* torch.optim.Adam's step (torch 2.10, single tensor, not capturable: exp_avg.lerp_, exp_avg_sq.mul_().addcmul_(), maximum,
+ * (sqrt / bias_correction2_sqrt).add_(eps), addcdiv_(value=-step_size)) over FLAT device buffers, fp32 per element in that order,
+ * with coupled weight decay and, when amsgrad != 0, the running maximum vmax of exp_avg_sq (vmax is not touched otherwise).
+ * state: the five doubles of tm_yogi_step, advanced by the same one-thread kernel in front.  beta1 must exceed 0.5 (lerp's other
+ * branch is not implemented). */
+int tm_adam_step(float *p, const float *g, float *m, float *v, float *vmax, double *state, int n, double lr, double beta1,
+                 double beta2, double eps, double weight_decay, int amsgrad, void *stream);
 /* The gradient step of the value net's online fit (csrc/valuenet_fit.hip): forward of model.Net, train.batch_loss and the gradient
  * of its MEAN with respect to the ten learnable tensors, for the minibatch rows idx[0 .. batch) of the training set (idx NULL: rows
  * 0 .. batch-1; repeats allowed; every entry must be a valid row - the caller checks).  params / grad: 478338 floats in
@@ -400,6 +407,23 @@ long long tm_valuenet_fit_workspace(int batch);
 int tm_valuenet_fit_grad(const float *params, const float *out_bounds, const int8_t *states, const float *value,
                          const float *variance, const float *weight, const int64_t *idx, int batch, int weighted,
                          float variance_clip, float *grad, float *loss, float *workspace, void *stream);
+/* The gradient step of the distributional head's online fit (csrc/distnet_fit.hip): forward of model_distributional.Net,
+ * Model_Dist.loss and the gradient of its MEAN with respect to the eight learnable tensors, for the minibatch rows idx[0 .. batch)
+ * (idx NULL: rows 0 .. batch-1; repeats allowed; every entry must be a valid row - the caller checks).  params / grad:
+ * TM_DISTNET_PARAMS(atoms) floats in model_distributional.PARAM_ORDER (FusedAdam's flat p / g buffers as they stand), 16-byte
+ * aligned; states int8 [rows][200]: the 20 visible rows (the kernels put the net's two empty rows on top); target fp32
+ * [rows][target_stride], the first `atoms` of a row used, every value finite and >= 0 (a row need not sum to 1: the logit gradient
+ * is (w / batch) (p sum t - t)); weight fp32 [rows] (read only when weighted != 0).  grad is OVERWRITTEN; loss = {mean, sample
+ * standard deviation (n - 1; NaN for batch 1, as torch.std_mean)} of the per-sample losses w sum_a (t log t - t log p).
+ * workspace: tm_distnet_fit_workspace(batch, atoms) floats, 16-byte aligned, no initial contents required.  Everything is enqueued
+ * on `stream` in a sequence of launches whose shapes depend on `batch` and `atoms` alone: no allocation, no host synchronisation,
+ * nothing read back - capturable in a HIP graph.  Deterministic (no atomics; fixed-order partial sums).  hipErrorInvalidValue, and
+ * nothing launched, for a NULL pointer (idx excepted), batch < 1 or > 2^20, atoms outside 1..64 or target_stride < atoms.
+ * tm_distnet_fit_workspace is host arithmetic only (callable without a GPU): -1 for arguments that are refused. */
+long long tm_distnet_fit_workspace(int batch, int atoms);
+int tm_distnet_fit_grad(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
+                        const int64_t *idx, int batch, int atoms, int weighted, float *grad, float *loss, float *workspace,
+                        void *stream);
 int tm_valuenet_prepare(const float *params, float *prepared, void *stream);
 int tm_valuenet_forward(const float *params, const float *prepared, const int8_t *states, int n, float *v, float *var,
                         float *scratch, void *stream);

@@ -48,9 +48,9 @@ def build_parser():
     add('--valuenet_backend', default='hip', choices=('hip', 'hip_bf16x3', 'torch'), help='[new] value net of ValueSim, '
         'ValueSimLP and ValueSimC, distributional head of DistValueSim: hip (fp32 matrix cores), hip_bf16x3 (split-precision '
         'bf16 matrix cores) or torch')
-    add('--fit_backend', default='torch', choices=('torch', 'hip'), help='[new] online mode: gradients of the value net\'s fits '
-        'through PyTorch autograd (torch) or the hand-written gfx950 forward / loss / backward kernels (hip); ValueSim, '
-        'ValueSimLP and ValueSimC (DistValueSim fits through torch only)')
+    add('--fit_backend', default='torch', choices=('torch', 'hip', 'hip_dist'), help='[new] online mode: gradients of the fits '
+        'through PyTorch autograd (torch) or the hand-written gfx950 forward / loss / backward kernels: hip for the value net '
+        'of ValueSim, ValueSimLP and ValueSimC, hip_dist for the distributional head of DistValueSim')
     return p
 
 
@@ -78,6 +78,8 @@ def main(argv=None):
                      'PyTables nor h5py nor libhdf5 exists in this image; util/gui.py), which this engine does not reimplement' % flag)
     if not args.agent_type:
         sys.exit('--agent_type is required (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
+    if args.fit_backend == 'hip_dist' and args.agent_type != 'DistValueSim':
+        sys.exit('--fit_backend hip_dist applies to DistValueSim only')
     from importlib import import_module
     from pyTetris import Tetris                       # the reference's own two import lines (play.py:1,81-82)
     _agent_module = import_module('agents.' + args.agent_type)
@@ -93,7 +95,7 @@ def main(argv=None):
     if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim'):
         extra['fit_backend'] = args.fit_backend      # (DistValueSim refuses 'hip' itself)
     elif args.fit_backend != 'torch':
-        sys.exit('--fit_backend applies to ValueSim, ValueSimLP and ValueSimC only')
+        sys.exit('--fit_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     agent.update_root(game)

@@ -2,22 +2,87 @@
 the graph, and its parts on their own (a validation pass, a checkpoint save).
     python scripts/fit_timing.py [tuples] [--fit_backend {torch,hip}]
     python scripts/fit_timing.py [tuples] --blocks 3 --json OUT      the two fit backends alternated in blocks of graph-replayed
-                                                                     iterations (no validation inside), one JSON file"""
+                                                                     iterations (no validation inside), one JSON file
+    python scripts/fit_timing.py [tuples] --head --blocks 3 --json OUT   the distributional head (50 atoms), three legs alternated:
+                                                                     torch autograd + torch.optim.Adam, eager (the default path);
+                                                                     torch autograd + FusedAdam, replayed; hip_dist, replayed
+    python scripts/fit_timing.py [tuples] --head --eager-iters 30 --fit_backend B    eager iterations of one leg alone (for a
+                                                                     kernel trace)"""
 import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tetris_mcts_amd import model as M, train as T  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("tuples", nargs="?", type=int, default=250000)
-ap.add_argument("--fit_backend", default="torch", choices=("torch", "hip"))
+ap.add_argument("--fit_backend", default="torch", choices=("torch", "hip", "hip_dist"))
+ap.add_argument("--head", action="store_true", help="time the distributional head's fit (Model_Dist, 50 atoms) instead of the value net's")
+ap.add_argument("--eager-iters", type=int, default=0, help="with --head: run this many eager iterations of --fit_backend and stop")
 ap.add_argument("--blocks", type=int, default=0, help="alternate torch / hip in this many blocks each and stop")
 ap.add_argument("--block-iters", type=int, default=1000)
 ap.add_argument("--batch", type=int, default=1024)
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
+if args.fit_backend == "hip_dist" and not args.head:
+    ap.error("--fit_backend hip_dist is the distributional head's: it needs --head")
 n = args.tuples
 out_json = os.path.abspath(args.json) if args.json else None
 rng = np.random.default_rng(0)
+if args.head:
+    from tetris_mcts_amd.model_distributional import Model_Dist
+    os.chdir("/tmp")      # (as the value net's mode below: nothing a fit writes lands in the repository)
+    atoms = 50
+    x = torch.zeros(n, 1, 22, 10, device="cuda")
+    x[:, :, 2:, :] = torch.from_numpy(rng.integers(-1, 2, size=(n, 1, 20, 10)).astype(np.float32)).cuda()
+    centre = (x.sum(dim=(1, 2, 3)) * 0.5 + 25).clamp(2, 47).reshape(-1, 1)      # a learnable target: a bump whose place follows the board
+    targets = torch.softmax(-0.5 * (torch.arange(atoms, device="cuda").reshape(1, -1) - centre) ** 2 / 4.0, 1)
+    targets[:, :2] = 0.0                                                           # empty low bins, rows that do not sum to 1
+    w = torch.from_numpy(rng.integers(10, 200, size=(n, 1)).astype(np.float32)).cuda()
+    data = [x, targets, w]
+    if args.eager_iters > 0:
+        os.environ["TM_TRAIN_GRAPH"] = "0"
+        mdl = Model_Dist(atoms=atoms, seed=0)
+        res = mdl.train_data(data, iters_per_val=10 ** 9, batch_size=args.batch, max_iters=args.eager_iters, log=False,
+                             early_stopping=False, fit_backend=args.fit_backend)
+        torch.cuda.synchronize()
+        print(res, flush=True)
+        sys.exit(0)
+    legs = ("torch_adam_eager", "torch_fusedadam_replayed", "hip_dist_replayed")
+    models = {leg: Model_Dist(atoms=atoms, seed=0) for leg in legs}
+    models["torch_fusedadam_replayed"]._fused_optimizer()
+    rows = []
+    for blk in range(-1, max(args.blocks, 1)):      # block -1 warms every leg up and is not reported
+        for leg in legs:
+            os.environ["TM_TRAIN_GRAPH"] = "0" if leg == "torch_adam_eager" else "1"
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            res = models[leg].train_data(data, iters_per_val=10 ** 9, batch_size=args.batch, max_iters=args.block_iters, log=False,
+                                         early_stopping=False, fit_backend="hip_dist" if leg == "hip_dist_replayed" else "torch")
+            torch.cuda.synchronize(); dt = time.perf_counter() - t0
+            # the same call cut short after its setup (the per-fit checks, the int8 copy, three eager iterations, the capture and
+            # one replay): the difference is the time of the iterations alone
+            t1 = time.perf_counter()
+            short = models[leg].train_data(data, iters_per_val=10 ** 9, batch_size=args.batch, max_iters=4, log=False,
+                                           early_stopping=False, fit_backend="hip_dist" if leg == "hip_dist_replayed" else "torch")
+            torch.cuda.synchronize(); ds = time.perf_counter() - t1
+            if blk >= 0:
+                rows.append(dict(block=blk, leg=leg, iters=res["iters"], graph_replay=res["graph_replay"],
+                                 ms_per_iter=1e3 * (dt - ds) / (res["iters"] - short["iters"]),
+                                 ms_per_iter_whole_call=1e3 * dt / res["iters"], setup_ms=1e3 * ds))
+                print(rows[-1], flush=True)
+    ms = {leg: [r["ms_per_iter"] for r in rows if r["leg"] == leg] for leg in legs}
+    med = {leg: float(np.median(ms[leg])) for leg in legs}
+    summary = dict(head="model_distributional.Net", atoms=atoms, tuples=n, batch=args.batch, block_iters=args.block_iters, blocks=rows,
+                   **{leg + "_ms": dict(min=min(ms[leg]), max=max(ms[leg]), median=med[leg]) for leg in legs},
+                   torch_adam_eager_over_hip_dist=med[legs[0]] / med[legs[2]], torch_fusedadam_replayed_over_hip_dist=med[legs[1]] / med[legs[2]],
+                   note="a block = one train_data call of block_iters iterations followed by the same call with max_iters=4; "
+                        "ms_per_iter is the difference over the iterations between them (the per-fit checks, the int8 copy, the three "
+                        "eager iterations and the capture fall out), ms_per_iter_whole_call the first call over all of its iterations, "
+                        "setup_ms the short call")
+    print(json.dumps({k: v for k, v in summary.items() if k != "blocks"}), flush=True)
+    if out_json:
+        os.makedirs(os.path.dirname(out_json), exist_ok=True)
+        with open(out_json, "w") as f:
+            json.dump(summary, f, indent=1)
+    sys.exit(0)
 states = torch.from_numpy(rng.integers(-1, 2, size=(n, 1, 20, 10)).astype(np.float32)).cuda()
 values = (states.sum(dim=(1, 2, 3)) * 0.5 + 20).reshape(-1, 1)
 variances = torch.full((n, 1), 4.0, device="cuda")

@@ -56,6 +56,9 @@ SYMBOLS = {
     "tm_core_get_unique_child_obs": [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "tm_core_get_all_childs": [i32, i32, vp, vp, vp, vp, vp],
     "tm_yogi_step": [vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, f64, vp],
+    "tm_adam_step": [vp, vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, f64, i32, vp],
+    "tm_distnet_fit_workspace": [i32, i32],  # (returns long long: restype set in lib())
+    "tm_distnet_fit_grad": [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "tm_valuenet_fit_workspace": [i32],      # (returns long long: restype set in lib())
     "tm_valuenet_fit_grad": [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp],
     "tm_valuenet_prepare": [vp, vp, vp],
@@ -102,6 +105,7 @@ def lib():
             f = getattr(L, name)
             f.argtypes, f.restype = args, i32
         L.tm_valuenet_fit_workspace.restype = C.c_longlong
+        L.tm_distnet_fit_workspace.restype = C.c_longlong
         L.tm_fill_norm_quantile.argtypes, L.tm_fill_norm_quantile.restype = [vp, i32], None
         L.tm_fill_norm_quantile_f64.argtypes, L.tm_fill_norm_quantile_f64.restype = [vp, i32], None
         L.tm_version.argtypes, L.tm_version.restype = [], C.c_char_p

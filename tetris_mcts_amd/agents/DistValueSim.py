@@ -27,17 +27,19 @@ class DistValueSim(TreeAgent):
     def __init__(self, atoms=50, vmin=0, vmax=5000, max_nodes=100000, model=None, evaluator=None, online=False,
                  min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, valuenet_backend=None, fit_backend="torch",
                  **kwargs):
-        """fit_backend: "torch" only - the HIP gradient step (csrc/valuenet_fit.hip) is the value net's Gaussian loss, not
-        this head's, and is refused here.
+        """fit_backend: how train_nodes takes the gradients of the head's fits - "torch" (autograd, torch.optim.Adam) or
+        "hip_dist" (csrc/distnet_fit.hip and the fused Adam).  "hip" names the value net's step (csrc/valuenet_fit.hip: the
+        Gaussian loss, not this head's) and is refused here.
         valuenet_backend: the Model_Dist backend of the model the agent builds when `model` is None (None: Model_Dist's
         default; "hip", "hip_bf16x3" - the split-precision kernels - or "torch").
         online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
         least `min_visits_to_store` visits whose seven children have all been visited (its commented store_nodes, default 50)
         as (board, distribution, visits) tuples, train_nodes fits the head on them (memory_size / memory_growth_rate as
         ValueSim's)."""
-        if fit_backend != "torch":
-            raise ValueError("DistValueSim fits its distributional head through PyTorch: fit_backend=%r is not available "
-                             "(the HIP gradient step is the value net's)" % (fit_backend,))
+        if fit_backend not in ("torch", "hip_dist"):
+            raise ValueError("DistValueSim: fit_backend must be 'torch' or 'hip_dist', not %r ('hip' is the value net's gradient "
+                             "step)" % (fit_backend,))
+        self.fit_backend = fit_backend
         kwargs.pop("min_visit", None)
         kwargs.pop("gamma", None)                      # the distributional backup does not discount
         self.atoms, self.vrange = int(atoms), (float(vmin), float(vmax))
@@ -154,7 +156,7 @@ class DistValueSim(TreeAgent):
             os.makedirs(os.path.dirname(os.path.abspath(dump_path)), exist_ok=True)
             np.savez(dump_path, states=data[0].cpu().numpy(), values=data[1].cpu().numpy(), weights=data[2].cpu().numpy())
         self.n_trains += 1
-        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000)     # DistValueSimOnline.py:165
+        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend)     # DistValueSimOnline.py:165
         opts.update(train_kwargs)
         res = self.model.train_data(data, **opts)
         self.model.training(False)

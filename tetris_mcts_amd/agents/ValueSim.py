@@ -17,7 +17,7 @@ class ValueSim(TreeAgent):
         "hip_bf16x3", the split-precision kernels; "torch").  `fit_backend`: how the online fits take their gradients
         (train.train_data: "torch", the default, or "hip", csrc/valuenet_fit.hip)."""
         if fit_backend not in ("torch", "hip"):
-            raise ValueError("fit_backend must be 'torch' or 'hip', not %r" % (fit_backend,))
+            raise ValueError("fit_backend must be 'torch' or 'hip', not %r ('hip_dist' is DistValueSim's)" % (fit_backend,))
         self.fit_backend = fit_backend
         kwargs.pop("min_visit", None)  # play.py:89 forwards it; the reference ValueSim ignores it too
         benchmark = kwargs.get("benchmark", False)

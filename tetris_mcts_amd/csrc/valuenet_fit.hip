@@ -25,10 +25,11 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/tetris_mcts_hip.h"
+#include "fit_mma.h"      // f32x16, drow, vf_quad, vf_zero, vf_add, row_of, wave_sum, block_sum: shared with distnet_fit.hip
 
 namespace tmcts_vf {
+using namespace tmcts_fit;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int A1 = 32 * 18 * 8, A2 = 32 * 16 * 6, A3 = 32 * 14 * 4, HID = 256;
 constexpr int OFF_C1W = 0, OFF_C1B = 288, OFF_C2W = 320, OFF_C2B = 9536, OFF_C3W = 9568, OFF_C3B = 18784,
               OFF_F1W = 18816, OFF_F1B = 477568, OFF_FOW = 477824, OFF_FOB = 478336, NPARAM = 478338;
@@ -70,39 +71,6 @@ __host__ inline Layout layout(int B) {
     L.total = o;
     return L;
 }
-
-__device__ __forceinline__ int drow(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// one quad of K: four steps on each of the NT tiles
-template <int NT>
-__device__ __forceinline__ void vf_quad(f32x16 (&acc)[NT], const float4& a, const float4 (&b)[NT]) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b[t].x, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[t].y, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[t].z, acc[t], 0, 0, 0);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[t].w, acc[t], 0, 0, 0);
-}
-
-constexpr int CHUNK_QUADS = 4;          // quads of K per chunk: 32 terms per sequential chain
-template <int NT>
-__device__ __forceinline__ void vf_zero(f32x16 (&acc)[NT]) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
-}
-template <int NT>
-__device__ __forceinline__ void vf_add(f32x16 (&tot)[NT], const f32x16 (&acc)[NT]) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot[t][r] += acc[t][r];
-}
-
-__device__ __forceinline__ size_t row_of(const int64_t* __restrict__ idx, int b) { return idx ? (size_t)idx[b] : (size_t)b; }
 
 // ---- forward convolution: z[co][b, p] = bias[co] + sum_k W[co][k] in[b][ci][(y + ky) IW + x + kx], ReLU ----
 // M = 32 output channels, N = B * OP positions, K = CIN * 9.  CIN == 1: the input is the int8 state of row idx[b].
@@ -227,12 +195,6 @@ __global__ __launch_bounds__(256) void k_vf_fc1_fwd(const float* __restrict__ Wf
                 dst[drow(r, half)] = v > 0.0f ? v : 0.0f;
             }
         }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // ---- output layer, loss and their gradients: one wave per sample, in double ----
@@ -532,18 +494,6 @@ __global__ __launch_bounds__(256) void k_vf_reduce(const float* __restrict__ par
         for (int k = 0; k < G; ++k) t += sm[k * PER + o];
         out[i] = (float)t;
     }
-}
-
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 128; d >= 1; d >>= 1) {
-        if ((int)threadIdx.x < d) sm[threadIdx.x] += sm[threadIdx.x + d];
-        __syncthreads();
-    }
-    const double r = sm[0];
-    __syncthreads();
-    return r;
 }
 
 // mean and population standard deviation of the per-sample losses (one workgroup, double, fixed order)

@@ -46,7 +46,44 @@ __global__ __launch_bounds__(256) void k_yogi_step(float* __restrict__ p, const 
     v[i] = vi;
 }
 
+// torch.optim.Adam's single-tensor step (torch 2.10, not capturable), fp32 per element in its order of operations; the state is
+// the one k_yogi_tick advances.
+__global__ __launch_bounds__(256) void k_adam_step(float* __restrict__ p, const float* __restrict__ g_, float* __restrict__ m,
+                                                   float* __restrict__ v, float* __restrict__ vmax, const double* __restrict__ st,
+                                                   int n, float omb1, float b2, float omb2, float eps, float wd, int amsgrad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float step = (float)st[3], bc2 = (float)st[4];
+    float g = g_[i];
+    const float pi = p[i];
+    if (wd != 0.f) g = g + wd * pi;                       // grad.add(param, alpha=weight_decay)
+    float mi = m[i];
+    mi = mi + omb1 * (g - mi);                            // exp_avg.lerp_(grad, 1 - beta1)          (weight < 0.5: start + w (end - start))
+    float vi = v[i] * b2;                                 // exp_avg_sq.mul_(beta2)
+    vi = vi + (omb2 * g) * g;                             //           .addcmul_(grad, grad, value=1 - beta2)
+    float dv = vi;
+    if (amsgrad) {
+        const float vm = vmax[i];
+        dv = (vm != vm || vm > vi) ? vm : vi;             // torch.maximum(max_exp_avg_sq, exp_avg_sq) (NaN propagates)
+        vmax[i] = dv;
+    }
+    const float den = sqrtf(dv) / bc2 + eps;              // (sqrt / bias_correction2_sqrt).add_(eps)
+    p[i] = pi + (-step * mi) / den;                       // param.addcdiv_(exp_avg, denom, value=-step_size)
+    m[i] = mi;
+    v[i] = vi;
+}
+
 }  // namespace tmcts
+
+extern "C" int tm_adam_step(float* p, const float* g, float* m, float* v, float* vmax, double* state, int n, double lr, double beta1,
+                            double beta2, double eps, double weight_decay, int amsgrad, void* stream) {
+    if (!p || !g || !m || !v || !vmax || !state || n < 0 || !(beta1 > 0.5)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(tmcts::k_yogi_tick, dim3(1), dim3(1), 0, (hipStream_t)stream, state, lr, beta1, beta2);
+    if (n > 0)
+        hipLaunchKernelGGL(tmcts::k_adam_step, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, state, n,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, amsgrad);
+    return (int)hipGetLastError();
+}
 
 extern "C" int tm_yogi_step(float* p, const float* g, float* m, float* v, double* state, int n, double lr, double beta1, double beta2,
                             double eps, double weight_decay, void* stream) {

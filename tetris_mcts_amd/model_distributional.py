@@ -191,10 +191,30 @@ class Model_Dist:
             self.optimizer = torch.optim.Adam(self.model.parameters(), lr=1e-4, eps=1e-5, amsgrad=True)
         return self.optimizer
 
-    def train_data(self, data, **kwargs):
+    def _fused_optimizer(self, commit=True):
+        """the model's optimiser as a train.FusedAdam (one HIP kernel a step, a flat gradient buffer), the state of the Adam it
+        replaces carried over through a copy of its state dict; with `commit` it becomes the model's optimiser for later fits
+        (train_data commits only once a hip_dist fit has passed its checks: a refused fit leaves the model as it was)"""
+        import copy
+        from .train import FusedAdam
+        old = getattr(self, "optimizer", None)
+        if isinstance(old, FusedAdam):
+            return old
+        new = FusedAdam(self.model.parameters(), lr=1e-4, eps=1e-5, amsgrad=True)
+        if old is not None:
+            new.load_state_dict(copy.deepcopy(old.state_dict()))
+        if commit:
+            self.optimizer = new
+        return new
+
+    def train_data(self, data, fit_backend="torch", **kwargs):
         """data: [states [n,1,22,10], distributions [n,atoms], weights [n,1]]; Model.train_data (model/model.py:176-249) with
-        this class's loss; data-parallel over the ranks as train.train_data describes."""
+        this class's loss; data-parallel over the ranks as train.train_data describes.  fit_backend: "torch" (the default:
+        autograd and the model's optimiser as it stands) or "hip_dist" (csrc/distnet_fit.hip's gradient step and the fused Adam;
+        train.HipDistFit lists what it needs); "hip" names the value net's step and is refused."""
         from . import train as T
+        if fit_backend not in ("torch", "hip_dist"):
+            raise ValueError("Model_Dist.train_data: fit_backend must be 'torch' or 'hip_dist', not %r" % (fit_backend,))
         data = [torch.as_tensor(d, dtype=torch.float32, device=self.device) for d in data]
         best = {}
 
@@ -206,7 +226,15 @@ class Model_Dist:
 
         def loss_fn(net, batch, weighted):
             return self.loss(batch[0], batch[1], batch[2] if weighted else None)
-        res = T.train_data(self.model, self._optimizer(), data, save=save, load=load, loss_fn=loss_fn, **kwargs)
+        if fit_backend == "hip_dist":
+            loss_fn.is_model_dist_loss = True      # (what tm_distnet_fit_grad computes: train_data refuses any other loss_fn)
+            kwargs["fit_backend"] = fit_backend
+        opt = self._fused_optimizer(commit=False) if fit_backend == "hip_dist" else self._optimizer()
+        try:
+            res = T.train_data(self.model, opt, data, save=save, load=load, loss_fn=loss_fn, **kwargs)
+        finally:
+            if getattr(opt, "_flat", None) is not None:      # flattened = past HipDistFit's checks: the parameters are its views now
+                self.optimizer = opt
         self.model.eval()
         self.weights_changed()
         return res

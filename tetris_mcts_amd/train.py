@@ -156,6 +156,127 @@ class Yogi(Optimizer):
         return loss
 
 
+class FusedAdam(torch.optim.Adam):
+    """torch.optim.Adam (AMSGrad and coupled weight decay included) with Yogi's fused surface, for the distributional head's fit.
+
+    Parameters on the GPU: the step is ONE HIP kernel over flat buffers (csrc/yogi.hip `tm_adam_step`: torch's single-tensor step
+    per element, fp32, in its order of operations) - the parameters, their gradients and the three moments become views of five
+    flat tensors at the first step (`flatten`, in the order the parameters were given: model_distributional.PARAM_ORDER for
+    Net.parameters()), the step count lives on the device, and train_data replays an iteration from a HIP graph.  The state dict
+    is torch.optim.Adam's (per parameter: step, exp_avg, exp_avg_sq, max_exp_avg_sq), so a state saved by either loads into the
+    other.  Parameters on the CPU: torch's own step (this class IS torch.optim.Adam there: the same bits)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, fused=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+        self._fused_wanted = fused
+        self._flat = None
+
+    def fused(self):
+        """whether step() is the one-kernel form: every parameter on one GPU, float32, a single group with torch's plain
+        options (or asked for / refused at construction)"""
+        if self._fused_wanted is False:
+            return False
+        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        g0 = self.param_groups[0]
+        ok = (len(self.param_groups) == 1 and len(ps) > 0 and all(p.is_cuda and p.dtype == torch.float32 for p in ps)
+              and len({p.device for p in ps}) == 1 and not g0.get("maximize") and not g0.get("decoupled_weight_decay")
+              and not isinstance(g0["lr"], torch.Tensor) and g0["betas"][0] > 0.5)
+        if self._fused_wanted and not ok:
+            raise ValueError("FusedAdam(fused=True) needs float32 parameters on one GPU in a single group")
+        return ok
+
+    def flatten(self):
+        """(idempotent) the parameters that take gradients, their gradients and moments as views of flat buffers"""
+        if self._flat is not None:
+            return self._flat
+        ps = [p for p in self.param_groups[0]["params"] if p.requires_grad]
+        dev, n = ps[0].device, sum(p.numel() for p in ps)
+        F = dict(params=ps, n=n, p=torch.empty(n, device=dev), g=torch.zeros(n, device=dev), m=torch.zeros(n, device=dev),
+                 v=torch.zeros(n, device=dev), vmax=torch.zeros(n, device=dev), state=torch.zeros(8, dtype=torch.float64, device=dev))
+        off, steps = 0, set()
+        with torch.no_grad():
+            for p in ps:
+                k = p.numel()
+                sl = slice(off, off + k)
+                F["p"][sl].copy_(p.reshape(-1))
+                p.data = F["p"][sl].view_as(p)
+                if p.grad is not None:
+                    F["g"][sl].copy_(p.grad.reshape(-1))
+                p.grad = F["g"][sl].view_as(p)
+                st = self.state[p]
+                if st:       # moments loaded from a state dict (or steps taken by torch's per-tensor form)
+                    F["m"][sl].copy_(st["exp_avg"].reshape(-1))
+                    F["v"][sl].copy_(st["exp_avg_sq"].reshape(-1))
+                    if "max_exp_avg_sq" in st:
+                        F["vmax"][sl].copy_(st["max_exp_avg_sq"].reshape(-1))
+                    steps.add(int(st["step"]))
+                st["exp_avg"], st["exp_avg_sq"] = F["m"][sl].view_as(p), F["v"][sl].view_as(p)
+                st["max_exp_avg_sq"] = F["vmax"][sl].view_as(p)
+                st["step"] = torch.tensor(float(st["step"]) if "step" in st else 0.0)
+                off += k
+        if len(steps) > 1:
+            raise ValueError("FusedAdam: the parameters' step counts differ (%s)" % sorted(steps))
+        t = steps.pop() if steps else 0
+        b1, b2 = self.param_groups[0]["betas"]
+        lr = self.param_groups[0]["lr"]
+        if t > 0:
+            F["state"].copy_(torch.tensor([t, b1 ** t, b2 ** t, lr / (1 - b1 ** t), math.sqrt(1 - b2 ** t), 0, 0, 0], dtype=torch.float64))
+        F["t"] = t
+        self._flat = F
+        return F
+
+    def flat_grad(self):
+        return self.flatten()["g"] if self.fused() else None
+
+    def zero_grad(self, set_to_none=True):
+        """In the fused form the gradients are zeroed, never cleared: they stay the views of the flat buffer that autograd
+        accumulates into and the kernel reads, so EVERY parameter is stepped in every iteration (one that received no gradient
+        moves by its momentum, where torch.optim.Adam would skip it; Net's eight tensors always receive one).  Anywhere else
+        (CPU parameters, flattened or not) this is torch.optim.Adam.zero_grad."""
+        if self._flat is not None and self.fused():
+            self._flat["g"].zero_()
+            return
+        super().zero_grad(set_to_none=set_to_none)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        if self._flat is not None:       # the loaded moments are tensors of their own: back into the flat buffers
+            ps = self._flat["params"]
+            with torch.no_grad():
+                for p in ps:
+                    p.data = p.data.clone()
+                    p.grad = None
+            self._flat = None
+            self.flatten()
+
+    def state_dict(self):
+        if self._flat is not None and self.fused():
+            for p in self._flat["params"]:
+                self.state[p]["step"] = torch.tensor(float(self._flat["t"]))
+        return super().state_dict()
+
+    def _fused_step(self):
+        from . import _lib
+        F = self.flatten()
+        g = self.param_groups[0]
+        _lib.check(_lib.lib().tm_adam_step(F["p"].data_ptr(), F["g"].data_ptr(), F["m"].data_ptr(), F["v"].data_ptr(),
+                                           F["vmax"].data_ptr(), F["state"].data_ptr(), F["n"], float(g["lr"]), float(g["betas"][0]),
+                                           float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(bool(g["amsgrad"])),
+                                           torch.cuda.current_stream(F["p"].device).cuda_stream), "tm_adam_step")
+        F["t"] += 1
+
+    def step(self, closure=None):
+        if not self.fused():
+            return super().step(closure)      # torch.optim.Adam itself (on flattened CPU parameters too: the views are its state)
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        with torch.no_grad():
+            self._fused_step()
+        return loss
+
+
 def gaussian_kl(var_pred, mean_pred, var, mean):
     """KL( N(mean,var) || N(mean_pred,var_pred) ) up to the factor 1/2 the reference also drops."""
     return var_pred.log() + ((mean - mean_pred) ** 2 + var) / var_pred - var.log() - 1.0
@@ -282,6 +403,116 @@ class HipFit:
         return self.loss[0]
 
 
+def dist_batch_loss(net, batch, weighted):
+    """Model_Dist.loss as a train_data loss_fn: batch = [states [b,1,22,10], targets [b,atoms], weights [b,1]]"""
+    state, value, weight = batch
+    per = torch.xlogy(value, value) - value * net.log_prob(state)
+    if weighted:
+        per = weight.reshape(-1, 1) * per
+    std, mean = torch.std_mean(per.sum(dim=1))
+    return mean, std
+
+
+# The mark by which train_data(fit_backend="hip_dist") recognises "the model's own loss".  It is a convention, not a check: setting it
+# on a function ASSERTS that the function computes what tm_distnet_fit_grad computes (Model_Dist.loss: per sample
+# w sum_a (xlogy(t, t) - t log p), mean and n-1 standard deviation over the batch).  The kernels take the training gradient either
+# way; a marked function that computes something else would only make validation measure another quantity than the one fitted.
+# Model_Dist.train_data's closure around Model_Dist.loss carries the mark, and so does this function; nothing else should.
+dist_batch_loss.is_model_dist_loss = True
+
+
+def flat_order_is_dist_param_order(net, optimizer):
+    """Whether FusedAdam's flat buffers hold (or, before flatten(), will hold) exactly the eight tensors of model_distributional.Net in its PARAM_ORDER - the layout
+    tm_distnet_fit_grad reads its parameters in and writes its gradient in."""
+    from .model_distributional import PARAM_ORDER
+    named = dict(net.named_parameters())
+    want = [named.get(k) for k in PARAM_ORDER]
+    # (the order flatten() WILL use, read without flattening: a refused fit leaves the optimiser and the parameters as they were)
+    flat = getattr(optimizer, "_flat", None)
+    got = flat["params"] if flat is not None else [p for g in optimizer.param_groups[:1] for p in g["params"] if p.requires_grad]
+    return (len(optimizer.param_groups) == 1 and all(w is not None for w in want) and len(got) == len(want) == len(named)
+            and all(a is b for a, b in zip(got, want)))
+
+
+class HipDistFit:
+    """The per-fit state of fit_backend="hip_dist" (HipFit's sibling for the distributional head): the checks (once per fit), the
+    int8 copy of the 20 visible rows of the training states, the targets, the weights and the workspace; grad(idx) is one call
+    of tm_distnet_fit_grad on the current stream."""
+
+    def __init__(self, net, optimizer, train, batch):
+        from . import _lib
+        from .model_distributional import Net, ROW
+        B = "fit_backend='hip_dist'"
+        if len(train) != 3:
+            raise ValueError(B + " needs data = [states, targets, weights]")
+        states, target, weight = train
+        rows = states.shape[0]
+        if rows < 1 or states.numel() != rows * 220:
+            raise ValueError(B + " needs states of 22 x 10 cells a row, got shape %s" % (tuple(states.shape),))
+        if not isinstance(net, Net):
+            raise ValueError(B + " computes model_distributional.Net, not %s" % type(net).__name__)
+        atoms = net.seq.fc_v.out_features
+        if not (1 <= atoms <= ROW):
+            raise ValueError(B + " holds 1..64 atoms, the net has %d" % atoms)
+        if target.dim() != 2 or target.shape[0] != rows or target.shape[1] != atoms:
+            raise ValueError(B + " needs targets [rows, atoms] = [%d, %d] as the net's atoms, got %s" % (rows, atoms, tuple(target.shape)))
+        if weight.shape[0] != rows or weight.numel() != rows:
+            raise ValueError(B + " needs one weight a row")
+        if not isinstance(optimizer, FusedAdam):
+            raise ValueError(B + " writes FusedAdam's flat gradient buffer: the optimizer must be a train.FusedAdam, not %s"
+                             % type(optimizer).__name__)
+        if not flat_order_is_dist_param_order(net, optimizer):
+            raise ValueError(B + ": the optimizer's flat buffers are not the net's tensors in model_distributional.PARAM_ORDER")
+        s3 = states.reshape(rows, 22, 10)
+        if not bool(((s3 == s3.round()) & (s3.abs() <= 127)).all()):
+            raise ValueError(B + " reads the states as int8: they must be integers in [-127, 127]")
+        if not bool((s3[:, :2] == 0).all()):
+            raise ValueError(B + " supplies the two top rows of the 22 itself: they must be all zero in the data")
+        if not bool((torch.isfinite(target) & (target >= 0)).all()):
+            raise ValueError(B + " needs finite targets >= 0")
+        if not all(d.is_cuda and d.dtype == torch.float32 for d in train):
+            raise ValueError(B + " needs float32 CUDA tensors (the data is %s on %s)" % (states.dtype, states.device))
+        if not optimizer.fused():
+            raise ValueError(B + ": the FusedAdam's fused() must hold (float32 parameters on one GPU in a single group)")
+        F = optimizer.flatten()
+        if F["n"] != 279232 + 129 * atoms or F["p"].device != states.device:
+            raise ValueError(B + ": %d flat parameters on %s, expected %d on %s" % (F["n"], F["p"].device, 279232 + 129 * atoms, states.device))
+        if batch < 1:
+            raise ValueError(B + " needs a batch of at least one row per rank")
+        self._lib, self.F, self.batch, self.rows, self.dev, self.atoms = _lib, F, batch, rows, states.device, atoms
+        self.states = s3[:, 2:].reshape(rows, 200).to(torch.int8).contiguous()
+        self.target = target.contiguous()
+        self.weight = weight.reshape(rows).contiguous()
+        n_ws = _lib.lib().tm_distnet_fit_workspace(batch, atoms)
+        if n_ws < 0:
+            raise ValueError(B + ": a batch of %d rows is refused" % batch)
+        self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
+        self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
+        self._idx_checked = False
+
+    def check_idx(self, idx):
+        """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= self.rows:
+            raise ValueError("fit_backend='hip_dist': indices in [%d, %d] do not all name one of the %d training rows" % (lo, hi, self.rows))
+
+    def grad(self, idx, weighted):
+        """as HipFit.grad: the loss (a 0-d device tensor) of the rows idx; the gradient of its mean lands in the optimiser's flat
+        buffer.  The first call of a fit that is not being captured checks the index range (one host synchronisation)."""
+        if idx.dtype != torch.int64 or idx.numel() != self.batch:
+            raise ValueError("fit_backend='hip_dist': expected %d int64 indices, got %d %s" % (self.batch, idx.numel(), idx.dtype))
+        if not self._idx_checked and not torch.cuda.is_current_stream_capturing():
+            self.check_idx(idx)
+            self._idx_checked = True
+        idx = idx.contiguous()
+        F = self.F
+        self._lib.check(self._lib.lib().tm_distnet_fit_grad(
+            F["p"].data_ptr(), self.states.data_ptr(), self.target.data_ptr(), self.target.stride(0), self.weight.data_ptr(),
+            idx.data_ptr(), self.batch, self.atoms, int(bool(weighted)), F["g"].data_ptr(), self.loss.data_ptr(), self.ws.data_ptr(),
+            torch.cuda.current_stream(self.dev).cuda_stream), "tm_distnet_fit_grad")
+        return self.loss[0]
+
+
 def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validation_fraction=0.1,
                sample_replacement=True, oversampling=False, weighted=True, early_stopping=True, early_stopping_patience=10,
                early_stopping_threshold=1.0, shuffle=False, max_iters=100000, grad_clip=0.0, save=None, load=None,
@@ -303,10 +534,19 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     writing the loss and Yogi's flat gradient buffer; the minibatch is gathered inside the kernels from an int8 copy of the
     states).  The index draws, the all-reduce, the gradient norm, clipping, the optimiser step, validation, early stopping and
     the best-weights reload are the same code for both.  "hip" is for Net + batch_loss on the GPU with the fused Yogi and
-    refuses anything else with a ValueError (HipFit)."""
+    refuses anything else with a ValueError (HipFit).  "hip_dist" is the same for the distributional head: ONE call of
+    tm_distnet_fit_grad (csrc/distnet_fit.hip) for model_distributional.Net + Model_Dist.loss on data = [states [n,1,22,10],
+    targets [n,atoms], weights [n,1]] with a FusedAdam (HipDistFit); validation goes through `loss_fn` (Model_Dist's own, or
+    dist_batch_loss when none is given) on torch."""
     import torch.distributed as tdist
-    if fit_backend not in ("torch", "hip"):
-        raise ValueError("fit_backend must be 'torch' or 'hip', not %r" % (fit_backend,))
+    if fit_backend not in ("torch", "hip", "hip_dist"):
+        raise ValueError("fit_backend must be 'torch', 'hip' or 'hip_dist', not %r" % (fit_backend,))
+    if fit_backend == "hip_dist":
+        if loss_fn is not None and not getattr(loss_fn, "is_model_dist_loss", False):
+            raise ValueError("fit_backend='hip_dist' computes Model_Dist.loss: a custom loss_fn needs fit_backend='torch'")
+        if oversampling:
+            raise ValueError("fit_backend='hip_dist' does not sample by the visit weights: oversampling needs fit_backend='torch'")
+        loss_fn = loss_fn or dist_batch_loss
     if fit_backend == "hip":
         if loss_fn is not None:
             raise ValueError("fit_backend='hip' computes train.batch_loss: a custom loss_fn needs fit_backend='torch'")
@@ -337,9 +577,10 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     iters_done = 0
     net.train()
     # the one-kernel optimiser step (Yogi on the GPU): parameters and gradients are views of flat buffers from here on
-    hip = HipFit(net, optimizer, train, batch_size // world) if fit_backend == "hip" else None
+    hip = (HipFit(net, optimizer, train, batch_size // world) if fit_backend == "hip" else
+           HipDistFit(net, optimizer, train, batch_size // world) if fit_backend == "hip_dist" else None)
     if hip is not None and hip.rows != n - n_val:      # every draw below is an index into [0, n - n_val): the rows the kernels hold
-        raise ValueError("fit_backend='hip': %d training rows, but the index draws cover %d" % (hip.rows, n - n_val))
+        raise ValueError("fit_backend=%r: %d training rows, but the index draws cover %d" % (fit_backend, hip.rows, n - n_val))
     flat_g = optimizer.flat_grad() if hasattr(optimizer, "flat_grad") else None
 
     def one_iteration():
