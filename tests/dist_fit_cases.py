@@ -29,14 +29,22 @@ SPW = 4             # samples per wave of the convolutions' weight-gradient part
 TILE = 32           # the matrix core's tile (fc1 forward and data gradient: 32 samples a wave), HEAD_CHUNK (samples per partial of the
                     # FC bias sums) and the 32-sample chunks of the FC weight gradients' K
 FC_KC = 256         # samples per split of the FC weight gradients; also the threads of the loss kernel's strided sum
-RED_G = 16          # k_df_reduce adds its S partials in 16 interleaved groups: S = B (the convolutions' bias sums) passes 16 at
-                    # B = 16, S = ceil(B / SPW) (their weight gradients) at B = 64; S = ceil(B / 32) and ceil(B / 256) would pass it
-                    # at B = 512 and 4 096 only, where nothing else changes (left to the large-batch timing runs)
+RED_G = 16          # k_df_reduce<16> adds its S partials in 16 interleaved groups: S = B (the convolutions' bias sums) passes 16
+                    # at B = 16, S = ceil(B / SPW) (their weight gradients) at B = 64, S = ceil(B / TILE) (the FC bias sums) at
+                    # B = 512 (LARGE_BATCHES: 480 / 512 / 513)
+RED_G_FC = 4        # k_df_reduce<4> adds the s1 = ceil(B / FC_KC) splits of the two FC weight gradients in 4 groups: s1 passes
+                    # 4 at B = 1 025 (LARGE_BATCHES: 1 000 / 1 024 / 1 025; 1 024 is the batch every DistValueSim fit uses)
 # (k_df_head's four samples a workgroup is SPW's 3 / 4 / 5 again)
 BATCHES = (1, 2, SPW - 1, SPW, SPW + 1, RED_G - 1, RED_G, RED_G + 1, TILE - 1, TILE, TILE + 1, RED_G * SPW - SPW, RED_G * SPW,
            RED_G * SPW + 1, FC_KC - 1, FC_KC, FC_KC + 1)
+# past the candidate rows of the cases above: hchunks = ceil(B / TILE) at 15 / 16 / 17, and s1 at 3 (with a split of one sample),
+# at 4 (with a ragged last split of 232 = 7 K chunks and 8 samples; and full) and at 5 (the last split of one sample)
+LARGE_BATCHES = (RED_G * TILE - TILE, RED_G * TILE, RED_G * TILE + 1, 1000, RED_G_FC * FC_KC, RED_G_FC * FC_KC + 1)
 KINK_CAP = 0.25     # the filter may drop at most this share of the candidate rows
 CANDIDATES = 420
+LARGE_CANDIDATES = 1400                                    # a second candidate set for the nets of the large batches
+LARGE_NETS = ("fixture", "seed7", "seed64", "fitted")
+LARGE_SETS = tuple("%s, %d rows" % (k, LARGE_CANDIDATES) for k in LARGE_NETS)          # their names in KINK_KEPT
 
 
 def n_params(atoms):
@@ -109,7 +117,12 @@ def off_the_kink(W, states):
     return keep.numpy()
 
 
-KINK_KEPT = {}      # net name -> share of the candidate rows the filter kept (tests/test_dist_fit_hip.py asserts the cap)
+KINK_KEPT = {}      # candidate set (a net's name, or one of LARGE_SETS) -> share of its rows the filter kept
+                    # (tests/test_dist_fit_hip.py asserts the cap)
+
+
+def candidates(name):
+    return LARGE_CANDIDATES if name in LARGE_SETS else CANDIDATES
 
 
 def _restrict(name, data, W):
@@ -146,6 +159,41 @@ def case_names(full=True):
     return list(_build_cases(full, names_only=True))
 
 
+def large_cases(names_only=False):
+    """the regimes past BATCHES, on candidate sets of LARGE_CANDIDATES rows (same dataset / off_the_kink rule, same cap); their
+    indices come from a generator of their own.  Built once; names_only builds no data."""
+    if names_only:
+        return _build_large(None, True)
+    if "large" not in _CASES:
+        _CASES["large"] = _build_large(nets(), False)
+    return _CASES["large"]
+
+
+def _build_large(N, names_only):
+    out = {}
+    rng = np.random.default_rng(12)
+    data = {} if names_only else {k: _restrict(s, dataset(LARGE_CANDIDATES, N[k][0], 7), N[k][1]) for k, s in zip(LARGE_NETS, LARGE_SETS)}
+
+    def add(name, net, batch, weighted=True, idx="random", tstride=None):
+        if names_only:
+            out[name] = None
+            return
+        a, W = N[net]
+        d = data[net]
+        n = len(d[0])
+        assert batch <= n
+        ix = rng.integers(0, n, batch) if isinstance(idx, str) else idx
+        out[name] = dict(W=W, atoms=a, data=d, idx=ix, batch=batch, weighted=weighted, tstride=tstride or a)
+
+    for b in LARGE_BATCHES:
+        add("fixture, batch %d" % b, "fixture", b)
+    b3 = RED_G * TILE + 1                                     # s1 = 3: fc_v's partial stride (64 x 128) against atoms x 128 outputs
+    add("seed7, batch %d, stride 64" % b3, "seed7", b3, tstride=64)
+    add("seed64, batch %d" % b3, "seed64", b3)
+    add("fitted, batch %d, unweighted, idx NULL" % (RED_G_FC * FC_KC), "fitted", RED_G_FC * FC_KC, weighted=False, idx=None)
+    return out
+
+
 def _build_cases(full, names_only=False):
     out, N = {}, nets()
     rng = np.random.default_rng(11)
@@ -180,6 +228,10 @@ def _build_cases(full, names_only=False):
         d=lambda: _restrict("fixture", dataset(CANDIDATES, 50, 7, normalised=False), N["fixture"][1]))
     add("fitted, targets off 1, batch 33, unweighted", "fitted", 33, weighted=False,
         d=lambda: _restrict("fitted", dataset(CANDIDATES, 50, 7, normalised=False), N["fitted"][1]))
+    if full:          # last, with candidate rows and a generator of their own: every case above keeps its rows and its index draw
+        large = large_cases(names_only)
+        assert not set(large) & set(out)
+        out.update(large)
     return out
 
 
@@ -209,9 +261,14 @@ def reference(name, case, dtype):
 
 
 # ---- the device side (imported lazily: the CPU tests use the references alone) ----
-def hip_grad(case, device="cuda", grad_fill=None):
+def hip_grad(case, device="cuda", grad_fill=None, place=None):
     """one tm_distnet_fit_grad call for a case: (flat gradient float32 array, loss [2] float32 array).  The targets' padding
-    (target_stride > atoms), the workspace and the outputs start as NaN: nothing of them may be read."""
+    (target_stride > atoms), the workspace and the outputs start as NaN: nothing of them may be read.
+
+    `place(n_workspace, n_grad, inputs)` may supply the three buffers the call writes, as float32 views (workspace, grad, loss)
+    of storage of its own (fit_hip_cases.Arena: guard bands around each); `inputs` is the dict of the device tensors the call
+    reads, handed over before the launch.  The buffers are filled as without `place`.  A read past an input cannot be seen
+    this way (a stray read changes nothing); stray stores within 64 KiB of a buffer and stores into an input can."""
     from tetris_mcts_amd import _lib
     lib = _lib.lib()
     (states, target, weight), idx, B, atoms, stride = case["data"], case["idx"], case["batch"], case["atoms"], case["tstride"]
@@ -230,9 +287,14 @@ def hip_grad(case, device="cuda", grad_fill=None):
         idx_t = None
     n_ws = lib.tm_distnet_fit_workspace(B, atoms)
     assert n_ws > 0
-    ws = torch.full((n_ws,), float("nan"), dtype=torch.float32, device=dev)
-    grad = torch.full((n_params(atoms),), float("nan") if grad_fill is None else grad_fill, dtype=torch.float32, device=dev)
-    loss = torch.full((2,), float("nan"), dtype=torch.float32, device=dev)
+    if place is None:
+        ws, grad, loss = (torch.empty(n, dtype=torch.float32, device=dev) for n in (n_ws, n_params(atoms), 2))
+    else:
+        ws, grad, loss = place(n_ws, n_params(atoms), dict(params=P, states=s8, targets=t, weight=w, idx=idx_t))
+        assert (ws.numel(), grad.numel(), loss.numel()) == (n_ws, n_params(atoms), 2) and all(b.dtype == torch.float32 for b in (ws, grad, loss))
+    ws.fill_(float("nan"))
+    grad.fill_(float("nan") if grad_fill is None else grad_fill)
+    loss.fill_(float("nan"))
     _lib.check(lib.tm_distnet_fit_grad(P.data_ptr(), s8.data_ptr(), t.data_ptr(), stride, w.data_ptr(),
                                        idx_t.data_ptr() if idx_t is not None else None, B, atoms, int(case["weighted"]),
                                        grad.data_ptr(), loss.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),

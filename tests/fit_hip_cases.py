@@ -20,6 +20,13 @@ if ROOT not in sys.path:
 M_CAP, U = 8.0, 2.0 ** -24
 N_LEARN = 478338
 BATCHES = (1, 31, 32, 33, 256, 512, 1000, 1024)
+# the batch decides the shape of the two-stage reductions of csrc/valuenet_fit.hip through s1 = ceil(B / FC_KC) splits of fc1's
+# weight gradient (added by k_vf_reduce<RED_G_FC> in 4 interleaved groups), hchunks = ceil(B / HEAD_CHUNK) partials of the FC bias
+# sums and chunks = ceil(B / SPW) partials of the convolutions' weight gradients (both added in RED_G = 16 groups).  BATCHES ends
+# at s1 = 4: LARGE_BATCHES are the smallest batches with a split of one sample (257) and with a group of more than one split
+# (1 025: s1 = 5, hchunks = 33, chunks = 257).  Their cases come after all others and draw from a generator of their own.
+FC_KC, HEAD_CHUNK, SPW, RED_G_FC, RED_G = 256, 32, 4, 4, 16
+LARGE_BATCHES = (FC_KC + 1, RED_G_FC * FC_KC + 1)
 
 
 def boards(n, seed):
@@ -131,6 +138,30 @@ def _restrict(data, net):
     return tuple(a[keep] for a in data)
 
 
+def _fresh_rows():
+    return _restrict(dataset(1800, 7), fresh_net(0))
+
+
+def large_cases(data=None):
+    """the regimes past BATCHES: a split of fc1's weight gradient that holds one sample, and more splits than the second stage has
+    groups.  `data` is the fresh net's filtered candidate set (built here when not given)."""
+    data = _fresh_rows() if data is None else data
+    n = len(data[0])
+    b1, b5 = LARGE_BATCHES
+    assert n >= b5
+    rng = np.random.default_rng(12)
+    out = {}
+    out["fresh net, batch %d" % b1] = dict(net=fresh_net(0), data=data, idx=rng.integers(0, n, b1), batch=b1, weighted=True)
+    out["fresh net, batch %d" % b5] = dict(net=fresh_net(0), data=data, idx=rng.integers(0, n, b5), batch=b5, weighted=True)
+    out["fresh net, batch %d, unweighted, idx NULL" % b5] = dict(net=fresh_net(0), data=data, idx=None, batch=b5, weighted=False)
+    ck = "value_net_online_r06.pt"
+    big = dataset(800, 21, scale=40.0)
+    big = _restrict(big, net_from_checkpoint(ck, big[1], big[2]))
+    out["%s, weighted, batch %d" % (ck, b5)] = dict(net=net_from_checkpoint(ck, big[1], big[2]), data=big,
+                                                   idx=rng.integers(0, len(big[0]), b5), batch=b5, weighted=True)
+    return out
+
+
 def cases(full=True):
     """name -> dict(net, data = (states, value, variance, weight), idx (array or None), batch, weighted)"""
     out = {}
@@ -138,7 +169,7 @@ def cases(full=True):
     gold = (g["tr_states"].reshape(-1, 200).astype(np.int8), g["tr_values"].reshape(-1).copy(), g["tr_variances"].reshape(-1).copy(),
             g["tr_weights"].reshape(-1) / g["tr_weights"].mean())
     out["golden batch, tr_params0"] = dict(net=net_from_flat(g["tr_params0"]), data=gold, idx=None, batch=48, weighted=True)
-    data = _restrict(dataset(1800, 7), fresh_net(0))
+    data = _fresh_rows()
     n = len(data[0])
     assert n >= 1024
     rng = np.random.default_rng(11)
@@ -163,6 +194,8 @@ def cases(full=True):
     with torch.no_grad():
         sat.head.fc_out.bias.copy_(torch.tensor([12.0, -12.0]))
     out["saturated sigmoid"] = dict(net=sat, data=data, idx=rng.integers(0, n, 64), batch=64, weighted=True)
+    if full:
+        out.update(large_cases(data))          # last, with a generator of their own: every case above keeps its index draw
     return out
 
 
@@ -199,8 +232,14 @@ def measure(got, g32, g64):
 
 
 # ---- the device side (imported lazily: the CPU tests use the references alone) ----
-def hip_grad(case, device="cuda", grad_fill=None):
-    """one tm_valuenet_fit_grad call for a case: (flat gradient [478338] float32 array, loss [2] float32 array)"""
+def hip_grad(case, device="cuda", grad_fill=None, place=None):
+    """one tm_valuenet_fit_grad call for a case: (flat gradient [478338] float32 array, loss [2] float32 array).
+
+    `place(n_workspace, n_grad, inputs)` may supply the three buffers the call writes, as float32 views (workspace, grad, loss)
+    of storage of its own (tests: an arena with guard bands, `Arena` below); `inputs` is the dict of the device tensors the call
+    reads, handed over before the launch so that the caller can copy them.  The buffers are filled as without `place`.  A read
+    past an input cannot be seen this way (a stray read changes nothing); stray stores within 64 KiB of a buffer and stores into
+    an input can."""
     from tetris_mcts_amd import _lib
     lib = _lib.lib()
     net, (states, value, variance, weight), idx, B = case["net"], case["data"], case["idx"], case["batch"]
@@ -218,15 +257,60 @@ def hip_grad(case, device="cuda", grad_fill=None):
         idx_t = None
     n_ws = lib.tm_valuenet_fit_workspace(B)
     assert n_ws > 0
-    ws = torch.full((n_ws,), float("nan"), dtype=torch.float32, device=dev)       # no initial contents required
-    grad = torch.full((N_LEARN,), float("nan") if grad_fill is None else grad_fill, dtype=torch.float32, device=dev)
-    loss = torch.full((2,), float("nan"), dtype=torch.float32, device=dev)
+    if place is None:
+        ws, grad, loss = (torch.empty(n, dtype=torch.float32, device=dev) for n in (n_ws, N_LEARN, 2))
+    else:
+        ws, grad, loss = place(n_ws, N_LEARN, dict(params=P, bounds=bounds, states=s8, value=val, variance=var, weight=w, idx=idx_t))
+        assert (ws.numel(), grad.numel(), loss.numel()) == (n_ws, N_LEARN, 2) and all(t.dtype == torch.float32 for t in (ws, grad, loss))
+    ws.fill_(float("nan"))                                                         # no initial contents required
+    grad.fill_(float("nan") if grad_fill is None else grad_fill)
+    loss.fill_(float("nan"))
     _lib.check(lib.tm_valuenet_fit_grad(P.data_ptr(), bounds.data_ptr(), s8.data_ptr(), val.data_ptr(), var.data_ptr(), w.data_ptr(),
                                         idx_t.data_ptr() if idx_t is not None else None, B, int(case["weighted"]), 0.1,
                                         grad.data_ptr(), loss.data_ptr(), ws.data_ptr(),
                                         torch.cuda.current_stream(dev).cuda_stream), "tm_valuenet_fit_grad")
     torch.cuda.synchronize()
     return grad.cpu().numpy(), loss.cpu().numpy()
+
+
+class Arena:
+    """The three buffers a fit call writes, carved out of one device tensor with a guard band of GUARD bytes before, between
+    and after them, for hip_grad's `place`.  Every segment starts on a 16-byte boundary and has exactly the size the ABI states;
+    the whole arena starts as PATTERN (a finite float, so that the guards compare as integers).  After the call `check()` asserts
+    that every byte outside the three segments is unchanged and that every input is bit-identical to the copy taken before the
+    launch.  What this cannot see: a read past an input or past a segment, and a store that lands inside another of the three
+    segments or beyond the guard bands."""
+    GUARD, PATTERN = 64 * 1024, 0x5A5A5A5A
+
+    def __init__(self, device="cuda"):
+        self.device, self.arena, self.segments, self.inputs, self.before = torch.device(device), None, [], None, None
+
+    def __call__(self, n_ws, n_grad, inputs):
+        g = self.GUARD // 4
+        off, self.segments = g, []
+        for n in (n_ws, n_grad, 2):
+            assert off % 4 == 0
+            self.segments.append((off, n))
+            off = (off + n + 3) // 4 * 4 + g          # the padding up to the 16-byte boundary belongs to the guard
+        self.arena = torch.full((off,), self.PATTERN, dtype=torch.int32, device=self.device)
+        assert self.arena.data_ptr() % 16 == 0
+        self.inputs = {k: v for k, v in inputs.items() if v is not None}
+        self.before = {k: v.clone() for k, v in self.inputs.items()}
+        views = [self.arena[o:o + n].view(torch.float32) for o, n in self.segments]
+        assert all(v.data_ptr() % 16 == 0 and v.data_ptr() == self.arena.data_ptr() + 4 * o for v, (o, n) in zip(views, self.segments))
+        return views
+
+    def check(self):
+        torch.cuda.synchronize()
+        outside = torch.ones(self.arena.numel(), dtype=torch.bool, device=self.device)
+        for o, n in self.segments:
+            outside[o:o + n] = False
+        assert int(outside.sum()) >= 4 * (self.GUARD // 4)
+        touched = torch.nonzero(outside & (self.arena != self.PATTERN)).flatten()
+        assert touched.numel() == 0, ("stores outside the buffers at float offsets", touched[:8].tolist(), self.segments)
+        for k, v in self.inputs.items():
+            a, b = v.cpu().numpy(), self.before[k].cpu().numpy()
+            assert a.tobytes() == b.tobytes(), ("input changed", k)
 
 
 def digest_case():

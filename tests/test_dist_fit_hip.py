@@ -299,13 +299,16 @@ def test_the_default_path_is_the_path_without_the_keyword():
 
 # ----------------------------------------------------------------------------------------------------------- the yardstick
 def test_the_kink_filter_keeps_its_cap():
-    """the filter drops at most a quarter of the candidate rows, for every net of the cases"""
+    """the filter drops at most a quarter of the candidate rows, for every net of the cases and for every candidate set of the
+    large-batch cases"""
     import dist_fit_cases as DC
     DC.cases(full=False)
-    assert set(DC.KINK_KEPT) == set(DC.nets())
+    DC.large_cases()
+    assert set(DC.KINK_KEPT) == set(DC.nets()) | set(DC.LARGE_SETS) and len(DC.KINK_KEPT) == len(DC.nets()) + len(DC.LARGE_NETS)
     for name, kept in DC.KINK_KEPT.items():
-        print("off the kink: %-12s keeps %.1f %% of %d rows" % (name, 100 * kept, DC.CANDIDATES))
+        print("off the kink: %-20s keeps %.1f %% of %d rows" % (name, 100 * kept, DC.candidates(name)))
         assert kept >= 1.0 - DC.KINK_CAP, (name, kept)
+    assert {DC.candidates(n) for n in DC.LARGE_SETS} == {1400} and {DC.candidates(n) for n in DC.nets()} == {420}
 
 
 def test_the_yardstick_has_a_denominator_in_every_regime():
@@ -329,6 +332,31 @@ def test_the_yardstick_has_a_denominator_in_every_regime():
         assert np.isfinite(l64[0]) and np.isfinite(l32[0])
         assert np.isfinite(l64[1]) == (case["batch"] > 1)          # torch.std_mean's n - 1: NaN for one sample
     assert seen >= 15
+
+
+def _distinct(states, targets):
+    """the number of distinct rows (a state with its target; empty boards under the same piece recur among the states alone)"""
+    return len(np.unique(np.concatenate([np.asarray(states, np.float32), np.asarray(targets, np.float32).reshape(len(states), -1)], 1), axis=0))
+
+
+def test_the_yardstick_has_a_denominator_in_the_large_batch_regimes():
+    """the cases past dist_fit_cases.BATCHES (batch 480 - 1 025, on candidate sets of 1 400 rows): finite references, torch's fp32
+    gradients differ from its fp64 gradients in every tensor, and every set has more distinct rows than the largest batch"""
+    import dist_fit_cases as DC
+    torch.set_num_threads(4)
+    large = DC.large_cases()
+    assert list(large) == DC.case_names()[-len(large):] == list(DC.large_cases(names_only=True)) and len(large) == 9
+    assert sorted(c["batch"] for c in large.values()) == [480, 512, 513, 513, 513, 1000, 1024, 1024, 1025]
+    null = large["fitted, batch 1024, unweighted, idx NULL"]
+    assert null["idx"] is None and _distinct(null["data"][0][:1024], null["data"][1][:1024]) == 1024
+    for name, case in large.items():
+        assert _distinct(*case["data"][:2]) > max(DC.LARGE_BATCHES), name
+        g64, l64 = DC.reference(name, case, torch.float64)
+        g32, l32 = DC.reference(name, case, torch.float32)
+        for t, a, b in zip(DC.TENSORS, g32, g64):
+            assert np.isfinite(b).all() and np.isfinite(a).all() and np.abs(b).max() > 0 and np.abs(a - b).max() > 0, (name, t)
+        assert all(np.isfinite(l64)) and all(np.isfinite(l32))
+        assert l32[0] != l64[0] and l32[1] != l64[1], (name, "the loss outputs' denominators")
 
 
 # ------------------------------------------------------------------------------------------------- code object and source

@@ -193,3 +193,22 @@ def test_the_yardstick_has_a_denominator_in_every_regime():
         for t, a in zip(FC.TENSORS, g):
             zero = t in ("conv1.weight", "conv1.bias", "conv2.weight", "conv2.bias", "conv3.weight", "conv3.bias", "fc1.weight")
             assert (np.abs(a).max() == 0) == zero, (t, dt)
+
+
+def test_the_yardstick_has_a_denominator_in_the_large_batch_regimes():
+    """the cases past fit_hip_cases.BATCHES (batch 257 and 1 025: more splits of fc1's weight gradient than its second stage has
+    groups): finite references, and torch's fp32 gradients differ from its fp64 gradients in every tensor"""
+    import fit_hip_cases as FC
+    torch.set_num_threads(4)
+    large = FC.large_cases()
+    assert sorted(c["batch"] for c in large.values()) == [257, 1025, 1025, 1025]
+    null = large["fresh net, batch 1025, unweighted, idx NULL"]
+    rows = np.concatenate([null["data"][0][:1025].astype(np.float32), null["data"][1][:1025].reshape(-1, 1)], 1)
+    assert null["idx"] is None and len(np.unique(rows, axis=0)) == 1025          # 1 025 distinct rows (a state with its value)
+    for name, case in large.items():
+        g64, l64 = FC.reference(case, torch.float64)
+        g32, l32 = FC.reference(case, torch.float32)
+        for t, a, b in zip(FC.TENSORS, g32, g64):
+            assert np.isfinite(a).all() and np.isfinite(b).all() and np.abs(b).max() > 0 and np.abs(a - b).max() > 0, (name, t)
+        assert all(np.isfinite(l64)) and all(np.isfinite(l32)) and l64[0] != 0
+        assert l32[0] != l64[0] and l32[1] != l64[1], (name, "the loss outputs' denominators")

@@ -24,7 +24,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # DC.BATCHES holds one batch at, below and above each, next to 1, 2 and 65 (the cases themselves are built at the first use)
 assert ({1, 2, 31, 32, 33, 65, 256} | {DC.SPW + d for d in (-1, 0, 1)} | {DC.FC_KC + d for d in (-1, 0, 1)}
         | {DC.RED_G + d for d in (-1, 0, 1)} | {60, 64, 65}) <= set(DC.BATCHES)
-assert (DC.SPW, DC.TILE, DC.FC_KC, DC.RED_G) == (4, 32, 256, 16)
+assert (DC.SPW, DC.TILE, DC.FC_KC, DC.RED_G, DC.RED_G_FC) == (4, 32, 256, 16, 4)
+# DC.LARGE_BATCHES: the ceil(B / 32) partials of the FC bias sums below, at and above the 16 groups (15 / 16 / 17 partials), and
+# the ceil(B / 256) splits of the FC weight gradients at 3 (a split of one sample), 4 (ragged and full) and 5 > the 4 groups of
+# k_df_reduce<4> (a last split of one sample); 1 024 is the batch of every DistValueSim fit
+assert set(DC.LARGE_BATCHES) == {480, 512, 513, 1000, 1024, 1025} and not set(DC.LARGE_BATCHES) & set(DC.BATCHES)
+assert [-(-b // DC.TILE) for b in (480, 512, 513)] == [DC.RED_G - 1, DC.RED_G, DC.RED_G + 1]
+assert [-(-b // DC.FC_KC) for b in (513, 1000, 1024, 1025)] == [3, DC.RED_G_FC, DC.RED_G_FC, DC.RED_G_FC + 1]
+assert (513 % DC.FC_KC, 1000 % DC.FC_KC, 1025 % DC.FC_KC) == (1, 7 * DC.TILE + 8, 1)
+assert max(-(-b // DC.FC_KC) for b in DC.BATCHES) == 2 and max(-(-b // DC.TILE) for b in DC.BATCHES) == 9          # what BATCHES reaches
+assert DC.case_names()[-len(DC.large_cases(names_only=True)):] == list(DC.large_cases(names_only=True))
+assert {"fixture, batch %d" % b for b in DC.LARGE_BATCHES} | {"seed7, batch 513, stride 64", "seed64, batch 513",
+                                                               "fitted, batch 1024, unweighted, idx NULL"} == set(DC.large_cases(names_only=True))
 
 
 @pytest.mark.parametrize("name", DC.case_names())
@@ -68,15 +79,37 @@ def test_same_bits_from_call_to_call_and_from_process_to_process():
     g1, l1 = DC.hip_grad(case)
     g2, l2 = DC.hip_grad(case)
     assert g1.tobytes() == g2.tobytes() and l1.tobytes() == l2.tobytes()
-    big = DC.cases()["fixture, batch 257"]
-    b1, b2 = DC.hip_grad(big), DC.hip_grad(big)
-    assert b1[0].tobytes() == b2[0].tobytes() and b1[1].tobytes() == b2[1].tobytes()
+    for big in ("fixture, batch 257", "fixture, batch 1025"):               # 1 025: groups of the second stages with two terms
+        b1, b2 = DC.hip_grad(DC.cases()[big]), DC.hip_grad(DC.cases()[big])
+        assert b1[0].tobytes() == b2[0].tobytes() and b1[1].tobytes() == b2[1].tobytes(), big
     mine = hashlib.sha256(g1.tobytes() + l1.tobytes()).hexdigest()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "dist_fit_cases.py"), "digest"], cwd=ROOT, capture_output=True,
                        text=True, timeout=600)                                 # a fresh child process
     assert r.returncode == 0, r.stderr[-2000:]
     theirs = [ln.split()[1] for ln in r.stdout.splitlines() if ln.startswith("DIGEST ")]
     assert theirs == [mine]
+
+
+@pytest.mark.parametrize("name,tstride", [("fixture, batch 1", None), ("fixture, batch 33", None), ("seed7, batch 33, stride 64", 7),
+                                          ("fixture, batch 257", None), ("fixture, batch 1025", None)])
+def test_the_call_writes_only_where_it_says(name, tstride):
+    """workspace (exactly tm_distnet_fit_workspace(batch, atoms) floats), grad (the parameter count) and loss (2) carved out of one
+    device tensor, each on a 16-byte boundary with 64 KiB of guard before, between and after (fit_hip_cases.Arena): after the call
+    every guard byte holds its pattern, every input (params, states, targets, weight, idx) is bit-identical to its copy from before
+    the call, and grad and loss are bit for bit what the call gives with buffers of the allocator's choosing.  50 atoms, and 7
+    atoms with a target stride of 7 (no padding between the rows).  Reads past an input cannot be seen this way."""
+    case = DC.cases()[name]
+    if tstride is not None:
+        case = dict(case, tstride=tstride)
+        assert case["atoms"] == tstride == 7
+    arena = DC.FC.Arena()
+    got, loss = DC.hip_grad(case, place=arena)
+    arena.check()
+    assert set(arena.inputs) == {"params", "states", "targets", "weight", "idx"}
+    print("%-28s arena of %d floats, segments (offset, floats) %s" % (name, arena.arena.numel(), arena.segments))
+    plain, plain_loss = DC.hip_grad(case)
+    assert np.isfinite(got).all() and got.tobytes() == plain.tobytes()
+    assert loss.tobytes() == plain_loss.tobytes() and np.isfinite(loss[0]) and np.isfinite(loss[1]) == (case["batch"] > 1)
 
 
 def test_refused_arguments_launch_nothing():

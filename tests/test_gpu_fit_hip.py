@@ -19,6 +19,12 @@ import fit_hip_cases as FC
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = FC.cases()
+# the kernels' blocking constants along the batch (csrc/valuenet_fit.hip) and the batches past them: a split of fc1's weight
+# gradient with one sample, and s1 = 5 splits for the 4 groups of k_vf_reduce<4> (with 33 > 16 partials of the FC bias sums)
+assert (FC.FC_KC, FC.HEAD_CHUNK, FC.SPW, FC.RED_G_FC, FC.RED_G) == (256, 32, 4, 4, 16) and FC.LARGE_BATCHES == (257, 1025)
+assert -(-1025 // FC.FC_KC) == 5 > FC.RED_G_FC and -(-1025 // FC.HEAD_CHUNK) == 33 > FC.RED_G and -(-1025 // FC.SPW) == 257
+assert list(CASES)[-4:] == ["fresh net, batch 257", "fresh net, batch 1025", "fresh net, batch 1025, unweighted, idx NULL",
+                            "value_net_online_r06.pt, weighted, batch 1025"]          # after every earlier case
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -75,15 +81,32 @@ def test_same_bits_from_call_to_call_and_from_process_to_process():
     g1, l1 = FC.hip_grad(case)
     g2, l2 = FC.hip_grad(case)
     assert g1.tobytes() == g2.tobytes() and l1.tobytes() == l2.tobytes()
-    big = CASES["fresh net, batch 1024"]
-    b1, b2 = FC.hip_grad(big), FC.hip_grad(big)
-    assert b1[0].tobytes() == b2[0].tobytes() and b1[1].tobytes() == b2[1].tobytes()
+    for big in ("fresh net, batch 1024", "fresh net, batch 1025"):          # 1 025: groups of the second stages with two terms
+        b1, b2 = FC.hip_grad(CASES[big]), FC.hip_grad(CASES[big])
+        assert b1[0].tobytes() == b2[0].tobytes() and b1[1].tobytes() == b2[1].tobytes(), big
     mine = hashlib.sha256(g1.tobytes() + l1.tobytes()).hexdigest()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fit_hip_cases.py"), "digest"], cwd=ROOT, capture_output=True,
                        text=True, timeout=600)                                 # a fresh child process
     assert r.returncode == 0, r.stderr[-2000:]
     theirs = [ln.split()[1] for ln in r.stdout.splitlines() if ln.startswith("DIGEST ")]
     assert theirs == [mine]
+
+
+@pytest.mark.parametrize("name", ["fresh net, batch 1", "fresh net, batch 33", "fresh net, batch 257", "fresh net, batch 1025"])
+def test_the_call_writes_only_where_it_says(name):
+    """workspace (exactly tm_valuenet_fit_workspace(batch) floats), grad (478 338) and loss (2) carved out of one device tensor,
+    each on a 16-byte boundary with 64 KiB of guard before, between and after (FC.Arena): after the call every guard byte holds
+    its pattern, every input (params, bounds, states, value, variance, weight, idx) is bit-identical to its copy from before the
+    call, and grad and loss are bit for bit what the call gives with buffers of the allocator's choosing.  Reads past an input
+    cannot be seen this way."""
+    case = CASES[name]
+    arena = FC.Arena()
+    got, loss = FC.hip_grad(case, place=arena)
+    arena.check()
+    assert set(arena.inputs) == {"params", "bounds", "states", "value", "variance", "weight", "idx"}
+    print("%-28s arena of %d floats, segments (offset, floats) %s" % (name, arena.arena.numel(), arena.segments))
+    plain, plain_loss = FC.hip_grad(case)
+    assert np.isfinite(got).all() and got.tobytes() == plain.tobytes() and loss.tobytes() == plain_loss.tobytes()
 
 
 def test_refused_arguments_launch_nothing():
