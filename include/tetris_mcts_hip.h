@@ -424,6 +424,33 @@ long long tm_distnet_fit_workspace(int batch, int atoms);
 int tm_distnet_fit_grad(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
                         const int64_t *idx, int batch, int atoms, int weighted, float *grad, float *loss, float *workspace,
                         void *stream);
+/* The validation pass of the value net's online fit (csrc/valuenet_fit.hip): the forward and the per-sample losses of
+ * tm_valuenet_fit_grad (the same kernels with idx NULL, the same statements for the loss) over the n held-out rows, reduced per chunk
+ * of `chunk` rows to what train.validation_loss collects: rows_out[c] = {w, mean, std} in double for the rows c*chunk up to
+ * min(n, (c+1)*chunk) - w the sum of their weights when weighted != 0, else their count; mean and population std (0 for one row)
+ * of their losses, the weight multiplied in when weighted != 0.  rows_out: ceil(n / chunk) x 3 doubles.  With n == chunk == slab the
+ * (float) of mean and std are the bits of the gradient step's loss[0], loss[1] on the same rows.  params, out_bounds, states, value,
+ * variance, weight: as for the gradient step, n rows of each.  The rows are forwarded `slab` at a time (slab >= chunk >= 1, a
+ * multiple of chunk, at most 2^20); the result does not depend on slab.  workspace: tm_valuenet_fit_validate_workspace(slab) floats
+ * (a function of slab alone, never of n), 16-byte aligned, no initial contents required.  Everything is enqueued on `stream`: no
+ * allocation, no host synchronisation, nothing read back, nothing written outside rows_out and the workspace.  Deterministic (no
+ * atomics; one workgroup per chunk adds in double in the order of the gradient step's loss).  hipErrorInvalidValue, and nothing
+ * launched, for a NULL pointer, n < 1, a chunk or slab that is refused, or a misaligned workspace.
+ * tm_valuenet_fit_validate_workspace is host arithmetic only (callable without a GPU): -1 for a slab that is refused. */
+long long tm_valuenet_fit_validate_workspace(int slab);
+int tm_valuenet_fit_validate(const float *params, const float *out_bounds, const int8_t *states, const float *value,
+                             const float *variance, const float *weight, long long n, int chunk, int slab, int weighted,
+                             float variance_clip, double *rows_out, float *workspace, void *stream);
+/* The validation pass of the distributional head's online fit (csrc/distnet_fit.hip): as the value net's above, with the forward and
+ * the per-sample losses of tm_distnet_fit_grad.  rows_out[c] = {w, mean, std}: std is the sample standard deviation (n - 1; NaN for
+ * a chunk of one row, as torch.std_mean - train's host loop maps it to 0).  params (16-byte aligned), states, target, target_stride,
+ * weight, atoms: as for the gradient step, n rows of each.  workspace: tm_distnet_fit_validate_workspace(slab, atoms) floats, 16-byte
+ * aligned.  hipErrorInvalidValue, and nothing launched, for a NULL pointer, n < 1, a chunk or slab that is refused, atoms outside
+ * 1..64, target_stride < atoms, or a misaligned workspace.  The workspace function is host arithmetic only: -1 when refused. */
+long long tm_distnet_fit_validate_workspace(int slab, int atoms);
+int tm_distnet_fit_validate(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
+                            long long n, int chunk, int slab, int atoms, int weighted, double *rows_out, float *workspace,
+                            void *stream);
 int tm_valuenet_prepare(const float *params, float *prepared, void *stream);
 int tm_valuenet_forward(const float *params, const float *prepared, const int8_t *states, int n, float *v, float *var,
                         float *scratch, void *stream);

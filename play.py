@@ -51,6 +51,8 @@ def build_parser():
     add('--fit_backend', default='torch', choices=('torch', 'hip', 'hip_dist'), help='[new] online mode: gradients of the fits '
         'through PyTorch autograd (torch) or the hand-written gfx950 forward / loss / backward kernels: hip for the value net '
         'of ValueSim, ValueSimLP and ValueSimC, hip_dist for the distributional head of DistValueSim')
+    add('--validation_backend', default='torch', choices=('torch', 'hip'), help='[new] online mode: validation of the fits through '
+        'PyTorch (torch) or the forward of the same gfx950 kernels (hip: needs --fit_backend hip or hip_dist)')
     return p
 
 
@@ -80,6 +82,8 @@ def main(argv=None):
         sys.exit('--agent_type is required (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     if args.fit_backend == 'hip_dist' and args.agent_type != 'DistValueSim':
         sys.exit('--fit_backend hip_dist applies to DistValueSim only')
+    if args.validation_backend == 'hip' and args.fit_backend == 'torch':
+        sys.exit('--validation_backend hip reads the parameters of a HIP fit: it needs --fit_backend hip or hip_dist')
     from importlib import import_module
     from pyTetris import Tetris                       # the reference's own two import lines (play.py:1,81-82)
     _agent_module = import_module('agents.' + args.agent_type)
@@ -94,6 +98,7 @@ def main(argv=None):
         sys.exit('--valuenet_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
     if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim'):
         extra['fit_backend'] = args.fit_backend      # (DistValueSim refuses 'hip' itself)
+        extra['validation_backend'] = args.validation_backend
     elif args.fit_backend != 'torch':
         sys.exit('--fit_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,

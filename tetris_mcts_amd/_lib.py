@@ -61,6 +61,10 @@ SYMBOLS = {
     "tm_distnet_fit_grad": [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "tm_valuenet_fit_workspace": [i32],      # (returns long long: restype set in lib())
     "tm_valuenet_fit_grad": [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp],
+    "tm_valuenet_fit_validate_workspace": [i32],         # (returns long long: restype set in lib())
+    "tm_valuenet_fit_validate": [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, C.c_float, vp, vp, vp],
+    "tm_distnet_fit_validate_workspace": [i32, i32],     # (returns long long: restype set in lib())
+    "tm_distnet_fit_validate": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
     "tm_valuenet_prepare": [vp, vp, vp],
     "tm_valuenet_forward": [vp, vp, vp, i32, vp, vp, vp, vp],
     "tm_valuenet_forward_plain": [vp, vp, i32, vp, vp, vp, vp],
@@ -106,6 +110,8 @@ def lib():
             f.argtypes, f.restype = args, i32
         L.tm_valuenet_fit_workspace.restype = C.c_longlong
         L.tm_distnet_fit_workspace.restype = C.c_longlong
+        L.tm_valuenet_fit_validate_workspace.restype = C.c_longlong
+        L.tm_distnet_fit_validate_workspace.restype = C.c_longlong
         L.tm_fill_norm_quantile.argtypes, L.tm_fill_norm_quantile.restype = [vp, i32], None
         L.tm_fill_norm_quantile_f64.argtypes, L.tm_fill_norm_quantile_f64.restype = [vp, i32], None
         L.tm_version.argtypes, L.tm_version.restype = [], C.c_char_p

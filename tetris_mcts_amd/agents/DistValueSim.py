@@ -26,10 +26,12 @@ class DistValueSim(TreeAgent):
 
     def __init__(self, atoms=50, vmin=0, vmax=5000, max_nodes=100000, model=None, evaluator=None, online=False,
                  min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, valuenet_backend=None, fit_backend="torch",
-                 **kwargs):
+                 validation_backend="torch", **kwargs):
         """fit_backend: how train_nodes takes the gradients of the head's fits - "torch" (autograd, torch.optim.Adam) or
         "hip_dist" (csrc/distnet_fit.hip and the fused Adam).  "hip" names the value net's step (csrc/valuenet_fit.hip: the
         Gaussian loss, not this head's) and is refused here.
+        validation_backend: how those fits validate - "torch" or "hip" (the same kernels' forward over the held-out rows; it
+        needs fit_backend="hip_dist").
         valuenet_backend: the Model_Dist backend of the model the agent builds when `model` is None (None: Model_Dist's
         default; "hip", "hip_bf16x3" - the split-precision kernels - or "torch").
         online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
@@ -39,7 +41,11 @@ class DistValueSim(TreeAgent):
         if fit_backend not in ("torch", "hip_dist"):
             raise ValueError("DistValueSim: fit_backend must be 'torch' or 'hip_dist', not %r ('hip' is the value net's gradient "
                              "step)" % (fit_backend,))
-        self.fit_backend = fit_backend
+        if validation_backend not in ("torch", "hip"):
+            raise ValueError("DistValueSim: validation_backend must be 'torch' or 'hip', not %r" % (validation_backend,))
+        if validation_backend == "hip" and fit_backend != "hip_dist":
+            raise ValueError("DistValueSim: validation_backend='hip' needs fit_backend='hip_dist'")
+        self.fit_backend, self.validation_backend = fit_backend, validation_backend
         kwargs.pop("min_visit", None)
         kwargs.pop("gamma", None)                      # the distributional backup does not discount
         self.atoms, self.vrange = int(atoms), (float(vmin), float(vmax))
@@ -156,7 +162,8 @@ class DistValueSim(TreeAgent):
             os.makedirs(os.path.dirname(os.path.abspath(dump_path)), exist_ok=True)
             np.savez(dump_path, states=data[0].cpu().numpy(), values=data[1].cpu().numpy(), weights=data[2].cpu().numpy())
         self.n_trains += 1
-        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend)     # DistValueSimOnline.py:165
+        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend,     # DistValueSimOnline.py:165
+                    validation_backend=self.validation_backend)
         opts.update(train_kwargs)
         res = self.model.train_data(data, **opts)
         self.model.training(False)

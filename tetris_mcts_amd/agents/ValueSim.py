@@ -12,13 +12,19 @@ class ValueSim(TreeAgent):
     low = 1
 
     def __init__(self, online=True, memory_size=500000, min_visits_to_store=10, gamma=0.999, memory_growth_rate=5000,
-                 max_nodes=100000, model=None, evaluator=None, valuenet_backend="hip", fit_backend="torch", **kwargs):
+                 max_nodes=100000, model=None, evaluator=None, valuenet_backend="hip", fit_backend="torch",
+                 validation_backend="torch", **kwargs):
         """`valuenet_backend`: the Model_VV backend of the model the agent builds when `model` is None ("hip", the default;
         "hip_bf16x3", the split-precision kernels; "torch").  `fit_backend`: how the online fits take their gradients
-        (train.train_data: "torch", the default, or "hip", csrc/valuenet_fit.hip)."""
+        (train.train_data: "torch", the default, or "hip", csrc/valuenet_fit.hip).  `validation_backend`: how they validate
+        ("torch", the default, or "hip": the same kernels' forward over the held-out rows; it needs fit_backend="hip")."""
         if fit_backend not in ("torch", "hip"):
             raise ValueError("fit_backend must be 'torch' or 'hip', not %r ('hip_dist' is DistValueSim's)" % (fit_backend,))
-        self.fit_backend = fit_backend
+        if validation_backend not in ("torch", "hip"):
+            raise ValueError("validation_backend must be 'torch' or 'hip', not %r" % (validation_backend,))
+        if validation_backend == "hip" and fit_backend != "hip":
+            raise ValueError("validation_backend='hip' needs fit_backend='hip'")
+        self.fit_backend, self.validation_backend = fit_backend, validation_backend
         kwargs.pop("min_visit", None)  # play.py:89 forwards it; the reference ValueSim ignores it too
         benchmark = kwargs.get("benchmark", False)
         # device-side harvest buffer per game (64 B per tuple); a GC at a 100 000-entry pool frees a few thousand
@@ -125,7 +131,8 @@ class ValueSim(TreeAgent):
         if dump_data:
             self.dump_training_set(dump_path, *data)
         self.n_trains += 1
-        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend)
+        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend,
+                    validation_backend=self.validation_backend)
         opts.update(train_kwargs)
         res = self.model.train_data(data, **opts)
         self.model.training(False)

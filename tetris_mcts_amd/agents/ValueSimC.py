@@ -72,7 +72,7 @@ class ValueSimC(ValueSim):
         if self.dump_path:
             self.dump_training_set(self.dump_path, state[:d_size], value[:d_size], variance[:d_size], visit[:d_size])
         opts = dict(iters_per_val=100, batch_size=512, max_iters=50000, sample_replacement=True, oversampling=False,
-                    fit_backend=self.fit_backend)
+                    fit_backend=self.fit_backend, validation_backend=self.validation_backend)
         opts.update(train_kwargs)
         res = self.model.train_data([state[:d_size], value[:d_size], variance[:d_size], visit[:d_size]], **opts)
         self.model.training(False)

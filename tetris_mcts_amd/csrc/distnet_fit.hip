@@ -22,6 +22,10 @@
 // Determinism: every output element, and every partial sum, is produced by one wave in one fixed order; batch reductions are
 // partial sums in the workspace and a second stage that adds them in a fixed order.  There are no atomics.  All launch shapes
 // follow from `batch` and `atoms` alone.
+//
+// The validation pass (tm_distnet_fit_validate) is the same forward (forward(): the same kernels and instantiations, idx NULL) over
+// the held-out rows, a slab at a time, k_df_head<false> for the per-sample losses and k_df_val_moments for each chunk's
+// {w, mean, n - 1 std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -207,6 +211,8 @@ __device__ __forceinline__ double wave_max(double v) {
 // ---- output layer, log-softmax, loss and their gradients: one wave per sample, lane a = atom a, in double ----
 // per = w sum_a (t log t - t log p); dzv[b][a] = (w / B) (p_a sum_a t - t_a) (zero for a >= atoms);
 // dh[b][i] = (sum_a dzv[a] Wv[a][i]) times 1 where h > 0, 0.01 elsewhere.
+// GRAD = false (the validation pass): per alone, by the same statements; dzv and dh are not touched.
+template <bool GRAD>
 __global__ __launch_bounds__(256) void k_df_head(const float* __restrict__ Wv, const float* __restrict__ bv,
                                                  const float* __restrict__ h, const float* __restrict__ target, int tstride,
                                                  const float* __restrict__ weight, const int64_t* __restrict__ idx, int B,
@@ -236,8 +242,9 @@ __global__ __launch_bounds__(256) void k_df_head(const float* __restrict__ Wv, c
     const double w = weighted ? (double)weight[row] : 1.0;
     const double term = t > 0.0 ? t * log(t) - t * logp : 0.0;
     const double loss = w * wave_sum(term);
-    const double dz = on ? (w / (double)B) * (p * T - t) : 0.0;
     if (lane == 0) per[b] = loss;
+    if (!GRAD) return;
+    const double dz = on ? (w / (double)B) * (p * T - t) : 0.0;
     dzv[(size_t)b * ROW + lane] = (float)dz;
     double g0 = 0.0, g1 = 0.0;
     for (int a = 0; a < atoms; ++a) {
@@ -525,22 +532,49 @@ __global__ __launch_bounds__(256) void k_df_reduce(const float* __restrict__ par
 // (one workgroup, double, fixed order)
 __global__ __launch_bounds__(256) void k_df_loss(const double* __restrict__ per, int B, float* __restrict__ loss) {
     __shared__ double sm[256];
-    double s = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) s += per[b];
-    const double mean = block_sum(s, sm) / (double)B;
-    double q = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        const double d = per[b] - mean;
-        q += d * d;
-    }
-    const double var = block_sum(q, sm) / (double)(B - 1);
+    double mean, ssq;
+    block_moments(per, B, sm, mean, ssq);
+    const double var = ssq / (double)(B - 1);
     if (threadIdx.x == 0) {
         loss[0] = (float)mean;
         loss[1] = (float)sqrt(var);
     }
 }
 
+// a validation pass's chunks of one slab: {w, mean, n - 1 std} per chunk (one workgroup each; fit_mma.h chunk_moments)
+__global__ __launch_bounds__(256) void k_df_val_moments(const double* __restrict__ per, const float* __restrict__ weight, int B,
+                                                        int chunk, int weighted, double* __restrict__ rows) {
+    __shared__ double sm[256];
+    chunk_moments<1>(per, weight, B, chunk, weighted, rows, sm);
+}
+
 static inline int blocks_for_waves(long long waves) { return (int)((waves + 3) / 4); }
+static inline long long tiles(long long n) { return (n + 31) / 32; }
+
+// the forward of B rows (states: int8 [.][200], row idx[b], or row b when idx is NULL) into a1, a2, h: the launches of the
+// gradient step and of the validation pass
+static void forward(const float* P, const int8_t* states, const int64_t* idx, int B, float* a1, float* a2, float* h, hipStream_t st) {
+    hipLaunchKernelGGL((k_df_conv_fwd<1, 22, 10, 0, S1, 3>), dim3(blocks_for_waves((tiles((long long)B * P1) + 2) / 3)), dim3(256), 0, st,
+                       P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
+    hipLaunchKernelGGL((k_df_conv_fwd<32, 19, 7, S1, P2, 2>), dim3(blocks_for_waves((tiles((long long)B * P2) + 1) / 2)), dim3(256), 0, st,
+                       P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
+    hipLaunchKernelGGL((k_df_fc1_fwd<1>), dim3(blocks_for_waves(4 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a2, B, h);
+}
+
+// the validation pass's workspace, in floats: the forward's activations of one slab and its per-row losses (doubles)
+struct ValLayout {
+    long long a1, a2, h, per, total;
+};
+__host__ inline ValLayout val_layout(int slab) {
+    ValLayout L;
+    long long o = 0, b = slab;
+    L.a1 = o; o += b * A1;
+    L.a2 = o; o += b * A2;
+    L.h = o; o += b * HID;
+    L.per = o; o += up4(b * 2);
+    L.total = o;
+    return L;
+}
 
 }  // namespace tmcts_df
 
@@ -567,15 +601,10 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
     double* per = reinterpret_cast<double*>(ws + L.per);
     const float* P = params;
     const int OFF_FVB = OFF_FVW + atoms * HID;
-    auto tiles = [](long long n) { return (n + 31) / 32; };
     // ---- forward ----
-    hipLaunchKernelGGL((k_df_conv_fwd<1, 22, 10, 0, S1, 3>), dim3(blocks_for_waves((tiles((long long)B * P1) + 2) / 3)), dim3(256), 0, st,
-                       P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
-    hipLaunchKernelGGL((k_df_conv_fwd<32, 19, 7, S1, P2, 2>), dim3(blocks_for_waves((tiles((long long)B * P2) + 1) / 2)), dim3(256), 0, st,
-                       P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
-    hipLaunchKernelGGL((k_df_fc1_fwd<1>), dim3(blocks_for_waves(4 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a2, B, h);
+    forward(P, states, idx, B, a1, a2, h, st);
     // ---- output layer, loss, and the bias sums of the two FC layers ----
-    hipLaunchKernelGGL(k_df_head, dim3((B + 3) / 4), dim3(256), 0, st, P + OFF_FVW, P + OFF_FVB, h, target, target_stride, weight, idx,
+    hipLaunchKernelGGL(k_df_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P + OFF_FVW, P + OFF_FVB, h, target, target_stride, weight, idx,
                        B, atoms, weighted, dzv, per, dh);
     hipLaunchKernelGGL(k_df_loss, dim3(1), dim3(256), 0, st, per, B, loss);
     hipLaunchKernelGGL(k_df_head_part, dim3(L.hchunks), dim3(HEAD_PART), 0, st, dzv, dh, B, hp);
@@ -602,6 +631,37 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
     hipLaunchKernelGGL((k_df_reduce<16>), dim3(512 / 16), dim3(256), 0, st, pw1, L.chunks, 512LL, 512, grad + OFF_C1W);
     hipLaunchKernelGGL((k_df_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 64LL, 32, grad + OFF_C1B);
     hipLaunchKernelGGL((k_df_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 64LL, 32, grad + OFF_C2B);
+    return (int)hipGetLastError();
+}
+
+long long tm_distnet_fit_validate_workspace(int slab, int atoms) {
+    if (slab < 1 || slab > tmcts_df::MAX_BATCH || atoms < 1 || atoms > tmcts_df::ROW) return -1;
+    return tmcts_df::val_layout(slab).total;
+}
+
+int tm_distnet_fit_validate(const float* params, const int8_t* states, const float* target, int target_stride, const float* weight,
+                            long long n, int chunk, int slab, int atoms, int weighted, double* rows_out, float* workspace,
+                            void* stream_) {
+    using namespace tmcts_df;
+    if (!params || !states || !target || !weight || !rows_out || !workspace) return (int)hipErrorInvalidValue;
+    if (n < 1 || chunk < 1 || slab < chunk || slab > MAX_BATCH || slab % chunk) return (int)hipErrorInvalidValue;
+    if (atoms < 1 || atoms > ROW || target_stride < atoms) return (int)hipErrorInvalidValue;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)params & 15) || ((uintptr_t)rows_out & 7)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream_;
+    const ValLayout L = val_layout(slab);
+    float *a1 = workspace + L.a1, *a2 = workspace + L.a2, *h = workspace + L.h;
+    double* per = reinterpret_cast<double*>(workspace + L.per);
+    const int OFF_FVB = OFF_FVW + atoms * HID;
+    // slab by slab on the one stream: a slab's kernels have read the workspace before the next slab's overwrite it
+    for (long long r0 = 0; r0 < n; r0 += slab) {
+        const int B = (int)(n - r0 < slab ? n - r0 : slab);
+        forward(params, states + r0 * 200, (const int64_t*)nullptr, B, a1, a2, h, st);
+        hipLaunchKernelGGL(k_df_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params + OFF_FVW, params + OFF_FVB, h,
+                           target + r0 * target_stride, target_stride, weight + r0, (const int64_t*)nullptr, B, atoms, weighted,
+                           (float*)nullptr, per, (float*)nullptr);
+        hipLaunchKernelGGL(k_df_val_moments, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
+                           rows_out + 3 * (r0 / chunk));
+    }
     return (int)hipGetLastError();
 }
 

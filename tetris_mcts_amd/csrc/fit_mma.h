@@ -1,6 +1,6 @@
-// What the two gradient steps (csrc/valuenet_fit.hip, csrc/distnet_fit.hip) share: the register layout of
-// v_mfma_f32_32x32x2_f32, a quad of K steps on NT tiles, the chunked accumulation and the wave / block sums of the second
-// stages.  Device inline functions only: each file keeps its own kernels.
+// What the two gradient steps and their validation passes (csrc/valuenet_fit.hip, csrc/distnet_fit.hip) share: the register
+// layout of v_mfma_f32_32x32x2_f32, a quad of K steps on NT tiles, the chunked accumulation, the wave / block sums of the second
+// stages and the moments of the per-sample losses.  Device inline functions only: each file keeps its own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -60,6 +60,44 @@ __device__ __forceinline__ double block_sum(double v, double* sm) {
     const double r = sm[0];
     __syncthreads();
     return r;
+}
+
+// mean of the n per-sample losses per[0..n) and the sum of their squared deviations from it, by a workgroup of 256 threads in
+// one fixed order (thread t takes the samples t, t + 256, ...).  The loss of a gradient step (k_vf_loss, k_df_loss) and a
+// chunk of a validation pass (chunk_moments) are both this function: the same losses give the same bits.
+__device__ __forceinline__ void block_moments(const double* __restrict__ per, int n, double* sm, double& mean, double& ssq) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < n; b += 256) s += per[b];
+    mean = block_sum(s, sm) / (double)n;
+    double q = 0.0;
+    for (int b = threadIdx.x; b < n; b += 256) {
+        const double d = per[b] - mean;
+        q += d * d;
+    }
+    ssq = block_sum(q, sm);
+}
+
+// One chunk of a validation pass (workgroup blockIdx.x of 256 threads): rows[3 c] = {w, mean, std} of the per-sample losses
+// of the slab's rows [c chunk, min(B, (c + 1) chunk)), in double.  w: the sum of the rows' weights (block_moments' order) when
+// `weighted`, else their count.  std divides by count - DDOF (the value net: 0; the head: 1, NaN for one row as torch.std_mean).
+template <int DDOF>
+__device__ __forceinline__ void chunk_moments(const double* __restrict__ per, const float* __restrict__ weight, int B, int chunk,
+                                              int weighted, double* __restrict__ rows, double* sm) {
+    const int b0 = blockIdx.x * chunk, cnt = min(chunk, B - b0);
+    if (cnt < 1) return;
+    double mean, ssq, w = (double)cnt;
+    block_moments(per + b0, cnt, sm, mean, ssq);
+    if (weighted) {
+        double s = 0.0;
+        for (int b = threadIdx.x; b < cnt; b += 256) s += (double)weight[b0 + b];
+        w = block_sum(s, sm);
+    }
+    if (threadIdx.x == 0) {
+        double* dst = rows + 3 * (size_t)blockIdx.x;
+        dst[0] = w;
+        dst[1] = mean;
+        dst[2] = sqrt(ssq / (double)(cnt - DDOF));
+    }
 }
 
 }  // namespace tmcts_fit

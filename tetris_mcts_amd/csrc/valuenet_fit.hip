@@ -21,6 +21,10 @@
 // Determinism: every output element, and every partial sum, is produced by one wave in one fixed order; batch reductions
 // (weight and bias gradients, the loss) are partial sums in the workspace and a second stage that adds them in a fixed
 // order.  There are no atomics.  All launch shapes follow from `batch` alone.
+//
+// The validation pass (tm_valuenet_fit_validate) is the same forward (forward(): the same kernels and instantiations, idx NULL)
+// over the held-out rows, a slab at a time, k_vf_head<false> for the per-sample losses and k_vf_val_moments for each chunk's
+// {w, mean, std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -200,6 +204,8 @@ __global__ __launch_bounds__(256) void k_vf_fc1_fwd(const float* __restrict__ Wf
 // ---- output layer, loss and their gradients: one wave per sample, in double ----
 // per = log var_p + ((value - v_p)^2 + max(variance, clip)) / var_p - log max(variance, clip) - 1, times the weight;
 // dzo[b][2] = d(mean of per) / d(fc_out pre-activation), dh[b][i] = (dzo . W_out[:, i]) where h > 0.
+// GRAD = false (the validation pass): per alone, by the same statements; dzo and dh are not touched.
+template <bool GRAD>
 __global__ __launch_bounds__(256) void k_vf_head(const float* __restrict__ P, const float* __restrict__ bounds,
                                                  const float* __restrict__ h, const float* __restrict__ value,
                                                  const float* __restrict__ variance, const float* __restrict__ weight,
@@ -229,11 +235,12 @@ __global__ __launch_bounds__(256) void k_vf_head(const float* __restrict__ P, co
     const size_t row = row_of(idx, b);
     const double val = (double)value[row], vt = (double)fmaxf(variance[row], clip), w = weighted ? (double)weight[row] : 1.0;
     const double diff = val - vp, num = diff * diff + vt;
+    if (lane == 0) per[b] = w * (log(varp) + num / varp - log(vt) - 1.0);
+    if (!GRAD) return;
     const double scale = w / (double)B;
     const double dvp = -2.0 * diff / varp * scale, dvarp = (1.0 / varp - num / (varp * varp)) * scale;
     const double g0 = dvp * (double)bounds[0] * ds[0], g1 = dvarp * (double)bounds[1] * ds[1];
     if (lane == 0) {
-        per[b] = w * (log(varp) + num / varp - log(vt) - 1.0);
         dzo[2 * b] = (float)g0;
         dzo[2 * b + 1] = (float)g1;
     }
@@ -499,22 +506,53 @@ __global__ __launch_bounds__(256) void k_vf_reduce(const float* __restrict__ par
 // mean and population standard deviation of the per-sample losses (one workgroup, double, fixed order)
 __global__ __launch_bounds__(256) void k_vf_loss(const double* __restrict__ per, int B, float* __restrict__ loss) {
     __shared__ double sm[256];
-    double s = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) s += per[b];
-    const double mean = block_sum(s, sm) / (double)B;
-    double q = 0.0;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        const double d = per[b] - mean;
-        q += d * d;
-    }
-    const double var = block_sum(q, sm) / (double)B;
+    double mean, ssq;
+    block_moments(per, B, sm, mean, ssq);
+    const double var = ssq / (double)B;
     if (threadIdx.x == 0) {
         loss[0] = (float)mean;
         loss[1] = (float)sqrt(var);
     }
 }
 
+// a validation pass's chunks of one slab: {w, mean, population std} per chunk (one workgroup each; fit_mma.h chunk_moments)
+__global__ __launch_bounds__(256) void k_vf_val_moments(const double* __restrict__ per, const float* __restrict__ weight, int B,
+                                                        int chunk, int weighted, double* __restrict__ rows) {
+    __shared__ double sm[256];
+    chunk_moments<0>(per, weight, B, chunk, weighted, rows, sm);
+}
+
 static inline int blocks_for_waves(long long waves) { return (int)((waves + 3) / 4); }
+static inline long long tiles(long long n) { return (n + 31) / 32; }
+
+// the forward of B rows (states: int8 [.][200], row idx[b], or row b when idx is NULL) into a1, a2, a3, h: the launches of the
+// gradient step and of the validation pass
+static void forward(const float* P, const int8_t* states, const int64_t* idx, int B, float* a1, float* a2, float* a3, float* h,
+                    hipStream_t st) {
+    hipLaunchKernelGGL((k_vf_conv_fwd<1, 20, 10, 3>), dim3(blocks_for_waves((tiles((long long)B * 144) + 2) / 3)), dim3(256), 0, st,
+                       P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
+    hipLaunchKernelGGL((k_vf_conv_fwd<32, 18, 8, 3>), dim3(blocks_for_waves((tiles((long long)B * 96) + 2) / 3)), dim3(256), 0, st,
+                       P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
+    hipLaunchKernelGGL((k_vf_conv_fwd<32, 16, 6, 2>), dim3(blocks_for_waves((tiles((long long)B * 56) + 1) / 2)), dim3(256), 0, st,
+                       P + OFF_C3W, P + OFF_C3B, a2, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a3);
+    hipLaunchKernelGGL((k_vf_fc1_fwd<1>), dim3(blocks_for_waves(8 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a3, B, h);
+}
+
+// the validation pass's workspace, in floats: the forward's activations of one slab and its per-row losses (doubles)
+struct ValLayout {
+    long long a1, a2, a3, h, per, total;
+};
+__host__ inline ValLayout val_layout(int slab) {
+    ValLayout L;
+    long long o = 0, b = slab;
+    L.a1 = o; o += b * A1;
+    L.a2 = o; o += b * A2;
+    L.a3 = o; o += b * A3;
+    L.h = o; o += b * HID;
+    L.per = o; o += up4(b * 2);
+    L.total = o;
+    return L;
+}
 
 }  // namespace tmcts_vf
 
@@ -541,17 +579,10 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
     float *pw1 = ws + L.pw1, *cb = ws + L.cb, *hp = ws + L.hp;
     double* per = reinterpret_cast<double*>(ws + L.per);
     const float* P = params;
-    auto tiles = [](long long n) { return (n + 31) / 32; };
     // ---- forward ----
-    hipLaunchKernelGGL((k_vf_conv_fwd<1, 20, 10, 3>), dim3(blocks_for_waves((tiles((long long)B * 144) + 2) / 3)), dim3(256), 0, st,
-                       P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
-    hipLaunchKernelGGL((k_vf_conv_fwd<32, 18, 8, 3>), dim3(blocks_for_waves((tiles((long long)B * 96) + 2) / 3)), dim3(256), 0, st,
-                       P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
-    hipLaunchKernelGGL((k_vf_conv_fwd<32, 16, 6, 2>), dim3(blocks_for_waves((tiles((long long)B * 56) + 1) / 2)), dim3(256), 0, st,
-                       P + OFF_C3W, P + OFF_C3B, a2, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a3);
-    hipLaunchKernelGGL((k_vf_fc1_fwd<1>), dim3(blocks_for_waves(8 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a3, B, h);
+    forward(P, states, idx, B, a1, a2, a3, h, st);
     // ---- output layer, loss, and the small batch sums ----
-    hipLaunchKernelGGL(k_vf_head, dim3((B + 3) / 4), dim3(256), 0, st, P, out_bounds, h, value, variance, weight, idx, B, weighted,
+    hipLaunchKernelGGL(k_vf_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P, out_bounds, h, value, variance, weight, idx, B, weighted,
                        variance_clip, dzo, per, dh);
     hipLaunchKernelGGL(k_vf_loss, dim3(1), dim3(256), 0, st, per, B, loss);
     hipLaunchKernelGGL(k_vf_head_part, dim3(L.hchunks), dim3(256), 0, st, dzo, h, dh, B, hp);
@@ -581,6 +612,35 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
     hipLaunchKernelGGL((k_vf_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 96LL, 32, grad + OFF_C1B);
     hipLaunchKernelGGL((k_vf_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 96LL, 32, grad + OFF_C2B);
     hipLaunchKernelGGL((k_vf_reduce<16>), dim3(2), dim3(256), 0, st, cb + 64, B, 96LL, 32, grad + OFF_C3B);
+    return (int)hipGetLastError();
+}
+
+long long tm_valuenet_fit_validate_workspace(int slab) {
+    if (slab < 1 || slab > tmcts_vf::MAX_BATCH) return -1;
+    return tmcts_vf::val_layout(slab).total;
+}
+
+int tm_valuenet_fit_validate(const float* params, const float* out_bounds, const int8_t* states, const float* value,
+                             const float* variance, const float* weight, long long n, int chunk, int slab, int weighted,
+                             float variance_clip, double* rows_out, float* workspace, void* stream_) {
+    using namespace tmcts_vf;
+    if (!params || !out_bounds || !states || !value || !variance || !weight || !rows_out || !workspace)
+        return (int)hipErrorInvalidValue;
+    if (n < 1 || chunk < 1 || slab < chunk || slab > MAX_BATCH || slab % chunk) return (int)hipErrorInvalidValue;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)rows_out & 7)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream_;
+    const ValLayout L = val_layout(slab);
+    float *a1 = workspace + L.a1, *a2 = workspace + L.a2, *a3 = workspace + L.a3, *h = workspace + L.h;
+    double* per = reinterpret_cast<double*>(workspace + L.per);
+    // slab by slab on the one stream: a slab's kernels have read the workspace before the next slab's overwrite it
+    for (long long r0 = 0; r0 < n; r0 += slab) {
+        const int B = (int)(n - r0 < slab ? n - r0 : slab);
+        forward(params, states + r0 * 200, (const int64_t*)nullptr, B, a1, a2, a3, h, st);
+        hipLaunchKernelGGL(k_vf_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params, out_bounds, h, value + r0, variance + r0,
+                           weight + r0, (const int64_t*)nullptr, B, weighted, variance_clip, (float*)nullptr, per, (float*)nullptr);
+        hipLaunchKernelGGL(k_vf_val_moments, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
+                           rows_out + 3 * (r0 / chunk));
+    }
     return (int)hipGetLastError();
 }
 

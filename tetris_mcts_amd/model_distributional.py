@@ -211,10 +211,15 @@ class Model_Dist:
         """data: [states [n,1,22,10], distributions [n,atoms], weights [n,1]]; Model.train_data (model/model.py:176-249) with
         this class's loss; data-parallel over the ranks as train.train_data describes.  fit_backend: "torch" (the default:
         autograd and the model's optimiser as it stands) or "hip_dist" (csrc/distnet_fit.hip's gradient step and the fused Adam;
-        train.HipDistFit lists what it needs); "hip" names the value net's step and is refused."""
+        train.HipDistFit lists what it needs); "hip" names the value net's step and is refused.  validation_backend (in kwargs): "torch"
+        or "hip" (csrc/distnet_fit.hip's validation pass; it needs fit_backend="hip_dist")."""
         from . import train as T
         if fit_backend not in ("torch", "hip_dist"):
             raise ValueError("Model_Dist.train_data: fit_backend must be 'torch' or 'hip_dist', not %r" % (fit_backend,))
+        if kwargs.get("validation_backend", "torch") not in ("torch", "hip"):
+            raise ValueError("Model_Dist.train_data: validation_backend must be 'torch' or 'hip', not %r" % (kwargs["validation_backend"],))
+        if kwargs.get("validation_backend", "torch") == "hip" and fit_backend != "hip_dist":
+            raise ValueError("Model_Dist.train_data: validation_backend='hip' needs fit_backend='hip_dist'")
         data = [torch.as_tensor(d, dtype=torch.float32, device=self.device) for d in data]
         best = {}
 

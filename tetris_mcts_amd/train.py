@@ -306,8 +306,15 @@ def validation_loss(net, data, weighted, chunk=1024, loss_fn=None):
         mean, std = loss_fn(net, b, weighted)
         w = b[-1].sum() if weighted else torch.full((), float(b[0].shape[0]), device=mean.device)
         rows.append(torch.stack([w.to(torch.float64), mean.to(torch.float64), std.to(torch.float64)]))
+    return combine_chunk_rows(torch.stack(rows).cpu().tolist())
+
+
+def combine_chunk_rows(rows):
+    """(mean, std) of a validation set from its chunks' [w, mean, std] (Python floats): the reference's arithmetic, in Python
+    doubles as there.  Both validation backends end here - "torch" with the rows validation_loss collected, "hip" with the rows
+    tm_valuenet_fit_validate / tm_distnet_fit_validate wrote."""
     tot_w, acc, acc2 = 0.0, 0.0, 0.0
-    for w, mean, std in torch.stack(rows).cpu().tolist():      # (the reference's arithmetic, in Python doubles as there)
+    for w, mean, std in rows:
         if math.isnan(std):
             std = 0.0
         tot_w += w
@@ -336,12 +343,26 @@ def flat_order_is_param_order(net, optimizer):
             and not any(named[k].requires_grad for k in PARAM_ORDER[10:] if k in named))
 
 
+# validation_backend="hip": the chunk is validation_loss's (the chunks' rows feed the same host combination), the slab the
+# number of rows forwarded per launch sequence (DESIGN 3.3 has the measurement behind it; the result does not depend on it)
+VALIDATION_CHUNK = 1024
+VALIDATION_SLAB = 4096
+
+
+def _validation_slab(rows, chunk, slab):
+    """the slab of a validation pass over `rows` rows: a multiple of `chunk`, no larger than the rows need"""
+    if chunk < 1 or slab < chunk or slab % chunk:
+        raise ValueError("validation_backend='hip' needs slab >= chunk >= 1 and a slab that is a multiple of the chunk, got "
+                         "chunk %d, slab %d" % (chunk, slab))
+    return min(slab, (rows + chunk - 1) // chunk * chunk)
+
+
 class HipFit:
     """The per-fit state of fit_backend="hip": the checks (once per fit), the int8 copy of the training states, the flattened
     targets, the output bounds and the workspace; grad(idx) is one call of tm_valuenet_fit_grad on the current stream."""
     N_PARAMS = 478338
 
-    def __init__(self, net, optimizer, train, batch):
+    def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB):
         from . import _lib
         from .model import Net
         if len(train) != 4:
@@ -361,6 +382,20 @@ class HipFit:
                              "whose fused() holds (float32 parameters on one GPU in a single group)")
         if any(t.shape[0] != rows for t in train[1:]) or any(t.numel() != rows for t in train[1:]):
             raise ValueError("fit_backend='hip' needs one value, variance and weight a row")
+        if val is not None:      # validation_backend="hip": the same checks on the held-out rows, before the optimiser is touched
+            V = "validation_backend='hip'"
+            vrows = val[0].shape[0]
+            if len(val) != 4 or vrows < 1 or val[0].numel() != vrows * 200:
+                raise ValueError(V + " needs validation data = [states of 20 x 10 cells a row, values, variances, weights]")
+            if not bool(((val[0] == val[0].round()) & (val[0].abs() <= 127)).all()):
+                raise ValueError(V + " reads the states as int8: they must be integers in [-127, 127]")
+            if not all(d.is_cuda and d.dtype == torch.float32 for d in val):
+                raise ValueError(V + " needs float32 CUDA tensors (the validation data is on %s)" % (val[0].device,))
+            if any(t.shape[0] != vrows or t.numel() != vrows for t in val[1:]):
+                raise ValueError(V + " needs one value, variance and weight a row")
+            val_slab = _validation_slab(vrows, val_chunk, val_slab)
+            if _lib.lib().tm_valuenet_fit_validate_workspace(val_slab) < 0:
+                raise ValueError(V + ": a slab of %d rows is refused" % val_slab)
         F = optimizer.flatten()
         if F["n"] != self.N_PARAMS or not flat_order_is_param_order(net, optimizer):
             raise ValueError("fit_backend='hip': the optimizer's flat buffers are not the net's learnable tensors in "
@@ -377,6 +412,25 @@ class HipFit:
         self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
         self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
         self._idx_checked = False
+        self.val_rows = 0
+        if val is not None:      # the int8 copy of the held-out states (once per fit), the slab's workspace and the chunks' rows
+            self.val_rows, self.val_chunk, self.val_slab = vrows, val_chunk, val_slab
+            self.val_states = val[0].reshape(vrows, 200).to(torch.int8).contiguous()
+            self.val_value, self.val_variance, self.val_weight = (t.reshape(vrows).contiguous() for t in val[1:])
+            self.val_ws = torch.empty(_lib.lib().tm_valuenet_fit_validate_workspace(val_slab), dtype=torch.float32, device=self.dev)
+            self.val_out = torch.zeros((vrows + val_chunk - 1) // val_chunk, 3, dtype=torch.float64, device=self.dev)
+
+    def validate(self, weighted):
+        """the held-out rows' [w, mean, std] per chunk (a list of lists of Python floats, what combine_chunk_rows takes), at the
+        optimiser's flat parameters as they stand: ONE call of tm_valuenet_fit_validate on the current stream and ONE .cpu()"""
+        if not self.val_rows:
+            raise ValueError("validation_backend='hip': this fit holds no validation rows")
+        self._lib.check(self._lib.lib().tm_valuenet_fit_validate(
+            self.F["p"].data_ptr(), self.bounds.data_ptr(), self.val_states.data_ptr(), self.val_value.data_ptr(),
+            self.val_variance.data_ptr(), self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab,
+            int(bool(weighted)), float(variance_bound), self.val_out.data_ptr(), self.val_ws.data_ptr(),
+            torch.cuda.current_stream(self.dev).cuda_stream), "tm_valuenet_fit_validate")
+        return self.val_out.cpu().tolist()
 
     def check_idx(self, idx):
         """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
@@ -439,7 +493,7 @@ class HipDistFit:
     int8 copy of the 20 visible rows of the training states, the targets, the weights and the workspace; grad(idx) is one call
     of tm_distnet_fit_grad on the current stream."""
 
-    def __init__(self, net, optimizer, train, batch):
+    def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB):
         from . import _lib
         from .model_distributional import Net, ROW
         B = "fit_backend='hip_dist'"
@@ -474,6 +528,27 @@ class HipDistFit:
             raise ValueError(B + " needs float32 CUDA tensors (the data is %s on %s)" % (states.dtype, states.device))
         if not optimizer.fused():
             raise ValueError(B + ": the FusedAdam's fused() must hold (float32 parameters on one GPU in a single group)")
+        if val is not None:      # validation_backend="hip": the same checks on the held-out rows, before the optimiser is touched
+            V = "validation_backend='hip'"
+            vrows = val[0].shape[0]
+            if len(val) != 3 or vrows < 1 or val[0].numel() != vrows * 220:
+                raise ValueError(V + " needs validation data = [states of 22 x 10 cells a row, targets, weights]")
+            v3 = val[0].reshape(vrows, 22, 10)
+            if val[1].dim() != 2 or val[1].shape[0] != vrows or val[1].shape[1] != atoms:
+                raise ValueError(V + " needs targets [rows, atoms] = [%d, %d], got %s" % (vrows, atoms, tuple(val[1].shape)))
+            if val[2].shape[0] != vrows or val[2].numel() != vrows:
+                raise ValueError(V + " needs one weight a row")
+            if not bool(((v3 == v3.round()) & (v3.abs() <= 127)).all()):
+                raise ValueError(V + " reads the states as int8: they must be integers in [-127, 127]")
+            if not bool((v3[:, :2] == 0).all()):
+                raise ValueError(V + " supplies the two top rows of the 22 itself: they must be all zero in the data")
+            if not bool((torch.isfinite(val[1]) & (val[1] >= 0)).all()):
+                raise ValueError(V + " needs finite targets >= 0")
+            if not all(d.is_cuda and d.dtype == torch.float32 for d in val):
+                raise ValueError(V + " needs float32 CUDA tensors (the validation data is %s on %s)" % (val[0].dtype, val[0].device))
+            val_slab = _validation_slab(vrows, val_chunk, val_slab)
+            if _lib.lib().tm_distnet_fit_validate_workspace(val_slab, atoms) < 0:
+                raise ValueError(V + ": a slab of %d rows is refused" % val_slab)
         F = optimizer.flatten()
         if F["n"] != 279232 + 129 * atoms or F["p"].device != states.device:
             raise ValueError(B + ": %d flat parameters on %s, expected %d on %s" % (F["n"], F["p"].device, 279232 + 129 * atoms, states.device))
@@ -489,6 +564,27 @@ class HipDistFit:
         self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
         self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
         self._idx_checked = False
+        self.val_rows = 0
+        if val is not None:      # the int8 copy of the held-out states (once per fit), the slab's workspace and the chunks' rows
+            self.val_rows, self.val_chunk, self.val_slab = vrows, val_chunk, val_slab
+            self.val_states = v3[:, 2:].reshape(vrows, 200).to(torch.int8).contiguous()
+            self.val_target = val[1].contiguous()
+            self.val_weight = val[2].reshape(vrows).contiguous()
+            self.val_ws = torch.empty(_lib.lib().tm_distnet_fit_validate_workspace(val_slab, atoms), dtype=torch.float32,
+                                      device=self.dev)
+            self.val_out = torch.zeros((vrows + val_chunk - 1) // val_chunk, 3, dtype=torch.float64, device=self.dev)
+
+    def validate(self, weighted):
+        """as HipFit.validate: the held-out rows' [w, mean, std] per chunk from ONE call of tm_distnet_fit_validate on the current
+        stream and ONE .cpu() (a one-row chunk's std is NaN, as torch.std_mean's: combine_chunk_rows maps it to 0)"""
+        if not self.val_rows:
+            raise ValueError("validation_backend='hip': this fit holds no validation rows")
+        self._lib.check(self._lib.lib().tm_distnet_fit_validate(
+            self.F["p"].data_ptr(), self.val_states.data_ptr(), self.val_target.data_ptr(), self.val_target.stride(0),
+            self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab, self.atoms, int(bool(weighted)),
+            self.val_out.data_ptr(), self.val_ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream),
+            "tm_distnet_fit_validate")
+        return self.val_out.cpu().tolist()
 
     def check_idx(self, idx):
         """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
@@ -516,7 +612,8 @@ class HipDistFit:
 def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validation_fraction=0.1,
                sample_replacement=True, oversampling=False, weighted=True, early_stopping=True, early_stopping_patience=10,
                early_stopping_threshold=1.0, shuffle=False, max_iters=100000, grad_clip=0.0, save=None, load=None,
-               generator=None, log=True, data_parallel=True, group=None, loss_fn=None, fit_backend="torch"):
+               generator=None, log=True, data_parallel=True, group=None, loss_fn=None, fit_backend="torch",
+               validation_backend="torch"):
     """data = [states f32 [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (device tensors); with `loss_fn`
     (net, batch, weighted) -> (mean, std) any list of arrays whose LAST one holds the sample weights (Model.train_data is
     generic in the reference too, model/model.py:176-249: the model class supplies `_loss`).
@@ -537,10 +634,22 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     refuses anything else with a ValueError (HipFit).  "hip_dist" is the same for the distributional head: ONE call of
     tm_distnet_fit_grad (csrc/distnet_fit.hip) for model_distributional.Net + Model_Dist.loss on data = [states [n,1,22,10],
     targets [n,atoms], weights [n,1]] with a FusedAdam (HipDistFit); validation goes through `loss_fn` (Model_Dist's own, or
-    dist_batch_loss when none is given) on torch."""
+    dist_batch_loss when none is given) on torch.
+
+    `validation_backend`: "torch" (the default) validates with validation_loss (eager forwards, 1 024 rows at a time); "hip"
+    replaces that call with ONE call of tm_valuenet_fit_validate / tm_distnet_fit_validate on the current stream (the gradient
+    step's own forward and per-sample losses over the held-out rows, reduced per chunk of 1 024 on the device) and one .cpu()
+    of the chunks' rows, which feed the same host combination (combine_chunk_rows).  It reads the optimiser's flat parameter
+    buffer as it stands, so it needs fit_backend "hip" or "hip_dist" and refuses anything else with a ValueError before the
+    model, the optimiser or a sampling stream is touched; with validation_fraction 0 it is accepted and does nothing."""
     import torch.distributed as tdist
     if fit_backend not in ("torch", "hip", "hip_dist"):
         raise ValueError("fit_backend must be 'torch', 'hip' or 'hip_dist', not %r" % (fit_backend,))
+    if validation_backend not in ("torch", "hip"):
+        raise ValueError("validation_backend must be 'torch' or 'hip', not %r" % (validation_backend,))
+    if validation_backend == "hip" and fit_backend == "torch":
+        raise ValueError("validation_backend='hip' reads the flat parameter buffer of a HIP fit: it needs fit_backend='hip' or "
+                         "'hip_dist' (a custom loss_fn, CPU tensors and the torch fit validate with validation_backend='torch')")
     if fit_backend == "hip_dist":
         if loss_fn is not None and not getattr(loss_fn, "is_model_dist_loss", False):
             raise ValueError("fit_backend='hip_dist' computes Model_Dist.loss: a custom loss_fn needs fit_backend='torch'")
@@ -577,8 +686,9 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     iters_done = 0
     net.train()
     # the one-kernel optimiser step (Yogi on the GPU): parameters and gradients are views of flat buffers from here on
-    hip = (HipFit(net, optimizer, train, batch_size // world) if fit_backend == "hip" else
-           HipDistFit(net, optimizer, train, batch_size // world) if fit_backend == "hip_dist" else None)
+    hip_val = val if validation_backend == "hip" else None
+    hip = (HipFit(net, optimizer, train, batch_size // world, val=hip_val) if fit_backend == "hip" else
+           HipDistFit(net, optimizer, train, batch_size // world, val=hip_val) if fit_backend == "hip_dist" else None)
     if hip is not None and hip.rows != n - n_val:      # every draw below is an index into [0, n - n_val): the rows the kernels hold
         raise ValueError("fit_backend=%r: %d training rows, but the index draws cover %d" % (fit_backend, hip.rows, n - n_val))
     flat_g = optimizer.flat_grad() if hasattr(optimizer, "flat_grad") else None
@@ -652,9 +762,12 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
             one_iteration()
         iters_done = it + 1
         if (it + 1) % iters_per_val == 0 and val is not None:
-            net.eval()
-            vmean, vstd = validation_loss(net, val, weighted, loss_fn=loss_fn)
-            net.train()
+            if hip_val is not None:
+                vmean, vstd = combine_chunk_rows(hip.validate(weighted))
+            else:
+                net.eval()
+                vmean, vstd = validation_loss(net, val, weighted, loss_fn=loss_fn)
+                net.train()
             vstd /= max(n_val, 1) ** 0.5
             mark = ""
             if early_stopping:
