@@ -43,6 +43,11 @@ extern "C" {
 #define TM_VALUENET_PREPARED 477184    /* floats: conv2 + conv3 + fc1 operand streams */
 #define TM_VALUENET_PREPARED_X3 27648  /* floats (55 296 bf16): conv2 + conv3 weights as bf16 hi / mid / lo planes, tm_valuenet_prepare_x3;
                                           the _x3 forwards take TM_VALUENET_SCRATCH_MFMA floats of scratch per state, as the fp32 ones */
+#define TM_VALUENET_PREPARED_FC1_X3 688128  /* floats (1 376 256 bf16 = 3 x 256 x 1 792): fc1's weights as bf16 hi / mid / lo planes,
+                                          tm_valuenet_prepare_fc1_x3 */
+/* fc1 of the TM_VALUENET_BF16X3 backend (tm_search_set_valuenet_fc1) */
+#define TM_VALUENET_FC1_FP32 0         /* k_vn_fc1: the fp32 fma chain (the default) */
+#define TM_VALUENET_FC1_BF16X3 1       /* k_vn_fc1_x3, tm_valuenet_forward_requests_x3f: fc1 as a three-way bf16 split as well */
 /* evaluator backends of the native search loop (tm_search_set_valuenet) */
 #define TM_VALUENET_FP32 0             /* tm_valuenet_forward_requests: fp32 matrix cores, the oracle's bits (the default) */
 #define TM_VALUENET_BF16X3 1           /* tm_valuenet_forward_requests_x3 (TM_KIND_DIST: tm_distnet_forward_requests_x3): the
@@ -316,6 +321,14 @@ int tm_search_set_epoch(tm_search *h, int epoch);
  * backend's outputs an epoch of their own (tm_search_set_epoch): obs_eval must not mix the two (TM_KIND_DIST keeps no
  * obs_eval). */
 int tm_search_set_valuenet(tm_search *h, int backend);
+/* fc1 of the value net under TM_VALUENET_BF16X3: TM_VALUENET_FC1_FP32 (the default) or TM_VALUENET_FC1_BF16X3
+ * (tm_valuenet_forward_requests_x3f).  Under TM_VALUENET_FC1_BF16X3, vn_prepared points at TM_VALUENET_PREPARED +
+ * TM_VALUENET_PREPARED_X3 + TM_VALUENET_PREPARED_FC1_X3 floats, in that order: tm_valuenet_prepare's streams, then
+ * tm_valuenet_prepare_x3's planes, then tm_valuenet_prepare_fc1_x3's.  hipErrorInvalidValue for any other value, on a
+ * TM_KIND_DIST store, and for TM_VALUENET_FC1_BF16X3 while the backend is not TM_VALUENET_BF16X3 (set the backend first;
+ * setting the backend to TM_VALUENET_FP32 puts fc1 back to TM_VALUENET_FC1_FP32).  Its outputs get an epoch of their own, as
+ * every backend's. */
+int tm_search_set_valuenet_fc1(tm_search *h, int mode);
 int tm_root_stats(const tm_store *s, float *stats /* [G][3][7] */, int32_t *action /* [G] */, void *stream);
 /* one game's tree in the reference's array layout (agents/agent.py:58-88), for inspection and tests */
 int tm_export_game(const tm_store *s, int game, int32_t *child /* [N][7] */, float *score, int32_t *n_to_o,
@@ -477,6 +490,16 @@ int tm_valuenet_forward_x3(const float *params, const float *prepared, const flo
                            float *v, float *var, float *scratch, void *stream);
 int tm_valuenet_forward_requests_x3(const float *params, const float *prepared, const float *prepared_x3, const tm_store *s,
                                     float *scratch, void *stream);
+/* The same backend with fc1 split as well (valuenet_fc1_x3.inc, k_vn_fc1_x3): fc1's weights and its
+ * input as three bf16 planes each, six plane products per step of 32 k, fp32 accumulation from the bias, the output layer in
+ * fp32 as always.  Not bit-equal to the _x3 entries above; a state's outputs depend on that state only.
+ * tm_valuenet_prepare_fc1_x3 writes fc1's planes (TM_VALUENET_PREPARED_FC1_X3 floats, after every weight change).  A NULL
+ * prepared_x3 or prepared_fc1_x3: hipErrorInvalidValue. */
+int tm_valuenet_prepare_fc1_x3(const float *params, float *prepared_fc1_x3, void *stream);
+int tm_valuenet_forward_x3f(const float *params, const float *prepared, const float *prepared_x3, const float *prepared_fc1_x3,
+                            const int8_t *states, int n, float *v, float *var, float *scratch, void *stream);
+int tm_valuenet_forward_requests_x3f(const float *params, const float *prepared, const float *prepared_x3,
+                                     const float *prepared_fc1_x3, const tm_store *s, float *scratch, void *stream);
 
 /* distributional value head (model/model_distributional.py:18-57 `Net`, Model_Dist.inference :100-107), the leaf evaluator
  * of TM_KIND_DIST: states int8 [n][200] (the 20 visible rows; the net's two extra rows on top are empty) -> softmax over

@@ -48,6 +48,9 @@ def build_parser():
     add('--valuenet_backend', default='hip', choices=('hip', 'hip_bf16x3', 'torch'), help='[new] value net of ValueSim, '
         'ValueSimLP and ValueSimC, distributional head of DistValueSim: hip (fp32 matrix cores), hip_bf16x3 (split-precision '
         'bf16 matrix cores) or torch')
+    add('--valuenet_fc1', default='fp32', choices=('fp32', 'bf16x3'), help='[new] fc1 of the value net of ValueSim, ValueSimLP and '
+        'ValueSimC under --valuenet_backend hip_bf16x3: fp32 (the fp32 matrix pipe) or bf16x3 (split-precision as the '
+        'convolutions; for the leaf-parallel kinds)')
     add('--fit_backend', default='torch', choices=('torch', 'hip', 'hip_dist'), help='[new] online mode: gradients of the fits '
         'through PyTorch autograd (torch) or the hand-written gfx950 forward / loss / backward kernels: hip for the value net '
         'of ValueSim, ValueSimLP and ValueSimC, hip_dist for the distributional head of DistValueSim')
@@ -84,6 +87,11 @@ def main(argv=None):
         sys.exit('--fit_backend hip_dist applies to DistValueSim only')
     if args.validation_backend == 'hip' and args.fit_backend == 'torch':
         sys.exit('--validation_backend hip reads the parameters of a HIP fit: it needs --fit_backend hip or hip_dist')
+    if args.valuenet_fc1 != 'fp32':
+        if args.agent_type not in ('ValueSim', 'ValueSimLP', 'ValueSimC'):
+            sys.exit('--valuenet_fc1 applies to ValueSim, ValueSimLP and ValueSimC only (the distributional head has no such option)')
+        if args.valuenet_backend != 'hip_bf16x3':
+            sys.exit('--valuenet_fc1 bf16x3 needs --valuenet_backend hip_bf16x3')
     from importlib import import_module
     from pyTetris import Tetris                       # the reference's own two import lines (play.py:1,81-82)
     _agent_module = import_module('agents.' + args.agent_type)
@@ -96,6 +104,8 @@ def main(argv=None):
         extra['valuenet_backend'] = args.valuenet_backend
     elif args.valuenet_backend != 'hip':
         sys.exit('--valuenet_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
+    if args.valuenet_fc1 != 'fp32':
+        extra['valuenet_fc1'] = args.valuenet_fc1
     if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim'):
         extra['fit_backend'] = args.fit_backend      # (DistValueSim refuses 'hip' itself)
         extra['validation_backend'] = args.validation_backend

@@ -89,6 +89,10 @@ SYMBOLS = {
     "tm_search_stats": [vp, vp, i32, i32],
     "tm_search_set_epoch": [vp, i32],
     "tm_search_set_valuenet": [vp, i32],
+    "tm_valuenet_prepare_fc1_x3": [vp, vp, vp],
+    "tm_valuenet_forward_x3f": [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "tm_valuenet_forward_requests_x3f": [vp, vp, vp, vp, C.POINTER(TmStore), vp, vp],
+    "tm_search_set_valuenet_fc1": [vp, i32],
 }
 
 _lib = None

@@ -13,9 +13,10 @@ class ValueSim(TreeAgent):
 
     def __init__(self, online=True, memory_size=500000, min_visits_to_store=10, gamma=0.999, memory_growth_rate=5000,
                  max_nodes=100000, model=None, evaluator=None, valuenet_backend="hip", fit_backend="torch",
-                 validation_backend="torch", **kwargs):
+                 validation_backend="torch", valuenet_fc1="fp32", **kwargs):
         """`valuenet_backend`: the Model_VV backend of the model the agent builds when `model` is None ("hip", the default;
-        "hip_bf16x3", the split-precision kernels; "torch").  `fit_backend`: how the online fits take their gradients
+        "hip_bf16x3", the split-precision kernels; "torch"), `valuenet_fc1` its fc1 ("fp32", the default; "bf16x3": fc1 split
+        as well, with "hip_bf16x3" only - Model_VV refuses any other pairing).  `fit_backend`: how the online fits take their gradients
         (train.train_data: "torch", the default, or "hip", csrc/valuenet_fit.hip).  `validation_backend`: how they validate
         ("torch", the default, or "hip": the same kernels' forward over the held-out rows; it needs fit_backend="hip")."""
         if fit_backend not in ("torch", "hip"):
@@ -40,7 +41,12 @@ class ValueSim(TreeAgent):
         self.min_visits_to_store = min_visits_to_store
         self.evaluator = evaluator
         if evaluator is None:
-            self.model = model if model is not None else Model(backend=valuenet_backend)
+            if model is not None:
+                self.model = model
+            elif valuenet_fc1 == "fp32":
+                self.model = Model(backend=valuenet_backend)
+            else:
+                self.model = Model(backend=valuenet_backend, fc1=valuenet_fc1)
             if model is None:
                 self.model.load()
             self.model.training(False)

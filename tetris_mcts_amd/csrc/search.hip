@@ -44,6 +44,7 @@ struct tm_search {
     double tree_ms, nn_ms;
     long long n_timed, n_runs, extra_launches, launches, gc_launches;
     int vn_backend = TM_VALUENET_FP32;   // tm_search_set_valuenet
+    int vn_fc1 = TM_VALUENET_FC1_FP32;   // tm_search_set_valuenet_fc1
 };
 
 #define TM_TRY(x) do { int e_ = (int)(x); if (e_ != 0) return e_; } while (0)
@@ -196,6 +197,9 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
             return tm_distnet_forward_requests(vn_params, vn_prepared, &h->sub[k], scr, st[k]);
         }
         float* scr = vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA;
+        if (h->vn_backend == TM_VALUENET_BF16X3 && h->vn_fc1 == TM_VALUENET_FC1_BF16X3)      // ... then fc1's planes (tm_search_set_valuenet_fc1)
+            return tm_valuenet_forward_requests_x3f(vn_params, vn_prepared, vn_prepared + TM_VALUENET_PREPARED,
+                                                    vn_prepared + TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3, &h->sub[k], scr, st[k]);
         if (h->vn_backend == TM_VALUENET_BF16X3)      // vn_prepared: the fp32 operand streams, then the planes (tm_search_set_valuenet)
             return tm_valuenet_forward_requests_x3(vn_params, vn_prepared, vn_prepared + TM_VALUENET_PREPARED, &h->sub[k], scr, st[k]);
         return tm_valuenet_forward_requests(vn_params, vn_prepared, &h->sub[k], scr, st[k]);
@@ -286,6 +290,16 @@ int tm_search_set_epoch(tm_search* h, int epoch) {
 int tm_search_set_valuenet(tm_search* h, int backend) {
     if (backend != TM_VALUENET_FP32 && backend != TM_VALUENET_BF16X3) return (int)hipErrorInvalidValue;
     h->vn_backend = backend;
+    if (backend == TM_VALUENET_FP32) h->vn_fc1 = TM_VALUENET_FC1_FP32;      // (the split fc1 belongs to the split backend)
+    return 0;
+}
+
+// fc1 of the value net under TM_VALUENET_BF16X3 (include/tetris_mcts_hip.h: TM_VALUENET_FC1_FP32 / TM_VALUENET_FC1_BF16X3)
+int tm_search_set_valuenet_fc1(tm_search* h, int mode) {
+    if (mode != TM_VALUENET_FC1_FP32 && mode != TM_VALUENET_FC1_BF16X3) return (int)hipErrorInvalidValue;
+    if (h->full.kind == TM_KIND_DIST) return (int)hipErrorInvalidValue;
+    if (mode == TM_VALUENET_FC1_BF16X3 && h->vn_backend != TM_VALUENET_BF16X3) return (int)hipErrorInvalidValue;
+    h->vn_fc1 = mode;
     return 0;
 }
 

@@ -554,6 +554,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 4
 }
 
 #include "valuenet_x3.inc"
+#include "valuenet_fc1_x3.inc"
 
 }  // namespace tmcts_vn
 
@@ -592,6 +593,29 @@ static int vn_fc1_launch(const float* P, const float* prepared, const ReqList& r
     return vn_fc1_launch_shape<2, 4, 256, 6, 2, 1>(P, prepared, rq, n, v, var, scratch, stream);
 }
 
+// k_vn_fc1_x3 (valuenet_fc1_x3.inc) in k_vn_fc1's place.  Two shapes, both 6 bytes x 4 096 elements of planes a buffer: tiles of 32
+// states in chunks of 128 k, one workgroup a CU (the single-leaf kinds: a launch's items fit one round), and tiles of 64 states
+// in chunks of 64 k, two workgroups a CU, once the 32-state tiles of n rows would be more than two rounds of the former's grid
+// (n > 4 096 on 256 CUs: the leaf-parallel kinds' request slots; half the weight traffic a state).
+template <int RT, int NY, int KC, int WRING, int PF, int WG_PER_CU>
+static int vn_fc1_x3_launch_shape(const float* P, const __bf16* fc1_planes, const ReqList& rq, int n, float* v, float* var,
+                                  float* scratch, hipStream_t stream, int cus) {
+    constexpr int SS = TM_VALUENET_SCRATCH_MFMA, ROWS = 16 * RT;
+    const int items = fc1_item_count(n, ROWS, NY), resident = cus * WG_PER_CU;
+    hipLaunchKernelGGL((k_vn_fc1_x3<RT, NY, KC, WRING, PF>), dim3(items < resident ? items : resident), dim3(512), 0, stream, P,
+                       fc1_planes, scratch, SS, n, scratch + A3, SS, rq, reinterpret_cast<int32_t*>(scratch + A3 + HID), ROWS * SS,
+                       v, var);
+    return (int)hipGetLastError();
+}
+static int vn_fc1_x3_launch(const float* P, const __bf16* fc1_planes, const ReqList& rq, int n, float* v, float* var,
+                            float* scratch, hipStream_t stream) {
+    const int cus = vn_compute_units();
+    if (cus <= 0) return (int)hipErrorInvalidDevice;
+    if (fc1_item_count(n, 32, 4) > 2 * cus)
+        return vn_fc1_x3_launch_shape<4, 4, 64, 3, 2, 2>(P, fc1_planes, rq, n, v, var, scratch, stream, cus);
+    return vn_fc1_x3_launch_shape<2, 4, 128, 6, 2, 1>(P, fc1_planes, rq, n, v, var, scratch, stream, cus);
+}
+
 extern "C" {
 
 int tm_valuenet_prepare(const float* P, float* prepared, void* stream_) {
@@ -620,10 +644,11 @@ int tm_valuenet_forward_plain(const float* P, const int8_t* states, int n, float
     return (int)hipGetLastError();
 }
 
-// planes != nullptr: the convolutions of the split-precision backend (k_vn_conv_x3), fc1 and the output layer as always
+// planes != nullptr: the convolutions of the split-precision backend (k_vn_conv_x3), fc1 and the output layer as always -
+// unless fc1_planes != nullptr: k_vn_fc1_x3
 static int vn_forward_impl(const float* P, const float* prepared, const __bf16* planes, const int8_t* states,
                            const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n, float* v, float* var,
-                           float* scratch, hipStream_t stream) {
+                           float* scratch, hipStream_t stream, const __bf16* fc1_planes = nullptr) {
     if (n <= 0) return 0;
     constexpr int SS = TM_VALUENET_SCRATCH_MFMA;   // a3 (1792) + hidden (256) + 16 pad words (word 0 of a tile's first row: its arrival counter)
     static_assert(SS >= A3 + HID + 1 && SS % 4 == 0, "scratch row");
@@ -653,6 +678,7 @@ static int vn_forward_impl(const float* P, const float* prepared, const __bf16* 
         hipLaunchKernelGGL(k_vn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, obs_key, rq,
                            max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
     }
+    if (fc1_planes) return vn_fc1_x3_launch(P, fc1_planes, rq, n, v, var, scratch, stream);
     return vn_fc1_launch(P, prepared, rq, n, v, var, scratch, stream);
 }
 
@@ -706,6 +732,31 @@ int tm_valuenet_forward_requests_x3(const float* P, const float* prepared, const
     const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
     return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->obs_key, rq, s->max_nodes,
                            s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
+}
+
+// ---- the same backend with fc1 split as well (valuenet_fc1_x3.inc) ----
+int tm_valuenet_prepare_fc1_x3(const float* P, float* prepared_fc1_x3, void* stream_) {
+    if (!prepared_fc1_x3) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_vn_prepare_fc1_x3, dim3((HID * A3 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
+                       reinterpret_cast<__bf16*>(prepared_fc1_x3));
+    return (int)hipGetLastError();
+}
+
+int tm_valuenet_forward_x3f(const float* P, const float* prepared, const float* prepared_x3, const float* prepared_fc1_x3,
+                            const int8_t* states, int n, float* v, float* var, float* scratch, void* stream_) {
+    if (!prepared_x3 || !prepared_fc1_x3) return (int)hipErrorInvalidValue;
+    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), states, nullptr,
+                           ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch, (hipStream_t)stream_,
+                           reinterpret_cast<const __bf16*>(prepared_fc1_x3));
+}
+
+int tm_valuenet_forward_requests_x3f(const float* P, const float* prepared, const float* prepared_x3, const float* prepared_fc1_x3,
+                                     const tm_store* s, float* scratch, void* stream_) {
+    if (!prepared_x3 || !prepared_fc1_x3) return (int)hipErrorInvalidValue;
+    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
+    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->obs_key, rq, s->max_nodes,
+                           s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_,
+                           reinterpret_cast<const __bf16*>(prepared_fc1_x3));
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@ tests/test_gpu_heads_accuracy.py).  Back ends:
                    three bf16 planes (six plane products, fp32 accumulation), the rest as
                    "hip": the same accuracy contract (for operands of magnitude 2^-110 and above: planes below
                    bf16's normal range are lost, DESIGN.md section 4), not bit-equal to "hip" (opt-in);
+                   with fc1="bf16x3" fc1 is split the same way (tm_valuenet_forward_x3f, k_vn_fc1_x3: opt-in, for
+                   the leaf-parallel kinds; fc1="fp32", the default, keeps k_vn_fc1);
   * "torch"      — PyTorch-ROCm ops (MIOpen / rocBLAS), used for training and as a cross-check.
 """
 import ctypes as C
@@ -29,6 +31,8 @@ PREPARED = 477184       # TM_VALUENET_PREPARED: floats of tm_valuenet_prepare's 
 PREPARED_X3 = 27648     # TM_VALUENET_PREPARED_X3: floats of tm_valuenet_prepare_x3's bf16 planes
 HIP_BACKENDS = ("hip", "hip_bf16x3")    # the backends the native search loop (search.hip) runs
 VALUENET_BACKEND = {"hip": 0, "hip_bf16x3": 1}      # TM_VALUENET_FP32 / TM_VALUENET_BF16X3 (tm_search_set_valuenet)
+PREPARED_FC1_X3 = 688128    # TM_VALUENET_PREPARED_FC1_X3: floats of tm_valuenet_prepare_fc1_x3's bf16 planes
+VALUENET_FC1 = {"fp32": 0, "bf16x3": 1}             # TM_VALUENET_FC1_FP32 / TM_VALUENET_FC1_BF16X3 (tm_search_set_valuenet_fc1)
 PARAM_ORDER = ["head.conv1.weight", "head.conv1.bias", "head.conv2.weight", "head.conv2.bias", "head.conv3.weight",
                "head.conv3.bias", "head.fc1.weight", "head.fc1.bias", "head.fc_out.weight", "head.fc_out.bias",
                "out_ubound", "out_lbound"]
@@ -66,9 +70,14 @@ class Net(nn.Module):
 class Model_VV:
     """Inference-side mirror of the reference's Model_VV (load / inference / training(False))."""
 
-    def __init__(self, backend="hip", device="cuda", seed=None, **kwargs):
+    def __init__(self, backend="hip", device="cuda", seed=None, fc1="fp32", **kwargs):
+        if fc1 not in VALUENET_FC1:
+            raise ValueError("Model_VV: fc1 is 'fp32' or 'bf16x3', not %r" % (fc1,))
+        if fc1 == "bf16x3" and backend != "hip_bf16x3":
+            raise ValueError("Model_VV: fc1='bf16x3' belongs to backend='hip_bf16x3', not %r" % (backend,))
         if seed is not None:
             torch.manual_seed(seed)
+        self.fc1 = fc1
         self.device = torch.device(device)
         self.model = Net().to(self.device).eval()
         self.backend = backend
@@ -186,8 +195,13 @@ class Model_VV:
             if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[1] < SCRATCH_MFMA:
                 self._scratch = torch.zeros(B, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
             P, prep = self.flat_params(), self._prepared_x3()
-            _lib.check(_lib.lib().tm_valuenet_forward_x3(_p(P), _p(prep), _p(prep[PREPARED:]), _p(states), B, _p(v_out),
-                                                         _p(var_out), _p(self._scratch), _stream()), "tm_valuenet_forward_x3")
+            if self.fc1 == "bf16x3":
+                _lib.check(_lib.lib().tm_valuenet_forward_x3f(_p(P), _p(prep), _p(prep[PREPARED:]),
+                                                              _p(prep[PREPARED + PREPARED_X3:]), _p(states), B, _p(v_out),
+                                                              _p(var_out), _p(self._scratch), _stream()), "tm_valuenet_forward_x3f")
+            else:
+                _lib.check(_lib.lib().tm_valuenet_forward_x3(_p(P), _p(prep), _p(prep[PREPARED:]), _p(states), B, _p(v_out),
+                                                             _p(var_out), _p(self._scratch), _stream()), "tm_valuenet_forward_x3")
         elif self.backend == "hip_plain":
             if self._scratch_plain is None or self._scratch_plain.shape[0] < B:
                 self._scratch_plain = torch.empty(B, 9728, dtype=torch.float32, device=self.device)
@@ -202,19 +216,26 @@ class Model_VV:
     def _prepared_x3(self):
         """"hip_bf16x3": one buffer of PREPARED + PREPARED_X3 floats, tm_valuenet_prepare's operand streams (fc1 runs on them)
         followed by tm_valuenet_prepare_x3's planes - the layout tm_search_run takes under TM_VALUENET_BF16X3.  It lives in
-        _prepared, so everything that invalidates the fp32 streams (set_flat_params, load, train_data) invalidates the planes."""
+        _prepared, so everything that invalidates the fp32 streams (set_flat_params, load, train_data) invalidates the planes.
+        fc1="bf16x3": PREPARED_FC1_X3 more floats behind them, tm_valuenet_prepare_fc1_x3's planes of fc1
+        (tm_search_set_valuenet_fc1's layout)."""
         if self._prepared is None:
             P = self.flat_params()
-            prep = torch.empty(PREPARED + PREPARED_X3, dtype=torch.float32, device=self.device)
+            x3f = self.fc1 == "bf16x3"
+            prep = torch.empty(PREPARED + PREPARED_X3 + (PREPARED_FC1_X3 if x3f else 0), dtype=torch.float32, device=self.device)
             _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(prep), _stream()), "tm_valuenet_prepare")
             _lib.check(_lib.lib().tm_valuenet_prepare_x3(_p(P), _p(prep[PREPARED:]), _stream()), "tm_valuenet_prepare_x3")
+            if x3f:
+                _lib.check(_lib.lib().tm_valuenet_prepare_fc1_x3(_p(P), _p(prep[PREPARED + PREPARED_X3:]), _stream()),
+                           "tm_valuenet_prepare_fc1_x3")
             self._prepared = prep
         return self._prepared
 
     @torch.no_grad()
     def hip_buffers(self, n_states):
         """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip); for
-        "hip_bf16x3" the prepared buffer holds the planes behind the streams (tm_search_set_valuenet)."""
+        "hip_bf16x3" the prepared buffer holds the planes behind the streams (tm_search_set_valuenet), and fc1's planes behind
+        those under fc1="bf16x3" (tm_search_set_valuenet_fc1)."""
         if self._scratch is None or self._scratch.shape[0] < n_states or self._scratch.shape[1] < SCRATCH_MFMA:
             self._scratch = torch.zeros(n_states, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
         P = self.flat_params()
@@ -235,6 +256,12 @@ class Model_VV:
         P = self.flat_params()
         if self.backend == "hip_bf16x3":
             prep = self._prepared_x3()
+            if self.fc1 == "bf16x3":
+                _lib.check(_lib.lib().tm_valuenet_forward_requests_x3f(_p(P), _p(prep), _p(prep[PREPARED:]),
+                                                                       _p(prep[PREPARED + PREPARED_X3:]), C.byref(store.s),
+                                                                       _p(self._scratch), _stream()),
+                           "tm_valuenet_forward_requests_x3f")
+                return
             _lib.check(_lib.lib().tm_valuenet_forward_requests_x3(_p(P), _p(prep), _p(prep[PREPARED:]), C.byref(store.s),
                                                                   _p(self._scratch), _stream()), "tm_valuenet_forward_requests_x3")
             return
