@@ -29,10 +29,10 @@ SPW = 4             # samples per wave of the convolutions' weight-gradient part
 TILE = 32           # the matrix core's tile (fc1 forward and data gradient: 32 samples a wave), HEAD_CHUNK (samples per partial of the
                     # FC bias sums) and the 32-sample chunks of the FC weight gradients' K
 FC_KC = 256         # samples per split of the FC weight gradients; also the threads of the loss kernel's strided sum
-RED_G = 16          # k_df_reduce<16> adds its S partials in 16 interleaved groups: S = B (the convolutions' bias sums) passes 16
+RED_G = 16          # k_fit_reduce<16> adds its S partials in 16 interleaved groups: S = B (the convolutions' bias sums) passes 16
                     # at B = 16, S = ceil(B / SPW) (their weight gradients) at B = 64, S = ceil(B / TILE) (the FC bias sums) at
                     # B = 512 (LARGE_BATCHES: 480 / 512 / 513)
-RED_G_FC = 4        # k_df_reduce<4> adds the s1 = ceil(B / FC_KC) splits of the two FC weight gradients in 4 groups: s1 passes
+RED_G_FC = 4        # k_fit_reduce<4> adds the s1 = ceil(B / FC_KC) splits of the two FC weight gradients in 4 groups: s1 passes
                     # 4 at B = 1 025 (LARGE_BATCHES: 1 000 / 1 024 / 1 025; 1 024 is the batch every DistValueSim fit uses)
 # (k_df_head's four samples a workgroup is SPW's 3 / 4 / 5 again)
 BATCHES = (1, 2, SPW - 1, SPW, SPW + 1, RED_G - 1, RED_G, RED_G + 1, TILE - 1, TILE, TILE + 1, RED_G * SPW - SPW, RED_G * SPW,

@@ -21,7 +21,7 @@ M_CAP, U = 8.0, 2.0 ** -24
 N_LEARN = 478338
 BATCHES = (1, 31, 32, 33, 256, 512, 1000, 1024)
 # the batch decides the shape of the two-stage reductions of csrc/valuenet_fit.hip through s1 = ceil(B / FC_KC) splits of fc1's
-# weight gradient (added by k_vf_reduce<RED_G_FC> in 4 interleaved groups), hchunks = ceil(B / HEAD_CHUNK) partials of the FC bias
+# weight gradient (added by k_fit_reduce<RED_G_FC> in 4 interleaved groups), hchunks = ceil(B / HEAD_CHUNK) partials of the FC bias
 # sums and chunks = ceil(B / SPW) partials of the convolutions' weight gradients (both added in RED_G = 16 groups).  BATCHES ends
 # at s1 = 4: LARGE_BATCHES are the smallest batches with a split of one sample (257) and with a group of more than one split
 # (1 025: s1 = 5, hchunks = 33, chunks = 257).  Their cases come after all others and draw from a generator of their own.

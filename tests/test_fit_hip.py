@@ -142,7 +142,7 @@ def test_command_lines_list_the_flag():
 
 
 def test_fit_kernels_use_no_scratch_memory(tmp_path):
-    """every kernel of csrc/valuenet_fit.hip: no private segment, no spilled registers (read from the built code object)"""
+    """every kernel of csrc/valuenet_fit.hip (csrc/fit_mma.h's shared ones included): no private segment, no spilled registers (read from the built code object)"""
     import shutil
     objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
     obj = os.path.join(ROOT, "tetris_mcts_amd", "csrc", "_obj", "valuenet_fit.o")
@@ -158,19 +158,20 @@ def test_fit_kernels_use_no_scratch_memory(tmp_path):
     notes = subprocess.check_output([readelf, "--notes", str(tmp_path / cos[0])]).decode()
     found = re.findall(r"\.name:\s+(\S+)\s.*?\.private_segment_fixed_size:\s+(\d+).*?\.sgpr_spill_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", notes, re.S)
     names = [n for n, _, _, _ in found]
-    for want in ("k_vf_conv_fwd", "k_vf_fc1_fwd", "k_vf_head", "k_vf_fc1_dw", "k_vf_fc1_bwd_data", "k_vf_conv_bwd_data", "k_vf_conv_dw",
-                 "k_vf_reduce", "k_vf_loss"):
+    for want in ("k_vf_conv_fwd", "k_fit_fc1_fwd", "k_vf_head", "k_vf_fc1_dw", "k_fit_fc1_bwd_data", "k_vf_conv_bwd_data", "k_vf_conv_dw",
+                 "k_fit_reduce", "k_fit_loss", "k_fit_val_moments"):
         assert any(want in n for n in names), want
     assert len(found) >= 15
     for name, scratch, sspill, vspill in found:
-        assert "k_vf_" in name and "k_vn_conv" not in name and "k_vn_fc1" not in name, name
+        assert ("k_vf_" in name or "k_fit_" in name) and "k_vn_conv" not in name and "k_vn_fc1" not in name, name
         assert int(scratch) == 0 and int(sspill) == 0 and int(vspill) == 0, (name, scratch, sspill, vspill)
 
 
 def test_the_source_has_no_atomics():
-    src = open(os.path.join(ROOT, "tetris_mcts_amd", "csrc", "valuenet_fit.hip")).read().lower()
-    code = "\n".join(ln.split("//")[0] for ln in src.splitlines())
-    assert "atomic" not in code and "hipmalloc" not in code and "synchronize" not in code and "memcpy" not in code
+    for f in ("valuenet_fit.hip", "fit_mma.h"):
+        src = open(os.path.join(ROOT, "tetris_mcts_amd", "csrc", f)).read().lower()
+        code = "\n".join(ln.split("//")[0] for ln in src.splitlines())
+        assert "atomic" not in code and "hipmalloc" not in code and "synchronize" not in code and "memcpy" not in code, f
 
 
 def test_the_yardstick_has_a_denominator_in_every_regime():

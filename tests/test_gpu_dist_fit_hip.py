@@ -20,14 +20,14 @@ import dist_fit_cases as DC
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the kernels' blocking constants along the batch (csrc/distnet_fit.hip): SPW = 4 (and k_df_head's four samples a workgroup), the
-# 32-sample tile / HEAD_CHUNK / K chunk, FC_KC = 256, and the 16 groups of k_df_reduce over B and over ceil(B / 4) partials;
+# 32-sample tile / HEAD_CHUNK / K chunk, FC_KC = 256, and the 16 groups of k_fit_reduce over B and over ceil(B / 4) partials;
 # DC.BATCHES holds one batch at, below and above each, next to 1, 2 and 65 (the cases themselves are built at the first use)
 assert ({1, 2, 31, 32, 33, 65, 256} | {DC.SPW + d for d in (-1, 0, 1)} | {DC.FC_KC + d for d in (-1, 0, 1)}
         | {DC.RED_G + d for d in (-1, 0, 1)} | {60, 64, 65}) <= set(DC.BATCHES)
 assert (DC.SPW, DC.TILE, DC.FC_KC, DC.RED_G, DC.RED_G_FC) == (4, 32, 256, 16, 4)
 # DC.LARGE_BATCHES: the ceil(B / 32) partials of the FC bias sums below, at and above the 16 groups (15 / 16 / 17 partials), and
 # the ceil(B / 256) splits of the FC weight gradients at 3 (a split of one sample), 4 (ragged and full) and 5 > the 4 groups of
-# k_df_reduce<4> (a last split of one sample); 1 024 is the batch of every DistValueSim fit
+# k_fit_reduce<4> (a last split of one sample); 1 024 is the batch of every DistValueSim fit
 assert set(DC.LARGE_BATCHES) == {480, 512, 513, 1000, 1024, 1025} and not set(DC.LARGE_BATCHES) & set(DC.BATCHES)
 assert [-(-b // DC.TILE) for b in (480, 512, 513)] == [DC.RED_G - 1, DC.RED_G, DC.RED_G + 1]
 assert [-(-b // DC.FC_KC) for b in (513, 1000, 1024, 1025)] == [3, DC.RED_G_FC, DC.RED_G_FC, DC.RED_G_FC + 1]

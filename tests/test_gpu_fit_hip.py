@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = FC.cases()
 # the kernels' blocking constants along the batch (csrc/valuenet_fit.hip) and the batches past them: a split of fc1's weight
-# gradient with one sample, and s1 = 5 splits for the 4 groups of k_vf_reduce<4> (with 33 > 16 partials of the FC bias sums)
+# gradient with one sample, and s1 = 5 splits for the 4 groups of k_fit_reduce<4> (with 33 > 16 partials of the FC bias sums)
 assert (FC.FC_KC, FC.HEAD_CHUNK, FC.SPW, FC.RED_G_FC, FC.RED_G) == (256, 32, 4, 4, 16) and FC.LARGE_BATCHES == (257, 1025)
 assert -(-1025 // FC.FC_KC) == 5 > FC.RED_G_FC and -(-1025 // FC.HEAD_CHUNK) == 33 > FC.RED_G and -(-1025 // FC.SPW) == 257
 assert list(CASES)[-4:] == ["fresh net, batch 257", "fresh net, batch 1025", "fresh net, batch 1025, unweighted, idx NULL",

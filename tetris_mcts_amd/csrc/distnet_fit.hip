@@ -24,7 +24,7 @@
 // follow from `batch` and `atoms` alone.
 //
 // The validation pass (tm_distnet_fit_validate) is the same forward (forward(): the same kernels and instantiations, idx NULL) over
-// the held-out rows, a slab at a time, k_df_head<false> for the per-sample losses and k_df_val_moments for each chunk's
+// the held-out rows, a slab at a time, k_df_head<false> for the per-sample losses and k_fit_val_moments<1> for each chunk's
 // {w, mean, n - 1 std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -43,9 +43,6 @@ constexpr int SPW = 4;                  // samples per wave of the convolutions'
 constexpr int FC_KC = 256;              // samples per split of the two FC weight gradients
 constexpr int HEAD_CHUNK = 32;          // samples per partial of the bias sums of fc1 and fc_v
 constexpr int HEAD_PART = HID + ROW;    // floats of such a partial: db_fc1[128], db_v[64]
-constexpr float SLOPE = 0.01f;
-
-__host__ __device__ constexpr long long up4(long long x) { return (x + 3) / 4 * 4; }
 
 // The workspace, in floats (every segment starts at a multiple of four: 16-byte loads).
 struct Layout {
@@ -75,8 +72,6 @@ __host__ inline Layout layout(int B) {
     L.total = o;
     return L;
 }
-
-__device__ __forceinline__ float leaky(float v) { return v > 0.0f ? v : SLOPE * v; }
 
 // ---- forward convolution 4 x 4: z[co][b, p] = bias[co] + sum_k W[co][k] in[b][ci][(y + ky) IW + x + kx], LeakyReLU ----
 // M = 32 output channels, N = B * OP positions, K = CIN * 16.  CIN == 1: the input is the int8 state of row idx[b] under two
@@ -143,62 +138,7 @@ __global__ __launch_bounds__(256) void k_df_conv_fwd(const float* __restrict__ W
         if (ok[t]) {
             float* dst = out + (size_t)nb[t] * (32 * OSTR) + np[t];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dst[drow(r, half) * OSTR] = leaky(tot[t][r]);
-        }
-}
-
-// ---- fc1 forward: h[b][j] = leaky(bias[j] + sum_k Wf[j][k] a2[b][k]); M = 128 units, N = B, K = 2048 ----
-template <int NT>
-__global__ __launch_bounds__(256) void k_df_fc1_fwd(const float* __restrict__ Wf, const float* __restrict__ bias,
-                                                    const float* __restrict__ a2, int B, float* __restrict__ h) {
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), mt = wave & 3, n0 = (wave >> 2) * NT * 32;
-    if (n0 >= B) return;
-    bool ok[NT];
-    const float* brow[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int n = n0 + 32 * t + l31;
-        ok[t] = n < B;
-        brow[t] = a2 + (size_t)(ok[t] ? n : 0) * A2 + 4 * half;
-    }
-    const float* arow = Wf + (size_t)(32 * mt + l31) * A2 + 4 * half;
-    // the running total as an unevaluated sum hi + lo: TwoSum keeps what the addition of a chunk rounds away
-    f32x16 hi[NT], lo[NT], acc[NT];
-    vf_zero<NT>(lo);
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hi[t][r] = bias[32 * mt + drow(r, half)];
-#pragma unroll 1
-    for (int qc = 0; qc < A2 / 8; qc += CHUNK_QUADS) {
-        vf_zero<NT>(acc);
-#pragma unroll
-        for (int q = qc; q < qc + CHUNK_QUADS; ++q) {
-            const float4 a = *reinterpret_cast<const float4*>(arow + 8 * q);
-            float4 b4[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                b4[t] = *reinterpret_cast<const float4*>(brow[t] + 8 * q);
-                if (!ok[t]) b4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            vf_quad<NT>(acc, a, b4);
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float x = hi[t][r], y = acc[t][r], sum = x + y, yy = sum - x;
-                lo[t][r] += (x - (sum - yy)) + (y - yy);
-                hi[t][r] = sum;
-            }
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-        if (ok[t]) {
-            float* dst = h + (size_t)(n0 + 32 * t + l31) * HID + 32 * mt;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dst[drow(r, half)] = leaky(hi[t][r] + lo[t][r]);
+            for (int r = 0; r < 16; ++r) dst[drow(r, half) * OSTR] = Leaky::fwd(tot[t][r]);
         }
 }
 
@@ -266,50 +206,9 @@ __global__ __launch_bounds__(192) void k_df_head_part(const float* __restrict__ 
     part[(size_t)blockIdx.x * HEAD_PART + i] = s;
 }
 
-// ---- fc1 data gradient: dz2[b][k] = (sum_j dh[b][j] Wf[j][k]) times the slope of a2[b][k]; M = B, N = 2048, K = 128 ----
-template <int NT>
-__global__ __launch_bounds__(256) void k_df_fc1_bwd_data(const float* __restrict__ Wf, const float* __restrict__ dh,
-                                                         const float* __restrict__ a2, int B, float* __restrict__ dz2) {
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
-    constexpr int NG = A2 / 32 / NT;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), ng = wave % NG, m0 = (wave / NG) * 32;
-    if (m0 >= B) return;
-    const bool mok = m0 + l31 < B;
-    const float* arow = dh + (size_t)(mok ? m0 + l31 : 0) * HID + 4 * half;
-    const float* bcol = Wf + (size_t)(4 * half) * A2 + ng * NT * 32 + l31;
-    f32x16 tot[NT], acc[NT];
-    vf_zero<NT>(tot);
-#pragma unroll 1
-    for (int qc = 0; qc < HID / 8; qc += CHUNK_QUADS) {
-        vf_zero<NT>(acc);
-#pragma unroll
-        for (int q = qc; q < qc + CHUNK_QUADS; ++q) {
-            float4 a = *reinterpret_cast<const float4*>(arow + 8 * q);
-            if (!mok) a = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 b4[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float* c = bcol + (size_t)(8 * q) * A2 + 32 * t;
-                b4[t] = make_float4(c[0], c[A2], c[2 * A2], c[3 * A2]);
-            }
-            vf_quad<NT>(acc, a, b4);
-        }
-        vf_add<NT>(tot, acc);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int b = m0 + drow(r, half);
-            if (b < B) {
-                const size_t o = (size_t)b * A2 + (ng * NT + t) * 32 + l31;
-                dz2[o] = a2[o] > 0.0f ? tot[t][r] : SLOPE * tot[t][r];
-            }
-        }
-}
-
 // ---- FC weight gradient: part[s][m][n] = sum over the samples of split s of dA[b][m] act[b][n]; M = MS, N = NS, K = samples.
 // fc1: dA = dh (MS = 128), act = a2 (NS = 2048); fc_v: dA = dzv (MS = 64, zero beyond the atoms), act = h (NS = 128) ----
+// (chunks of 32 samples here and ONE chain a split in valuenet_fit.hip's k_vf_fc1_dw: one kernel for both would change that one's bits)
 template <int MS, int NS, int NT>
 __global__ __launch_bounds__(256) void k_df_fc_dw(const float* __restrict__ dA, const float* __restrict__ act, int B,
                                                   float* __restrict__ part) {
@@ -412,7 +311,7 @@ __global__ __launch_bounds__(256) void k_df_conv_bwd_data(const float* __restric
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const size_t o = ib[t] + (size_t)drow(r, half) * S1;
-                dzi[o] = real[t] ? (ain[o] > 0.0f ? tot[t][r] : SLOPE * tot[t][r]) : 0.0f;
+                dzi[o] = real[t] ? Leaky::bwd(ain[o], tot[t][r]) : 0.0f;
             }
         }
 }
@@ -507,50 +406,6 @@ __global__ __launch_bounds__(64) void k_df_conv_bias_part(const float* __restric
     cb[(size_t)b * 64 + i] = s;
 }
 
-// ---- second stage: out[i] = sum_s part[s * stride + i], the partials of group g = s mod G added in ascending s (in double),
-// the G group sums added in ascending g ----
-template <int G>
-__global__ __launch_bounds__(256) void k_df_reduce(const float* __restrict__ part, int S, long long stride, int n,
-                                                   float* __restrict__ out) {
-    constexpr int PER = 256 / G;
-    __shared__ double sm[256];
-    const int o = threadIdx.x % PER, g = threadIdx.x / PER, i = blockIdx.x * PER + o;
-    double acc = 0.0;
-    if (i < n)
-        for (int s = g; s < S; s += G) acc += (double)part[(size_t)s * stride + i];
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    if (g == 0 && i < n) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < G; ++k) t += sm[k * PER + o];
-        out[i] = (float)t;
-    }
-}
-
-// mean and sample standard deviation (n - 1: torch.std_mean's default; NaN for one sample, as torch) of the per-sample losses
-// (one workgroup, double, fixed order)
-__global__ __launch_bounds__(256) void k_df_loss(const double* __restrict__ per, int B, float* __restrict__ loss) {
-    __shared__ double sm[256];
-    double mean, ssq;
-    block_moments(per, B, sm, mean, ssq);
-    const double var = ssq / (double)(B - 1);
-    if (threadIdx.x == 0) {
-        loss[0] = (float)mean;
-        loss[1] = (float)sqrt(var);
-    }
-}
-
-// a validation pass's chunks of one slab: {w, mean, n - 1 std} per chunk (one workgroup each; fit_mma.h chunk_moments)
-__global__ __launch_bounds__(256) void k_df_val_moments(const double* __restrict__ per, const float* __restrict__ weight, int B,
-                                                        int chunk, int weighted, double* __restrict__ rows) {
-    __shared__ double sm[256];
-    chunk_moments<1>(per, weight, B, chunk, weighted, rows, sm);
-}
-
-static inline int blocks_for_waves(long long waves) { return (int)((waves + 3) / 4); }
-static inline long long tiles(long long n) { return (n + 31) / 32; }
-
 // the forward of B rows (states: int8 [.][200], row idx[b], or row b when idx is NULL) into a1, a2, h: the launches of the
 // gradient step and of the validation pass
 static void forward(const float* P, const int8_t* states, const int64_t* idx, int B, float* a1, float* a2, float* h, hipStream_t st) {
@@ -558,7 +413,7 @@ static void forward(const float* P, const int8_t* states, const int64_t* idx, in
                        P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
     hipLaunchKernelGGL((k_df_conv_fwd<32, 19, 7, S1, P2, 2>), dim3(blocks_for_waves((tiles((long long)B * P2) + 1) / 2)), dim3(256), 0, st,
                        P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
-    hipLaunchKernelGGL((k_df_fc1_fwd<1>), dim3(blocks_for_waves(4 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a2, B, h);
+    hipLaunchKernelGGL((k_fit_fc1_fwd<HID, A2, Leaky, 1>), dim3(blocks_for_waves(4 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a2, B, h);
 }
 
 // the validation pass's workspace, in floats: the forward's activations of one slab and its per-row losses (doubles)
@@ -606,18 +461,18 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
     // ---- output layer, loss, and the bias sums of the two FC layers ----
     hipLaunchKernelGGL(k_df_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P + OFF_FVW, P + OFF_FVB, h, target, target_stride, weight, idx,
                        B, atoms, weighted, dzv, per, dh);
-    hipLaunchKernelGGL(k_df_loss, dim3(1), dim3(256), 0, st, per, B, loss);
+    hipLaunchKernelGGL(k_fit_loss<1>, dim3(1), dim3(256), 0, st, per, B, loss);
     hipLaunchKernelGGL(k_df_head_part, dim3(L.hchunks), dim3(HEAD_PART), 0, st, dzv, dh, B, hp);
-    hipLaunchKernelGGL((k_df_reduce<16>), dim3(HID / 16), dim3(256), 0, st, hp, L.hchunks, (long long)HEAD_PART, HID, grad + OFF_F1B);
-    hipLaunchKernelGGL((k_df_reduce<16>), dim3((atoms + 15) / 16), dim3(256), 0, st, hp + HID, L.hchunks, (long long)HEAD_PART, atoms,
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(HID / 16), dim3(256), 0, st, hp, L.hchunks, (long long)HEAD_PART, HID, grad + OFF_F1B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3((atoms + 15) / 16), dim3(256), 0, st, hp + HID, L.hchunks, (long long)HEAD_PART, atoms,
                        grad + OFF_FVB);
     // ---- the FC layers backward ----
     hipLaunchKernelGGL((k_df_fc_dw<ROW, HID, 2>), dim3(blocks_for_waves((long long)L.s1 * 2 * 2)), dim3(256), 0, st, dzv, h, B, pfv);
-    hipLaunchKernelGGL((k_df_reduce<4>), dim3((atoms * HID + 63) / 64), dim3(256), 0, st, pfv, L.s1, (long long)ROW * HID, atoms * HID,
+    hipLaunchKernelGGL((k_fit_reduce<4>), dim3((atoms * HID + 63) / 64), dim3(256), 0, st, pfv, L.s1, (long long)ROW * HID, atoms * HID,
                        grad + OFF_FVW);
     hipLaunchKernelGGL((k_df_fc_dw<HID, A2, 2>), dim3(blocks_for_waves((long long)L.s1 * 4 * 32)), dim3(256), 0, st, dh, a2, B, pf1);
-    hipLaunchKernelGGL((k_df_reduce<4>), dim3(HID * A2 / 64), dim3(256), 0, st, pf1, L.s1, (long long)HID * A2, HID * A2, grad + OFF_F1W);
-    hipLaunchKernelGGL((k_df_fc1_bwd_data<2>), dim3(blocks_for_waves(tiles(B) * 32)), dim3(256), 0, st, P + OFF_F1W, dh, a2, B, dz2);
+    hipLaunchKernelGGL((k_fit_reduce<4>), dim3(HID * A2 / 64), dim3(256), 0, st, pf1, L.s1, (long long)HID * A2, HID * A2, grad + OFF_F1W);
+    hipLaunchKernelGGL((k_fit_fc1_bwd_data<HID, A2, Leaky, 2>), dim3(blocks_for_waves(tiles(B) * 32)), dim3(256), 0, st, P + OFF_F1W, dh, a2, B, dz2);
     // ---- convolutions backward ----
     hipLaunchKernelGGL((k_df_conv_dw<32, 7, S1, 4, P2, P2, 4>), dim3(blocks_for_waves((long long)L.chunks * 4)), dim3(256), 0, st, dz2, a1,
                        (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw2);
@@ -627,10 +482,10 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
                        (const float*)nullptr, states, idx, B, pw1);
     hipLaunchKernelGGL(k_df_conv_bias_part, dim3(B), dim3(64), 0, st, dz1, dz2, B, cb);
     // ---- second stages of the convolutions' sums ----
-    hipLaunchKernelGGL((k_df_reduce<16>), dim3(16384 / 16), dim3(256), 0, st, pw2, L.chunks, 16384LL, 16384, grad + OFF_C2W);
-    hipLaunchKernelGGL((k_df_reduce<16>), dim3(512 / 16), dim3(256), 0, st, pw1, L.chunks, 512LL, 512, grad + OFF_C1W);
-    hipLaunchKernelGGL((k_df_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 64LL, 32, grad + OFF_C1B);
-    hipLaunchKernelGGL((k_df_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 64LL, 32, grad + OFF_C2B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(16384 / 16), dim3(256), 0, st, pw2, L.chunks, 16384LL, 16384, grad + OFF_C2W);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(512 / 16), dim3(256), 0, st, pw1, L.chunks, 512LL, 512, grad + OFF_C1W);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 64LL, 32, grad + OFF_C1B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 64LL, 32, grad + OFF_C2B);
     return (int)hipGetLastError();
 }
 
@@ -659,7 +514,7 @@ int tm_distnet_fit_validate(const float* params, const int8_t* states, const flo
         hipLaunchKernelGGL(k_df_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params + OFF_FVW, params + OFF_FVB, h,
                            target + r0 * target_stride, target_stride, weight + r0, (const int64_t*)nullptr, B, atoms, weighted,
                            (float*)nullptr, per, (float*)nullptr);
-        hipLaunchKernelGGL(k_df_val_moments, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
+        hipLaunchKernelGGL(k_fit_val_moments<1>, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
                            rows_out + 3 * (r0 / chunk));
     }
     return (int)hipGetLastError();

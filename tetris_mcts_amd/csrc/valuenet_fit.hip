@@ -23,13 +23,13 @@
 // order.  There are no atomics.  All launch shapes follow from `batch` alone.
 //
 // The validation pass (tm_valuenet_fit_validate) is the same forward (forward(): the same kernels and instantiations, idx NULL)
-// over the held-out rows, a slab at a time, k_vf_head<false> for the per-sample losses and k_vf_val_moments for each chunk's
-// {w, mean, std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
+// over the held-out rows, a slab at a time, k_vf_head<false> for the per-sample losses and k_fit_val_moments<0> for each chunk's
+// {w, mean, population std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include "../../include/tetris_mcts_hip.h"
-#include "fit_mma.h"      // f32x16, drow, vf_quad, vf_zero, vf_add, row_of, wave_sum, block_sum: shared with distnet_fit.hip
+#include "fit_mma.h"      // what this file shares with distnet_fit.hip: the MFMA helpers, fc1, the second stages, the loss
 
 namespace tmcts_vf {
 using namespace tmcts_fit;
@@ -42,8 +42,6 @@ constexpr int SPW = 4;                  // samples per wave of the convolutions'
 constexpr int FC1_KC = 256;             // samples per split of fc1's weight gradient
 constexpr int HEAD_CHUNK = 32;          // samples per partial of the small batch sums (fc_out, fc1 bias)
 constexpr int HEAD_PART = 772;          // floats of such a partial: dW_out[2][256], db_fc1[256], db_out[2], pad
-
-__host__ __device__ constexpr long long up4(long long x) { return (x + 3) / 4 * 4; }
 
 // The workspace, in floats (every segment starts at a multiple of four: 16-byte loads).
 struct Layout {
@@ -143,64 +141,6 @@ __global__ __launch_bounds__(256) void k_vf_conv_fwd(const float* __restrict__ W
         }
 }
 
-// ---- fc1 forward: h[b][j] = relu(bias[j] + sum_k Wf[j][k] a3[b][k]); M = 256 units, N = B, K = 1792 ----
-template <int NT>
-__global__ __launch_bounds__(256) void k_vf_fc1_fwd(const float* __restrict__ Wf, const float* __restrict__ bias,
-                                                    const float* __restrict__ a3, int B, float* __restrict__ h) {
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), mt = wave & 7, n0 = (wave >> 3) * NT * 32;
-    if (n0 >= B) return;
-    bool ok[NT];
-    const float* brow[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int n = n0 + 32 * t + l31;
-        ok[t] = n < B;
-        brow[t] = a3 + (size_t)(ok[t] ? n : 0) * A3 + 4 * half;
-    }
-    const float* arow = Wf + (size_t)(32 * mt + l31) * A3 + 4 * half;
-    // the running total as an unevaluated sum hi + lo: TwoSum keeps what the addition of a chunk rounds away
-    f32x16 hi[NT], lo[NT], acc[NT];
-    vf_zero<NT>(lo);
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hi[t][r] = bias[32 * mt + drow(r, half)];
-#pragma unroll 1
-    for (int qc = 0; qc < A3 / 8; qc += CHUNK_QUADS) {
-        vf_zero<NT>(acc);
-#pragma unroll
-        for (int q = qc; q < qc + CHUNK_QUADS; ++q) {
-            const float4 a = make_float4(arow[8 * q], arow[8 * q + 1], arow[8 * q + 2], arow[8 * q + 3]);
-            float4 b4[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                b4[t] = *reinterpret_cast<const float4*>(brow[t] + 8 * q);
-                if (!ok[t]) b4[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            vf_quad<NT>(acc, a, b4);
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float x = hi[t][r], y = acc[t][r], sum = x + y, yy = sum - x;
-                lo[t][r] += (x - (sum - yy)) + (y - yy);
-                hi[t][r] = sum;
-            }
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-        if (ok[t]) {
-            float* dst = h + (size_t)(n0 + 32 * t + l31) * HID + 32 * mt;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = hi[t][r] + lo[t][r];
-                dst[drow(r, half)] = v > 0.0f ? v : 0.0f;
-            }
-        }
-}
-
 // ---- output layer, loss and their gradients: one wave per sample, in double ----
 // per = log var_p + ((value - v_p)^2 + max(variance, clip)) / var_p - log max(variance, clip) - 1, times the weight;
 // dzo[b][2] = d(mean of per) / d(fc_out pre-activation), dh[b][i] = (dzo . W_out[:, i]) where h > 0.
@@ -269,49 +209,8 @@ __global__ __launch_bounds__(256) void k_vf_head_part(const float* __restrict__ 
     if (i < 2) dst[3 * HID + i] = bo;
 }
 
-// ---- fc1 data gradient: dz3[b][k] = (sum_j dh[b][j] Wf[j][k]) where a3[b][k] > 0; M = B, N = 1792, K = 256 ----
-template <int NT>
-__global__ __launch_bounds__(256) void k_vf_fc1_bwd_data(const float* __restrict__ Wf, const float* __restrict__ dh,
-                                                         const float* __restrict__ a3, int B, float* __restrict__ dz3) {
-    const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
-    constexpr int NG = A3 / 32 / NT;
-    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), ng = wave % NG, m0 = (wave / NG) * 32;
-    if (m0 >= B) return;
-    const bool mok = m0 + l31 < B;
-    const float* arow = dh + (size_t)(mok ? m0 + l31 : 0) * HID + 4 * half;
-    const float* bcol = Wf + (size_t)(4 * half) * A3 + ng * NT * 32 + l31;
-    f32x16 tot[NT], acc[NT];
-    vf_zero<NT>(tot);
-#pragma unroll 1
-    for (int qc = 0; qc < HID / 8; qc += CHUNK_QUADS) {
-        vf_zero<NT>(acc);
-#pragma unroll
-        for (int q = qc; q < qc + CHUNK_QUADS; ++q) {
-            float4 a = *reinterpret_cast<const float4*>(arow + 8 * q);
-            if (!mok) a = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 b4[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float* c = bcol + (size_t)(8 * q) * A3 + 32 * t;
-                b4[t] = make_float4(c[0], c[A3], c[2 * A3], c[3 * A3]);
-            }
-            vf_quad<NT>(acc, a, b4);
-        }
-        vf_add<NT>(tot, acc);
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int b = m0 + drow(r, half);
-            if (b < B) {
-                const size_t o = (size_t)b * A3 + (ng * NT + t) * 32 + l31;
-                dz3[o] = a3[o] > 0.0f ? tot[t][r] : 0.0f;
-            }
-        }
-}
-
 // ---- fc1 weight gradient: part[s][j][k] = sum over the samples of split s of dh[b][j] a3[b][k]; M = 256, N = 1792 ----
+// (a split is ONE chain here and chunks of 32 in distnet_fit.hip's k_df_fc_dw: one kernel for both would change this one's bits)
 template <int NT>
 __global__ __launch_bounds__(256) void k_vf_fc1_dw(const float* __restrict__ dh, const float* __restrict__ a3, int B,
                                                    float* __restrict__ part) {
@@ -482,49 +381,6 @@ __global__ __launch_bounds__(128) void k_vf_conv_bias_part(const float* __restri
     cb[(size_t)b * 96 + i] = s;
 }
 
-// ---- second stage: out[i] = sum_s part[s * stride + i], the partials of group g = s mod G added in ascending s (in double),
-// the G group sums added in ascending g ----
-template <int G>
-__global__ __launch_bounds__(256) void k_vf_reduce(const float* __restrict__ part, int S, long long stride, int n,
-                                                   float* __restrict__ out) {
-    constexpr int PER = 256 / G;
-    __shared__ double sm[256];
-    const int o = threadIdx.x % PER, g = threadIdx.x / PER, i = blockIdx.x * PER + o;
-    double acc = 0.0;
-    if (i < n)
-        for (int s = g; s < S; s += G) acc += (double)part[(size_t)s * stride + i];
-    sm[threadIdx.x] = acc;
-    __syncthreads();
-    if (g == 0 && i < n) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < G; ++k) t += sm[k * PER + o];
-        out[i] = (float)t;
-    }
-}
-
-// mean and population standard deviation of the per-sample losses (one workgroup, double, fixed order)
-__global__ __launch_bounds__(256) void k_vf_loss(const double* __restrict__ per, int B, float* __restrict__ loss) {
-    __shared__ double sm[256];
-    double mean, ssq;
-    block_moments(per, B, sm, mean, ssq);
-    const double var = ssq / (double)B;
-    if (threadIdx.x == 0) {
-        loss[0] = (float)mean;
-        loss[1] = (float)sqrt(var);
-    }
-}
-
-// a validation pass's chunks of one slab: {w, mean, population std} per chunk (one workgroup each; fit_mma.h chunk_moments)
-__global__ __launch_bounds__(256) void k_vf_val_moments(const double* __restrict__ per, const float* __restrict__ weight, int B,
-                                                        int chunk, int weighted, double* __restrict__ rows) {
-    __shared__ double sm[256];
-    chunk_moments<0>(per, weight, B, chunk, weighted, rows, sm);
-}
-
-static inline int blocks_for_waves(long long waves) { return (int)((waves + 3) / 4); }
-static inline long long tiles(long long n) { return (n + 31) / 32; }
-
 // the forward of B rows (states: int8 [.][200], row idx[b], or row b when idx is NULL) into a1, a2, a3, h: the launches of the
 // gradient step and of the validation pass
 static void forward(const float* P, const int8_t* states, const int64_t* idx, int B, float* a1, float* a2, float* a3, float* h,
@@ -535,7 +391,7 @@ static void forward(const float* P, const int8_t* states, const int64_t* idx, in
                        P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
     hipLaunchKernelGGL((k_vf_conv_fwd<32, 16, 6, 2>), dim3(blocks_for_waves((tiles((long long)B * 56) + 1) / 2)), dim3(256), 0, st,
                        P + OFF_C3W, P + OFF_C3B, a2, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a3);
-    hipLaunchKernelGGL((k_vf_fc1_fwd<1>), dim3(blocks_for_waves(8 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a3, B, h);
+    hipLaunchKernelGGL((k_fit_fc1_fwd<HID, A3, Relu, 1>), dim3(blocks_for_waves(8 * tiles(B))), dim3(256), 0, st, P + OFF_F1W, P + OFF_F1B, a3, B, h);
 }
 
 // the validation pass's workspace, in floats: the forward's activations of one slab and its per-row losses (doubles)
@@ -584,15 +440,15 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
     // ---- output layer, loss, and the small batch sums ----
     hipLaunchKernelGGL(k_vf_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P, out_bounds, h, value, variance, weight, idx, B, weighted,
                        variance_clip, dzo, per, dh);
-    hipLaunchKernelGGL(k_vf_loss, dim3(1), dim3(256), 0, st, per, B, loss);
+    hipLaunchKernelGGL(k_fit_loss<0>, dim3(1), dim3(256), 0, st, per, B, loss);
     hipLaunchKernelGGL(k_vf_head_part, dim3(L.hchunks), dim3(256), 0, st, dzo, h, dh, B, hp);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3((512 + 15) / 16), dim3(256), 0, st, hp, L.hchunks, (long long)HEAD_PART, 512, grad + OFF_FOW);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(256 / 16), dim3(256), 0, st, hp + 512, L.hchunks, (long long)HEAD_PART, 256, grad + OFF_F1B);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(1), dim3(256), 0, st, hp + 768, L.hchunks, (long long)HEAD_PART, 2, grad + OFF_FOB);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3((512 + 15) / 16), dim3(256), 0, st, hp, L.hchunks, (long long)HEAD_PART, 512, grad + OFF_FOW);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(256 / 16), dim3(256), 0, st, hp + 512, L.hchunks, (long long)HEAD_PART, 256, grad + OFF_F1B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(1), dim3(256), 0, st, hp + 768, L.hchunks, (long long)HEAD_PART, 2, grad + OFF_FOB);
     // ---- fc1 backward ----
     hipLaunchKernelGGL((k_vf_fc1_dw<2>), dim3(blocks_for_waves((long long)L.s1 * 8 * 28)), dim3(256), 0, st, dh, a3, B, pf1);
-    hipLaunchKernelGGL((k_vf_reduce<4>), dim3(HID * A3 / 64), dim3(256), 0, st, pf1, L.s1, (long long)HID * A3, HID * A3, grad + OFF_F1W);
-    hipLaunchKernelGGL((k_vf_fc1_bwd_data<2>), dim3(blocks_for_waves(tiles(B) * 28)), dim3(256), 0, st, P + OFF_F1W, dh, a3, B, dz3);
+    hipLaunchKernelGGL((k_fit_reduce<4>), dim3(HID * A3 / 64), dim3(256), 0, st, pf1, L.s1, (long long)HID * A3, HID * A3, grad + OFF_F1W);
+    hipLaunchKernelGGL((k_fit_fc1_bwd_data<HID, A3, Relu, 2>), dim3(blocks_for_waves(tiles(B) * 28)), dim3(256), 0, st, P + OFF_F1W, dh, a3, B, dz3);
     // ---- convolutions backward ----
     hipLaunchKernelGGL((k_vf_conv_dw<32, 16, 6, 3>), dim3(blocks_for_waves((long long)L.chunks * 3)), dim3(256), 0, st, dz3, a2,
                        (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw3);
@@ -606,12 +462,12 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
                        states, idx, B, pw1);
     hipLaunchKernelGGL(k_vf_conv_bias_part, dim3(B), dim3(128), 0, st, dz1, dz2, dz3, B, cb);
     // ---- second stages of the convolutions' sums ----
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw3, L.chunks, 9216LL, 9216, grad + OFF_C3W);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw2, L.chunks, 9216LL, 9216, grad + OFF_C2W);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(288 / 16), dim3(256), 0, st, pw1, L.chunks, 288LL, 288, grad + OFF_C1W);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 96LL, 32, grad + OFF_C1B);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 96LL, 32, grad + OFF_C2B);
-    hipLaunchKernelGGL((k_vf_reduce<16>), dim3(2), dim3(256), 0, st, cb + 64, B, 96LL, 32, grad + OFF_C3B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw3, L.chunks, 9216LL, 9216, grad + OFF_C3W);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw2, L.chunks, 9216LL, 9216, grad + OFF_C2W);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(288 / 16), dim3(256), 0, st, pw1, L.chunks, 288LL, 288, grad + OFF_C1W);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 96LL, 32, grad + OFF_C1B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 96LL, 32, grad + OFF_C2B);
+    hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb + 64, B, 96LL, 32, grad + OFF_C3B);
     return (int)hipGetLastError();
 }
 
@@ -638,7 +494,7 @@ int tm_valuenet_fit_validate(const float* params, const float* out_bounds, const
         forward(params, states + r0 * 200, (const int64_t*)nullptr, B, a1, a2, a3, h, st);
         hipLaunchKernelGGL(k_vf_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params, out_bounds, h, value + r0, variance + r0,
                            weight + r0, (const int64_t*)nullptr, B, weighted, variance_clip, (float*)nullptr, per, (float*)nullptr);
-        hipLaunchKernelGGL(k_vf_val_moments, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
+        hipLaunchKernelGGL(k_fit_val_moments<0>, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
                            rows_out + 3 * (r0 / chunk));
     }
     return (int)hipGetLastError();

@@ -18,44 +18,43 @@ from torch.optim.optimizer import Optimizer
 variance_bound = 1e-1
 
 
-class Yogi(Optimizer):
-    """Yogi (Zaheer et al. 2018) with the reference's conventions: v0 = g0^2 (before weight decay), coupled weight
-    decay added to the gradient, bias-corrected step  p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).
+class _FlatBuffers:
+    """The fused surface Yogi and FusedAdam share: the parameters that take gradients, their gradients and the moments named by
+    `_MOMENTS` as views of flat buffers (`_flat`: params, n, p, g, m, v[, vmax], state, t), stepped by ONE HIP kernel with the
+    step count on the device.  A subclass names itself (`_NAME`, for the messages) and its moments, says how its state dict keeps
+    a step count (`_step_value`), and makes the C call (`_launch`)."""
+    _NAME, _MOMENTS = None, ()
 
-    Parameters on the GPU: the step is ONE HIP kernel over flat buffers (csrc/yogi.hip `tm_yogi_step`: the same operations per
-    element in the same order) - the parameters, their gradients and the two moments become views of four flat tensors at the
-    first step (`flatten`), the step count lives on the device, and an iteration of the fit is a fixed sequence of launches
-    that train_data replays from a HIP graph.  The state dict keeps the reference's layout (per parameter: step, exp_avg,
-    exp_avg_sq), so checkpoints load on either side.  Parameters on the CPU: the reference's own sequence of tensor operations."""
+    def _fusable(self):
+        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+        return (len(self.param_groups) == 1 and len(ps) > 0 and all(p.is_cuda and p.dtype == torch.float32 for p in ps)
+                and len({p.device for p in ps}) == 1)
 
-    def __init__(self, params, lr=1e-2, betas=(0.9, 0.999), eps=1e-3, weight_decay=0.0, fused=None):
-        if lr <= 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
-            raise ValueError("invalid Yogi hyper-parameters")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self._fused_wanted = fused
-        self._flat = None
-
-    # ---- the fused form ----
     def fused(self):
         """whether step() is the one-kernel form: every parameter on one GPU, float32, a single group (or asked for / refused
         at construction)"""
         if self._fused_wanted is False:
             return False
-        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
-        ok = (len(self.param_groups) == 1 and len(ps) > 0 and all(p.is_cuda and p.dtype == torch.float32 for p in ps)
-              and len({p.device for p in ps}) == 1)
+        ok = self._fusable()
         if self._fused_wanted and not ok:
-            raise ValueError("Yogi(fused=True) needs float32 parameters on one GPU in a single group")
+            raise ValueError(self._NAME + "(fused=True) needs float32 parameters on one GPU in a single group")
         return ok
 
+    def _takes_flat_route(self):
+        """whether zero_grad and state_dict go through the flat buffers"""
+        return self._flat is not None
+
     def flatten(self):
-        """(idempotent) the parameters that take gradients, their gradients and moments as views of flat buffers"""
+        """(idempotent) the parameters that take gradients, their gradients and moments as views of flat buffers, in the order
+        the parameters were given"""
         if self._flat is not None:
             return self._flat
         ps = [p for p in self.param_groups[0]["params"] if p.requires_grad]
         dev, n = ps[0].device, sum(p.numel() for p in ps)
-        F = dict(params=ps, n=n, p=torch.empty(n, device=dev), g=torch.zeros(n, device=dev), m=torch.zeros(n, device=dev),
-                 v=torch.zeros(n, device=dev), state=torch.zeros(8, dtype=torch.float64, device=dev))
+        moments = list(zip(("m", "v", "vmax"), self._MOMENTS))
+        F = dict(params=ps, n=n, p=torch.empty(n, device=dev), g=torch.zeros(n, device=dev))
+        F.update((key, torch.zeros(n, device=dev)) for key, _ in moments)
+        F["state"] = torch.zeros(8, dtype=torch.float64, device=dev)
         off, steps = 0, set()
         with torch.no_grad():
             for p in ps:
@@ -67,15 +66,17 @@ class Yogi(Optimizer):
                     F["g"][sl].copy_(p.grad.reshape(-1))
                 p.grad = F["g"][sl].view_as(p)
                 st = self.state[p]
-                if st:       # moments loaded from a checkpoint (or steps taken by the per-tensor form)
-                    F["m"][sl].copy_(st["exp_avg"].reshape(-1))
-                    F["v"][sl].copy_(st["exp_avg_sq"].reshape(-1))
+                if st:       # moments loaded from a state dict (or steps taken by the per-tensor form)
+                    for key, name in moments:
+                        if key != "vmax" or name in st:      # (torch's Adam keeps no maximum unless amsgrad is set)
+                            F[key][sl].copy_(st[name].reshape(-1))
                     steps.add(int(st["step"]))
-                st["exp_avg"], st["exp_avg_sq"] = F["m"][sl].view_as(p), F["v"][sl].view_as(p)
-                st.setdefault("step", 0)
+                for key, name in moments:
+                    st[name] = F[key][sl].view_as(p)
+                st["step"] = self._step_value(st.get("step", 0))
                 off += k
         if len(steps) > 1:
-            raise ValueError("Yogi: the parameters' step counts differ (%s)" % sorted(steps))
+            raise ValueError("%s: the parameters' step counts differ (%s)" % (self._NAME, sorted(steps)))
         t = steps.pop() if steps else 0
         b1, b2 = self.param_groups[0]["betas"]
         lr = self.param_groups[0]["lr"]
@@ -89,7 +90,7 @@ class Yogi(Optimizer):
         return self.flatten()["g"] if self.fused() else None
 
     def zero_grad(self, set_to_none=True):
-        if self._flat is not None:
+        if self._takes_flat_route():
             self._flat["g"].zero_()      # (the gradients stay the views they are: autograd accumulates into them in place)
             return
         super().zero_grad(set_to_none=set_to_none)
@@ -106,20 +107,44 @@ class Yogi(Optimizer):
             self.flatten()
 
     def state_dict(self):
-        if self._flat is not None:
+        if self._takes_flat_route():
             for p in self._flat["params"]:
-                self.state[p]["step"] = self._flat["t"]
+                self.state[p]["step"] = self._step_value(self._flat["t"])
         return super().state_dict()
 
     def _fused_step(self):
         from . import _lib
         F = self.flatten()
-        g = self.param_groups[0]
+        self._launch(_lib, F, self.param_groups[0], torch.cuda.current_stream(F["p"].device).cuda_stream)
+        F["t"] += 1
+
+
+class Yogi(_FlatBuffers, Optimizer):
+    """Yogi (Zaheer et al. 2018) with the reference's conventions: v0 = g0^2 (before weight decay), coupled weight
+    decay added to the gradient, bias-corrected step  p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).
+
+    Parameters on the GPU: the step is ONE HIP kernel over flat buffers (csrc/yogi.hip `tm_yogi_step`: the same operations per
+    element in the same order) - the parameters, their gradients and the two moments become views of four flat tensors at the
+    first step (`flatten`), the step count lives on the device, and an iteration of the fit is a fixed sequence of launches
+    that train_data replays from a HIP graph.  The state dict keeps the reference's layout (per parameter: step, exp_avg,
+    exp_avg_sq), so checkpoints load on either side.  Parameters on the CPU: the reference's own sequence of tensor operations."""
+    _NAME, _MOMENTS = "Yogi", ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-2, betas=(0.9, 0.999), eps=1e-3, weight_decay=0.0, fused=None):
+        if lr <= 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1):
+            raise ValueError("invalid Yogi hyper-parameters")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._fused_wanted = fused
+        self._flat = None
+
+    @staticmethod
+    def _step_value(t):
+        return t      # the reference's layout: an int
+
+    def _launch(self, _lib, F, g, stream):
         _lib.check(_lib.lib().tm_yogi_step(F["p"].data_ptr(), F["g"].data_ptr(), F["m"].data_ptr(), F["v"].data_ptr(),
                                            F["state"].data_ptr(), F["n"], float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                                           float(g["eps"]), float(g["weight_decay"]), torch.cuda.current_stream(F["p"].device).cuda_stream),
-                   "tm_yogi_step")
-        F["t"] += 1
+                                           float(g["eps"]), float(g["weight_decay"]), stream), "tm_yogi_step")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -156,7 +181,7 @@ class Yogi(Optimizer):
         return loss
 
 
-class FusedAdam(torch.optim.Adam):
+class FusedAdam(_FlatBuffers, torch.optim.Adam):
     """torch.optim.Adam (AMSGrad and coupled weight decay included) with Yogi's fused surface, for the distributional head's fit.
 
     Parameters on the GPU: the step is ONE HIP kernel over flat buffers (csrc/yogi.hip `tm_adam_step`: torch's single-tensor step
@@ -165,105 +190,35 @@ class FusedAdam(torch.optim.Adam):
     Net.parameters()), the step count lives on the device, and train_data replays an iteration from a HIP graph.  The state dict
     is torch.optim.Adam's (per parameter: step, exp_avg, exp_avg_sq, max_exp_avg_sq), so a state saved by either loads into the
     other.  Parameters on the CPU: torch's own step (this class IS torch.optim.Adam there: the same bits)."""
+    _NAME, _MOMENTS = "FusedAdam", ("exp_avg", "exp_avg_sq", "max_exp_avg_sq")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, fused=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
         self._fused_wanted = fused
         self._flat = None
 
-    def fused(self):
-        """whether step() is the one-kernel form: every parameter on one GPU, float32, a single group with torch's plain
-        options (or asked for / refused at construction)"""
-        if self._fused_wanted is False:
-            return False
-        ps = [p for g in self.param_groups for p in g["params"] if p.requires_grad]
+    def _fusable(self):
+        """as Yogi's, and torch's plain options"""
         g0 = self.param_groups[0]
-        ok = (len(self.param_groups) == 1 and len(ps) > 0 and all(p.is_cuda and p.dtype == torch.float32 for p in ps)
-              and len({p.device for p in ps}) == 1 and not g0.get("maximize") and not g0.get("decoupled_weight_decay")
-              and not isinstance(g0["lr"], torch.Tensor) and g0["betas"][0] > 0.5)
-        if self._fused_wanted and not ok:
-            raise ValueError("FusedAdam(fused=True) needs float32 parameters on one GPU in a single group")
-        return ok
+        return (super()._fusable() and not g0.get("maximize") and not g0.get("decoupled_weight_decay")
+                and not isinstance(g0["lr"], torch.Tensor) and g0["betas"][0] > 0.5)
 
-    def flatten(self):
-        """(idempotent) the parameters that take gradients, their gradients and moments as views of flat buffers"""
-        if self._flat is not None:
-            return self._flat
-        ps = [p for p in self.param_groups[0]["params"] if p.requires_grad]
-        dev, n = ps[0].device, sum(p.numel() for p in ps)
-        F = dict(params=ps, n=n, p=torch.empty(n, device=dev), g=torch.zeros(n, device=dev), m=torch.zeros(n, device=dev),
-                 v=torch.zeros(n, device=dev), vmax=torch.zeros(n, device=dev), state=torch.zeros(8, dtype=torch.float64, device=dev))
-        off, steps = 0, set()
-        with torch.no_grad():
-            for p in ps:
-                k = p.numel()
-                sl = slice(off, off + k)
-                F["p"][sl].copy_(p.reshape(-1))
-                p.data = F["p"][sl].view_as(p)
-                if p.grad is not None:
-                    F["g"][sl].copy_(p.grad.reshape(-1))
-                p.grad = F["g"][sl].view_as(p)
-                st = self.state[p]
-                if st:       # moments loaded from a state dict (or steps taken by torch's per-tensor form)
-                    F["m"][sl].copy_(st["exp_avg"].reshape(-1))
-                    F["v"][sl].copy_(st["exp_avg_sq"].reshape(-1))
-                    if "max_exp_avg_sq" in st:
-                        F["vmax"][sl].copy_(st["max_exp_avg_sq"].reshape(-1))
-                    steps.add(int(st["step"]))
-                st["exp_avg"], st["exp_avg_sq"] = F["m"][sl].view_as(p), F["v"][sl].view_as(p)
-                st["max_exp_avg_sq"] = F["vmax"][sl].view_as(p)
-                st["step"] = torch.tensor(float(st["step"]) if "step" in st else 0.0)
-                off += k
-        if len(steps) > 1:
-            raise ValueError("FusedAdam: the parameters' step counts differ (%s)" % sorted(steps))
-        t = steps.pop() if steps else 0
-        b1, b2 = self.param_groups[0]["betas"]
-        lr = self.param_groups[0]["lr"]
-        if t > 0:
-            F["state"].copy_(torch.tensor([t, b1 ** t, b2 ** t, lr / (1 - b1 ** t), math.sqrt(1 - b2 ** t), 0, 0, 0], dtype=torch.float64))
-        F["t"] = t
-        self._flat = F
-        return F
-
-    def flat_grad(self):
-        return self.flatten()["g"] if self.fused() else None
-
-    def zero_grad(self, set_to_none=True):
+    def _takes_flat_route(self):
         """In the fused form the gradients are zeroed, never cleared: they stay the views of the flat buffer that autograd
         accumulates into and the kernel reads, so EVERY parameter is stepped in every iteration (one that received no gradient
         moves by its momentum, where torch.optim.Adam would skip it; Net's eight tensors always receive one).  Anywhere else
-        (CPU parameters, flattened or not) this is torch.optim.Adam.zero_grad."""
-        if self._flat is not None and self.fused():
-            self._flat["g"].zero_()
-            return
-        super().zero_grad(set_to_none=set_to_none)
+        (CPU parameters, flattened or not) zero_grad and state_dict are torch.optim.Adam's."""
+        return self._flat is not None and self.fused()
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        if self._flat is not None:       # the loaded moments are tensors of their own: back into the flat buffers
-            ps = self._flat["params"]
-            with torch.no_grad():
-                for p in ps:
-                    p.data = p.data.clone()
-                    p.grad = None
-            self._flat = None
-            self.flatten()
+    @staticmethod
+    def _step_value(t):
+        return torch.tensor(float(t))      # torch.optim.Adam's layout: a 0-d float tensor
 
-    def state_dict(self):
-        if self._flat is not None and self.fused():
-            for p in self._flat["params"]:
-                self.state[p]["step"] = torch.tensor(float(self._flat["t"]))
-        return super().state_dict()
-
-    def _fused_step(self):
-        from . import _lib
-        F = self.flatten()
-        g = self.param_groups[0]
+    def _launch(self, _lib, F, g, stream):
         _lib.check(_lib.lib().tm_adam_step(F["p"].data_ptr(), F["g"].data_ptr(), F["m"].data_ptr(), F["v"].data_ptr(),
                                            F["vmax"].data_ptr(), F["state"].data_ptr(), F["n"], float(g["lr"]), float(g["betas"][0]),
                                            float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), int(bool(g["amsgrad"])),
-                                           torch.cuda.current_stream(F["p"].device).cuda_stream), "tm_adam_step")
-        F["t"] += 1
+                                           stream), "tm_adam_step")
 
     def step(self, closure=None):
         if not self.fused():
@@ -357,86 +312,58 @@ def _validation_slab(rows, chunk, slab):
     return min(slab, (rows + chunk - 1) // chunk * chunk)
 
 
-class HipFit:
-    """The per-fit state of fit_backend="hip": the checks (once per fit), the int8 copy of the training states, the flattened
-    targets, the output bounds and the workspace; grad(idx) is one call of tm_valuenet_fit_grad on the current stream."""
-    N_PARAMS = 478338
+class _HipFitBase:
+    """What the per-fit states of fit_backend="hip" and "hip_dist" share: the order of the checks (once per fit, everything that
+    can refuse before the optimiser is flattened), the workspaces of the gradient step and of the validation pass, the index
+    check and the two calls.  A subclass names its backend (`BACKEND`, for the messages), checks the net, the optimiser and one
+    list of rows (`_check`, `_check_rows`, `_check_flat`), keeps its copies of the rows (`_keep`) and makes the C calls
+    (`_workspace`, `_grad`, `_validate`)."""
+    BACKEND = None
 
     def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB):
         from . import _lib
-        from .model import Net
-        if len(train) != 4:
-            raise ValueError("fit_backend='hip' needs data = [states, values, variances, weights]")
-        states = train[0]
-        rows = states.shape[0]
-        if rows < 1 or states.numel() != rows * 200:
-            raise ValueError("fit_backend='hip' needs states of 20 x 10 cells a row, got shape %s" % (tuple(states.shape),))
-        if not bool(((states == states.round()) & (states.abs() <= 127)).all()):
-            raise ValueError("fit_backend='hip' reads the states as int8: they must be integers in [-127, 127]")
-        if not all(d.is_cuda and d.dtype == torch.float32 for d in train):
-            raise ValueError("fit_backend='hip' needs float32 CUDA tensors (the data is on %s)" % (states.device,))
-        if not isinstance(net, Net):
-            raise ValueError("fit_backend='hip' computes model.Net, not %s" % type(net).__name__)
-        if not (hasattr(optimizer, "fused") and optimizer.fused()):
-            raise ValueError("fit_backend='hip' writes the fused Yogi's flat gradient buffer: the optimizer must be a Yogi "
-                             "whose fused() holds (float32 parameters on one GPU in a single group)")
-        if any(t.shape[0] != rows for t in train[1:]) or any(t.numel() != rows for t in train[1:]):
-            raise ValueError("fit_backend='hip' needs one value, variance and weight a row")
+        self._lib = _lib
+        L, V = "fit_backend='%s'" % self.BACKEND, "validation_backend='hip'"
+        rows = self._check(net, optimizer, train, L)
         if val is not None:      # validation_backend="hip": the same checks on the held-out rows, before the optimiser is touched
-            V = "validation_backend='hip'"
-            vrows = val[0].shape[0]
-            if len(val) != 4 or vrows < 1 or val[0].numel() != vrows * 200:
-                raise ValueError(V + " needs validation data = [states of 20 x 10 cells a row, values, variances, weights]")
-            if not bool(((val[0] == val[0].round()) & (val[0].abs() <= 127)).all()):
-                raise ValueError(V + " reads the states as int8: they must be integers in [-127, 127]")
-            if not all(d.is_cuda and d.dtype == torch.float32 for d in val):
-                raise ValueError(V + " needs float32 CUDA tensors (the validation data is on %s)" % (val[0].device,))
-            if any(t.shape[0] != vrows or t.numel() != vrows for t in val[1:]):
-                raise ValueError(V + " needs one value, variance and weight a row")
+            vrows = self._check_rows(val, V, "validation data")
             val_slab = _validation_slab(vrows, val_chunk, val_slab)
-            if _lib.lib().tm_valuenet_fit_validate_workspace(val_slab) < 0:
+            if self._workspace(val_slab, validation=True) < 0:
                 raise ValueError(V + ": a slab of %d rows is refused" % val_slab)
         F = optimizer.flatten()
-        if F["n"] != self.N_PARAMS or not flat_order_is_param_order(net, optimizer):
-            raise ValueError("fit_backend='hip': the optimizer's flat buffers are not the net's learnable tensors in "
-                             "model.PARAM_ORDER")
+        self._check_flat(net, optimizer, F, train[0].device, L)
         if batch < 1:
-            raise ValueError("fit_backend='hip' needs a batch of at least one row per rank")
-        self._lib, self.F, self.batch, self.rows, self.dev = _lib, F, batch, rows, states.device
-        self.states = states.reshape(rows, 200).to(torch.int8).contiguous()
-        self.value, self.variance, self.weight = (t.reshape(rows).contiguous() for t in train[1:])
-        self.bounds = torch.cat([net.out_ubound.detach().reshape(2), net.out_lbound.detach().reshape(2)]).float().contiguous()
-        n_ws = _lib.lib().tm_valuenet_fit_workspace(batch)
+            raise ValueError(L + " needs a batch of at least one row per rank")
+        self.F, self.batch, self.rows, self.dev = F, batch, rows, train[0].device
+        self._keep(train, rows, "")
+        n_ws = self._workspace(batch)
         if n_ws < 0:
-            raise ValueError("fit_backend='hip': a batch of %d rows is refused" % batch)
+            raise ValueError(L + ": a batch of %d rows is refused" % batch)
         self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
         self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
         self._idx_checked = False
         self.val_rows = 0
         if val is not None:      # the int8 copy of the held-out states (once per fit), the slab's workspace and the chunks' rows
             self.val_rows, self.val_chunk, self.val_slab = vrows, val_chunk, val_slab
-            self.val_states = val[0].reshape(vrows, 200).to(torch.int8).contiguous()
-            self.val_value, self.val_variance, self.val_weight = (t.reshape(vrows).contiguous() for t in val[1:])
-            self.val_ws = torch.empty(_lib.lib().tm_valuenet_fit_validate_workspace(val_slab), dtype=torch.float32, device=self.dev)
+            self._keep(val, vrows, "val_")
+            self.val_ws = torch.empty(self._workspace(val_slab, validation=True), dtype=torch.float32, device=self.dev)
             self.val_out = torch.zeros((vrows + val_chunk - 1) // val_chunk, 3, dtype=torch.float64, device=self.dev)
 
     def validate(self, weighted):
         """the held-out rows' [w, mean, std] per chunk (a list of lists of Python floats, what combine_chunk_rows takes), at the
-        optimiser's flat parameters as they stand: ONE call of tm_valuenet_fit_validate on the current stream and ONE .cpu()"""
+        optimiser's flat parameters as they stand: ONE call of tm_valuenet_fit_validate / tm_distnet_fit_validate on the current
+        stream and ONE .cpu() (the head's std of a one-row chunk is NaN, as torch.std_mean's: combine_chunk_rows maps it to 0)"""
         if not self.val_rows:
             raise ValueError("validation_backend='hip': this fit holds no validation rows")
-        self._lib.check(self._lib.lib().tm_valuenet_fit_validate(
-            self.F["p"].data_ptr(), self.bounds.data_ptr(), self.val_states.data_ptr(), self.val_value.data_ptr(),
-            self.val_variance.data_ptr(), self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab,
-            int(bool(weighted)), float(variance_bound), self.val_out.data_ptr(), self.val_ws.data_ptr(),
-            torch.cuda.current_stream(self.dev).cuda_stream), "tm_valuenet_fit_validate")
+        self._validate(int(bool(weighted)), torch.cuda.current_stream(self.dev).cuda_stream)
         return self.val_out.cpu().tolist()
 
     def check_idx(self, idx):
         """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
         lo, hi = int(idx.min()), int(idx.max())
         if lo < 0 or hi >= self.rows:
-            raise ValueError("fit_backend='hip': indices in [%d, %d] do not all name one of the %d training rows" % (lo, hi, self.rows))
+            raise ValueError("fit_backend='%s': indices in [%d, %d] do not all name one of the %d training rows"
+                             % (self.BACKEND, lo, hi, self.rows))
 
     def grad(self, idx, weighted):
         """loss (a 0-d device tensor) of the rows idx (int64, every value in [0, rows)); the gradient of its mean lands in the
@@ -444,17 +371,72 @@ class HipFit:
         fit that is not being captured checks the range here (one host synchronisation), and train_data's draws are indices
         into [0, rows) by construction; a caller who changes where idx comes from between calls calls check_idx itself."""
         if idx.dtype != torch.int64 or idx.numel() != self.batch:
-            raise ValueError("fit_backend='hip': expected %d int64 indices, got %d %s" % (self.batch, idx.numel(), idx.dtype))
+            raise ValueError("fit_backend='%s': expected %d int64 indices, got %d %s" % (self.BACKEND, self.batch, idx.numel(), idx.dtype))
         if not self._idx_checked and not torch.cuda.is_current_stream_capturing():
             self.check_idx(idx)
             self._idx_checked = True
-        idx = idx.contiguous()
+        self._grad(idx.contiguous(), int(bool(weighted)), torch.cuda.current_stream(self.dev).cuda_stream)
+        return self.loss[0]
+
+
+class HipFit(_HipFitBase):
+    """The per-fit state of fit_backend="hip": the checks (once per fit), the int8 copy of the training states, the flattened
+    targets, the output bounds and the workspace; grad(idx) is one call of tm_valuenet_fit_grad on the current stream."""
+    BACKEND = "hip"
+    N_PARAMS = 478338
+
+    def _check_rows(self, data, L, what):
+        """the checks of one list of rows (`what`: "data", the training rows, or "validation data"); the number of rows"""
+        rows = data[0].shape[0]
+        if len(data) != 4 or rows < 1 or data[0].numel() != rows * 200:
+            if what != "data":
+                raise ValueError(L + " needs validation data = [states of 20 x 10 cells a row, values, variances, weights]")
+            if len(data) != 4:
+                raise ValueError(L + " needs data = [states, values, variances, weights]")
+            raise ValueError(L + " needs states of 20 x 10 cells a row, got shape %s" % (tuple(data[0].shape),))
+        if not bool(((data[0] == data[0].round()) & (data[0].abs() <= 127)).all()):
+            raise ValueError(L + " reads the states as int8: they must be integers in [-127, 127]")
+        if not all(d.is_cuda and d.dtype == torch.float32 for d in data):
+            raise ValueError(L + " needs float32 CUDA tensors (the %s is on %s)" % (what, data[0].device))
+        if any(t.shape[0] != rows or t.numel() != rows for t in data[1:]):
+            raise ValueError(L + " needs one value, variance and weight a row")
+        return rows
+
+    def _check(self, net, optimizer, train, L):
+        from .model import Net
+        rows = self._check_rows(train, L, "data")
+        if not isinstance(net, Net):
+            raise ValueError(L + " computes model.Net, not %s" % type(net).__name__)
+        if not (hasattr(optimizer, "fused") and optimizer.fused()):
+            raise ValueError(L + " writes the fused Yogi's flat gradient buffer: the optimizer must be a Yogi "
+                             "whose fused() holds (float32 parameters on one GPU in a single group)")
+        self.bounds = torch.cat([net.out_ubound.detach().reshape(2), net.out_lbound.detach().reshape(2)]).float().contiguous()
+        return rows
+
+    def _check_flat(self, net, optimizer, F, dev, L):
+        if F["n"] != self.N_PARAMS or not flat_order_is_param_order(net, optimizer):
+            raise ValueError(L + ": the optimizer's flat buffers are not the net's learnable tensors in model.PARAM_ORDER")
+
+    def _keep(self, data, rows, pre):
+        setattr(self, pre + "states", data[0].reshape(rows, 200).to(torch.int8).contiguous())
+        for name, t in zip(("value", "variance", "weight"), data[1:]):
+            setattr(self, pre + name, t.reshape(rows).contiguous())
+
+    def _workspace(self, n, validation=False):
+        return self._lib.lib().tm_valuenet_fit_validate_workspace(n) if validation else self._lib.lib().tm_valuenet_fit_workspace(n)
+
+    def _validate(self, weighted, stream):
+        self._lib.check(self._lib.lib().tm_valuenet_fit_validate(
+            self.F["p"].data_ptr(), self.bounds.data_ptr(), self.val_states.data_ptr(), self.val_value.data_ptr(),
+            self.val_variance.data_ptr(), self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab, weighted,
+            float(variance_bound), self.val_out.data_ptr(), self.val_ws.data_ptr(), stream), "tm_valuenet_fit_validate")
+
+    def _grad(self, idx, weighted, stream):
         F = self.F
         self._lib.check(self._lib.lib().tm_valuenet_fit_grad(
             F["p"].data_ptr(), self.bounds.data_ptr(), self.states.data_ptr(), self.value.data_ptr(), self.variance.data_ptr(),
-            self.weight.data_ptr(), idx.data_ptr(), self.batch, int(bool(weighted)), float(variance_bound), F["g"].data_ptr(),
-            self.loss.data_ptr(), self.ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream), "tm_valuenet_fit_grad")
-        return self.loss[0]
+            self.weight.data_ptr(), idx.data_ptr(), self.batch, weighted, float(variance_bound), F["g"].data_ptr(),
+            self.loss.data_ptr(), self.ws.data_ptr(), stream), "tm_valuenet_fit_grad")
 
 
 def dist_batch_loss(net, batch, weighted):
@@ -488,125 +470,82 @@ def flat_order_is_dist_param_order(net, optimizer):
             and all(a is b for a, b in zip(got, want)))
 
 
-class HipDistFit:
+class HipDistFit(_HipFitBase):
     """The per-fit state of fit_backend="hip_dist" (HipFit's sibling for the distributional head): the checks (once per fit), the
     int8 copy of the 20 visible rows of the training states, the targets, the weights and the workspace; grad(idx) is one call
     of tm_distnet_fit_grad on the current stream."""
+    BACKEND = "hip_dist"
+    N_PARAMS_0 = 279232      # the flat parameters without fc_v's 129 an atom
 
-    def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB):
-        from . import _lib
-        from .model_distributional import Net, ROW
-        B = "fit_backend='hip_dist'"
-        if len(train) != 3:
-            raise ValueError(B + " needs data = [states, targets, weights]")
-        states, target, weight = train
-        rows = states.shape[0]
-        if rows < 1 or states.numel() != rows * 220:
-            raise ValueError(B + " needs states of 22 x 10 cells a row, got shape %s" % (tuple(states.shape),))
-        if not isinstance(net, Net):
-            raise ValueError(B + " computes model_distributional.Net, not %s" % type(net).__name__)
-        atoms = net.seq.fc_v.out_features
-        if not (1 <= atoms <= ROW):
-            raise ValueError(B + " holds 1..64 atoms, the net has %d" % atoms)
+    def _check_rows(self, data, L, what):
+        """the checks of one list of rows (`what`: "data", the training rows, or "validation data"); the number of rows"""
+        rows, atoms = data[0].shape[0], self.atoms
+        if len(data) != 3 or rows < 1 or data[0].numel() != rows * 220:
+            if what != "data":
+                raise ValueError(L + " needs validation data = [states of 22 x 10 cells a row, targets, weights]")
+            if len(data) != 3:
+                raise ValueError(L + " needs data = [states, targets, weights]")
+            raise ValueError(L + " needs states of 22 x 10 cells a row, got shape %s" % (tuple(data[0].shape),))
+        states, target, weight = data
         if target.dim() != 2 or target.shape[0] != rows or target.shape[1] != atoms:
-            raise ValueError(B + " needs targets [rows, atoms] = [%d, %d] as the net's atoms, got %s" % (rows, atoms, tuple(target.shape)))
+            raise ValueError(L + " needs targets [rows, atoms] = [%d, %d]%s, got %s"
+                             % (rows, atoms, " as the net's atoms" if what == "data" else "", tuple(target.shape)))
         if weight.shape[0] != rows or weight.numel() != rows:
-            raise ValueError(B + " needs one weight a row")
-        if not isinstance(optimizer, FusedAdam):
-            raise ValueError(B + " writes FusedAdam's flat gradient buffer: the optimizer must be a train.FusedAdam, not %s"
-                             % type(optimizer).__name__)
-        if not flat_order_is_dist_param_order(net, optimizer):
-            raise ValueError(B + ": the optimizer's flat buffers are not the net's tensors in model_distributional.PARAM_ORDER")
+            raise ValueError(L + " needs one weight a row")
         s3 = states.reshape(rows, 22, 10)
         if not bool(((s3 == s3.round()) & (s3.abs() <= 127)).all()):
-            raise ValueError(B + " reads the states as int8: they must be integers in [-127, 127]")
+            raise ValueError(L + " reads the states as int8: they must be integers in [-127, 127]")
         if not bool((s3[:, :2] == 0).all()):
-            raise ValueError(B + " supplies the two top rows of the 22 itself: they must be all zero in the data")
+            raise ValueError(L + " supplies the two top rows of the 22 itself: they must be all zero in the data")
         if not bool((torch.isfinite(target) & (target >= 0)).all()):
-            raise ValueError(B + " needs finite targets >= 0")
-        if not all(d.is_cuda and d.dtype == torch.float32 for d in train):
-            raise ValueError(B + " needs float32 CUDA tensors (the data is %s on %s)" % (states.dtype, states.device))
-        if not optimizer.fused():
-            raise ValueError(B + ": the FusedAdam's fused() must hold (float32 parameters on one GPU in a single group)")
-        if val is not None:      # validation_backend="hip": the same checks on the held-out rows, before the optimiser is touched
-            V = "validation_backend='hip'"
-            vrows = val[0].shape[0]
-            if len(val) != 3 or vrows < 1 or val[0].numel() != vrows * 220:
-                raise ValueError(V + " needs validation data = [states of 22 x 10 cells a row, targets, weights]")
-            v3 = val[0].reshape(vrows, 22, 10)
-            if val[1].dim() != 2 or val[1].shape[0] != vrows or val[1].shape[1] != atoms:
-                raise ValueError(V + " needs targets [rows, atoms] = [%d, %d], got %s" % (vrows, atoms, tuple(val[1].shape)))
-            if val[2].shape[0] != vrows or val[2].numel() != vrows:
-                raise ValueError(V + " needs one weight a row")
-            if not bool(((v3 == v3.round()) & (v3.abs() <= 127)).all()):
-                raise ValueError(V + " reads the states as int8: they must be integers in [-127, 127]")
-            if not bool((v3[:, :2] == 0).all()):
-                raise ValueError(V + " supplies the two top rows of the 22 itself: they must be all zero in the data")
-            if not bool((torch.isfinite(val[1]) & (val[1] >= 0)).all()):
-                raise ValueError(V + " needs finite targets >= 0")
-            if not all(d.is_cuda and d.dtype == torch.float32 for d in val):
-                raise ValueError(V + " needs float32 CUDA tensors (the validation data is %s on %s)" % (val[0].dtype, val[0].device))
-            val_slab = _validation_slab(vrows, val_chunk, val_slab)
-            if _lib.lib().tm_distnet_fit_validate_workspace(val_slab, atoms) < 0:
-                raise ValueError(V + ": a slab of %d rows is refused" % val_slab)
-        F = optimizer.flatten()
-        if F["n"] != 279232 + 129 * atoms or F["p"].device != states.device:
-            raise ValueError(B + ": %d flat parameters on %s, expected %d on %s" % (F["n"], F["p"].device, 279232 + 129 * atoms, states.device))
-        if batch < 1:
-            raise ValueError(B + " needs a batch of at least one row per rank")
-        self._lib, self.F, self.batch, self.rows, self.dev, self.atoms = _lib, F, batch, rows, states.device, atoms
-        self.states = s3[:, 2:].reshape(rows, 200).to(torch.int8).contiguous()
-        self.target = target.contiguous()
-        self.weight = weight.reshape(rows).contiguous()
-        n_ws = _lib.lib().tm_distnet_fit_workspace(batch, atoms)
-        if n_ws < 0:
-            raise ValueError(B + ": a batch of %d rows is refused" % batch)
-        self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
-        self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
-        self._idx_checked = False
-        self.val_rows = 0
-        if val is not None:      # the int8 copy of the held-out states (once per fit), the slab's workspace and the chunks' rows
-            self.val_rows, self.val_chunk, self.val_slab = vrows, val_chunk, val_slab
-            self.val_states = v3[:, 2:].reshape(vrows, 200).to(torch.int8).contiguous()
-            self.val_target = val[1].contiguous()
-            self.val_weight = val[2].reshape(vrows).contiguous()
-            self.val_ws = torch.empty(_lib.lib().tm_distnet_fit_validate_workspace(val_slab, atoms), dtype=torch.float32,
-                                      device=self.dev)
-            self.val_out = torch.zeros((vrows + val_chunk - 1) // val_chunk, 3, dtype=torch.float64, device=self.dev)
+            raise ValueError(L + " needs finite targets >= 0")
+        if not all(d.is_cuda and d.dtype == torch.float32 for d in data):
+            raise ValueError(L + " needs float32 CUDA tensors (the %s is %s on %s)" % (what, states.dtype, states.device))
+        return rows
 
-    def validate(self, weighted):
-        """as HipFit.validate: the held-out rows' [w, mean, std] per chunk from ONE call of tm_distnet_fit_validate on the current
-        stream and ONE .cpu() (a one-row chunk's std is NaN, as torch.std_mean's: combine_chunk_rows maps it to 0)"""
-        if not self.val_rows:
-            raise ValueError("validation_backend='hip': this fit holds no validation rows")
+    def _check(self, net, optimizer, train, L):
+        from .model_distributional import Net, ROW
+        if not isinstance(net, Net):
+            raise ValueError(L + " computes model_distributional.Net, not %s" % type(net).__name__)
+        self.atoms = net.seq.fc_v.out_features
+        if not (1 <= self.atoms <= ROW):
+            raise ValueError(L + " holds 1..64 atoms, the net has %d" % self.atoms)
+        if not isinstance(optimizer, FusedAdam):
+            raise ValueError(L + " writes FusedAdam's flat gradient buffer: the optimizer must be a train.FusedAdam, not %s"
+                             % type(optimizer).__name__)
+        if not flat_order_is_dist_param_order(net, optimizer):
+            raise ValueError(L + ": the optimizer's flat buffers are not the net's tensors in model_distributional.PARAM_ORDER")
+        rows = self._check_rows(train, L, "data")
+        if not optimizer.fused():
+            raise ValueError(L + ": the FusedAdam's fused() must hold (float32 parameters on one GPU in a single group)")
+        return rows
+
+    def _check_flat(self, net, optimizer, F, dev, L):
+        want = self.N_PARAMS_0 + 129 * self.atoms
+        if F["n"] != want or F["p"].device != dev:
+            raise ValueError(L + ": %d flat parameters on %s, expected %d on %s" % (F["n"], F["p"].device, want, dev))
+
+    def _keep(self, data, rows, pre):
+        setattr(self, pre + "states", data[0].reshape(rows, 22, 10)[:, 2:].reshape(rows, 200).to(torch.int8).contiguous())
+        setattr(self, pre + "target", data[1].contiguous())
+        setattr(self, pre + "weight", data[2].reshape(rows).contiguous())
+
+    def _workspace(self, n, validation=False):
+        lib = self._lib.lib()
+        return lib.tm_distnet_fit_validate_workspace(n, self.atoms) if validation else lib.tm_distnet_fit_workspace(n, self.atoms)
+
+    def _validate(self, weighted, stream):
         self._lib.check(self._lib.lib().tm_distnet_fit_validate(
             self.F["p"].data_ptr(), self.val_states.data_ptr(), self.val_target.data_ptr(), self.val_target.stride(0),
-            self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab, self.atoms, int(bool(weighted)),
-            self.val_out.data_ptr(), self.val_ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream),
-            "tm_distnet_fit_validate")
-        return self.val_out.cpu().tolist()
+            self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab, self.atoms, weighted,
+            self.val_out.data_ptr(), self.val_ws.data_ptr(), stream), "tm_distnet_fit_validate")
 
-    def check_idx(self, idx):
-        """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
-        lo, hi = int(idx.min()), int(idx.max())
-        if lo < 0 or hi >= self.rows:
-            raise ValueError("fit_backend='hip_dist': indices in [%d, %d] do not all name one of the %d training rows" % (lo, hi, self.rows))
-
-    def grad(self, idx, weighted):
-        """as HipFit.grad: the loss (a 0-d device tensor) of the rows idx; the gradient of its mean lands in the optimiser's flat
-        buffer.  The first call of a fit that is not being captured checks the index range (one host synchronisation)."""
-        if idx.dtype != torch.int64 or idx.numel() != self.batch:
-            raise ValueError("fit_backend='hip_dist': expected %d int64 indices, got %d %s" % (self.batch, idx.numel(), idx.dtype))
-        if not self._idx_checked and not torch.cuda.is_current_stream_capturing():
-            self.check_idx(idx)
-            self._idx_checked = True
-        idx = idx.contiguous()
+    def _grad(self, idx, weighted, stream):
         F = self.F
         self._lib.check(self._lib.lib().tm_distnet_fit_grad(
             F["p"].data_ptr(), self.states.data_ptr(), self.target.data_ptr(), self.target.stride(0), self.weight.data_ptr(),
-            idx.data_ptr(), self.batch, self.atoms, int(bool(weighted)), F["g"].data_ptr(), self.loss.data_ptr(), self.ws.data_ptr(),
-            torch.cuda.current_stream(self.dev).cuda_stream), "tm_distnet_fit_grad")
-        return self.loss[0]
+            idx.data_ptr(), self.batch, self.atoms, weighted, F["g"].data_ptr(), self.loss.data_ptr(), self.ws.data_ptr(), stream),
+            "tm_distnet_fit_grad")
 
 
 def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validation_fraction=0.1,
