@@ -49,7 +49,7 @@ def lib():
         L.orc_agent_expand_game.argtypes = [vp, vp]
         L.orc_agent_remove_nodes.argtypes = [vp]
         for name in ("child", "score", "n_to_o", "visit", "value", "variance", "end_obs", "obs_state", "games",
-                     "stats", "mem_state", "mem_value", "mem_variance", "mem_visit", "mem_dist", "rng"):
+                     "stats", "mem_state", "mem_value", "mem_variance", "mem_visit", "mem_dist", "rng", "dist_census"):
             f = getattr(L, "orc_agent_" + name)
             f.restype, f.argtypes = vp, [vp]
         for name in ("root", "episode", "error", "n_avail", "n_obs_avail", "memory_index"):
@@ -255,6 +255,16 @@ class Agent:
         """kind 6: (node_stats [n,5] = visit, mean, score, variance, M2; node_dist [n,bins]) as core_distributional.py holds them"""
         n = self.max_nodes
         return self._arr("node_stats", np.float32, (n, 5)), self._arr("node_dist", np.float32, (n, self.bins))
+
+    DIST_CENSUS = ("shifts", "s_ge_1", "whole_bin", "s_ge_bins", "rounded_source", "negative", "repeated_node", "longest_trace")
+
+    def dist_census(self):
+        """kind 6: counters of what the backups' shifts looked like so far (dist_oracle.c distpy_shift, agent_oracle.c
+        mcts_dist) - shifts, those with s = int(bin_shift) >= 1, whole-bin ones (x != 0, fraction == 0), those with s >= bins,
+        those in which a source bin's b + bin_shift rounds up across an integer, those with x < 0; backups whose trace names a
+        node twice; the longest trace.  Measurements only."""
+        c = np.ctypeslib.as_array(C.cast(self.L.orc_agent_dist_census(self.h), C.POINTER(C.c_long)), (8,))
+        return dict(zip(self.DIST_CENSUS, (int(v) for v in c)))
 
     def memory(self):
         m = self.L.orc_agent_memory_index(self.h)

@@ -63,19 +63,37 @@ double orc_norm_quantile(double t); /* uct_oracle.c (special.h:26-33 == agents/s
 
 static int py_index(int i, int n) { return i < 0 ? i + n : i; } /* Python / numba wraparound indexing */
 
-void orc_distpy_shift(const float *dist, int bins, double x, double vmin, double vmax, float *result) {
+/* Census of the shifts (counters only; nothing reads them back): cen = NULL, or the eight counters of one agent -
+ * [0] shifts, [1] s >= 1 (s = int(bin_shift)), [2] whole-bin (x != 0 and fraction == 0), [3] s >= bins (all mass in the
+ * top atom), [4] shifts in which some source bin's b + bin_shift rounds up across an integer (int(b + bin_shift) != b + s:
+ * a gather that assumes lo(b) = b + s misses it), [5] x < 0; [6] and [7] belong to the backup's caller (agent_oracle.c). */
+static void distpy_shift(const float *dist, int bins, double x, double vmin, double vmax, float *result, long *cen) {
     double delta = (vmax - vmin) / bins;
     for (int b = 0; b < bins; ++b) result[b] = 0.0f;
     double bin_shift = x / delta;
     double fraction = bin_shift - floor(bin_shift);
+    int rounded = 0;
     for (int b = 0; b < bins; ++b) {
         int b_lb = (int)(b + bin_shift); /* int(): truncation toward zero */
+        rounded |= b_lb != b + (int)bin_shift;
         if (b_lb >= bins) b_lb = bins - 1;
         int b_ub = (b_lb + 1 >= bins) ? bins - 1 : b_lb + 1;
         int lo = py_index(b_lb, bins), hi = py_index(b_ub, bins);
         if (lo >= 0) result[lo] = (float)((double)result[lo] + (double)dist[b] * (1 - fraction));
         if (hi >= 0) result[hi] = (float)((double)result[hi] + (double)dist[b] * fraction);
     }
+    if (cen) {
+        cen[0] += 1;
+        cen[1] += (int)bin_shift >= 1;
+        cen[2] += x != 0 && fraction == 0;
+        cen[3] += (int)bin_shift >= bins;
+        cen[4] += rounded;
+        cen[5] += x < 0;
+    }
+}
+
+void orc_distpy_shift(const float *dist, int bins, double x, double vmin, double vmax, float *result) {
+    distpy_shift(dist, bins, x, vmin, vmax, result, NULL);
 }
 
 int orc_distpy_policy(const int32_t *child_nodes, int nc, const float *node_stats /* [n][5] */, double curr_reward) {
@@ -101,15 +119,16 @@ int orc_distpy_policy(const int32_t *child_nodes, int nc, const float *node_stat
     return child_nodes[best];
 }
 
-void orc_distpy_backup(const int32_t *trace, int len, float *node_stats /* [n][5] */, float *node_dist /* [n][bins] */,
-                       int bins, double r, const float *dist, double vmin, double vmax, float *scratch /* [bins] */) {
+void orc_distpy_backup_census(const int32_t *trace, int len, float *node_stats /* [n][5] */, float *node_dist /* [n][bins] */,
+                              int bins, double r, const float *dist, double vmin, double vmax, float *scratch /* [bins] */,
+                              long *cen /* NULL, or the shift counters above */) {
     double delta = (vmax - vmin) / bins, mean = 0;
     for (int b = 0; b < bins; ++b) mean += (double)dist[b] * ((b + 0.5) * delta);   /* mean_dist :40-46 */
     for (int t = 0; t < len; ++t) {
         int idx = trace[t];
         float *ns = node_stats + (size_t)idx * 5, *nd = node_dist + (size_t)idx * bins;
         double _r = r - (double)ns[2];
-        orc_distpy_shift(dist, bins, _r, vmin, vmax, scratch);
+        distpy_shift(dist, bins, _r, vmin, vmax, scratch, cen);
         for (int b = 0; b < bins; ++b) {
             float m = nd[b] * ns[0];
             float u = m + scratch[b];
@@ -123,4 +142,9 @@ void orc_distpy_backup(const int32_t *trace, int len, float *node_stats /* [n][5
         ns[4] = (float)((double)ns[4] + d1 * d2);
         if (ns[0] > 1.0f) ns[3] = (float)((double)ns[4] / ((double)ns[0] - 1.0));
     }
+}
+
+void orc_distpy_backup(const int32_t *trace, int len, float *node_stats, float *node_dist, int bins, double r, const float *dist,
+                       double vmin, double vmax, float *scratch) {
+    orc_distpy_backup_census(trace, len, node_stats, node_dist, bins, r, dist, vmin, vmax, scratch, NULL);
 }

@@ -616,6 +616,77 @@ def gen_distpy():
     print("ref_distpy.npz: %d shift, %d policy, %d backup cases" % (out["s_n"], out["p_n"], out["b_n"]))
 
 
+def gen_distpy_edges():
+    """ref_distpy_edges.npz: shift_distribution and backup_trace_distributional (agents/core_distributional.py:12-37,108-124,
+    run as plain Python like gen_distpy) at the parameters of tests/dist_regimes.py, where bins are a few points wide or less:
+    shifts of exactly one bin, of a whole number of bins, up to and beyond the top atom, and - for the two settings whose bin
+    width is no binary fraction - every integer shift below 200 in which some source bin's b + bin_shift rounds up across an
+    integer (the mass of that bin lands one atom higher than its neighbours').  The backup runs twice: on the float32
+    statistics as gen_distpy runs it, which gives the statistics, and on a float64 copy of them, which gives the distributions -
+    a plain-Python `r - ns[2]` on a float32 row is a float32 under NumPy 2 and bin_shift with it, whereas numba types both
+    float64; at bins this narrow the float32 bin_shift is off by more than the fixtures' tolerance, and where a bin index hangs
+    on its last bit the mass lands in another atom."""
+    ref_shims.install()
+    from agents import core_distributional as cd
+    rng = np.random.default_rng(20261018)
+    out = {}
+    configs = ((50, 0.0, 50.0), (30, 0.0, 70.0), (50, 0.0, 7.0), (64, 0.0, 32.0), (1, 0.0, 10.0), (2, 0.0, 100.0), (7, 0.0, 300.0),
+               (63, 0.0, 1000.0), (50, -100.0, 400.0))
+
+    def rounds(bins, bs):
+        return any(int(b + bs) != b + int(bs) for b in range(bins))
+    n_rounded = 0
+    for ci, (bins, vmin, vmax) in enumerate(configs):
+        delta = (vmax - vmin) / bins
+        whole = next(k for k in range(2, 40) if (k * delta / delta) == k)             # a whole number of bins > 1
+        xs = [0.0, delta, whole * delta, 1.37 * delta, (bins - 1 + 0.5) * delta, (bins + 0.25) * delta, (bins + 3.5) * delta]
+        bs = [x / delta for x in xs]
+        assert bs[1] == 1.0 and bs[2] == whole and bs[3] != np.floor(bs[3])
+        assert int(bs[4]) == bins - 1 and int(bs[5]) == bins and int(bs[6]) > bins
+        if (bins, vmax) in ((30, 70.0), (50, 7.0)):
+            rx = [float(x) for x in range(1, 200) if rounds(bins, x / delta)]
+            assert rx, (bins, vmax)
+            n_rounded += len(rx)
+            xs += rx
+        d = rng.random((len(xs), bins)).astype(np.float32)
+        d /= d.sum(1, keepdims=True)
+        r = np.stack([np.asarray(cd.shift_distribution(d[i], xs[i], vmin, vmax), np.float32) for i in range(len(xs))])
+        out.update({"s_cfg_%d" % ci: np.array([bins, vmin, vmax]), "s_dist_%d" % ci: d, "s_x_%d" % ci: np.array(xs), "s_out_%d" % ci: r})
+    out["s_n"] = len(configs)
+    # backup_trace_distributional: integer scores like the game's, leaves up to a third of the range above the highest node
+    n = 0
+    for bins, vmin, vmax in configs:
+        span = vmax - vmin
+        for tl in (1, 19):
+            n_nodes = 24
+            ns = np.zeros((n_nodes, 5), np.float32)
+            ns[:, 0] = rng.integers(0, 25, n_nodes)
+            ns[:, 1] = rng.random(n_nodes) * span * 0.3
+            ns[:, 2] = rng.integers(0, max(2, int(0.9 * span)), n_nodes)
+            ns[:, 4] = rng.random(n_nodes) * 3000 * (ns[:, 0] > 0)
+            ns[:, 3] = np.where(ns[:, 0] > 1, ns[:, 4] / np.maximum(ns[:, 0] - 1, 1), 0)
+            nd = rng.random((n_nodes, bins)).astype(np.float32)
+            nd /= nd.sum(1, keepdims=True)
+            nd[ns[:, 0] == 0] = 0
+            trace = rng.choice(np.arange(1, n_nodes), tl, replace=False).astype(np.int32)
+            d = rng.random(bins).astype(np.float32)
+            d /= d.sum()
+            r = float(ns[trace, 2].max() + rng.integers(0, int(0.3 * span) + 2))
+            ns_in, nd_in = ns.copy(), nd.copy()
+            ns64 = ns.astype(np.float64)
+            cd.backup_trace_distributional(trace, ns, nd.copy(), r, d, vmin, vmax)        # the statistics, as gen_distpy runs it
+            cd.backup_trace_distributional(trace, ns64, nd, r, d, vmin, vmax)             # the distributions: float64 scalars
+            out.update({"b_stats_in_%d" % n: ns_in, "b_dist_in_%d" % n: nd_in, "b_trace_%d" % n: trace, "b_r_%d" % n: r,
+                        "b_leaf_%d" % n: d, "b_vmin_%d" % n: vmin, "b_vmax_%d" % n: vmax, "b_stats_out_%d" % n: ns,
+                        "b_dist_out_%d" % n: nd})
+            n += 1
+    out["b_n"] = n
+    path = os.path.join(OUT, "ref_distpy_edges.npz")
+    np.savez_compressed(path, **out)
+    print("ref_distpy_edges.npz: %d shift settings (%d cases, %d of them with a rounded source), %d backup cases, %d bytes" % (
+        out["s_n"], sum(len(out["s_x_%d" % i]) for i in range(out["s_n"])), n_rounded, out["b_n"], os.path.getsize(path)))
+
+
 def gen_dist():
     """ref_dist.npz: the reference's distribution helpers (core.h:387-449, compiled through oracle/ref_dist_shim.cpp) on
     seeded categorical distributions.  Only cases in which the reference's write to result[bins] adds exactly 0 or does not
@@ -827,7 +898,7 @@ def gen_heads_trained():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["uct", "uct_live", "valuenet", "agents", "cppagent", "mixture", "vanilla", "online", "online_py", "agents_env", "training", "vanillac", "dist", "distnet", "treeagent", "distpy", "heads_trained"]
+    which = sys.argv[1:] or ["uct", "uct_live", "valuenet", "agents", "cppagent", "mixture", "vanilla", "online", "online_py", "agents_env", "training", "vanillac", "dist", "distnet", "treeagent", "distpy", "distpy_edges", "heads_trained"]
     params = None
     if "uct" in which:
         gen_uct()
@@ -855,6 +926,8 @@ if __name__ == "__main__":
         gen_treeagent()
     if "distpy" in which:
         gen_distpy()
+    if "distpy_edges" in which:
+        gen_distpy_edges()
     if "dist" in which:
         gen_dist()
     if "distnet" in which:

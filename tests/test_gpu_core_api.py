@@ -253,3 +253,83 @@ def test_distributional_numba_kernels_match_the_reference_functions(oracle, gold
             assert gs[i].tobytes() == os_.tobytes() and gd[i].tobytes() == od.tobytes(), (N, bins, i)
             n += 1
     assert n == 12
+
+
+def test_distributional_numba_kernels_at_narrow_bins(oracle, golden_dir):
+    """tm_distpy_shift / tm_distpy_backup at the settings of tests/dist_regimes.py (ref_distpy_edges.npz: whole-bin shifts, shifts
+    up to and beyond the top atom, integer shifts in which a source bin rounds up across an integer; 1, 2, 7, 63 and 64 atoms;
+    vmin != 0): the oracle's bits, and the reference functions' values within the float tolerance of the other distpy cases."""
+    import torch
+    from tetris_mcts_amd import _lib
+    from tetris_mcts_amd.store import _p, _stream
+    from test_oracle_dist import ATOL, RTOL, distpy_edge_backups, distpy_edge_shifts
+    L, OL = _lib.lib(), oracle.lib()
+    cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    groups = {}
+    for c in distpy_edge_shifts(golden_dir):
+        groups.setdefault((c["bins"], c["vmin"], c["vmax"]), []).append(c)
+    n = 0
+    for (bins, vmin, vmax), cs in groups.items():
+        d = cuda(np.stack([c["dist"] for c in cs]).astype(np.float32))
+        x = cuda(np.array([c["x"] for c in cs], np.float64))
+        out = torch.zeros_like(d)
+        _lib.check(L.tm_distpy_shift(len(cs), bins, _p(d), _p(x), vmin, vmax, _p(out), _stream()), "tm_distpy_shift")
+        got = out.cpu().numpy()
+        for i, c in enumerate(cs):
+            assert np.allclose(got[i], c["out"], rtol=RTOL, atol=ATOL), (bins, vmax, c["x"])
+            want = np.zeros(bins, np.float32)
+            src = np.ascontiguousarray(c["dist"], np.float32)
+            OL.orc_distpy_shift(oracle.ptr(src), bins, c["x"], vmin, vmax, oracle.ptr(want))
+            assert got[i].tobytes() == want.tobytes(), (bins, vmax, c["x"])
+            n += 1
+    assert n == 73 and len(groups) == 9
+    n = 0
+    for c in distpy_edge_backups(golden_dir):
+        (N, bins), tl, vmin, vmax = c["dist_in"].shape, len(c["trace"]), float(c["vmin"]), float(c["vmax"])
+        ns, nd = cuda(c["stats_in"][None]), cuda(c["dist_in"][None])
+        tr, tlen = cuda(c["trace"][None].astype(np.int32)), cuda(np.full(1, tl, np.int32))
+        r, leaf = cuda(np.array([float(c["r"])], np.float64)), cuda(c["leaf"][None].astype(np.float32))
+        scratch = torch.zeros(1, bins, device="cuda")
+        _lib.check(L.tm_distpy_backup(1, N, bins, _p(tr), _p(tlen), tl, _p(ns), _p(nd), _p(r), _p(leaf), vmin, vmax, _p(scratch),
+                                      _stream()), "tm_distpy_backup")
+        gs, gd = ns.cpu().numpy()[0], nd.cpu().numpy()[0]
+        assert np.allclose(gs, c["stats_out"], rtol=1e-5, atol=1e-4), (n, bins)
+        assert np.allclose(gd, c["dist_out"], rtol=RTOL, atol=ATOL), (n, bins)
+        os_, od = c["stats_in"].copy(), c["dist_in"].copy()
+        t_, l_, sc = np.ascontiguousarray(c["trace"], np.int32), np.ascontiguousarray(c["leaf"], np.float32), np.zeros(bins, np.float32)
+        OL.orc_distpy_backup(oracle.ptr(t_), tl, oracle.ptr(os_), oracle.ptr(od), bins, float(c["r"]), oracle.ptr(l_), vmin, vmax,
+                             oracle.ptr(sc))
+        assert gs.tobytes() == os_.tobytes() and gd.tobytes() == od.tobytes(), (n, bins)
+        n += 1
+    assert n == 18
+
+
+def test_distpy_shift_with_negative_shifts_wraps_like_the_oracle(oracle):
+    """x < 0 never occurs in a search (a node never scores more than the leaf below it; the census of tests/test_oracle_dist.py
+    counts none), but tm_distpy_shift is a drop-in for the reference function, whose negative bin indices wrap around the Python
+    way: the oracle's py_index is the expected result, bit for bit, at -0.5, -1.5 and -(bins + 2) bins."""
+    import torch
+    import dist_regimes as R
+    from tetris_mcts_amd import _lib
+    from tetris_mcts_amd.store import _p, _stream
+    L, OL = _lib.lib(), oracle.lib()
+    rng = np.random.default_rng(20261019)
+    for bins, vmin, vmax in sorted({(r.atoms, r.vmin, r.vmax) for r in R.REGIMES + (R.SUITE_SETTING,)}):
+        delta = (vmax - vmin) / bins
+        xs = np.array([-0.5 * delta, -1.5 * delta, -(bins + 2) * delta], np.float64)
+        d = rng.random((len(xs), bins)).astype(np.float32)
+        d /= d.sum(1, keepdims=True)
+        want = np.zeros_like(d)
+        for i in range(len(xs)):
+            OL.orc_distpy_shift(oracle.ptr(np.ascontiguousarray(d[i])), bins, float(xs[i]), vmin, vmax, oracle.ptr(want[i]))
+        td, tx = torch.from_numpy(d).cuda(), torch.from_numpy(xs).cuda()
+        out = torch.full_like(td, float("nan"))
+        _lib.check(L.tm_distpy_shift(len(xs), bins, _p(td), _p(tx), vmin, vmax, _p(out), _stream()), "tm_distpy_shift")
+        assert out.cpu().numpy().tobytes() == want.tobytes(), (bins, vmin, vmax)
+        if bins >= 4:
+            # the wraparound really is in these cases: bin 0 shifted down one and a half bins puts half its mass into the LAST atom
+            e = np.zeros(bins, np.float32)
+            e[0] = 1.0
+            w = np.zeros(bins, np.float32)
+            OL.orc_distpy_shift(oracle.ptr(e), bins, float(xs[1]), vmin, vmax, oracle.ptr(w))
+            assert w[bins - 1] > 0

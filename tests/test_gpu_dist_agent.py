@@ -1,10 +1,19 @@
 """DistValueSim (TM_KIND_DIST, BASELINE configs[4]) on the GPU against the oracle's restatement of the same
 agent (oracle/agent_oracle.c kind 6 = TreeAgent's tree + agents/core_distributional.py's kernels as oracle/dist_oracle.c
 restates them, pinned on a pure-Python run of the reference functions).  Both sides evaluate leaves with the same hash
-distribution, so actions, root statistics, per-node statistics and all 50-atom distributions must agree bit for bit -
-through garbage collections too."""
+distribution, so actions, root statistics, per-node statistics and all distributions' atoms must agree bit for bit -
+through garbage collections too - at the default 50 atoms over [0, 5000) and in the regimes of tests/dist_regimes.py, whose
+bins are narrow enough that the backups' shifts move mass by whole bins, past the top atom and across rounding edges
+(tests/test_oracle_dist.py proves that of each regime on the CPU)."""
+import os
+import sys
+from functools import partial
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dist_regimes as R  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 _M = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -38,6 +47,10 @@ def test_hash_dist_matches_the_oracle(oracle):
     out = np.zeros((9, 50), np.float32)
     oracle.lib().orc_hash_dist(None, oracle.ptr(st), 9, 50, oracle.ptr(out))
     assert out.tobytes() == hash_dist(st.reshape(9, 20, 10)).tobytes()
+    for bins in sorted({r.atoms for r in R.REGIMES}):
+        out = np.zeros((9, bins), np.float32)
+        oracle.lib().orc_hash_dist(None, oracle.ptr(st), 9, bins, oracle.ptr(out))
+        assert out.tobytes() == hash_dist(st.reshape(9, 20, 10), bins=bins).tobytes(), bins
 
 
 @pytest.mark.parametrize("max_nodes,moves,sims", [(20000, 10, 120), (5000, 16, 150)])
@@ -45,11 +58,12 @@ def test_dist_agent_matches_the_oracle_bit_for_bit(oracle, max_nodes, moves, sim
     import torch
     from tetris_mcts_amd import agents
     from tetris_mcts_amd.pyTetris import Tetris
-    G = 6
+    G, bins = 6, 50
     env_args = ((20, 10), 1, 0, 0)
     seeds = 4242 + np.arange(G)
     game = Tetris(*env_args, seed=seeds, n_games=G)
-    agent = agents.DistValueSim(sims=sims, env=Tetris, env_args=env_args, n_games=G, max_nodes=max_nodes, evaluator=hash_dist)
+    agent = agents.DistValueSim(sims=sims, env=Tetris, env_args=env_args, n_games=G, max_nodes=max_nodes,
+                                evaluator=partial(hash_dist, bins=bins))
     agent.update_root(game)
     og = [oracle.Game(seed=int(s)) for s in seeds]
     oa = [oracle.Agent(6, max_nodes=max_nodes, low=5) for _ in range(G)]
@@ -90,8 +104,8 @@ def test_dist_agent_matches_the_oracle_bit_for_bit(oracle, max_nodes, moves, sim
         occ = np.nonzero(mark)[0]
         occ = occ[occ != 0]
         assert stat[g, occ][:, [0, 1, 2, 3]].tobytes() == np.ascontiguousarray(ns[occ][:, [0, 1, 3, 4]]).tobytes(), g
-        assert dist[g, occ, :50].tobytes() == np.ascontiguousarray(nd[occ]).tobytes(), g
-        assert np.all(dist[g, occ, 50:] == 0)
+        assert dist[g, occ, :bins].tobytes() == np.ascontiguousarray(nd[occ]).tobytes(), g
+        assert np.all(dist[g, occ, bins:] == 0)
     if max_nodes <= 5000:
         assert n_gc > 0          # the small pool went through collections
 
@@ -181,13 +195,15 @@ def test_dist_agent_with_the_hip_head_matches_the_oracle_bit_for_bit(oracle, max
             for g in np.nonzero(ended)[0]:
                 og[g].reset()
                 oa[g].update_root(og[g])
-    _compare_dist_trees(oracle, agent, oa, range(G), max_nodes)
+    _compare_dist_trees(oracle, agent, oa, range(G), max_nodes, bins=50)
     assert agent.store.search_stats(1, 0)["runs"] == moves             # the native loop ran the moves
     if max_nodes <= 4000:
         assert agent.store.counter("N_GC") > 0
 
 
-def _compare_dist_trees(oracle, agent, oa, games, max_nodes, oracles=None):
+def _compare_dist_trees(oracle, agent, oa, games, max_nodes, oracles=None, bins=50):
+    """root, simulation / expansion / collection counts, every reachable node's (visit, mean, variance, M2) and its `bins` atoms
+    against the oracles', bit for bit; the rows' padding beyond the atoms stays zero"""
     import torch
     s = agent.store
     assert (s.errors() == 0).all()
@@ -205,8 +221,93 @@ def _compare_dist_trees(oracle, agent, oa, games, max_nodes, oracles=None):
         occ = np.nonzero(mark)[0]
         occ = occ[occ != 0]
         assert stat[occ][:, [0, 1, 2, 3]].tobytes() == np.ascontiguousarray(ns[occ][:, [0, 1, 3, 4]]).tobytes(), g
-        assert dist[occ, :50].tobytes() == np.ascontiguousarray(nd[occ]).tobytes(), g
-        assert np.all(dist[occ, 50:] == 0)
+        assert nd.shape[1] == bins
+        assert dist[occ, :bins].tobytes() == np.ascontiguousarray(nd[occ]).tobytes(), g
+        assert np.all(dist[occ, bins:] == 0)
+
+
+def _play_against_the_oracle(agent, game, og, oa, moves, sims):
+    """`moves` moves of the device agent and of one oracle agent per game side by side: the same action and the same bits of
+    the root statistics on every move"""
+    G = len(oa)
+    for m in range(moves):
+        act = np.atleast_1d(agent.play())
+        stats = agent.get_stats().reshape(G, 3, 7)
+        for g in range(G):
+            a = oa[g].play(sims)
+            assert oa[g].error == 0, ("oracle", m, g, oa[g].error)
+            assert a == act[g], ("action", m, g, a, act[g], oa[g].stats(), stats[g])
+            assert oa[g].stats().tobytes() == stats[g].tobytes(), ("stats", m, g, oa[g].stats(), stats[g])
+            og[g].play(a)
+            oa[g].update_root(og[g])
+        game.play(act)
+        agent.update_root(game)
+        ended = np.atleast_1d(game.end)
+        assert [bool(e) for e in ended] == [o.end for o in og], m
+        if ended.any():
+            game.reset("ended")
+            agent.update_root(game)
+            for g in np.nonzero(ended)[0]:
+                og[g].reset()
+                oa[g].update_root(og[g])
+
+
+# every regime at its own pool (no collection), and two of them again with a pool small enough to collect
+_TREE_CASES = [(r.name, r.max_nodes) for r in R.REGIMES] + [("round", 2500), ("full_wave", 2500)]
+
+
+@pytest.mark.parametrize("name,max_nodes", _TREE_CASES, ids=["%s-%d" % c for c in _TREE_CASES])
+def test_dist_tree_kernels_match_the_oracle_in_every_regime(oracle, name, max_nodes):
+    """wave_dist_front / wave_dist_back with the hash evaluator in the regimes of tests/dist_regimes.py: other atom counts (1, 2,
+    7, 30, 63, 64 - the whole wave), vmin != 0, app 2 and 3 (the backup's sequential branch), and bins so narrow that most shifts
+    are whole-bin, pass the top atom or round a source bin up across an integer - which the backup's gather window has to cover.
+    Actions and root statistics on every move; at the end the root, the counters, every reachable node's statistics and atoms
+    and the zero padding."""
+    from tetris_mcts_amd import agents
+    from tetris_mcts_amd.pyTetris import Tetris
+    r = R.BY_NAME[name]
+    G = R.GAMES
+    game = Tetris(*R.env_args(r), seed=np.asarray(R.seeds()), n_games=G)
+    agent = agents.DistValueSim(atoms=r.atoms, vmin=r.vmin, vmax=r.vmax, sims=r.sims, env=Tetris, env_args=R.env_args(r), n_games=G,
+                                max_nodes=max_nodes, evaluator=partial(hash_dist, bins=r.atoms))
+    agent.update_root(game)
+    og, oa = R.oracle_side(oracle, r, max_nodes)
+    _play_against_the_oracle(agent, game, og, oa, r.moves, r.sims)
+    _compare_dist_trees(oracle, agent, oa, range(G), max_nodes, bins=r.atoms)
+    assert sum(o.n_sims for o in oa) == G * r.moves * r.sims
+    if max_nodes < r.max_nodes:
+        assert agent.store.counter("N_GC") > 0         # the small pool went through collections
+    else:
+        # the run is the one the CPU census proves non-trivial (tests/test_oracle_dist.py): the same seeds, sizes and pool
+        c = [o.dist_census() for o in oa]
+        assert sum(x["shifts"] for x in c) > 20000 and max(x["longest_trace"] for x in c) >= 9
+
+
+@pytest.mark.parametrize("atoms,name,max_nodes,moves,sims", [(7, "seven", 20000, 3, 80), (7, "seven", 1200, 6, 60),
+                                                             (64, "full_wave", 20000, 3, 80), (64, "full_wave", 1200, 6, 60)])
+def test_dist_agent_with_the_hip_head_matches_the_oracle_at_other_atom_counts(oracle, atoms, name, max_nodes, moves, sims):
+    """The head's request path inside the native loop (tm_distnet_forward_requests indexes its parameter blob with the store's
+    atom count) at 7 atoms over [0, 300) and 64 atoms over [0, 32), against oracle kind 6 with distnet_oracle.c as its evaluator:
+    actions, root statistics, every reachable node's statistics and atoms, with and without collections."""
+    from tetris_mcts_amd import agents
+    from tetris_mcts_amd.model_distributional import Model_Dist
+    from tetris_mcts_amd.pyTetris import Tetris
+    r = R.BY_NAME[name]
+    assert r.atoms == atoms
+    G, seed0 = 8, 777
+    model = Model_Dist(atoms=atoms, seed=atoms, backend="hip")
+    P = model.flat_params().cpu().numpy()
+    game = Tetris(*R.env_args(r), seed=np.asarray(R.seeds(G, seed0)), n_games=G)
+    agent = agents.DistValueSim(atoms=atoms, vmin=r.vmin, vmax=r.vmax, sims=sims, env=Tetris, env_args=R.env_args(r), n_games=G,
+                                max_nodes=max_nodes, model=model)
+    assert agent.search_model() is model
+    agent.update_root(game)
+    og, oa = R.oracle_side(oracle, r, max_nodes, n_games=G, seed0=seed0, evaluator="distnet", params=P)
+    _play_against_the_oracle(agent, game, og, oa, moves, sims)
+    _compare_dist_trees(oracle, agent, oa, range(G), max_nodes, bins=atoms)
+    assert agent.store.search_stats(1, 0)["runs"] == moves             # the native loop ran the moves
+    if max_nodes <= 4000:
+        assert agent.store.counter("N_GC") > 0
 
 
 def test_sampled_games_of_the_benchmarked_dist_batch(oracle):
@@ -253,7 +354,7 @@ def test_sampled_games_of_the_benchmarked_dist_batch(oracle):
                 assert st.tobytes() == stats[g].tobytes(), ("stats", m, g, st, stats[g])
     gs = agent.store.t["gs"]
     assert (gs[:, 8] == moves * sims).all() and int(gs[:, 6].abs().sum().item()) == 0
-    _compare_dist_trees(oracle, agent, oa, sample, N)
+    _compare_dist_trees(oracle, agent, oa, sample, N, bins=50)
     del agent
     torch.cuda.empty_cache()
 
@@ -286,25 +387,27 @@ def test_dist_agent_with_the_distributional_net():
     assert np.isfinite(mean).all() and (np.asarray(var) >= -1e-6).all()
 
 
-@pytest.mark.parametrize("max_nodes,sims,moves", [(3000, 150, 60), (1500, 60, 120)])
-def test_dist_online_harvest_matches_the_oracle(oracle, max_nodes, sims, moves):
+@pytest.mark.parametrize("regime,max_nodes,sims,moves", [(None, 3000, 150, 60), (None, 1500, 60, 120), ("full_wave", 3000, 60, 40),
+                                                         ("seven", 3000, 60, 40)],
+                         ids=["3000-150-60", "1500-60-120", "full_wave-3000-60-40", "seven-3000-60-40"])
+def test_dist_online_harvest_matches_the_oracle(oracle, regime, max_nodes, sims, moves):
     """The online leg (DistValueSimOnline.store_nodes, agents/DistValueSimOnline.py:116-141): what the collections harvest on the
-    device - freed nodes with enough visits whose seven children were all visited: board, 50-atom distribution, visit count, per
-    game in index order, collection after collection - is what oracle kind 6 stores, bit for bit; the search itself too."""
+    device - freed nodes with enough visits whose seven children were all visited: board, distribution, visit count, per game in
+    index order, collection after collection - is what oracle kind 6 stores, bit for bit; the search itself too.  At the default
+    50 atoms over [0, 5000), and at 64 and 7 atoms in the regimes `full_wave` and `seven` of tests/dist_regimes.py."""
     import torch
     from tetris_mcts_amd import agents, dist as tdist
     from tetris_mcts_amd.pyTetris import Tetris
     G = 6
-    env_args = ((20, 10), 1, 0, 0)
-    seeds = 31337 + np.arange(G)
+    r = R.SUITE_SETTING if regime is None else R.BY_NAME[regime]
+    bins, env_args = r.atoms, R.env_args(r)
+    seeds = (31337 if regime is None else R.SEED0) + np.arange(G)
     game = Tetris(*env_args, seed=seeds, n_games=G)
-    agent = agents.DistValueSim(sims=sims, env=Tetris, env_args=env_args, n_games=G, max_nodes=max_nodes, evaluator=hash_dist,
-                                online=True, min_visits_to_store=8, replay_cap=8192)
+    agent = agents.DistValueSim(atoms=bins, vmin=r.vmin, vmax=r.vmax, sims=sims, env=Tetris, env_args=env_args, n_games=G,
+                                max_nodes=max_nodes, evaluator=partial(hash_dist, bins=bins), online=True, min_visits_to_store=8,
+                                replay_cap=8192)
     agent.update_root(game)
-    og = [oracle.Game(seed=int(s)) for s in seeds]
-    oa = [oracle.Agent(6, max_nodes=max_nodes, low=5, online=True, min_visits_to_store=8, memory_size=100000) for _ in range(G)]
-    for g in range(G):
-        oa[g].update_root(og[g])
+    og, oa = R.oracle_side(oracle, r, max_nodes, n_games=G, seed0=int(seeds[0]), online=True, min_visits_to_store=8, memory_size=100000)
     for m in range(moves):
         act = np.atleast_1d(agent.play())
         stats = agent.get_stats().reshape(G, 3, 7)
@@ -335,7 +438,9 @@ def test_dist_online_harvest_matches_the_oracle(oracle, max_nodes, sims, moves):
         keys = s.t["replay_obs"][g, :cnt[g]]
         dev_states = tdist.render_observations(keys).reshape(-1, 200).cpu().numpy().astype(np.int8)
         assert np.array_equal(dev_states, st), g
-        assert s.t["replay_dist"][g, :cnt[g], :50].cpu().numpy().tobytes() == d.tobytes(), g
+        assert d.shape[1] == bins
+        assert s.t["replay_dist"][g, :cnt[g], :bins].cpu().numpy().tobytes() == d.tobytes(), g
+        assert float(s.t["replay_dist"][g, :cnt[g], bins:].abs().sum()) == 0.0
         assert s.t["replay_stat"][g, :cnt[g], 2].cpu().numpy().tobytes() == v.tobytes(), g
         total += int(cnt[g])
     assert total > 50 and s.counter("N_GC") == sum(o.n_gc for o in oa) > G

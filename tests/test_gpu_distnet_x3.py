@@ -131,8 +131,8 @@ def test_x3_request_path_equals_the_dense_path(golden_dir):
     assert torch.isnan(s.t["eval_dist"][~used]).all() and torch.isnan(s.t["eval_dist"][:, 50:]).all()
 
 
-def _compare_dist_trees(oracle, agent, oa, max_nodes):
-    """every reachable node's statistics and 50-atom distribution, bit for bit (tests/test_gpu_dist_agent.py)"""
+def _compare_dist_trees(oracle, agent, oa, max_nodes, bins=50):
+    """every reachable node's statistics and its `bins` atoms, bit for bit (tests/test_gpu_dist_agent.py)"""
     import torch
     s = agent.store
     assert (s.errors() == 0).all()
@@ -148,31 +148,29 @@ def _compare_dist_trees(oracle, agent, oa, max_nodes):
         occ = np.nonzero(mark)[0]
         occ = occ[occ != 0]
         assert stat[occ][:, [0, 1, 2, 3]].tobytes() == np.ascontiguousarray(ns[occ][:, [0, 1, 3, 4]]).tobytes(), g
-        assert dist[occ, :50].tobytes() == np.ascontiguousarray(nd[occ]).tobytes(), g
-        assert np.all(dist[occ, 50:] == 0)
+        assert nd.shape[1] == bins
+        assert dist[occ, :bins].tobytes() == np.ascontiguousarray(nd[occ]).tobytes(), g
+        assert np.all(dist[occ, bins:] == 0)
 
 
-def test_native_loop_on_x3_replays_in_the_oracle(oracle):
-    """DistValueSim on "hip_bf16x3" inside the native launch loop (tm_search_run, TM_VALUENET_BF16X3) against oracle kind 6
-    whose evaluator callable runs a second "hip_bf16x3" head on the same weights: actions, root statistics, every reachable
-    node's statistics and distribution, through garbage collections"""
+def _native_loop_replay(oracle, atoms, vmin, vmax, G, sims, max_nodes, moves):
     import torch
     from tetris_mcts_amd import agents
     from tetris_mcts_amd.pyTetris import Tetris
-    G, sims, max_nodes, moves = 6, 150, 3000, 12
     env_args = ((20, 10), 1, 0, 0)
     seeds = 919 + np.arange(G)
-    model = _model("hip_bf16x3", seed=0)
-    evm = _model("hip_bf16x3", model.flat_params().cpu())
+    model = _model("hip_bf16x3", atoms=atoms, seed=0)
+    evm = _model("hip_bf16x3", model.flat_params().cpu(), atoms=atoms)
 
     def ev(states):
-        return evm.inference_device(torch.from_numpy(states.reshape(-1, 200)).cuda())[:, :50].cpu().numpy()
+        return evm.inference_device(torch.from_numpy(states.reshape(-1, 200)).cuda())[:, :atoms].cpu().numpy()
     game = Tetris(*env_args, seed=seeds, n_games=G)
-    agent = agents.DistValueSim(sims=sims, env=Tetris, env_args=env_args, n_games=G, max_nodes=max_nodes, model=model)
+    agent = agents.DistValueSim(atoms=atoms, vmin=vmin, vmax=vmax, sims=sims, env=Tetris, env_args=env_args, n_games=G,
+                                max_nodes=max_nodes, model=model)
     assert agent.search_model() is model
     agent.update_root(game)
     og = [oracle.Game(seed=int(s)) for s in seeds]
-    oa = [oracle.Agent(6, max_nodes=max_nodes, low=5, evaluator=ev) for _ in range(G)]
+    oa = [oracle.Agent(6, max_nodes=max_nodes, low=5, evaluator=ev, dist_bins=atoms, dist_vmin=vmin, dist_vmax=vmax) for _ in range(G)]
     for g in range(G):
         oa[g].update_root(og[g])
     for m in range(moves):
@@ -194,9 +192,22 @@ def test_native_loop_on_x3_replays_in_the_oracle(oracle):
             for g in np.nonzero(ended)[0]:
                 og[g].reset()
                 oa[g].update_root(og[g])
-    _compare_dist_trees(oracle, agent, oa, max_nodes)
+    _compare_dist_trees(oracle, agent, oa, max_nodes, bins=atoms)
     assert agent.store.search_stats(1, 0)["runs"] == moves             # the native loop ran the moves
     assert agent.store.counter("N_GC") > 0
+
+
+def test_native_loop_on_x3_replays_in_the_oracle(oracle):
+    """DistValueSim on "hip_bf16x3" inside the native launch loop (tm_search_run, TM_VALUENET_BF16X3) against oracle kind 6
+    whose evaluator callable runs a second "hip_bf16x3" head on the same weights: actions, root statistics, every reachable
+    node's statistics and distribution, through garbage collections"""
+    _native_loop_replay(oracle, 50, 0.0, 5000.0, G=6, sims=150, max_nodes=3000, moves=12)
+
+
+def test_native_loop_on_x3_replays_in_the_oracle_at_64_atoms(oracle):
+    """the same at 64 atoms over [0, 32) (the regime `full_wave` of tests/dist_regimes.py): the split-precision head's request
+    path indexes its parameter blob with the store's atom count, and the backup's shifts are whole-bin, most of them past the top"""
+    _native_loop_replay(oracle, 64, 0.0, 32.0, G=6, sims=60, max_nodes=1200, moves=6)
 
 
 def test_x3_planes_follow_weight_changes(golden_dir, tmp_path, monkeypatch):

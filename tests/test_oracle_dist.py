@@ -1,8 +1,13 @@
 """The distribution helpers of the reference (agents/cppmodule/core.h:387-449, BASELINE configs[4]'s pinnable part):
 oracle/dist_oracle.c against the reference's own outputs (tests/golden/ref_dist.npz, make_golden.py gen_dist)."""
 import os
+import sys
 
 import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dist_regimes as R  # noqa: E402
 
 
 def _cases(golden_dir):
@@ -123,6 +128,151 @@ def test_distpy_backup_matches_the_reference_function(oracle, golden_dir):
         assert ns[untouched].tobytes() == c["stats_in"][untouched].tobytes()
         n += 1
     assert n == 12
+
+
+def distpy_edge_shifts(golden_dir):
+    """ref_distpy_edges.npz (make_golden.py gen_distpy_edges): the shift cases, one dict per case as distpy_cases yields them,
+    with vmin and the bin count beside"""
+    g = np.load(os.path.join(golden_dir, "ref_distpy_edges.npz"))
+    for i in range(int(g["s_n"])):
+        bins, vmin, vmax = g["s_cfg_%d" % i]
+        for d, x, out in zip(g["s_dist_%d" % i], g["s_x_%d" % i], g["s_out_%d" % i]):
+            yield dict(bins=int(bins), vmin=float(vmin), vmax=float(vmax), dist=d, x=float(x), out=out)
+
+
+def distpy_edge_backups(golden_dir):
+    g = np.load(os.path.join(golden_dir, "ref_distpy_edges.npz"))
+    keys = ("stats_in", "dist_in", "trace", "r", "leaf", "vmin", "vmax", "stats_out", "dist_out")
+    for i in range(int(g["b_n"])):
+        yield {k: g["b_%s_%d" % (k, i)] for k in keys}
+
+
+def shift_class(bins, vmin, vmax, x):
+    """(s, whole-bin, a rounded source) of a shift, in the oracle's arithmetic"""
+    delta = (vmax - vmin) / bins
+    bs = x / delta
+    return int(bs), x != 0 and bs == np.floor(bs), any(int(b + bs) != b + int(bs) for b in range(bins))
+
+
+def test_distpy_shift_matches_the_reference_function_at_narrow_bins(oracle, golden_dir):
+    """shift_distribution at the settings of tests/dist_regimes.py: whole-bin shifts, shifts up to and beyond the top atom, and
+    the integer shifts in which a source bin rounds up across an integer - there the bin a mass lands in is at stake, not the
+    last digits, so the float tolerance of the existing cases decides between two different results."""
+    L = oracle.lib()
+    seen = dict.fromkeys(("cases", "whole", "top", "beyond", "rounded"), 0)
+    settings = set()
+    for c in distpy_edge_shifts(golden_dir):
+        bins, d = c["bins"], np.ascontiguousarray(c["dist"], np.float32)
+        assert len(d) == bins
+        out = np.zeros(bins, np.float32)
+        L.orc_distpy_shift(oracle.ptr(d), bins, c["x"], c["vmin"], c["vmax"], oracle.ptr(out))
+        assert np.allclose(out, c["out"], rtol=RTOL, atol=ATOL), (bins, c["vmax"], c["x"], np.abs(out - c["out"]).max())
+        assert abs(float(out.sum()) - float(d.sum())) < 1e-5
+        s, whole, rounded = shift_class(bins, c["vmin"], c["vmax"], c["x"])
+        if s >= bins:
+            assert out[bins - 1] == out.sum() and np.all(out[:bins - 1] == 0)        # all mass piled into the top atom
+        settings.add((bins, c["vmin"], c["vmax"]))
+        seen["cases"] += 1
+        seen["whole"] += whole
+        seen["top"] += s == bins - 1
+        seen["beyond"] += s >= bins
+        seen["rounded"] += rounded
+    want = {(r.atoms, r.vmin, r.vmax) for r in R.REGIMES}
+    assert settings == want and len(want) == 9
+    assert seen["cases"] == 73 and seen["whole"] >= 18 and seen["top"] >= 9 and seen["beyond"] >= 18 and seen["rounded"] >= 10, seen
+
+
+def test_a_rounded_source_lands_one_atom_higher(oracle):
+    """30 atoms over [0, 70), x = 35: bin_shift = 14.999999999999998, and b + bin_shift is exactly b + 15 from b = 2 on, so those
+    sources put (nearly) all their mass into atom b + 16 while bins 0 and 1 put theirs into 15 and 16."""
+    L = oracle.lib()
+    assert 35 / (70 / 30) == 14.999999999999998
+    for b, top in ((0, 15), (1, 16), (2, 18), (3, 19)):
+        d = np.zeros(30, np.float32)
+        d[b] = 1.0
+        out = np.zeros(30, np.float32)
+        L.orc_distpy_shift(oracle.ptr(d), 30, 35.0, 0.0, 70.0, oracle.ptr(out))
+        assert out[top] == 1.0 and out.sum() == 1.0, (b, np.nonzero(out)[0])
+
+
+def test_distpy_backup_matches_the_reference_function_at_narrow_bins(oracle, golden_dir):
+    L, n = oracle.lib(), 0
+    lens = []
+    for c in distpy_edge_backups(golden_dir):
+        ns = np.ascontiguousarray(c["stats_in"], np.float32).copy()
+        nd = np.ascontiguousarray(c["dist_in"], np.float32).copy()
+        tr = np.ascontiguousarray(c["trace"], np.int32)
+        leaf = np.ascontiguousarray(c["leaf"], np.float32)
+        bins = nd.shape[1]
+        scratch = np.zeros(bins, np.float32)
+        L.orc_distpy_backup(oracle.ptr(tr), len(tr), oracle.ptr(ns), oracle.ptr(nd), bins, float(c["r"]), oracle.ptr(leaf),
+                            float(c["vmin"]), float(c["vmax"]), oracle.ptr(scratch))
+        assert np.allclose(ns, c["stats_out"], rtol=1e-5, atol=1e-4), (n, np.abs(ns - c["stats_out"]).max())
+        assert np.allclose(nd, c["dist_out"], rtol=RTOL, atol=ATOL), (n, np.abs(nd - c["dist_out"]).max())
+        untouched = np.setdiff1d(np.arange(len(ns)), tr)
+        assert ns[untouched].tobytes() == c["stats_in"][untouched].tobytes()
+        assert nd[untouched].tobytes() == c["dist_in"][untouched].tobytes()
+        lens.append(len(tr))
+        n += 1
+    assert n == 18 and lens == [1, 19] * 9
+
+
+# ---- the regimes of tests/dist_regimes.py really are what they are for (the oracle alone; conditions, not measurements) ----
+@pytest.fixture(scope="module")
+def regime_census(oracle):
+    return {r.name: R.census(oracle, r) for r in R.REGIMES}
+
+
+@pytest.mark.parametrize("name", [r.name for r in R.REGIMES])
+def test_regime_exercises_what_it_is_for(regime_census, name):
+    """The GPU tests of tests/test_gpu_dist_agent.py compare the device with the oracle in these runs; this keeps them from
+    going green on trivial inputs.  The floors are a fifth or less of the counts the runs give: if a seed or a size change
+    moves a count below one, change the regime, not the floor."""
+    c = regime_census[name]
+    assert c["shifts"] > 20000
+    assert c["longest_trace"] >= 9                 # more than one chunk of eight trace nodes in wave_dist_back
+    assert c["negative"] == 0                      # a node never scores more than the leaf below it
+    assert c["repeated_node"] == 0                 # (app 2 and 3 too: the sequential branch computes what the chunked one would)
+    if name in ("whole", "full_wave"):
+        assert c["whole_bin"] == c["s_ge_1"] and c["s_ge_bins"] >= 1000 and c["rounded_source"] == 0
+    if name in ("round", "round_app3", "tiny_app2"):
+        assert c["rounded_source"] >= 100 and c["s_ge_bins"] >= 500
+    if name in ("round", "round_app3"):
+        assert c["whole_bin"] >= 500
+    if name in ("one", "two"):
+        assert c["s_ge_bins"] >= 500
+    if name in ("seven", "odd", "offset"):
+        assert c["s_ge_1"] >= 1000
+    if name == "offset":
+        assert c["whole_bin"] >= 500
+
+
+def test_whole_bin_regimes_have_no_other_nonzero_shift(oracle):
+    """`whole`, `full_wave`: bins one point and half a point wide, integer rewards - a shift is zero or a whole number of bins
+    (the census counts whole-bin shifts among all x != 0; here every x != 0 reaches at least one bin)"""
+    for name in ("whole", "full_wave"):
+        r = R.BY_NAME[name]
+        delta = (r.vmax - r.vmin) / r.atoms
+        assert all((x / delta) == np.floor(x / delta) and x / delta >= 1 for x in range(1, 400))
+
+
+def test_the_suites_own_setting_hardly_ever_shifts_by_a_bin(oracle):
+    """A recorded fact, and the reason the regimes exist: at 50 atoms over [0, 5000) - the setting of every other test of the
+    distributional tree kernels - fewer than 1 % of the backups' shifts reach one bin, none is whole-bin, none passes the top,
+    none has a rounded source."""
+    c = R.census(oracle, R.SUITE_SETTING)
+    assert c["shifts"] > 20000 and c["s_ge_1"] * 100 < c["shifts"]
+    assert c["whole_bin"] == 0 and c["s_ge_bins"] == 0 and c["rounded_source"] == 0 and c["negative"] == 0
+
+
+def test_the_census_changes_no_result(oracle):
+    """the counters are per agent (the GPU tests keep one oracle agent per game) and start at zero"""
+    og, oa = R.oracle_side(oracle, R.BY_NAME["round"], n_games=2)
+    assert all(v == 0 for v in oa[0].dist_census().values())
+    a = oa[0].play(50)
+    c0, c1 = oa[0].dist_census(), oa[1].dist_census()
+    assert c0["shifts"] == oa[0].trace_len_sum and c0["longest_trace"] == oa[0].max_trace_len and 0 <= a < 7
+    assert all(v == 0 for v in c1.values())
 
 
 def test_oracle_dist_agent_invariants(oracle):
