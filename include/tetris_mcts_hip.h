@@ -37,26 +37,29 @@ extern "C" {
 #define TM_GC_PART_DW 192   /* per-game scratch of a collection: (free nodes, free observations, harvested tuples) per collector workgroup */
 #define TM_VALUENET_PARAMS 478342
 #define TM_VALUENET_SCRATCH 9728       /* floats of scratch per state, tm_valuenet_forward_plain */
-#define TM_VALUENET_SCRATCH_MFMA 2064  /* floats of scratch per state, tm_valuenet_forward / _requests; no initial contents required (the
-                                          kernels keep a counter per tile of 32 or 64 states in the rows' padding: every evaluation
-                                          clears them first) */
-#define TM_VALUENET_PREPARED 477184    /* floats: conv2 + conv3 + fc1 operand streams */
-#define TM_VALUENET_PREPARED_X3 27648  /* floats (55 296 bf16): conv2 + conv3 weights as bf16 hi / mid / lo planes, tm_valuenet_prepare_x3;
-                                          the _x3 forwards take TM_VALUENET_SCRATCH_MFMA floats of scratch per state, as the fp32 ones */
-#define TM_VALUENET_PREPARED_FC1_X3 688128  /* floats (1 376 256 bf16 = 3 x 256 x 1 792): fc1's weights as bf16 hi / mid / lo planes,
-                                          tm_valuenet_prepare_fc1_x3 */
-/* fc1 of the TM_VALUENET_BF16X3 backend (tm_search_set_valuenet_fc1) */
+#define TM_VALUENET_SCRATCH_MFMA 2064  /* floats of scratch per state, tm_valuenet_forward / _requests in every mode; no initial contents
+                                          required (the kernels keep a counter per tile of 32 or 64 states in the rows' padding: every
+                                          evaluation clears them first) */
+/* the parts of tm_valuenet_prepare's buffer, in its order */
+#define TM_VALUENET_PREPARED 477184    /* floats: conv2 + conv3 + fc1 operand streams (every mode) */
+#define TM_VALUENET_PREPARED_X3 27648  /* floats (55 296 bf16): conv2 + conv3 weights as bf16 hi / mid / lo planes (TM_VALUENET_BF16X3) */
+#define TM_VALUENET_PREPARED_FC1_X3 688128  /* floats (1 376 256 bf16 = 3 x 256 x 1 792): fc1's weights as bf16 hi / mid / lo planes
+                                          (TM_VALUENET_FC1_BF16X3) */
+/* evaluator backends (the value net's and the distributional head's `backend` argument, tm_search_set_valuenet) */
+#define TM_VALUENET_FP32 0             /* fp32 matrix cores, the oracle's bits (the default) */
+#define TM_VALUENET_BF16X3 1           /* the convolutions after the first as three-way bf16 splits, fp32 accumulation */
+/* fc1 of the value net (its `fc1` argument); TM_VALUENET_FC1_BF16X3 goes with TM_VALUENET_BF16X3 only */
 #define TM_VALUENET_FC1_FP32 0         /* k_vn_fc1: the fp32 fma chain (the default) */
-#define TM_VALUENET_FC1_BF16X3 1       /* k_vn_fc1_x3, tm_valuenet_forward_requests_x3f: fc1 as a three-way bf16 split as well */
-/* evaluator backends of the native search loop (tm_search_set_valuenet) */
-#define TM_VALUENET_FP32 0             /* tm_valuenet_forward_requests: fp32 matrix cores, the oracle's bits (the default) */
-#define TM_VALUENET_BF16X3 1           /* tm_valuenet_forward_requests_x3 (TM_KIND_DIST: tm_distnet_forward_requests_x3): the
-                                          convolutions after the first as three-way bf16 splits, fp32 accumulation */
+#define TM_VALUENET_FC1_BF16X3 1       /* k_vn_fc1_x3: fc1 as a three-way bf16 split as well */
+/* floats of the prepared buffer of a mode */
+#define TM_VALUENET_PREPARED_TOTAL(backend, fc1) (TM_VALUENET_PREPARED + ((backend) == TM_VALUENET_BF16X3 ? TM_VALUENET_PREPARED_X3 : 0) + \
+                                                  ((fc1) == TM_VALUENET_FC1_BF16X3 ? TM_VALUENET_PREPARED_FC1_X3 : 0))
+#define TM_DISTNET_PREPARED_TOTAL(backend) (TM_DISTNET_PREPARED + ((backend) == TM_VALUENET_BF16X3 ? TM_DISTNET_PREPARED_X3 : 0))
 #define TM_DISTNET_PARAMS(atoms) (279232 + 129 * (atoms))  /* floats: conv1.w[32][1][4][4] conv1.b[32] conv2.w[32][32][4][4] conv2.b[32]
                                           fc1.w[128][2048] fc1.b[128] fc_v.w[atoms][128] fc_v.b[atoms] (model/model_distributional.py:33-42) */
 #define TM_DISTNET_PARAMS_50 285682    /* TM_DISTNET_PARAMS(50) */
-#define TM_DISTNET_PREPARED 278528     /* floats: conv2 + fc1 operand streams */
-#define TM_DISTNET_PREPARED_X3 24576   /* floats (49 152 bf16): conv2's weights as bf16 hi / mid / lo planes, tm_distnet_prepare_x3 */
+#define TM_DISTNET_PREPARED 278528     /* floats: conv2 + fc1 operand streams (every backend) */
+#define TM_DISTNET_PREPARED_X3 24576   /* floats (49 152 bf16): conv2's weights as bf16 hi / mid / lo planes (TM_VALUENET_BF16X3) */
 #define TM_DISTNET_SCRATCH 2048        /* floats of scratch per state (conv2's output), tm_distnet_forward / _requests */
 
 /* per-game control block (int32 words) */
@@ -299,8 +302,8 @@ int tm_store_slice(const tm_store *s, int first, int n, tm_store *out);
  * catch-up launches of games that collected garbage, tm_sims_remaining).  vn_params == NULL: no evaluator launches
  * (TM_KIND_VANILLA).  The evaluator follows the store's kind: the value net (tm_valuenet_forward_requests; vn_scratch:
  * n_games * eval_slots * TM_VALUENET_SCRATCH_MFMA floats, no initial contents required) or, for TM_KIND_DIST, the distributional head
- * (tm_distnet_forward_requests, or _x3 under tm_search_set_valuenet; vn_params / vn_prepared = its blobs, vn_scratch:
- * n_games * TM_DISTNET_SCRATCH floats).  ev_every > 0: HIP events
+ * (tm_distnet_forward_requests; vn_params / vn_prepared = its blobs, vn_scratch: n_games * TM_DISTNET_SCRATCH floats), in the
+ * mode of tm_search_set_valuenet.  ev_every > 0: HIP events
  * around every ev_every-th simulation of sub-batch 0 (on the stream it runs on), read back by tm_search_stats:
  * out = {runs, tree launches, catch-up launches, timed samples, sum tree-kernel ms, sum value-net ms, n_sub}. */
 typedef struct tm_search tm_search;
@@ -312,23 +315,12 @@ int tm_search_stats(tm_search *h, double *out, int n, int reset);
 /* the evaluator's weights changed: s->eval_epoch of the handle's copy of the store (outputs filed in obs_eval under another
  * epoch are not used; epochs are >= 1 and never reused for other weights) */
 int tm_search_set_epoch(tm_search *h, int epoch);
-/* the evaluator backend of tm_search_run's value net: TM_VALUENET_FP32 (the default) or TM_VALUENET_BF16X3.  Under
- * TM_VALUENET_BF16X3, vn_prepared points at TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3 floats: the fp32 operand streams of
- * tm_valuenet_prepare (fc1 stays on them) followed by the planes of tm_valuenet_prepare_x3.  hipErrorInvalidValue for any
- * other value.  On a TM_KIND_DIST store TM_VALUENET_BF16X3 selects the distributional head's split-precision backend
- * (tm_distnet_forward_requests_x3): vn_prepared then points at TM_DISTNET_PREPARED + TM_DISTNET_PREPARED_X3 floats, the
- * streams of tm_distnet_prepare (fc1 stays on them) followed by the planes of tm_distnet_prepare_x3.  The caller gives the
- * backend's outputs an epoch of their own (tm_search_set_epoch): obs_eval must not mix the two (TM_KIND_DIST keeps no
- * obs_eval). */
-int tm_search_set_valuenet(tm_search *h, int backend);
-/* fc1 of the value net under TM_VALUENET_BF16X3: TM_VALUENET_FC1_FP32 (the default) or TM_VALUENET_FC1_BF16X3
- * (tm_valuenet_forward_requests_x3f).  Under TM_VALUENET_FC1_BF16X3, vn_prepared points at TM_VALUENET_PREPARED +
- * TM_VALUENET_PREPARED_X3 + TM_VALUENET_PREPARED_FC1_X3 floats, in that order: tm_valuenet_prepare's streams, then
- * tm_valuenet_prepare_x3's planes, then tm_valuenet_prepare_fc1_x3's.  hipErrorInvalidValue for any other value, on a
- * TM_KIND_DIST store, and for TM_VALUENET_FC1_BF16X3 while the backend is not TM_VALUENET_BF16X3 (set the backend first;
- * setting the backend to TM_VALUENET_FP32 puts fc1 back to TM_VALUENET_FC1_FP32).  Its outputs get an epoch of their own, as
- * every backend's. */
-int tm_search_set_valuenet_fc1(tm_search *h, int mode);
+/* the mode of tm_search_run's evaluator: `backend` TM_VALUENET_FP32 (the default) or TM_VALUENET_BF16X3, `fc1`
+ * TM_VALUENET_FC1_FP32 (the default) or TM_VALUENET_FC1_BF16X3; vn_prepared is then the prepare call's buffer for that mode (or a
+ * larger one).  On a TM_KIND_DIST store `backend` is the distributional head's and fc1 must be TM_VALUENET_FC1_FP32.
+ * hipErrorInvalidValue, and nothing changed, for any other pair (tm_valuenet_check_mode).  The caller gives every mode's outputs
+ * an epoch of their own (tm_search_set_epoch): obs_eval must not mix them (TM_KIND_DIST keeps no obs_eval). */
+int tm_search_set_valuenet(tm_search *h, int backend, int fc1);
 int tm_root_stats(const tm_store *s, float *stats /* [G][3][7] */, int32_t *action /* [G] */, void *stream);
 /* one game's tree in the reference's array layout (agents/agent.py:58-88), for inspection and tests */
 int tm_export_game(const tm_store *s, int game, int32_t *child /* [N][7] */, float *score, int32_t *n_to_o,
@@ -385,12 +377,6 @@ int tm_distpy_backup(int n_trees, int n_nodes, int bins, const int32_t *trace, c
                      float *node_stats, float *node_dist, const double *r /* [B] */, const float *leaf_dist /* [B][bins] */,
                      double vmin, double vmax, float *scratch, void *stream);
 
-/* value network forward (model/model_vv.py:13-52; Model_VV.inference 210-217): states int8 [n][200] -> v[n], var[n].
- * params: 478342 floats in PyTorch state_dict layouts (order as in oracle/valuenet_oracle.c).
- * tm_valuenet_prepare re-lays the conv2/conv3/fc1 weights into MFMA operand streams (call after every weight
- * change); prepared: TM_VALUENET_PREPARED floats.  tm_valuenet_forward is the matrix-core path (scratch:
- * n x TM_VALUENET_SCRATCH_MFMA floats); tm_valuenet_forward_plain is the one-thread-per-output form with the
- * same fma-chain numerics (scratch: n x TM_VALUENET_SCRATCH floats).  Both are bit-identical by construction. */
 /* The optimiser step of the online fit, model/yogi.py:39-90 (Yogi: lr, betas, eps, coupled weight decay) over FLAT device buffers:
  * p (parameters), g (gradients), m / v (exp_avg / exp_avg_sq), n floats each; state = 8 doubles on the device, zero before the first
  * step ([0] the step count, [1] [2] beta^t, [3] lr / (1 - beta1^t), [4] sqrt(1 - beta2^t): advanced on the device, so that the call is
@@ -464,13 +450,31 @@ long long tm_distnet_fit_validate_workspace(int slab, int atoms);
 int tm_distnet_fit_validate(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
                             long long n, int chunk, int slab, int atoms, int weighted, double *rows_out, float *workspace,
                             void *stream);
-int tm_valuenet_prepare(const float *params, float *prepared, void *stream);
-int tm_valuenet_forward(const float *params, const float *prepared, const int8_t *states, int n, float *v, float *var,
-                        float *scratch, void *stream);
+/* value network forward (model/model_vv.py:13-52; Model_VV.inference 210-217): states int8 [n][200] -> v[n], var[n].
+ * params: 478342 floats in PyTorch state_dict layouts (order as in oracle/valuenet_oracle.c).
+ * It runs in one of three modes (backend, fc1), checked by tm_valuenet_check_mode (host arithmetic only: 0, or
+ * hipErrorInvalidValue for any other pair) before anything else in every call that takes them:
+ *   (TM_VALUENET_FP32, TM_VALUENET_FC1_FP32)      fp32 matrix cores; bit-identical to tm_valuenet_forward_plain by construction;
+ *   (TM_VALUENET_BF16X3, TM_VALUENET_FC1_FP32)    valuenet_x3.inc (numerics contract in DESIGN.md section 3.3): conv2 and conv3 on
+ *       the bf16 matrix cores, every operand split into three bf16 planes, six plane products per fp32 product, fp32 accumulation;
+ *       conv1, fc1 and the output layer as in fp32.  Within 1e-4 of the reference, not bit-equal to the fp32 mode;
+ *   (TM_VALUENET_BF16X3, TM_VALUENET_FC1_BF16X3)  valuenet_fc1_x3.inc, k_vn_fc1_x3: fc1's weights and its input as three bf16 planes
+ *       as well, six plane products per step of 32 k, fp32 accumulation from the bias.  Not bit-equal to the mode above.
+ * In every mode a state's outputs depend on that state only.
+ * tm_valuenet_prepare re-lays the weights for a mode (call after every weight change) into ONE buffer of
+ * TM_VALUENET_PREPARED_TOTAL(backend, fc1) floats: the fp32 MFMA operand streams of conv2 / conv3 / fc1 (always), then the
+ * convolutions' planes (TM_VALUENET_BF16X3), then fc1's planes (TM_VALUENET_FC1_BF16X3).  It writes exactly the parts the mode
+ * names, so a buffer prepared for a larger mode serves every smaller one.  prepared == NULL: hipErrorInvalidValue.
+ * The forwards take that buffer and n x TM_VALUENET_SCRATCH_MFMA floats of scratch; n <= 0: nothing to do, 0. */
+int tm_valuenet_check_mode(int backend, int fc1);
+int tm_valuenet_prepare(const float *params, float *prepared, int backend, int fc1, void *stream);
+int tm_valuenet_forward(const float *params, const float *prepared, int backend, int fc1, const int8_t *states, int n, float *v,
+                        float *var, float *scratch, void *stream);
 /* evaluate the tree engine's pending requests (s->eval_obs) and write s->eval_v / s->eval_var; the packed
  * observations are rendered inside the first kernel (no int8 staging).  scratch: G*eval_slots x TM_VALUENET_SCRATCH_MFMA */
-int tm_valuenet_forward_requests(const float *params, const float *prepared, const tm_store *s, float *scratch,
-                                 void *stream);
+int tm_valuenet_forward_requests(const float *params, const float *prepared, int backend, int fc1, const tm_store *s,
+                                 float *scratch, void *stream);
+/* the one-thread-per-output form with the fp32 mode's fma-chain numerics (scratch: n x TM_VALUENET_SCRATCH floats) */
 int tm_valuenet_forward_plain(const float *params, const int8_t *states, int n, float *v, float *var, float *scratch,
                               void *stream);
 /* How the matrix-core path's fc1 kernel deals its work (host arithmetic only, callable without a GPU; the kernel and its
@@ -479,51 +483,26 @@ int tm_valuenet_forward_plain(const float *params, const int8_t *states, int n, 
  * round robin); workgroup b of `grid` takes items b, b + grid, ...  Writes the workgroup's (tile, part) pairs to
  * items[0 .. 2 * cap) and returns how many it takes (possibly more than cap); -1 on arguments that make no grid. */
 int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t *items, int cap);
-/* The split-precision backend (valuenet_x3.inc; numerics contract in DESIGN.md section 3.3): conv2 and conv3 on the bf16 matrix
- * cores, every operand split into three bf16 planes, six plane products per fp32 product, fp32 accumulation; conv1, fc1 and
- * the output layer as in tm_valuenet_forward.  Within 1e-4 of the reference, not bit-equal to the fp32 path; a state's outputs
- * depend on that state only.  tm_valuenet_prepare_x3 writes the planes (TM_VALUENET_PREPARED_X3 floats, after every weight
- * change); the forwards take both prepared buffers (fc1 reads tm_valuenet_prepare's) and TM_VALUENET_SCRATCH_MFMA floats of
- * scratch per state.  prepared_x3 == NULL: hipErrorInvalidValue. */
-int tm_valuenet_prepare_x3(const float *params, float *prepared_x3, void *stream);
-int tm_valuenet_forward_x3(const float *params, const float *prepared, const float *prepared_x3, const int8_t *states, int n,
-                           float *v, float *var, float *scratch, void *stream);
-int tm_valuenet_forward_requests_x3(const float *params, const float *prepared, const float *prepared_x3, const tm_store *s,
-                                    float *scratch, void *stream);
-/* The same backend with fc1 split as well (valuenet_fc1_x3.inc, k_vn_fc1_x3): fc1's weights and its
- * input as three bf16 planes each, six plane products per step of 32 k, fp32 accumulation from the bias, the output layer in
- * fp32 as always.  Not bit-equal to the _x3 entries above; a state's outputs depend on that state only.
- * tm_valuenet_prepare_fc1_x3 writes fc1's planes (TM_VALUENET_PREPARED_FC1_X3 floats, after every weight change).  A NULL
- * prepared_x3 or prepared_fc1_x3: hipErrorInvalidValue. */
-int tm_valuenet_prepare_fc1_x3(const float *params, float *prepared_fc1_x3, void *stream);
-int tm_valuenet_forward_x3f(const float *params, const float *prepared, const float *prepared_x3, const float *prepared_fc1_x3,
-                            const int8_t *states, int n, float *v, float *var, float *scratch, void *stream);
-int tm_valuenet_forward_requests_x3f(const float *params, const float *prepared, const float *prepared_x3,
-                                     const float *prepared_fc1_x3, const tm_store *s, float *scratch, void *stream);
 
 /* distributional value head (model/model_distributional.py:18-57 `Net`, Model_Dist.inference :100-107), the leaf evaluator
  * of TM_KIND_DIST: states int8 [n][200] (the 20 visible rows; the net's two extra rows on top are empty) -> softmax over
  * `atoms` (<= 64) bins, dist[i * dist_stride + b].  params: TM_DISTNET_PARAMS(atoms) floats in PyTorch state_dict order and
- * layouts; tm_distnet_prepare re-lays conv2 / fc1 into MFMA operand streams (after every weight change).  fp32 matrix cores,
- * one k-ordered fma chain per pre-activation (oracle/distnet_oracle.c computes the same bits).  scratch: n x
- * TM_DISTNET_SCRATCH floats, no initial contents required. */
-int tm_distnet_prepare(const float *params, float *prepared, void *stream);
-int tm_distnet_forward(const float *params, const float *prepared, const int8_t *states, int n, int atoms, float *dist,
-                       int dist_stride, float *scratch, void *stream);
+ * layouts.  `backend` (any other value: hipErrorInvalidValue):
+ *   TM_VALUENET_FP32    fp32 matrix cores, one k-ordered fma chain per pre-activation (oracle/distnet_oracle.c computes the same bits);
+ *   TM_VALUENET_BF16X3  distnet_x3.inc (numerics contract in DESIGN.md section 3.8): conv2 on the bf16 matrix cores, every operand
+ *       split into three bf16 planes, six plane products per fp32 product, fp32 accumulation; conv1, fc1, fc_v and the softmax as
+ *       in fp32.  Within 1e-6 relative of the reference's Net, not bit-equal to the fp32 backend.
+ * A state's outputs depend on that state only.  tm_distnet_prepare re-lays the weights (after every weight change) into ONE
+ * buffer of TM_DISTNET_PREPARED_TOTAL(backend) floats: the fp32 operand streams of conv2 / fc1 (always), then conv2's planes
+ * (TM_VALUENET_BF16X3); a buffer prepared for TM_VALUENET_BF16X3 serves both backends.  prepared == NULL: hipErrorInvalidValue.
+ * scratch: n x TM_DISTNET_SCRATCH floats, no initial contents required. */
+int tm_distnet_prepare(const float *params, float *prepared, int backend, void *stream);
+int tm_distnet_forward(const float *params, const float *prepared, int backend, const int8_t *states, int n, int atoms,
+                       float *dist, int dist_stride, float *scratch, void *stream);
 /* the tree engine's pending requests (TM_KIND_DIST: s->eval_obs[g] = the leaf NODE of game g, rendered from its packed game
  * inside the first kernel) -> s->eval_dist[g][0 .. dist_bins); scratch: n_games x TM_DISTNET_SCRATCH floats */
-int tm_distnet_forward_requests(const float *params, const float *prepared, const tm_store *s, float *scratch, void *stream);
-/* The split-precision backend (distnet_x3.inc; numerics contract in DESIGN.md section 3.8): conv2 on the bf16 matrix cores,
- * every operand split into three bf16 planes, six plane products per fp32 product, fp32 accumulation; conv1, fc1, fc_v and
- * the softmax as in tm_distnet_forward.  Within 1e-6 relative of the reference's Net, not bit-equal to the fp32 path; a
- * state's outputs depend on that state only.  tm_distnet_prepare_x3 writes the planes (TM_DISTNET_PREPARED_X3 floats, after
- * every weight change); the forwards take both prepared buffers (fc1 reads tm_distnet_prepare's) and TM_DISTNET_SCRATCH
- * floats of scratch per state.  prepared_x3 == NULL, or arguments the fp32 calls refuse: hipErrorInvalidValue. */
-int tm_distnet_prepare_x3(const float *params, float *prepared_x3, void *stream);
-int tm_distnet_forward_x3(const float *params, const float *prepared, const float *prepared_x3, const int8_t *states,
-                          int n, int atoms, float *dist, int dist_stride, float *scratch, void *stream);
-int tm_distnet_forward_requests_x3(const float *params, const float *prepared, const float *prepared_x3,
-                                   const tm_store *s, float *scratch, void *stream);
+int tm_distnet_forward_requests(const float *params, const float *prepared, int backend, const tm_store *s, float *scratch,
+                                void *stream);
 
 const char *tm_version(void);
 /* sizeof(tm_store) and a few offsets, so a host mirror of the struct can be checked without a GPU */

@@ -257,3 +257,33 @@ def test_a_slice_begins_at_a_multiple_of_four_games():
             gs0 = C.cast(s.gs, C.c_void_p).value or 0
             gs1 = C.cast(out.gs, C.c_void_p).value or 0
             assert gs1 - gs0 == first * 64 * 4          # the control blocks: 64 words a game
+
+
+def test_the_evaluators_check_their_mode_before_anything_else():
+    """Through the loaded library, with null buffers and no states: every (backend, fc1) in {-1, 0, 1, 2}^2 is accepted (0) for the
+    three valid pairs (FP32, FC1_FP32), (BF16X3, FC1_FP32), (BF16X3, FC1_BF16X3) and refused with hipErrorInvalidValue for every
+    other one - the check precedes the n <= 0 return, so it needs no GPU.  The distributional head accepts backends 0 and 1.  The
+    _requests forms get a store of no games of their kind."""
+    L = _lib()
+    lib = L.lib()
+    INVALID, null = 1, C.c_void_p(0)        # hipErrorInvalidValue
+    valid = {(0, 0), (1, 0), (1, 1)}
+    vs, ds = L.TmStore(), L.TmStore()
+    vs.kind, vs.eval_slots = 0, 1           # TM_KIND_VALUESIM
+    ds.kind, ds.eval_slots, ds.dist_bins = 6, 1, 50         # TM_KIND_DIST
+    for backend in (-1, 0, 1, 2):
+        for fc1 in (-1, 0, 1, 2):
+            want = 0 if (backend, fc1) in valid else INVALID
+            assert lib.tm_valuenet_check_mode(backend, fc1) == want, (backend, fc1)
+            assert lib.tm_valuenet_forward(null, null, backend, fc1, null, 0, null, null, null, null) == want, (backend, fc1)
+            assert lib.tm_valuenet_forward_requests(null, null, backend, fc1, C.byref(vs), null, null) == want, (backend, fc1)
+            assert lib.tm_valuenet_prepare(null, null, backend, fc1, null) == INVALID, (backend, fc1)      # (a null buffer, whatever the mode)
+        want = 0 if backend in (0, 1) else INVALID
+        assert lib.tm_distnet_forward(null, null, backend, null, 0, 50, null, 64, null, null) == want, backend
+        assert lib.tm_distnet_forward_requests(null, null, backend, C.byref(ds), null, null) == want, backend
+        assert lib.tm_distnet_prepare(null, null, backend, null) == INVALID, backend
+    # the refusals that were there before keep their conditions
+    assert lib.tm_distnet_forward(null, null, 0, null, 0, 50, null, 49, null, null) == INVALID         # dist_stride < atoms
+    assert lib.tm_distnet_forward_requests(null, null, 0, C.byref(vs), null, null) == INVALID          # wrong store kind
+    ds.eval_slots = 7
+    assert lib.tm_distnet_forward_requests(null, null, 0, C.byref(ds), null, null) == INVALID          # eval_slots != 1

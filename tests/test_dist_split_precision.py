@@ -9,7 +9,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-NEW_SYMBOLS = ("tm_distnet_prepare_x3", "tm_distnet_forward_x3", "tm_distnet_forward_requests_x3")
 KEYS = ["seq__conv1__weight", "seq__conv1__bias", "seq__conv2__weight", "seq__conv2__bias", "seq__fc1__weight",
         "seq__fc1__bias", "seq__fc_v__weight", "seq__fc_v__bias"]
 
@@ -136,17 +135,11 @@ def test_emulated_split_conv2_is_as_accurate_as_fp32(boards):
 
 # ---- every layer accepts the backend ----
 def test_library_exports_the_split_precision_abi():
-    from tetris_mcts_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "tetris_mcts_hip.h")).read()
-    declared = set(re.findall(r"\b(tm_[a-z_0-9]+)\s*\(", hdr))
-    lib = _lib.lib()
-    for name in NEW_SYMBOLS:
-        assert name in declared and name in _lib.SYMBOLS, name
-        assert hasattr(lib, name), name
-    m = re.search(r"#define\s+TM_DISTNET_PREPARED_X3\s+(\d+)", hdr)
-    assert m and int(m.group(1)) == 24576
+    import abi_shape
+    abi_shape.check(abi_shape.DISTNET)
+    abi_shape.check_defines((("TM_DISTNET_PREPARED_X3", 24576),))
     from tetris_mcts_amd import model_distributional as md
-    assert md.PREPARED_X3 == int(m.group(1))
+    assert md.PREPARED_X3 == 24576
     assert md.HIP_BACKENDS == ("hip", "hip_bf16x3")
 
 

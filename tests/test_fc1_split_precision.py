@@ -13,8 +13,6 @@ from test_split_precision import OFF, PRODUCTS, _tol, forward, split3
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-NEW_SYMBOLS = ("tm_valuenet_prepare_fc1_x3", "tm_valuenet_forward_x3f", "tm_valuenet_forward_requests_x3f",
-               "tm_search_set_valuenet_fc1")
 
 
 def _fc1(P, a3, mode):
@@ -64,17 +62,11 @@ def test_emulated_fc1_split_holds_the_contract(pk, ok):
 
 
 def test_library_exports_the_fc1_abi():
-    from tetris_mcts_amd import _lib, model
-    hdr = open(os.path.join(ROOT, "include", "tetris_mcts_hip.h")).read()
-    declared = set(re.findall(r"\b(tm_[a-z_0-9]+)\s*\(", hdr))
-    lib = _lib.lib()
-    for name in NEW_SYMBOLS:
-        assert name in declared and name in _lib.SYMBOLS, name
-        assert hasattr(lib, name), name
-    for name, value in (("TM_VALUENET_PREPARED_FC1_X3", 688128), ("TM_VALUENET_FC1_FP32", 0), ("TM_VALUENET_FC1_BF16X3", 1),
-                        ("TM_VALUENET_PREPARED_X3", 27648)):
-        m = re.search(r"#define\s+%s\s+(\d+)" % name, hdr)
-        assert m and int(m.group(1)) == value, name
+    import abi_shape
+    from tetris_mcts_amd import model
+    abi_shape.check(abi_shape.VALUENET)
+    abi_shape.check_defines((("TM_VALUENET_PREPARED_FC1_X3", 688128), ("TM_VALUENET_FC1_FP32", 0), ("TM_VALUENET_FC1_BF16X3", 1),
+                             ("TM_VALUENET_PREPARED_X3", 27648)))
     assert 3 * 256 * 1792 // 2 == 688128 == model.PREPARED_FC1_X3
     assert model.VALUENET_FC1 == {"fp32": 0, "bf16x3": 1}
     assert model.VALUENET_BACKEND == {"hip": 0, "hip_bf16x3": 1} and model.HIP_BACKENDS == ("hip", "hip_bf16x3")

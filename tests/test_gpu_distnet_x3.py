@@ -102,8 +102,8 @@ def test_x3_outputs_depend_on_the_state_only(golden_dir):
 
 
 def test_x3_request_path_equals_the_dense_path(golden_dir):
-    """tm_distnet_forward_requests_x3 over a store's pending requests (nodes rendered inside k_dn_conv_x3) = tm_distnet_forward_x3
-    on the same boards from render_eval(), bit for bit; slots without a request are left untouched"""
+    """tm_distnet_forward_requests under TM_VALUENET_BF16X3 over a store's pending requests (nodes rendered inside k_dn_conv_x3) =
+    tm_distnet_forward under it on the same boards from render_eval(), bit for bit; slots without a request are left untouched"""
     import torch
     from tetris_mcts_amd import agents, store as st
     from tetris_mcts_amd.pyTetris import Tetris
@@ -235,14 +235,13 @@ def test_x3_planes_follow_weight_changes(golden_dir, tmp_path, monkeypatch):
 
 
 def test_search_handle_takes_the_backend_on_a_dist_store():
+    import abi_shape
     from tetris_mcts_amd import _lib, store as st
     s = st.TreeStore(4, 1000, kind=st.KIND_DIST, dist_bins=50, dist_range=(0.0, 5000.0))
     L = _lib.lib()
     h = C.c_void_p()
     _lib.check(L.tm_search_create(C.byref(h), C.byref(s.s), 1, 0), "tm_search_create")
     try:
-        assert L.tm_search_set_valuenet(h, 1) == 0
-        assert L.tm_search_set_valuenet(h, 0) == 0
-        assert L.tm_search_set_valuenet(h, 2) != 0
+        abi_shape.check_setter(L, h, dist=True)
     finally:
         L.tm_search_destroy(h)

@@ -272,6 +272,7 @@ def test_fc1_x3_planes_follow_a_fit(fixture_z, tmp_path, monkeypatch):
 
 
 def test_fc1_refusals_and_defaults(fixture_z):
+    import abi_shape
     import torch
     from tetris_mcts_amd import _lib, store as st
     from tetris_mcts_amd.model import Model_VV
@@ -295,13 +296,6 @@ def test_fc1_refusals_and_defaults(fixture_z):
         h = C.c_void_p()
         _lib.check(L.tm_search_create(C.byref(h), C.byref(s.s), 1, 0), "tm_search_create")
         try:
-            assert L.tm_search_set_valuenet_fc1(h, 2) != 0
-            assert L.tm_search_set_valuenet_fc1(h, 1) != 0           # the backend is fp32 (the default)
-            assert L.tm_search_set_valuenet(h, 1) == 0
-            assert (L.tm_search_set_valuenet_fc1(h, 1) != 0) == dist   # a distributional store has no such option
-            if not dist:
-                assert L.tm_search_set_valuenet_fc1(h, 0) == 0 and L.tm_search_set_valuenet_fc1(h, 1) == 0
-                assert L.tm_search_set_valuenet(h, 0) == 0            # ... and fc1 goes back to fp32 with the backend
-                assert L.tm_search_set_valuenet_fc1(h, 1) != 0
+            abi_shape.check_setter(L, h, dist)
         finally:
             L.tm_search_destroy(h)

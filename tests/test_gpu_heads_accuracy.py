@@ -145,26 +145,24 @@ def test_value_net_request_path_under_r06(oracle):
                     "value r06 requests %s" % name)
 
 
-@pytest.mark.parametrize("entry", ["tm_valuenet_forward", "tm_valuenet_forward_plain", "tm_valuenet_forward_x3"])
+@pytest.mark.parametrize("entry", ["tm_valuenet_forward", "tm_valuenet_forward_plain", "tm_valuenet_forward-bf16x3"])
 def test_value_net_n0_writes_nothing(entry):
     from tetris_mcts_amd import _lib
-    from tetris_mcts_amd.model import PREPARED
     from tetris_mcts_amd.store import _p, _stream
     P = H.value_regimes()["params"]
     m = vn_model("hip_bf16x3", P)
-    prep = m._prepared_x3()
+    prep = m._ensure_prepared()
     flat = m.flat_params()
     st = torch.zeros(4, 200, dtype=torch.int8, device="cuda")
     v, var = torch.full((4,), float("nan"), device="cuda"), torch.full((4,), float("nan"), device="cuda")
     scr = torch.full((4, H.VN_PLAIN_ROW), float("nan"), device="cuda")
     L = _lib.lib()
     if entry == "tm_valuenet_forward":
-        r = L.tm_valuenet_forward(_p(flat), _p(prep), _p(st), 0, _p(v), _p(var), _p(scr), _stream())
+        r = L.tm_valuenet_forward(_p(flat), _p(prep), 0, 0, _p(st), 0, _p(v), _p(var), _p(scr), _stream())
     elif entry == "tm_valuenet_forward_plain":
         r = L.tm_valuenet_forward_plain(_p(flat), _p(st), 0, _p(v), _p(var), _p(scr), _stream())
     else:
-        r = L.tm_valuenet_forward_x3(_p(flat), _p(prep), _p(prep[PREPARED:]), _p(st), 0, _p(v), _p(var),
-                                     _p(scr), _stream())
+        r = L.tm_valuenet_forward(_p(flat), _p(prep), 1, 0, _p(st), 0, _p(v), _p(var), _p(scr), _stream())
     torch.cuda.synchronize()
     assert r == 0
     assert torch.isnan(v).all() and torch.isnan(var).all() and torch.isnan(scr).all()
@@ -268,13 +266,10 @@ def test_dist_head_batch_sizes(oracle, backend):
 
 def _dn_call(m, st, n, atoms, out, stride):
     from tetris_mcts_amd import _lib
-    from tetris_mcts_amd.model_distributional import PREPARED
     from tetris_mcts_amd.store import _p, _stream
     P, prep, scr = m.hip_buffers(max(n, 1))
-    if m.backend == "hip":
-        return _lib.lib().tm_distnet_forward(P, prep, _p(st), n, atoms, _p(out), stride, scr, _stream())
-    full = m._prepared_x3()
-    return _lib.lib().tm_distnet_forward_x3(P, _p(full), _p(full[PREPARED:]), _p(st), n, atoms, _p(out), stride, scr, _stream())
+    return _lib.lib().tm_distnet_forward(P, prep, 1 if m.backend == "hip_bf16x3" else 0, _p(st), n, atoms, _p(out), stride, scr,
+                                         _stream())
 
 
 @pytest.mark.parametrize("backend", ["hip", "hip_bf16x3"])

@@ -10,7 +10,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 TOL = 1e-4
 OFF = dict(c1w=0, c1b=288, c2w=320, c2b=9536, c3w=9568, c3b=18784, f1w=18816, f1b=477568, fow=477824, fob=478336, ub=478338,
            lb=478340)
-NEW_SYMBOLS = ("tm_valuenet_prepare_x3", "tm_valuenet_forward_x3", "tm_valuenet_forward_requests_x3", "tm_search_set_valuenet")
 
 
 # ---- numpy emulation of the numerics contract ----
@@ -135,16 +134,9 @@ def test_emulated_split_holds_the_output_contract():
 
 
 def test_library_exports_the_split_precision_abi():
-    from tetris_mcts_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "tetris_mcts_hip.h")).read()
-    declared = set(re.findall(r"\b(tm_[a-z_0-9]+)\s*\(", hdr))
-    lib = _lib.lib()
-    for name in NEW_SYMBOLS:
-        assert name in declared and name in _lib.SYMBOLS, name
-        assert hasattr(lib, name), name
-    for name, value in (("TM_VALUENET_PREPARED_X3", 27648), ("TM_VALUENET_FP32", 0), ("TM_VALUENET_BF16X3", 1)):
-        m = re.search(r"#define\s+%s\s+(\d+)" % name, hdr)
-        assert m and int(m.group(1)) == value, name
+    import abi_shape
+    abi_shape.check(abi_shape.VALUENET)
+    abi_shape.check_defines((("TM_VALUENET_PREPARED_X3", 27648), ("TM_VALUENET_FP32", 0), ("TM_VALUENET_BF16X3", 1)))
     from tetris_mcts_amd import model
     assert model.PREPARED_X3 == 27648 and model.VALUENET_BACKEND == {"hip": 0, "hip_bf16x3": 1}
     assert "hip_bf16x3" in model.HIP_BACKENDS

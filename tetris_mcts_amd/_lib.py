@@ -65,19 +65,14 @@ SYMBOLS = {
     "tm_valuenet_fit_validate": [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, C.c_float, vp, vp, vp],
     "tm_distnet_fit_validate_workspace": [i32, i32],     # (returns long long: restype set in lib())
     "tm_distnet_fit_validate": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
-    "tm_valuenet_prepare": [vp, vp, vp],
-    "tm_valuenet_forward": [vp, vp, vp, i32, vp, vp, vp, vp],
+    "tm_valuenet_check_mode": [i32, i32],
+    "tm_valuenet_prepare": [vp, vp, i32, i32, vp],
+    "tm_valuenet_forward": [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
     "tm_valuenet_forward_plain": [vp, vp, i32, vp, vp, vp, vp],
-    "tm_valuenet_forward_requests": [vp, vp, C.POINTER(TmStore), vp, vp],
-    "tm_valuenet_prepare_x3": [vp, vp, vp],
-    "tm_valuenet_forward_x3": [vp, vp, vp, vp, i32, vp, vp, vp, vp],
-    "tm_valuenet_forward_requests_x3": [vp, vp, vp, C.POINTER(TmStore), vp, vp],
-    "tm_distnet_prepare": [vp, vp, vp],
-    "tm_distnet_forward": [vp, vp, vp, i32, i32, vp, i32, vp, vp],
-    "tm_distnet_forward_requests": [vp, vp, C.POINTER(TmStore), vp, vp],
-    "tm_distnet_prepare_x3": [vp, vp, vp],
-    "tm_distnet_forward_x3": [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp],
-    "tm_distnet_forward_requests_x3": [vp, vp, vp, C.POINTER(TmStore), vp, vp],
+    "tm_valuenet_forward_requests": [vp, vp, i32, i32, C.POINTER(TmStore), vp, vp],
+    "tm_distnet_prepare": [vp, vp, i32, vp],
+    "tm_distnet_forward": [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp],
+    "tm_distnet_forward_requests": [vp, vp, i32, C.POINTER(TmStore), vp, vp],
     "tm_dist_transform": [i32, i32, vp, f64, f64, vp, f64, vp, vp],
     "tm_dist_mean_variance": [i32, i32, vp, f64, f64, vp, vp],
     "tm_distpy_shift": [i32, i32, vp, vp, f64, f64, vp, vp],
@@ -88,11 +83,7 @@ SYMBOLS = {
     "tm_search_run": [vp, i32, vp, vp, vp, vp],
     "tm_search_stats": [vp, vp, i32, i32],
     "tm_search_set_epoch": [vp, i32],
-    "tm_search_set_valuenet": [vp, i32],
-    "tm_valuenet_prepare_fc1_x3": [vp, vp, vp],
-    "tm_valuenet_forward_x3f": [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
-    "tm_valuenet_forward_requests_x3f": [vp, vp, vp, vp, C.POINTER(TmStore), vp, vp],
-    "tm_search_set_valuenet_fc1": [vp, i32],
+    "tm_search_set_valuenet": [vp, i32, i32],
 }
 
 _lib = None

@@ -17,12 +17,13 @@ import numpy as np
 import torch
 
 from .. import store as st
-from .agent import TreeAgent
+from .agent import OnlineFit, TreeAgent
 
 
-class DistValueSim(TreeAgent):
+class DistValueSim(OnlineFit, TreeAgent):
     kind = st.KIND_DIST
     low = 5
+    DUMP_PATH = "./data/memory_dump"
 
     def __init__(self, atoms=50, vmin=0, vmax=5000, max_nodes=100000, model=None, evaluator=None, online=False,
                  min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, valuenet_backend=None, fit_backend="torch",
@@ -108,20 +109,8 @@ class DistValueSim(TreeAgent):
         mean, var = mean.cpu().numpy(), var.cpu().numpy()
         return (mean[0], var[0]) if self.n_games == 1 else (mean, var)
 
-    # ---- online training (DistValueSimOnline.py:143-170): tuples harvested on the device at the collections (tree.hip dist_keep /
-    # dist_harvest_store), all-gathered over the ranks, the head fitted on their union with Model_Dist's loss ----
-    def train_if_collected(self, every=1, min_tuples=1, **kwargs):
-        """as ValueSim.train_if_collected: look on every `every`-th call, fit once the job holds `min_tuples` fresh tuples"""
-        from .. import dist as tdist
-        if not self.online or self.store is None or self.store.s.replay_cap == 0:
-            return None
-        self._train_calls = getattr(self, "_train_calls", 0) + 1
-        if self._train_calls % max(1, int(every)):
-            return None
-        if tdist.all_sum(int(self.store.t["replay_count"].sum().item()), self.store.device) < max(1, int(min_tuples)):
-            return None
-        return self.train_nodes(**kwargs)
-
+    # ---- online training (DistValueSimOnline.py:143-170): agent.OnlineFit, with tuples harvested on the device at the collections
+    # (tree.hip dist_keep / dist_harvest_store), all-gathered over the ranks, the head fitted on their union with Model_Dist's loss ----
     def harvested(self):
         """(packed observations int32 [n,12], distributions float32 [n,64], visits float32 [n]) of this rank since the last
         drain; the device buffers are emptied."""
@@ -131,42 +120,23 @@ class DistValueSim(TreeAgent):
         s.t["replay_count"].zero_()
         return keys, dists, visits
 
-    def train_nodes(self, dump_data=False, dump_path="./data/memory_dump", **train_kwargs):
-        from sys import stderr
+    def _drain(self):
+        return self.harvested()
+
+    def _gather(self, rows):
         from .. import dist as tdist
-        if not self.online or self.evaluator is not None:
-            return None
-        keys, dists, visits = self.harvested()
-        dropped = self.store.counter("N_DROPPED")
-        if dropped > getattr(self, "_dropped_seen", 0):
-            print("WARNING: {} harvested tuples did not fit the device replay buffer (replay_cap={})".format(
-                dropped - getattr(self, "_dropped_seen", 0), self.store.s.replay_cap), file=stderr, flush=True)
-            self._dropped_seen = dropped
-        if self._memory is not None:
-            keys, dists, visits = (torch.cat([a, b]) for a, b in zip(self._memory, (keys, dists, visits)))
-        keys, dists, visits = keys[:self.memory_size], dists[:self.memory_size], visits[:self.memory_size]
-        keys_all, dists_all, visits_all = tdist.all_gather_rows(keys.view(torch.int32), dists, visits)
-        keys_all, dists_all, visits_all = tdist.job_memory(self.memory_size, keys_all, dists_all, visits_all)      # (memory_size is the job's)
-        d_size = int(keys_all.shape[0])
-        m_size = min(self.n_trains * self.memory_growth_rate, self.memory_size)
-        if d_size < max(m_size, 1):
-            print("Not enough training data ({} < {}), collecting more data.".format(d_size, m_size), file=stderr, flush=True)
-            self._memory = (keys, dists, visits)
-            return None
-        print("Enough training data ({} >= {}), proceed to training.".format(d_size, m_size), file=stderr, flush=True)
-        states = torch.zeros(d_size, 1, 22, 10, dtype=torch.float32, device=keys_all.device)
-        states[:, :, 2:, :] = tdist.render_observations(keys_all)          # the net's 22 rows: two empty ones on top
-        data = [states, dists_all[:, :self.atoms].contiguous(), visits_all.reshape(-1, 1)]
-        if dump_data and tdist.rank() == 0:
-            import os
-            os.makedirs(os.path.dirname(os.path.abspath(dump_path)), exist_ok=True)
-            np.savez(dump_path, states=data[0].cpu().numpy(), values=data[1].cpu().numpy(), weights=data[2].cpu().numpy())
-        self.n_trains += 1
-        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend,     # DistValueSimOnline.py:165
-                    validation_backend=self.validation_backend)
-        opts.update(train_kwargs)
-        res = self.model.train_data(data, **opts)
-        self.model.training(False)
-        self._memory = None
-        print("Training complete.", file=stderr, flush=True)
-        return res
+        return tdist.all_gather_rows(rows[0].view(torch.int32), *rows[1:])
+
+    def _training_set(self, rows):
+        from .. import dist as tdist
+        keys, dists, visits = rows
+        states = torch.zeros(keys.shape[0], 1, 22, 10, dtype=torch.float32, device=keys.device)
+        states[:, :, 2:, :] = tdist.render_observations(keys)          # the net's 22 rows: two empty ones on top
+        return [states, dists[:, :self.atoms].contiguous(), visits.reshape(-1, 1)]
+
+    def _dump(self, path, data):
+        import os
+        from .. import dist as tdist
+        if tdist.rank() == 0:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            np.savez(path, states=data[0].cpu().numpy(), values=data[1].cpu().numpy(), weights=data[2].cpu().numpy())

@@ -232,3 +232,77 @@ class TreeAgent(Agent):
 
     def close(self):
         pass
+
+
+class OnlineFit:
+    """The bookkeeping of the online fits, a mixin beside TreeAgent for ValueSim and DistValueSim: the reference trains inside
+    remove_nodes() (ValueSim.py:101-120,161-185; DistValueSimOnline.py:143-170); the batched engine harvests tuples at the
+    collections on the device and trains between moves, on the union over all games and all ranks (tetris_mcts_amd/dist.py).
+    The agent supplies what differs:
+      _drain()             this rank's tuples harvested since the last drain as a tuple of tensors with one row a tuple (the
+                           packed observations first); the device buffers are emptied
+      _gather(rows)        the rows of all ranks
+      _training_set(rows)  the job's rows -> the list model.train_data takes
+      _dump(path, data)    that list in the agent's np.savez layout (rank 0 writes)
+    and DUMP_PATH, online, evaluator, model, fit_backend, validation_backend, memory_size, memory_growth_rate, n_trains = 0 and
+    _memory = None (the rows carried over between two looks)."""
+    # Whether the rows an earlier look moved into _memory ("not enough training data") count towards train_if_collected's
+    # min_tuples.  ValueSim counts them, DistValueSim does not: a difference of behaviour between the two agents that is kept
+    # as it is.
+    COUNT_HELD = False
+
+    def train_if_collected(self, every=1, min_tuples=1, **kwargs):
+        """train_nodes() if garbage collections have harvested tuples since the last fit (the reference's remove_nodes ->
+        store_nodes -> train_nodes chain, ValueSim.py:101-120, runs at every collection of its one game); None otherwise.
+        One game: call it after every move with the defaults and the cadence is the reference's.  A batch of games collects
+        somewhere on nearly every move, and looking costs a device sync and a collective: `every` = look only on every k-th
+        call, `min_tuples` = fit only once the job (all ranks) holds that many fresh tuples (play.py: --train_every,
+        --train_min_tuples).  Every rank must call this on the same moves: the count is a collective."""
+        from .. import dist as tdist
+        if not self.online or self.store is None or self.store.s.replay_cap == 0:
+            return None
+        self._train_calls = getattr(self, "_train_calls", 0) + 1
+        if self._train_calls % max(1, int(every)):
+            return None
+        held = int(self._memory[0].shape[0]) if (self.COUNT_HELD and self._memory is not None) else 0
+        if tdist.all_sum(int(self.store.t["replay_count"].sum().item()) + held, self.store.device) < max(1, int(min_tuples)):
+            return None
+        return self.train_nodes(**kwargs)
+
+    def train_nodes(self, dump_data=False, dump_path=None, **train_kwargs):
+        from sys import stderr
+        from .. import dist as tdist
+        if not self.online or self.evaluator is not None:
+            return None
+        rows = self._drain()
+        dropped = self.store.counter("N_DROPPED")
+        if dropped > getattr(self, "_dropped_seen", 0):
+            # the reference keeps every qualifying observation up to memory_size (ValueSim.py:122-159): say so when the
+            # device-side harvest buffer was too small between two drains
+            print("WARNING: {} harvested tuples did not fit the device replay buffer (replay_cap={}); drain more often or "
+                  "raise replay_cap".format(dropped - getattr(self, "_dropped_seen", 0), self.store.s.replay_cap),
+                  file=stderr, flush=True)
+            self._dropped_seen = dropped
+        if self._memory is not None:
+            rows = tuple(torch.cat([a, b]) for a, b in zip(self._memory, rows))
+        rows = tuple(a[:self.memory_size] for a in rows)
+        rows_all = tdist.job_memory(self.memory_size, *self._gather(rows))      # (memory_size is the job's, not a rank's)
+        d_size = int(rows_all[0].shape[0])
+        m_size = min(self.n_trains * self.memory_growth_rate, self.memory_size)
+        if d_size < max(m_size, 1):
+            print("Not enough training data ({} < {}), collecting more data.".format(d_size, m_size), file=stderr, flush=True)
+            self._memory = rows
+            return None
+        print("Enough training data ({} >= {}), proceed to training.".format(d_size, m_size), file=stderr, flush=True)
+        data = self._training_set(rows_all)
+        if dump_data:
+            self._dump(dump_path or self.DUMP_PATH, data)
+        self.n_trains += 1
+        opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend,     # DistValueSimOnline.py:165
+                    validation_backend=self.validation_backend)
+        opts.update(train_kwargs)
+        res = self.model.train_data(data, **opts)
+        self.model.training(False)
+        self._memory = None
+        print("Training complete.", file=stderr, flush=True)
+        return res

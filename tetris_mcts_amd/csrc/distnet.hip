@@ -32,36 +32,10 @@ static_assert(OFF_FVW + 50 * HID + 50 == TM_DISTNET_PARAMS_50, "parameter blob s
 constexpr int A1CS = C1P;                         // conv1-output channel stride in LDS
 constexpr int WAVE_LDS = (32 * A1CS + 220 + 3) & ~3;   // floats per wave: a1, the 22 x 10 input
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "net_common.h"     // f32x16, f32x4, tm_exp, lds_fence, max_dynamic_lds
 
-__device__ inline double tm_exp(double x) {
-    if (x > 700.0) x = 700.0;
-    if (x < -700.0) x = -700.0;
-    const double inv_ln2 = 1.4426950408889634074, ln2_hi = 6.93147180369123816490e-01,
-                 ln2_lo = 1.90821492927058770002e-10;
-    double n = rint(x * inv_ln2);
-    double r = fma(-n, ln2_hi, x);
-    r = fma(-n, ln2_lo, r);
-    double p = 1.0 / 6227020800.0;
-    p = fma(p, r, 1.0 / 479001600.0);
-    p = fma(p, r, 1.0 / 39916800.0);
-    p = fma(p, r, 1.0 / 3628800.0);
-    p = fma(p, r, 1.0 / 362880.0);
-    p = fma(p, r, 1.0 / 40320.0);
-    p = fma(p, r, 1.0 / 5040.0);
-    p = fma(p, r, 1.0 / 720.0);
-    p = fma(p, r, 1.0 / 120.0);
-    p = fma(p, r, 1.0 / 24.0);
-    p = fma(p, r, 1.0 / 6.0);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    long long bits = __double_as_longlong(p);
-    bits += ((long long)n) << 52;
-    return __longlong_as_double(bits);
-}
-
+// (bf16x3.h's Leaky::fwd is this expression once more: it comes with distnet_x3.inc at the end of the file, after the fp32
+//  kernels that use this one)
 __device__ __forceinline__ float leaky(float v) { return v > 0.0f ? v : v * 0.01f; }
 
 // Operand streams ("T4", as valuenet.hip): for MFMA step s the A operand of lane l is W[row][k(s, l)]; four consecutive steps
@@ -83,12 +57,6 @@ __global__ void k_dn_prepare(const float* __restrict__ P, float* __restrict__ pr
         int k = 4 * s + (l >> 4), row = 16 * ht + (l & 15);
         prep[t] = P[OFF_F1W + (size_t)row * KFC + k];
     }
-}
-
-__device__ __forceinline__ void lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // conv2: 4x4 valid convolution 32 -> 32 channels over the 19 x 7 map = 64 output positions = two tiles of 32 on the matrix
@@ -434,34 +402,24 @@ __global__ __launch_bounds__(512) void k_dn_fc(const float* __restrict__ P, cons
 
 #include "distnet_x3.inc"
 
-static std::once_flag g_attr_once;
-static int g_attr_err = 0;
-
-// planes != nullptr: conv1 + conv2 of the split-precision backend (k_dn_conv_x3), k_dn_fc as always
-static int dn_forward_impl(const float* P, const float* prepared, const __bf16* planes, const int8_t* states,
+// backend BF16X3: conv1 + conv2 of the split-precision backend (k_dn_conv_x3) on the planes behind prepared's streams, k_dn_fc as
+// always
+static int dn_forward_impl(const float* P, const float* prepared, int backend, const int8_t* states,
                            const uint32_t* node_game, const int32_t* eval_obs, int max_nodes, int n, int atoms, float* out,
                            int out_stride, float* scratch, hipStream_t stream) {
     if (n <= 0) return 0;
     if (atoms < 1 || atoms > 64) return (int)hipErrorInvalidValue;
-    if (planes) {
+    if (backend == TM_VALUENET_BF16X3) {
+        if (!prepared) return (int)hipErrorInvalidValue;
         const int lds = 4 * X3_WAVE_BYTES;
-        static std::once_flag x3_once;
-        static int x3_err = 0;
-        std::call_once(x3_once, [&] {
-            x3_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_dn_conv_x3),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        if (x3_err) return x3_err;
+        if (const int e = max_dynamic_lds<k_dn_conv_x3>(lds)) return e;
         const int blocks = (n + 3) / 4 < 256 ? (n + 3) / 4 : 256;     // one workgroup per CU, waves stride over the states
+        const __bf16* planes = reinterpret_cast<const __bf16*>(prepared + TM_DISTNET_PREPARED);
         hipLaunchKernelGGL(k_dn_conv_x3, dim3(blocks), dim3(256), lds, stream, P, planes, states, node_game, eval_obs,
                            max_nodes, n, scratch, TM_DISTNET_SCRATCH);
     } else {
         const int lds = 4 * WAVE_LDS * (int)sizeof(float);
-        std::call_once(g_attr_once, [&] {
-            g_attr_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_dn_conv),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        if (g_attr_err) return g_attr_err;
+        if (const int e = max_dynamic_lds<k_dn_conv>(lds)) return e;
         int blocks = (n + 3) / 4;
         if (blocks > 512) blocks = 512;      // two resident workgroups per CU, waves stride over the states
         hipLaunchKernelGGL(k_dn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, node_game, eval_obs,
@@ -472,50 +430,37 @@ static int dn_forward_impl(const float* P, const float* prepared, const __bf16* 
     return (int)hipGetLastError();
 }
 
+// the head's backends: TM_VALUENET_FP32 and TM_VALUENET_BF16X3
+static bool dn_backend_ok(int backend) { return backend == TM_VALUENET_FP32 || backend == TM_VALUENET_BF16X3; }
+
 }  // namespace tmcts_dn
 
 using namespace tmcts_dn;
 
 extern "C" {
 
-int tm_distnet_prepare(const float* P, float* prepared, void* stream_) {
+// the parts of `prepared` the backend names: the fp32 streams always, then conv2's planes
+int tm_distnet_prepare(const float* P, float* prepared, int backend, void* stream_) {
+    if (!dn_backend_ok(backend) || !prepared) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(k_dn_prepare, dim3((PREP_TOTAL + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P, prepared);
+    if (backend == TM_VALUENET_BF16X3)
+        hipLaunchKernelGGL(k_dn_prepare_x3, dim3((X3_STEPS * 64 * 8 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
+                           reinterpret_cast<__bf16*>(prepared + TM_DISTNET_PREPARED));
     return (int)hipGetLastError();
 }
 
-int tm_distnet_forward(const float* P, const float* prepared, const int8_t* states, int n, int atoms, float* dist,
+int tm_distnet_forward(const float* P, const float* prepared, int backend, const int8_t* states, int n, int atoms, float* dist,
                        int dist_stride, float* scratch, void* stream_) {
-    if (dist_stride < atoms) return (int)hipErrorInvalidValue;
-    return dn_forward_impl(P, prepared, nullptr, states, nullptr, nullptr, 0, n, atoms, dist, dist_stride, scratch,
+    if (!dn_backend_ok(backend) || dist_stride < atoms) return (int)hipErrorInvalidValue;
+    return dn_forward_impl(P, prepared, backend, states, nullptr, nullptr, 0, n, atoms, dist, dist_stride, scratch,
                            (hipStream_t)stream_);
 }
 
-int tm_distnet_forward_requests(const float* P, const float* prepared, const tm_store* s, float* scratch, void* stream_) {
-    if (s->kind != TM_KIND_DIST || s->eval_slots != 1) return (int)hipErrorInvalidValue;
-    return dn_forward_impl(P, prepared, nullptr, nullptr, s->node_game, s->eval_obs, s->max_nodes, s->n_games, s->dist_bins,
+int tm_distnet_forward_requests(const float* P, const float* prepared, int backend, const tm_store* s, float* scratch,
+                                void* stream_) {
+    if (!dn_backend_ok(backend) || s->kind != TM_KIND_DIST || s->eval_slots != 1) return (int)hipErrorInvalidValue;
+    return dn_forward_impl(P, prepared, backend, nullptr, s->node_game, s->eval_obs, s->max_nodes, s->n_games, s->dist_bins,
                            s->eval_dist, TM_DIST_ROW, scratch, (hipStream_t)stream_);
-}
-
-// ---- the split-precision backend (distnet_x3.inc) ----
-int tm_distnet_prepare_x3(const float* P, float* prepared_x3, void* stream_) {
-    if (!prepared_x3) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_dn_prepare_x3, dim3((X3_STEPS * 64 * 8 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
-                       reinterpret_cast<__bf16*>(prepared_x3));
-    return (int)hipGetLastError();
-}
-
-int tm_distnet_forward_x3(const float* P, const float* prepared, const float* prepared_x3, const int8_t* states, int n,
-                          int atoms, float* dist, int dist_stride, float* scratch, void* stream_) {
-    if (!prepared_x3 || dist_stride < atoms) return (int)hipErrorInvalidValue;
-    return dn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), states, nullptr, nullptr, 0, n, atoms,
-                           dist, dist_stride, scratch, (hipStream_t)stream_);
-}
-
-int tm_distnet_forward_requests_x3(const float* P, const float* prepared, const float* prepared_x3, const tm_store* s,
-                                   float* scratch, void* stream_) {
-    if (!prepared_x3 || s->kind != TM_KIND_DIST || s->eval_slots != 1) return (int)hipErrorInvalidValue;
-    return dn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->node_game, s->eval_obs,
-                           s->max_nodes, s->n_games, s->dist_bins, s->eval_dist, TM_DIST_ROW, scratch, (hipStream_t)stream_);
 }
 
 }  // extern "C"

@@ -16,12 +16,10 @@
 //   * one wave computes one state from its own inputs, with the same instructions whatever the batch: a state's outputs
 //     depend on that state only, not on the batch size, its position in it or its neighbours, and are the same bits from
 //     launch to launch.
-#include "bf16x3.h"     // split3, bf16x8, bf16x4
+#include "bf16x3.h"     // split3, bf16x8, bf16x4, X3_ROW, store_planes
 
-// conv1's output in LDS: a row of X3_ROW bf16 per position (133 = 19 x 7, row p = y * 7 + x) = the hi, mid and lo planes of
-// its 32 channels (channel innermost: a lane's eight k of one MFMA step are eight channels at one tap, one 16-byte read per
-// plane) and 8 bf16 of padding (208-byte rows, as the value net's).  Then the 22 x 10 input board in fp32.
-constexpr int X3_ROW = 3 * 32 + 8;
+// conv1's output in LDS: a row of X3_ROW bf16 (bf16x3.h) per position (133 = 19 x 7, row p = y * 7 + x).  Then the 22 x 10
+// input board in fp32.
 constexpr int X3_A1_BYTES = C1P * X3_ROW * 2;
 constexpr int X3_WAVE_BYTES = X3_A1_BYTES + 220 * 4;          // 28 544: four waves = one workgroup per CU (111.5 of 160 KiB)
 static_assert(X3_A1_BYTES % 16 == 0, "input board aligned");
@@ -100,27 +98,6 @@ __device__ __forceinline__ void conv2_x3_mfma(const __bf16* in, const int (&brow
     }
 }
 
-// LeakyReLU of a conv1 accumulator tile (lane: its position, channels (r & 3) + 8 (r >> 2) + 4 (l >> 5)) split into the three
-// planes of the position's row: four runs of four consecutive channels, one 8-byte store per run and plane
-__device__ __forceinline__ void store_planes(__bf16* row, const f32x16& acc, int half) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        bf16x4 h, m, l;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            __bf16 a, b, c;
-            split3(leaky(acc[4 * q + r]), a, b, c);
-            h[r] = a;
-            m[r] = b;
-            l[r] = c;
-        }
-        __bf16* dst = row + 8 * q + 4 * half;
-        *reinterpret_cast<bf16x4*>(dst) = h;
-        *reinterpret_cast<bf16x4*>(dst + 32) = m;
-        *reinterpret_cast<bf16x4*>(dst + 64) = l;
-    }
-}
-
 // render + conv1 (fp32, k_dn_conv's) + conv2 (bf16x3) of one state per wave, four waves per workgroup, one workgroup per CU
 // (the LDS), so one wave per SIMD: the next state's request and packed game are fetched one state ahead, as in k_dn_conv.
 // (The planes and a2out are not __restrict__: the stores to a2out inside the state loop keep the weight loads in it,
@@ -162,7 +139,7 @@ __global__ __launch_bounds__(256, 1) void k_dn_conv_x3(const float* __restrict__
         for (int t = 0; t < 5; ++t) {
             const f32x16 acc = conv1_tile(x0, t, l31, bias1, w1, koff1);
             const int p = 32 * t + l31;
-            if (p < C1P) store_planes(a1 + p * X3_ROW, acc, half);
+            if (p < C1P) store_planes<Leaky>(a1 + p * X3_ROW, acc, half);
         }
         lds_fence();
         // ---- conv2: 64 positions = 2 tiles, straight to the scratch row of the state ----

@@ -43,8 +43,7 @@ struct tm_search {
     int ev_used;
     double tree_ms, nn_ms;
     long long n_timed, n_runs, extra_launches, launches, gc_launches;
-    int vn_backend = TM_VALUENET_FP32;   // tm_search_set_valuenet
-    int vn_fc1 = TM_VALUENET_FC1_FP32;   // tm_search_set_valuenet_fc1
+    int vn_backend = TM_VALUENET_FP32, vn_fc1 = TM_VALUENET_FC1_FP32;   // tm_search_set_valuenet
 };
 
 #define TM_TRY(x) do { int e_ = (int)(x); if (e_ != 0) return e_; } while (0)
@@ -189,20 +188,12 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
     };
     auto nn = [&](int k) -> int {
         if (!vn_params || h->sub[k].n_games == 0) return 0;
-        if (h->full.kind == TM_KIND_DIST) {    // the distributional head (distnet.hip): eval_obs names the leaf node
-            float* scr = vn_scratch + (size_t)h->first[k] * TM_DISTNET_SCRATCH;
-            if (h->vn_backend == TM_VALUENET_BF16X3)  // vn_prepared: the fp32 operand streams, then the planes
-                return tm_distnet_forward_requests_x3(vn_params, vn_prepared, vn_prepared + TM_DISTNET_PREPARED, &h->sub[k], scr,
-                                                      st[k]);
-            return tm_distnet_forward_requests(vn_params, vn_prepared, &h->sub[k], scr, st[k]);
-        }
-        float* scr = vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA;
-        if (h->vn_backend == TM_VALUENET_BF16X3 && h->vn_fc1 == TM_VALUENET_FC1_BF16X3)      // ... then fc1's planes (tm_search_set_valuenet_fc1)
-            return tm_valuenet_forward_requests_x3f(vn_params, vn_prepared, vn_prepared + TM_VALUENET_PREPARED,
-                                                    vn_prepared + TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3, &h->sub[k], scr, st[k]);
-        if (h->vn_backend == TM_VALUENET_BF16X3)      // vn_prepared: the fp32 operand streams, then the planes (tm_search_set_valuenet)
-            return tm_valuenet_forward_requests_x3(vn_params, vn_prepared, vn_prepared + TM_VALUENET_PREPARED, &h->sub[k], scr, st[k]);
-        return tm_valuenet_forward_requests(vn_params, vn_prepared, &h->sub[k], scr, st[k]);
+        // vn_prepared: one buffer, the fp32 operand streams and behind them the planes the mode names (tm_search_set_valuenet)
+        if (h->full.kind == TM_KIND_DIST)      // the distributional head (distnet.hip): eval_obs names the leaf node
+            return tm_distnet_forward_requests(vn_params, vn_prepared, h->vn_backend, &h->sub[k],
+                                               vn_scratch + (size_t)h->first[k] * TM_DISTNET_SCRATCH, st[k]);
+        return tm_valuenet_forward_requests(vn_params, vn_prepared, h->vn_backend, h->vn_fc1, &h->sub[k],
+                                            vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA, st[k]);
     };
     h->ev_used = 0;
     TM_TRY(hipEventRecord(h->ev_loop0, st[0]));
@@ -285,21 +276,14 @@ int tm_search_set_epoch(tm_search* h, int epoch) {
     return 0;
 }
 
-// The evaluator's backend for the runs that follow (include/tetris_mcts_hip.h: TM_VALUENET_FP32 / TM_VALUENET_BF16X3), the
-// value net's or, on a TM_KIND_DIST store, the distributional head's.
-int tm_search_set_valuenet(tm_search* h, int backend) {
-    if (backend != TM_VALUENET_FP32 && backend != TM_VALUENET_BF16X3) return (int)hipErrorInvalidValue;
+// The evaluator's mode for the runs that follow (include/tetris_mcts_hip.h): the value net's backend and fc1, or, on a
+// TM_KIND_DIST store, the distributional head's backend (it has no fc1 option).  Both values in one call: nothing depends on an
+// earlier one.
+int tm_search_set_valuenet(tm_search* h, int backend, int fc1) {
+    if (const int e = tm_valuenet_check_mode(backend, fc1)) return e;
+    if (h->full.kind == TM_KIND_DIST && fc1 != TM_VALUENET_FC1_FP32) return (int)hipErrorInvalidValue;
     h->vn_backend = backend;
-    if (backend == TM_VALUENET_FP32) h->vn_fc1 = TM_VALUENET_FC1_FP32;      // (the split fc1 belongs to the split backend)
-    return 0;
-}
-
-// fc1 of the value net under TM_VALUENET_BF16X3 (include/tetris_mcts_hip.h: TM_VALUENET_FC1_FP32 / TM_VALUENET_FC1_BF16X3)
-int tm_search_set_valuenet_fc1(tm_search* h, int mode) {
-    if (mode != TM_VALUENET_FC1_FP32 && mode != TM_VALUENET_FC1_BF16X3) return (int)hipErrorInvalidValue;
-    if (h->full.kind == TM_KIND_DIST) return (int)hipErrorInvalidValue;
-    if (mode == TM_VALUENET_FC1_BF16X3 && h->vn_backend != TM_VALUENET_BF16X3) return (int)hipErrorInvalidValue;
-    h->vn_fc1 = mode;
+    h->vn_fc1 = fc1;
     return 0;
 }
 

@@ -17,32 +17,7 @@ constexpr int A1 = 32 * 18 * 8, A2 = 32 * 16 * 6, A3 = 32 * 14 * 4, HID = 256;
 constexpr int OFF_C1W = 0, OFF_C1B = 288, OFF_C2W = 320, OFF_C2B = 9536, OFF_C3W = 9568, OFF_C3B = 18784,
               OFF_F1W = 18816, OFF_F1B = 477568, OFF_FOW = 477824, OFF_FOB = 478336, OFF_UB = 478338, OFF_LB = 478340;
 
-__device__ inline double tm_exp(double x) {
-    if (x > 700.0) x = 700.0;
-    if (x < -700.0) x = -700.0;
-    const double inv_ln2 = 1.4426950408889634074, ln2_hi = 6.93147180369123816490e-01,
-                 ln2_lo = 1.90821492927058770002e-10;
-    double n = rint(x * inv_ln2);
-    double r = fma(-n, ln2_hi, x);
-    r = fma(-n, ln2_lo, r);
-    double p = 1.0 / 6227020800.0;
-    p = fma(p, r, 1.0 / 479001600.0);
-    p = fma(p, r, 1.0 / 39916800.0);
-    p = fma(p, r, 1.0 / 3628800.0);
-    p = fma(p, r, 1.0 / 362880.0);
-    p = fma(p, r, 1.0 / 40320.0);
-    p = fma(p, r, 1.0 / 5040.0);
-    p = fma(p, r, 1.0 / 720.0);
-    p = fma(p, r, 1.0 / 120.0);
-    p = fma(p, r, 1.0 / 24.0);
-    p = fma(p, r, 1.0 / 6.0);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    long long bits = __double_as_longlong(p);
-    bits += ((long long)n) << 52;
-    return __longlong_as_double(bits);
-}
+#include "net_common.h"     // f32x16, f32x4, tm_exp, lds_fence, max_dynamic_lds
 
 // ---- reference-order plain kernels: one thread per output element ----
 template <int CIN, int H, int W>
@@ -107,7 +82,6 @@ namespace tmcts_vn {
 // four consecutive steps are stored together so one global_load_dwordx4 per lane feeds four MFMAs:
 //   T4[(s/4)*64 + l][s%4]
 // ===================================================================================================
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int SCHED_REGION_QUADS = 6;   // conv_mfma closes its scheduling region every this many quads of MFMA steps
 constexpr int PREP_W2 = 0, PREP_W3 = 9216, PREP_W1 = 18432, PREP_TOTAL = 18432 + 458752;
 constexpr int A1CS = 145;   // conv1-output channel stride in LDS (18*8 = 144, +1 against bank conflicts)
@@ -137,12 +111,6 @@ __global__ void k_vn_prepare(const float* __restrict__ P, float* __restrict__ pr
         int k = 4 * s + (l >> 4), row = 16 * ht + (l & 15);
         prep[t] = P[OFF_F1W + (size_t)row * A3 + k];
     }
-}
-
-__device__ __forceinline__ void lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // 3x3 valid convolution, 32 -> 32 channels, as TILES position tiles of 32 on the matrix cores.
@@ -262,7 +230,6 @@ __device__ __forceinline__ void render_obs(uint32_t kw, int lane, float* x0) {
 //                   of tiles - an L2-bandwidth problem (every tile streams the 1.8 MB of weights: twice the states per tile =
 //                   half the stream).  (<4, 2, 128, 3>, two workgroups of 128 units per tile, reads the activations half as
 //                   often and was measured at 121 us against 80: 224 workgroups of four dependent accumulators each.)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 // The output layer (256 -> 2, sigmoid, affine) is folded in: a tile's NY workgroups (parts of the hidden units) store
 // their part of h with write-through (sc1) stores, wait for them, and arrive on the tile's counter; the LAST to arrive reads
 // the other parts with sc1 loads (the valid hand-off form of MI355X_MICROARCH.md: 16-byte sc1 stores and loads, no fences)
@@ -618,8 +585,25 @@ static int vn_fc1_x3_launch(const float* P, const __bf16* fc1_planes, const ReqL
 
 extern "C" {
 
-int tm_valuenet_prepare(const float* P, float* prepared, void* stream_) {
-    hipLaunchKernelGGL(k_vn_prepare, dim3((PREP_TOTAL + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P, prepared);
+// the one check of the value net's mode: (FP32, FC1_FP32), (BF16X3, FC1_FP32), (BF16X3, FC1_BF16X3).  Host arithmetic only.
+int tm_valuenet_check_mode(int backend, int fc1) {
+    const bool ok = (backend == TM_VALUENET_FP32 && fc1 == TM_VALUENET_FC1_FP32) ||
+                    (backend == TM_VALUENET_BF16X3 && (fc1 == TM_VALUENET_FC1_FP32 || fc1 == TM_VALUENET_FC1_BF16X3));
+    return ok ? 0 : (int)hipErrorInvalidValue;
+}
+
+// the parts of `prepared` the mode names, in the buffer's order: the fp32 streams always, then the convolutions' planes, then fc1's
+int tm_valuenet_prepare(const float* P, float* prepared, int backend, int fc1, void* stream_) {
+    if (const int e = tm_valuenet_check_mode(backend, fc1)) return e;
+    if (!prepared) return (int)hipErrorInvalidValue;
+    hipStream_t stream = (hipStream_t)stream_;
+    hipLaunchKernelGGL(k_vn_prepare, dim3((PREP_TOTAL + 255) / 256), dim3(256), 0, stream, P, prepared);
+    if (backend == TM_VALUENET_BF16X3)
+        hipLaunchKernelGGL(k_vn_prepare_x3, dim3((2 * 18 * 64 * 8 + 255) / 256), dim3(256), 0, stream, P,
+                           reinterpret_cast<__bf16*>(prepared + TM_VALUENET_PREPARED));
+    if (fc1 == TM_VALUENET_FC1_BF16X3)
+        hipLaunchKernelGGL(k_vn_prepare_fc1_x3, dim3((HID * A3 + 255) / 256), dim3(256), 0, stream, P,
+                           reinterpret_cast<__bf16*>(prepared + TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3));
     return (int)hipGetLastError();
 }
 
@@ -644,57 +628,50 @@ int tm_valuenet_forward_plain(const float* P, const int8_t* states, int n, float
     return (int)hipGetLastError();
 }
 
-// planes != nullptr: the convolutions of the split-precision backend (k_vn_conv_x3), fc1 and the output layer as always -
-// unless fc1_planes != nullptr: k_vn_fc1_x3
-static int vn_forward_impl(const float* P, const float* prepared, const __bf16* planes, const int8_t* states,
+// backend BF16X3: the convolutions of the split-precision backend (k_vn_conv_x3) on the planes behind prepared's streams, fc1 and
+// the output layer as always - unless fc1 is FC1_BF16X3: k_vn_fc1_x3 on fc1's planes behind those
+static int vn_forward_impl(const float* P, const float* prepared, int backend, int fc1, const int8_t* states,
                            const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n, float* v, float* var,
-                           float* scratch, hipStream_t stream, const __bf16* fc1_planes = nullptr) {
+                           float* scratch, hipStream_t stream) {
+    if (const int e = tm_valuenet_check_mode(backend, fc1)) return e;
     if (n <= 0) return 0;
+    if (backend == TM_VALUENET_BF16X3 && !prepared) return (int)hipErrorInvalidValue;
     constexpr int SS = TM_VALUENET_SCRATCH_MFMA;   // a3 (1792) + hidden (256) + 16 pad words (word 0 of a tile's first row: its arrival counter)
     static_assert(SS >= A3 + HID + 1 && SS % 4 == 0, "scratch row");
-    if (planes) {
+    if (backend == TM_VALUENET_BF16X3) {
         const int lds = 4 * X3_WAVE_BYTES;
-        static std::once_flag x3_once;
-        static int x3_err = 0;
-        std::call_once(x3_once, [&] {
-            x3_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vn_conv_x3),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        if (x3_err) return x3_err;
+        if (const int e = max_dynamic_lds<k_vn_conv_x3>(lds)) return e;
         const int blocks = (n + 3) / 4 < 256 ? (n + 3) / 4 : 256;     // one workgroup per CU, waves stride over the states
+        const __bf16* planes = reinterpret_cast<const __bf16*>(prepared + TM_VALUENET_PREPARED);
         hipLaunchKernelGGL(k_vn_conv_x3, dim3(blocks), dim3(256), lds, stream, P, planes, states, obs_key, rq,
                            max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
     } else {
         const int lds = 4 * WAVE_LDS * (int)sizeof(float);
-        static std::once_flag attr_once;
-        static int attr_err = 0;
-        std::call_once(attr_once, [&] {
-            attr_err = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_vn_conv),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        if (attr_err) return attr_err;
+        if (const int e = max_dynamic_lds<k_vn_conv>(lds)) return e;
         int blocks = (n + 3) / 4;
         if (blocks > 256 * CONV_WG_PER_CU) blocks = 256 * CONV_WG_PER_CU;   // resident workgroups, waves stride over the states
         hipLaunchKernelGGL(k_vn_conv, dim3(blocks), dim3(256), lds, stream, P, prepared, states, obs_key, rq,
                            max_nodes, n, scratch, SS, reinterpret_cast<int32_t*>(scratch + A3 + HID), 32 * SS);
     }
-    if (fc1_planes) return vn_fc1_x3_launch(P, fc1_planes, rq, n, v, var, scratch, stream);
+    if (fc1 == TM_VALUENET_FC1_BF16X3)
+        return vn_fc1_x3_launch(P, reinterpret_cast<const __bf16*>(prepared + TM_VALUENET_PREPARED + TM_VALUENET_PREPARED_X3), rq, n, v, var, scratch, stream);
     return vn_fc1_launch(P, prepared, rq, n, v, var, scratch, stream);
 }
 
-// matrix-core path; prepared: tm_valuenet_prepare output; scratch: n x TM_VALUENET_SCRATCH_MFMA floats
-int tm_valuenet_forward(const float* P, const float* prepared, const int8_t* states, int n, float* v, float* var,
-                        float* scratch, void* stream_) {
-    return vn_forward_impl(P, prepared, nullptr, states, nullptr, ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch,
+// matrix-core path; prepared: tm_valuenet_prepare's output for this mode or a larger one; scratch: n x TM_VALUENET_SCRATCH_MFMA floats
+int tm_valuenet_forward(const float* P, const float* prepared, int backend, int fc1, const int8_t* states, int n, float* v,
+                        float* var, float* scratch, void* stream_) {
+    return vn_forward_impl(P, prepared, backend, fc1, states, nullptr, ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch,
                            (hipStream_t)stream_);
 }
 
 // the tree engine's evaluation requests, rendered inside the first kernel: v/var -> s->eval_v / s->eval_var
-int tm_valuenet_forward_requests(const float* P, const float* prepared, const tm_store* s, float* scratch, void* stream_) {
+int tm_valuenet_forward_requests(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
+                                 void* stream_) {
     // the requests of the last tm_sim_step launch, drawn from its dense list (s->eval_parity = that launch's)
     const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
-    return vn_forward_impl(P, prepared, nullptr, nullptr, s->obs_key, rq, s->max_nodes,
-                           s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
+    return vn_forward_impl(P, prepared, backend, fc1, nullptr, s->obs_key, rq, s->max_nodes, s->n_games * s->eval_slots,
+                           s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
 }
 
 // k_vn_fc1's item dealing (host arithmetic only: callable without a GPU): the items of workgroup b of a grid of `grid` workgroups
@@ -709,54 +686,6 @@ int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t* ite
         if (items && k < cap) { items[2 * k] = it.tile; items[2 * k + 1] = it.part; }
     }
     return k;
-}
-
-// ---- the split-precision backend (valuenet_x3.inc) ----
-int tm_valuenet_prepare_x3(const float* P, float* prepared_x3, void* stream_) {
-    if (!prepared_x3) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_vn_prepare_x3, dim3((2 * 18 * 64 * 8 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
-                       reinterpret_cast<__bf16*>(prepared_x3));
-    return (int)hipGetLastError();
-}
-
-int tm_valuenet_forward_x3(const float* P, const float* prepared, const float* prepared_x3, const int8_t* states, int n, float* v,
-                           float* var, float* scratch, void* stream_) {
-    if (!prepared_x3) return (int)hipErrorInvalidValue;
-    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), states, nullptr,
-                           ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch, (hipStream_t)stream_);
-}
-
-int tm_valuenet_forward_requests_x3(const float* P, const float* prepared, const float* prepared_x3, const tm_store* s,
-                                    float* scratch, void* stream_) {
-    if (!prepared_x3) return (int)hipErrorInvalidValue;
-    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
-    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->obs_key, rq, s->max_nodes,
-                           s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
-}
-
-// ---- the same backend with fc1 split as well (valuenet_fc1_x3.inc) ----
-int tm_valuenet_prepare_fc1_x3(const float* P, float* prepared_fc1_x3, void* stream_) {
-    if (!prepared_fc1_x3) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_vn_prepare_fc1_x3, dim3((HID * A3 + 255) / 256), dim3(256), 0, (hipStream_t)stream_, P,
-                       reinterpret_cast<__bf16*>(prepared_fc1_x3));
-    return (int)hipGetLastError();
-}
-
-int tm_valuenet_forward_x3f(const float* P, const float* prepared, const float* prepared_x3, const float* prepared_fc1_x3,
-                            const int8_t* states, int n, float* v, float* var, float* scratch, void* stream_) {
-    if (!prepared_x3 || !prepared_fc1_x3) return (int)hipErrorInvalidValue;
-    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), states, nullptr,
-                           ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch, (hipStream_t)stream_,
-                           reinterpret_cast<const __bf16*>(prepared_fc1_x3));
-}
-
-int tm_valuenet_forward_requests_x3f(const float* P, const float* prepared, const float* prepared_x3, const float* prepared_fc1_x3,
-                                     const tm_store* s, float* scratch, void* stream_) {
-    if (!prepared_x3 || !prepared_fc1_x3) return (int)hipErrorInvalidValue;
-    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
-    return vn_forward_impl(P, prepared, reinterpret_cast<const __bf16*>(prepared_x3), nullptr, s->obs_key, rq, s->max_nodes,
-                           s->n_games * s->eval_slots, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_,
-                           reinterpret_cast<const __bf16*>(prepared_fc1_x3));
 }
 
 }  // extern "C"

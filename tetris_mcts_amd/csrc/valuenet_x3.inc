@@ -16,12 +16,8 @@
 //   * one wave computes one state from its own inputs, with the same instructions whatever the batch: a state's outputs depend
 //     on that state only, not on the batch size, its position in it or its neighbours, and are the same bits from launch to
 //     launch.
-#include "bf16x3.h"     // split3, bf16x8, bf16x4
+#include "bf16x3.h"     // split3, bf16x8, bf16x4, X3_ROW, store_planes
 
-// Activations in LDS: a row of X3_ROW bf16 per position = the hi, mid and lo planes of its 32 channels (channel innermost: a
-// lane's eight consecutive k of one MFMA step are eight channels at one tap, one 16-byte read per plane) and 8 bf16 of
-// padding (208-byte rows: a wave's 16-byte reads of consecutive positions fall on distinct bank groups).
-constexpr int X3_ROW = 3 * 32 + 8;
 constexpr int X3_WAVE_BYTES = 144 * X3_ROW * 2 + 200 * 4;    // a1 planes (a2 overlays them), the input board in fp32
 static_assert((144 * X3_ROW * 2) % 16 == 0, "input board aligned");
 // one workgroup of four waves per CU: 123 KB of the 160 KB
@@ -67,28 +63,6 @@ __device__ __forceinline__ void conv_x3_mfma(const __bf16* in, const int (&brow)
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[t], 0, 0, 0);
             acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[t], 0, 0, 0);
         }
-    }
-}
-
-// ReLU of a 32 x 32 accumulator tile (lane: position 32 t + (l & 31), channels (r & 3) + 8 (r >> 2) + 4 (l >> 5)) split into
-// the three planes of the position's row: four runs of four consecutive channels, one 8-byte store per run and plane
-__device__ __forceinline__ void store_planes(__bf16* row, const f32x16& acc, int half) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        bf16x4 h, m, l;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float v = acc[4 * q + r] > 0.0f ? acc[4 * q + r] : 0.0f;
-            __bf16 a, b, c;
-            split3(v, a, b, c);
-            h[r] = a;
-            m[r] = b;
-            l[r] = c;
-        }
-        __bf16* dst = row + 8 * q + 4 * half;
-        *reinterpret_cast<bf16x4*>(dst) = h;
-        *reinterpret_cast<bf16x4*>(dst + 32) = m;
-        *reinterpret_cast<bf16x4*>(dst + 64) = l;
     }
 }
 
@@ -163,7 +137,7 @@ __global__ __launch_bounds__(256, 1) void k_vn_conv_x3(const float* __restrict__
 #pragma unroll
             for (int st = 0; st < 5; ++st)
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[st], x0[base + koff1[st]], acc, 0, 0, 0);
-            if (p < 144) store_planes(a1 + p * X3_ROW, acc, half);
+            if (p < 144) store_planes<Relu>(a1 + p * X3_ROW, acc, half);
         }
         lds_fence();
         // ---- conv2: 96 positions = 3 tiles ----
@@ -176,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void k_vn_conv_x3(const float* __restrict__
             conv_x3_mfma<3>(a1, brow2, W2, acc);
             lds_fence();   // a2 overlays a1: every read of a1 is complete before the first write
 #pragma unroll
-            for (int t = 0; t < 3; ++t) store_planes(a2 + (32 * t + l31) * X3_ROW, acc[t], half);
+            for (int t = 0; t < 3; ++t) store_planes<Relu>(a2 + (32 * t + l31) * X3_ROW, acc[t], half);
         }
         lds_fence();
         // ---- conv3: 56 positions = 2 tiles (the last 8 lanes of tile 1 are padding), fp32 out in k_vn_conv's layout ----

@@ -8,11 +8,11 @@ reference's own fp32 error against an fp64 forward plus 4 ulp of the largest out
 tests/test_gpu_heads_accuracy.py).  Back ends:
   * "hip"        — tm_valuenet_forward: hand-written gfx950 kernels (fp32 MFMA), bit-identical to
                    oracle/valuenet_oracle.c's fma chains;
-  * "hip_bf16x3" — tm_valuenet_forward_x3: conv2 / conv3 on the bf16 matrix cores with every operand split into
-                   three bf16 planes (six plane products, fp32 accumulation), the rest as
-                   "hip": the same accuracy contract (for operands of magnitude 2^-110 and above: planes below
-                   bf16's normal range are lost, DESIGN.md section 4), not bit-equal to "hip" (opt-in);
-                   with fc1="bf16x3" fc1 is split the same way (tm_valuenet_forward_x3f, k_vn_fc1_x3: opt-in, for
+  * "hip_bf16x3" — tm_valuenet_forward under TM_VALUENET_BF16X3: conv2 / conv3 on the bf16 matrix cores with every
+                   operand split into three bf16 planes (six plane products, fp32 accumulation; DESIGN.md section
+                   3.3), the rest as "hip": the same accuracy contract (for operands of magnitude 2^-110 and above:
+                   planes below bf16's normal range are lost, DESIGN.md section 4), not bit-equal to "hip" (opt-in);
+                   with fc1="bf16x3" fc1 is split the same way (TM_VALUENET_FC1_BF16X3, k_vn_fc1_x3: opt-in, for
                    the leaf-parallel kinds; fc1="fp32", the default, keeps k_vn_fc1);
   * "torch"      — PyTorch-ROCm ops (MIOpen / rocBLAS), used for training and as a cross-check.
 """
@@ -27,12 +27,14 @@ from . import _lib
 from .store import _p, _stream
 
 SCRATCH_MFMA = 2064     # TM_VALUENET_SCRATCH_MFMA (include/tetris_mcts_hip.h): floats of scratch per state (no initial contents required)
-PREPARED = 477184       # TM_VALUENET_PREPARED: floats of tm_valuenet_prepare's operand streams
-PREPARED_X3 = 27648     # TM_VALUENET_PREPARED_X3: floats of tm_valuenet_prepare_x3's bf16 planes
+# tm_valuenet_prepare's buffer, in its order (TM_VALUENET_PREPARED_TOTAL): the fp32 operand streams, then under "hip_bf16x3"
+# the convolutions' bf16 planes, then under fc1="bf16x3" fc1's
+PREPARED = 477184       # TM_VALUENET_PREPARED
+PREPARED_X3 = 27648     # TM_VALUENET_PREPARED_X3
+PREPARED_FC1_X3 = 688128    # TM_VALUENET_PREPARED_FC1_X3
 HIP_BACKENDS = ("hip", "hip_bf16x3")    # the backends the native search loop (search.hip) runs
-VALUENET_BACKEND = {"hip": 0, "hip_bf16x3": 1}      # TM_VALUENET_FP32 / TM_VALUENET_BF16X3 (tm_search_set_valuenet)
-PREPARED_FC1_X3 = 688128    # TM_VALUENET_PREPARED_FC1_X3: floats of tm_valuenet_prepare_fc1_x3's bf16 planes
-VALUENET_FC1 = {"fp32": 0, "bf16x3": 1}             # TM_VALUENET_FC1_FP32 / TM_VALUENET_FC1_BF16X3 (tm_search_set_valuenet_fc1)
+VALUENET_BACKEND = {"hip": 0, "hip_bf16x3": 1}      # TM_VALUENET_FP32 / TM_VALUENET_BF16X3 (the C ABI's `backend`)
+VALUENET_FC1 = {"fp32": 0, "bf16x3": 1}             # TM_VALUENET_FC1_FP32 / TM_VALUENET_FC1_BF16X3 (the C ABI's `fc1`)
 PARAM_ORDER = ["head.conv1.weight", "head.conv1.bias", "head.conv2.weight", "head.conv2.bias", "head.conv3.weight",
                "head.conv3.bias", "head.fc1.weight", "head.fc1.bias", "head.fc_out.weight", "head.fc_out.bias",
                "out_ubound", "out_lbound"]
@@ -67,8 +69,59 @@ class Net(nn.Module):
         return self.head(x) * self.out_ubound + self.out_lbound
 
 
-class Model_VV:
+class _HipHead:
+    """What Model_VV and Model_Dist share towards the C ABI: the flat parameter blob, the prepared buffer of the mode and the
+    scratch rows.  A subclass names PARAM_ORDER, SCRATCH_ROW (floats of scratch per state) and PREPARE (its prepare entry
+    point), and gives _mode(), the (backend[, fc1]) arguments of its entry points, and _prepared_floats(), the size of that
+    mode's prepared buffer."""
+
+    def weights_changed(self):
+        """call after the parameters were written (an optimiser step, load_state_dict): the blob and the prepared buffer -
+        operand streams and planes live in the one buffer - are rebuilt"""
+        self._flat = self._prepared = None
+
+    def flat_params(self):
+        if self._flat is None:
+            sd = self.model.state_dict()
+            self._flat = torch.cat([sd[k].detach().reshape(-1).float() for k in self.PARAM_ORDER]).contiguous()
+        return self._flat
+
+    def set_flat_params(self, flat):
+        """flat: the parameters in PARAM_ORDER (478342 floats for the value net, TM_DISTNET_PARAMS(atoms) for the head)"""
+        sd = self.model.state_dict()
+        off = 0
+        flat = torch.as_tensor(flat, dtype=torch.float32)
+        for k in self.PARAM_ORDER:
+            n = sd[k].numel()
+            sd[k].copy_(flat[off:off + n].reshape(sd[k].shape))
+            off += n
+        assert off == flat.numel()
+        self.weights_changed()
+
+    def _ensure_scratch(self, n):
+        if self._scratch is None or self._scratch.shape[0] < n or self._scratch.shape[1] < self.SCRATCH_ROW:
+            self._scratch = torch.zeros(n, self.SCRATCH_ROW, dtype=torch.float32, device=self.device)
+        return self._scratch
+
+    def _ensure_prepared(self):
+        """the mode's one buffer, one prepare call; a buffer prepared for a larger mode serves (the parts are prefixes)"""
+        total = self._prepared_floats()
+        if self._prepared is None or self._prepared.numel() < total:
+            prep = torch.empty(total, dtype=torch.float32, device=self.device)
+            _lib.check(getattr(_lib.lib(), self.PREPARE)(_p(self.flat_params()), _p(prep), *self._mode(), _stream()), self.PREPARE)
+            self._prepared = prep
+        return self._prepared
+
+    @torch.no_grad()
+    def hip_buffers(self, n_states):
+        """(params, the mode's prepared buffer, scratch for n_states) as ctypes pointers for the C ABI (search.hip)"""
+        scratch = self._ensure_scratch(n_states)      # (allocated first, then the blob, then the prepared buffer)
+        return _p(self.flat_params()), _p(self._ensure_prepared()), _p(scratch)
+
+
+class Model_VV(_HipHead):
     """Inference-side mirror of the reference's Model_VV (load / inference / training(False))."""
+    PARAM_ORDER, SCRATCH_ROW, PREPARE = PARAM_ORDER, SCRATCH_MFMA, "tm_valuenet_prepare"
 
     def __init__(self, backend="hip", device="cuda", seed=None, fc1="fp32", **kwargs):
         if fc1 not in VALUENET_FC1:
@@ -81,14 +134,24 @@ class Model_VV:
         self.device = torch.device(device)
         self.model = Net().to(self.device).eval()
         self.backend = backend
-        self._flat = None
-        self._prepared = None
-        self.weights_epoch = next_weights_epoch()
+        self.weights_changed()
         self._scratch = None         # "hip": rows of SCRATCH_MFMA floats (k_vn_fc1's per-tile counters live in their padding; every evaluation clears them)
         self._scratch_plain = None   # "hip_plain": its own buffer - never handed to the matrix-core kernels
 
     def training(self, mode=True):
         self.model.train(mode)
+
+    def _mode(self):
+        # ("torch", "hip_plain": the fp32 kernels, as inference_requests and hip_buffers always ran there)
+        return VALUENET_BACKEND.get(self.backend, 0), VALUENET_FC1[self.fc1]
+
+    def _prepared_floats(self):
+        return PREPARED + (PREPARED_X3 if self.backend == "hip_bf16x3" else 0) + (PREPARED_FC1_X3 if self.fc1 == "bf16x3" else 0)
+
+    def weights_changed(self):
+        """... and the tree engine's per-observation outputs filed under the old weights are not used"""
+        super().weights_changed()
+        self.weights_epoch = next_weights_epoch()
 
     # ---- training side (model/model.py:97-249, model_vv.py:125-134,227-231) ----
     def _optimizer(self):
@@ -124,9 +187,7 @@ class Model_VV:
             self.model.load_state_dict(best["model"])
         res = T.train_data(self.model, self._optimizer(), data, save=save, load=load, **kwargs)
         self.model.eval()
-        self._flat = None
-        self._prepared = None
-        self.weights_epoch = next_weights_epoch()
+        self.weights_changed()
         return res
 
     def load(self, filename=EXP_PATH + "model_checkpoint", verbose=True):
@@ -144,9 +205,7 @@ class Model_VV:
                           % (filename, e), file=stderr, flush=True)
         elif verbose:
             print("Checkpoint not found, using default model", flush=True)
-        self._flat = None
-        self._prepared = None
-        self.weights_epoch = next_weights_epoch()
+        self.weights_changed()
 
     def save(self, filename=EXP_PATH + "model_checkpoint", verbose=True):
         if verbose:
@@ -156,25 +215,6 @@ class Model_VV:
         torch.save({"model_state_dict": self.model.state_dict(), "optimizer_state_dict": self._optimizer().state_dict()},
                    filename)
 
-    def set_flat_params(self, flat):
-        """flat: 478342 floats in PARAM_ORDER (tests/golden/ref_valuenet.npz 'params')."""
-        sd = self.model.state_dict()
-        off = 0
-        flat = torch.as_tensor(flat, dtype=torch.float32)
-        for k in PARAM_ORDER:
-            n = sd[k].numel()
-            sd[k].copy_(flat[off:off + n].reshape(sd[k].shape))
-            off += n
-        self._flat = None
-        self._prepared = None
-        self.weights_epoch = next_weights_epoch()
-
-    def flat_params(self):
-        if self._flat is None:
-            sd = self.model.state_dict()
-            self._flat = torch.cat([sd[k].detach().reshape(-1).float() for k in PARAM_ORDER]).contiguous()
-        return self._flat
-
     @torch.no_grad()
     def inference_device(self, states, v_out=None, var_out=None):
         """states: int8 [B,200] (or [B,20,10]) on the device -> (v[B], var[B]) float32 device tensors."""
@@ -182,26 +222,10 @@ class Model_VV:
         if v_out is None:
             v_out = torch.empty(B, dtype=torch.float32, device=self.device)
             var_out = torch.empty(B, dtype=torch.float32, device=self.device)
-        if self.backend == "hip":
-            if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[1] < SCRATCH_MFMA:
-                self._scratch = torch.zeros(B, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
-            P = self.flat_params()
-            if self._prepared is None:
-                self._prepared = torch.empty(477184, dtype=torch.float32, device=self.device)
-                _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(self._prepared), _stream()), "tm_valuenet_prepare")
-            _lib.check(_lib.lib().tm_valuenet_forward(_p(P), _p(self._prepared), _p(states), B, _p(v_out), _p(var_out),
-                                                      _p(self._scratch), _stream()), "tm_valuenet_forward")
-        elif self.backend == "hip_bf16x3":
-            if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[1] < SCRATCH_MFMA:
-                self._scratch = torch.zeros(B, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
-            P, prep = self.flat_params(), self._prepared_x3()
-            if self.fc1 == "bf16x3":
-                _lib.check(_lib.lib().tm_valuenet_forward_x3f(_p(P), _p(prep), _p(prep[PREPARED:]),
-                                                              _p(prep[PREPARED + PREPARED_X3:]), _p(states), B, _p(v_out),
-                                                              _p(var_out), _p(self._scratch), _stream()), "tm_valuenet_forward_x3f")
-            else:
-                _lib.check(_lib.lib().tm_valuenet_forward_x3(_p(P), _p(prep), _p(prep[PREPARED:]), _p(states), B, _p(v_out),
-                                                             _p(var_out), _p(self._scratch), _stream()), "tm_valuenet_forward_x3")
+        if self.backend in HIP_BACKENDS:
+            P, prep, scr = self.hip_buffers(B)
+            _lib.check(_lib.lib().tm_valuenet_forward(P, prep, *self._mode(), _p(states), B, _p(v_out), _p(var_out), scr,
+                                                      _stream()), "tm_valuenet_forward")
         elif self.backend == "hip_plain":
             if self._scratch_plain is None or self._scratch_plain.shape[0] < B:
                 self._scratch_plain = torch.empty(B, 9728, dtype=torch.float32, device=self.device)
@@ -213,63 +237,12 @@ class Model_VV:
             var_out.copy_(out[:, 1])
         return v_out, var_out
 
-    def _prepared_x3(self):
-        """"hip_bf16x3": one buffer of PREPARED + PREPARED_X3 floats, tm_valuenet_prepare's operand streams (fc1 runs on them)
-        followed by tm_valuenet_prepare_x3's planes - the layout tm_search_run takes under TM_VALUENET_BF16X3.  It lives in
-        _prepared, so everything that invalidates the fp32 streams (set_flat_params, load, train_data) invalidates the planes.
-        fc1="bf16x3": PREPARED_FC1_X3 more floats behind them, tm_valuenet_prepare_fc1_x3's planes of fc1
-        (tm_search_set_valuenet_fc1's layout)."""
-        if self._prepared is None:
-            P = self.flat_params()
-            x3f = self.fc1 == "bf16x3"
-            prep = torch.empty(PREPARED + PREPARED_X3 + (PREPARED_FC1_X3 if x3f else 0), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(prep), _stream()), "tm_valuenet_prepare")
-            _lib.check(_lib.lib().tm_valuenet_prepare_x3(_p(P), _p(prep[PREPARED:]), _stream()), "tm_valuenet_prepare_x3")
-            if x3f:
-                _lib.check(_lib.lib().tm_valuenet_prepare_fc1_x3(_p(P), _p(prep[PREPARED + PREPARED_X3:]), _stream()),
-                           "tm_valuenet_prepare_fc1_x3")
-            self._prepared = prep
-        return self._prepared
-
-    @torch.no_grad()
-    def hip_buffers(self, n_states):
-        """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip); for
-        "hip_bf16x3" the prepared buffer holds the planes behind the streams (tm_search_set_valuenet), and fc1's planes behind
-        those under fc1="bf16x3" (tm_search_set_valuenet_fc1)."""
-        if self._scratch is None or self._scratch.shape[0] < n_states or self._scratch.shape[1] < SCRATCH_MFMA:
-            self._scratch = torch.zeros(n_states, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
-        P = self.flat_params()
-        if self.backend == "hip_bf16x3":
-            return _p(P), _p(self._prepared_x3()), _p(self._scratch)
-        if self._prepared is None:
-            self._prepared = torch.empty(477184, dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(self._prepared), _stream()), "tm_valuenet_prepare")
-        return _p(P), _p(self._prepared), _p(self._scratch)
-
     @torch.no_grad()
     def inference_requests(self, store):
-        """Evaluate a TreeStore's pending leaf requests in place (fused render + forward, HIP back end only)."""
-        import ctypes as C
-        B = store.n_games * store.eval_slots
-        if self._scratch is None or self._scratch.shape[0] < B or self._scratch.shape[1] < SCRATCH_MFMA:
-            self._scratch = torch.zeros(B, SCRATCH_MFMA, dtype=torch.float32, device=self.device)
-        P = self.flat_params()
-        if self.backend == "hip_bf16x3":
-            prep = self._prepared_x3()
-            if self.fc1 == "bf16x3":
-                _lib.check(_lib.lib().tm_valuenet_forward_requests_x3f(_p(P), _p(prep), _p(prep[PREPARED:]),
-                                                                       _p(prep[PREPARED + PREPARED_X3:]), C.byref(store.s),
-                                                                       _p(self._scratch), _stream()),
-                           "tm_valuenet_forward_requests_x3f")
-                return
-            _lib.check(_lib.lib().tm_valuenet_forward_requests_x3(_p(P), _p(prep), _p(prep[PREPARED:]), C.byref(store.s),
-                                                                  _p(self._scratch), _stream()), "tm_valuenet_forward_requests_x3")
-            return
-        if self._prepared is None:
-            self._prepared = torch.empty(477184, dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().tm_valuenet_prepare(_p(P), _p(self._prepared), _stream()), "tm_valuenet_prepare")
-        _lib.check(_lib.lib().tm_valuenet_forward_requests(_p(P), _p(self._prepared), C.byref(store.s),
-                                                           _p(self._scratch), _stream()), "tm_valuenet_forward_requests")
+        """Evaluate a TreeStore's pending leaf requests in place (fused render + forward, HIP back ends only)."""
+        P, prep, scr = self.hip_buffers(store.n_games * store.eval_slots)
+        _lib.check(_lib.lib().tm_valuenet_forward_requests(P, prep, *self._mode(), C.byref(store.s), scr, _stream()),
+                   "tm_valuenet_forward_requests")
 
     def inference(self, batch):
         """Reference signature (model_vv.py:210-217): float array [B,1,20,10] -> [v[B,1], var[B,1]] numpy."""

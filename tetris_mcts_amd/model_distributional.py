@@ -12,16 +12,21 @@ model_distributional.py:27).  Same module names, so `state_dict`s are interchang
                    fp32 error against an fp64 forward (DESIGN.md section 6), not bit-equal to "hip" (opt-in);
   * "torch"      - PyTorch-ROCm ops (MIOpen / rocBLAS): training (`loss`) and a cross-check.
 The distribution arithmetic around it is in csrc/tree.hip (wave_dist_front / wave_dist_back)."""
+import ctypes as C
 from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
+from .model import VALUENET_BACKEND, _HipHead
+from .store import _p, _stream
+
 PARAM_ORDER = ["seq.conv1.weight", "seq.conv1.bias", "seq.conv2.weight", "seq.conv2.bias", "seq.fc1.weight", "seq.fc1.bias",
                "seq.fc_v.weight", "seq.fc_v.bias"]
-PREPARED = 278528       # TM_DISTNET_PREPARED
-PREPARED_X3 = 24576     # TM_DISTNET_PREPARED_X3: floats of tm_distnet_prepare_x3's bf16 planes
+PREPARED = 278528       # TM_DISTNET_PREPARED: tm_distnet_prepare's fp32 operand streams
+PREPARED_X3 = 24576     # TM_DISTNET_PREPARED_X3: conv2's bf16 planes behind them under "hip_bf16x3"
 HIP_BACKENDS = ("hip", "hip_bf16x3")    # the backends the native search loop (search.hip) runs
 SCRATCH = 2048          # TM_DISTNET_SCRATCH
 ROW = 64                # TM_DIST_ROW
@@ -52,9 +57,10 @@ class Net(nn.Module):
         return F.log_softmax(self.seq(x), 1)
 
 
-class Model_Dist:
+class Model_Dist(_HipHead):
     """inference(batch [B,1,22,10]) -> [dist [B, atoms]] (model_distributional.py:100-107); loss = the cross entropy
     against a target distribution, -value * (log p - log value) summed over atoms (model_distributional.py:86-98)."""
+    PARAM_ORDER, SCRATCH_ROW, PREPARE = PARAM_ORDER, SCRATCH, "tm_distnet_prepare"
 
     def __init__(self, atoms=50, device=None, seed=None, backend=None):
         if seed is not None:
@@ -70,79 +76,24 @@ class Model_Dist:
     def training(self, mode=True):
         self.model.train(mode)
 
-    def weights_changed(self):
-        """call after the parameters were written (an optimiser step, load_state_dict): the HIP operand streams (and the
-        "hip_bf16x3" planes, which live in the same buffer) are rebuilt"""
-        self._flat = self._prepared = None
+    def _mode(self):
+        return (VALUENET_BACKEND.get(self.backend, 0),)      # ("torch": the fp32 kernels, as before)
 
-    def flat_params(self):
-        if self._flat is None:
-            sd = self.model.state_dict()
-            self._flat = torch.cat([sd[k].detach().reshape(-1).float() for k in PARAM_ORDER]).contiguous()
-        return self._flat
-
-    def set_flat_params(self, flat):
-        """flat: TM_DISTNET_PARAMS(atoms) floats in PARAM_ORDER"""
-        sd = self.model.state_dict()
-        off = 0
-        flat = torch.as_tensor(flat, dtype=torch.float32)
-        for k in PARAM_ORDER:
-            n = sd[k].numel()
-            sd[k].copy_(flat[off:off + n].reshape(sd[k].shape))
-            off += n
-        assert off == flat.numel()
-        self.weights_changed()
-
-    def _prepared_x3(self):
-        """"hip_bf16x3": one buffer of PREPARED + PREPARED_X3 floats, tm_distnet_prepare's operand streams (fc1 runs on them)
-        followed by tm_distnet_prepare_x3's planes - the layout tm_search_run takes under TM_VALUENET_BF16X3.  It lives in
-        _prepared, so everything that invalidates the fp32 streams (weights_changed) invalidates the planes."""
-        from . import _lib
-        from .store import _p, _stream
-        if self._prepared is None or self._prepared.numel() < PREPARED + PREPARED_X3:
-            P = self.flat_params()
-            prep = torch.empty(PREPARED + PREPARED_X3, dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().tm_distnet_prepare(_p(P), _p(prep), _stream()), "tm_distnet_prepare")
-            _lib.check(_lib.lib().tm_distnet_prepare_x3(_p(P), _p(prep[PREPARED:]), _stream()), "tm_distnet_prepare_x3")
-            self._prepared = prep
-        return self._prepared
-
-    @torch.no_grad()
-    def hip_buffers(self, n_states):
-        """(params, prepared operand streams, scratch for n_states) as ctypes pointers for the C ABI (search.hip); for
-        "hip_bf16x3" the prepared buffer holds the planes behind the streams (tm_search_set_valuenet)."""
-        from . import _lib
-        from .store import _p, _stream
-        if self._scratch is None or self._scratch.shape[0] < n_states:
-            self._scratch = torch.empty(n_states, SCRATCH, dtype=torch.float32, device=self.device)
-        P = self.flat_params()
-        if self.backend == "hip_bf16x3":
-            return _p(P), _p(self._prepared_x3()), _p(self._scratch)
-        if self._prepared is None:
-            self._prepared = torch.empty(PREPARED, dtype=torch.float32, device=self.device)
-            _lib.check(_lib.lib().tm_distnet_prepare(_p(P), _p(self._prepared), _stream()), "tm_distnet_prepare")
-        return _p(P), _p(self._prepared), _p(self._scratch)
+    def _prepared_floats(self):
+        return PREPARED + (PREPARED_X3 if self.backend == "hip_bf16x3" else 0)
 
     @torch.no_grad()
     def inference_device(self, states, out=None):
         """states: int8 [B,200] (or [B,20,10]) on the device, the 20 visible rows -> float32 [B, 64] (atoms first, zero padded
         rows are NOT guaranteed: only [:, :atoms] is written)."""
-        from . import _lib
-        from .store import _p, _stream
         B = states.shape[0]
         if out is None:
             out = torch.zeros(B, ROW, dtype=torch.float32, device=self.device)
-        if self.backend == "hip":
+        if self.backend in HIP_BACKENDS:
             P, prep, scr = self.hip_buffers(B)
             st = states.reshape(B, 200).to(torch.int8).contiguous()
-            _lib.check(_lib.lib().tm_distnet_forward(P, prep, _p(st), B, self.atoms, _p(out), out.stride(0), scr, _stream()),
-                       "tm_distnet_forward")
-        elif self.backend == "hip_bf16x3":
-            P, _, scr = self.hip_buffers(B)
-            prep = self._prepared_x3()
-            st = states.reshape(B, 200).to(torch.int8).contiguous()
-            _lib.check(_lib.lib().tm_distnet_forward_x3(P, _p(prep), _p(prep[PREPARED:]), _p(st), B, self.atoms, _p(out),
-                                                        out.stride(0), scr, _stream()), "tm_distnet_forward_x3")
+            _lib.check(_lib.lib().tm_distnet_forward(P, prep, *self._mode(), _p(st), B, self.atoms, _p(out), out.stride(0), scr,
+                                                     _stream()), "tm_distnet_forward")
         else:
             x = torch.zeros(B, 1, 22, 10, dtype=torch.float32, device=self.device)
             x[:, 0, 2:, :] = states.reshape(B, 20, 10).float()   # the reference's net sees 22 rows (model_distributional.py:27)
@@ -152,16 +103,9 @@ class Model_Dist:
     @torch.no_grad()
     def inference_requests(self, store):
         """Evaluate a TreeStore's pending leaf requests into its eval_dist (fused render + forward, HIP back ends only)."""
-        import ctypes as C
-        from . import _lib
-        from .store import _p, _stream
         P, prep, scr = self.hip_buffers(store.n_games)
-        if self.backend == "hip_bf16x3":
-            prep = self._prepared_x3()
-            _lib.check(_lib.lib().tm_distnet_forward_requests_x3(P, _p(prep), _p(prep[PREPARED:]), C.byref(store.s), scr,
-                                                                 _stream()), "tm_distnet_forward_requests_x3")
-            return
-        _lib.check(_lib.lib().tm_distnet_forward_requests(P, prep, C.byref(store.s), scr, _stream()), "tm_distnet_forward_requests")
+        _lib.check(_lib.lib().tm_distnet_forward_requests(P, prep, *self._mode(), C.byref(store.s), scr, _stream()),
+                   "tm_distnet_forward_requests")
 
     @torch.no_grad()
     def inference(self, batch):

@@ -198,14 +198,10 @@ class TreeStore:
             P, prep, scr = model.hip_buffers(self.n_games * self.eval_slots)
             # the version of the weights the evaluator runs on: what was filed per observation under another one is not used
             self.L.tm_search_set_epoch(h, int(getattr(model, "weights_epoch", 0)))
-            # the evaluator's backend, the value net's or the distributional head's (TM_VALUENET_FP32 / TM_VALUENET_BF16X3)
-            _lib.check(self.L.tm_search_set_valuenet(h, 1 if getattr(model, "backend", "hip") == "hip_bf16x3" else 0),
+            # the evaluator's mode, the value net's (backend, fc1) or the distributional head's backend (it has no fc1 option)
+            _lib.check(self.L.tm_search_set_valuenet(h, 1 if getattr(model, "backend", "hip") == "hip_bf16x3" else 0,
+                                                     1 if getattr(model, "fc1", "fp32") == "bf16x3" else 0),
                        "tm_search_set_valuenet")
-            # fc1 of the value net's split-precision backend (TM_VALUENET_FC1_FP32 / TM_VALUENET_FC1_BF16X3); the distributional
-            # head has no such option
-            if self.kind != KIND_DIST:
-                _lib.check(self.L.tm_search_set_valuenet_fc1(h, 1 if getattr(model, "fc1", "fp32") == "bf16x3" else 0),
-                           "tm_search_set_valuenet_fc1")
         _lib.check(self.L.tm_search_run(h, int(sims), P, prep, scr, _stream()), "tm_search_run")
 
     def search_stats(self, n_sub=1, ev_every=0, reset=True):
