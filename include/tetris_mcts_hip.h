@@ -283,12 +283,36 @@ int tm_gc_step(const tm_store *s, void *stream);
                                 visit (core.h:341-350; agent.cpp:536-545: and not finished); TM_KIND_VALUESIM / TM_KIND_CPPAGENT:
                                 not a leaf whose observation was evaluated under the current weights (s->obs_eval).  Results
                                 are identical either way; a Python evaluator callable keeps receiving all k children
-                                (agent.cpp:424-436), so the Python-driven loop does not set it */
+                                (agent.cpp:424-436), so the Python-driven loop sets it only where the caller promises a pure
+                                evaluator (TreeAgent's evaluator_pure) */
 #define TM_SIM_GC_MEM_MARKS 16 /* the collector workgroups keep their mark bitmaps in memory whatever the pool's size (the form pools of
                                   more than 100 000 nodes take, tree.hip gc_marks_in_lds); set by tm_sim_step / tm_gc_step themselves when
                                   TM_GC_MARKS_IN_MEMORY=1 is in the environment (tests) */
 int tm_sim_step(const tm_store *s, int flags, void *stream);
 int tm_eval_render(const tm_store *s, int8_t *out /* [G*eval_slots][200] */, void *stream);
+/* Dense requests for an evaluator the engine does not own (eval_requests.hip): instead of rendering every slot, hand the
+ * evaluator the posted ones only and put its rows back.  The REQUESTS of *s are the slots j in [0, n_games * eval_slots) with
+ * eval_obs[j] != 0, in ascending j; R = their number.  (eval_obs, not eval_list: the order is the same from run to run and the
+ * call does not depend on eval_parity.)  *s may be a tm_store_slice: slots are relative to it.
+ * tm_eval_gather, n = min(R, cap): for p < n, slots[p] = the p-th request and states[p] = the 200 bytes the render call above
+ * writes for that slot (TM_KIND_DIST: the node's observation, packed from node_game); with m = min(cap, ceil(n / pad) * pad),
+ * rows n <= p < m are all-zero states with slots[p] = -1, so the evaluator sees few distinct batch shapes; count[0] = R,
+ * count[1] = n; nothing at or beyond row m is written.  R > cap is no error: the caller sees it in count.  A request whose index
+ * lies outside the pool (no launch posts one) is listed and its row written as zeros.  states: 4-byte aligned.
+ * tm_eval_scatter: eval_v[slots[p]] = v[p], eval_var[slots[p]] = var[p] for p < count[1]; a slot outside the store is skipped;
+ * nothing else is written.  count is read on the device: the host needs no value to launch it.
+ * tm_eval_scatter_dist (TM_KIND_DIST only): the first dist_bins floats of row p of dist (rows of dist_stride floats) into
+ * eval_dist[slots[p]], nothing else of that row; hipErrorInvalidValue for any other kind and for dist_stride < dist_bins.
+ * All three enqueue on stream; they do not allocate, synchronise or read anything back.  hipErrorInvalidValue, nothing launched,
+ * for a NULL pointer, cap < 1 or pad < 1: checked before the first HIP call, so these answer on a machine without a GPU.
+ * A workgroup of the gather takes TM_EVAL_GATHER_SHARE slots and counts the requests before them itself: no workgroup waits
+ * for another one, no atomic decides the order. */
+#define TM_EVAL_GATHER_SHARE 512
+int tm_eval_gather(const tm_store *s, int cap, int pad, int8_t *states /* [cap][200] */, int32_t *slots /* [cap] */,
+                   int32_t *count /* device int32[2] */, void *stream);
+int tm_eval_scatter(const tm_store *s, const int32_t *slots, const int32_t *count, const float *v, const float *var, void *stream);
+int tm_eval_scatter_dist(const tm_store *s, const int32_t *slots, const int32_t *count, const float *dist, int dist_stride,
+                         void *stream);
 
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel

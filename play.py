@@ -56,6 +56,11 @@ def build_parser():
         'of ValueSim, ValueSimLP and ValueSimC, hip_dist for the distributional head of DistValueSim')
     add('--validation_backend', default='torch', choices=('torch', 'hip'), help='[new] online mode: validation of the fits through '
         'PyTorch (torch) or the forward of the same gfx950 kernels (hip: needs --fit_backend hip or hip_dist)')
+    add('--dense_requests', default=False, action='store_true', help='[new] with --valuenet_backend torch: hand the evaluator the '
+        'posted leaf requests as a dense batch instead of every slot of every game')
+    add('--evaluator_pure', default=False, action='store_true', help='[new] with --valuenet_backend torch: the evaluator is a '
+        'function of the state and the weights alone, so the search posts only the requests its backup will use (ValueSim and '
+        'ValueSimC without leaf parallelism: together with --dense_requests)')
     return p
 
 
@@ -92,6 +97,13 @@ def main(argv=None):
             sys.exit('--valuenet_fc1 applies to ValueSim, ValueSimLP and ValueSimC only (the distributional head has no such option)')
         if args.valuenet_backend != 'hip_bf16x3':
             sys.exit('--valuenet_fc1 bf16x3 needs --valuenet_backend hip_bf16x3')
+    for flag in ('dense_requests', 'evaluator_pure'):
+        if getattr(args, flag) and not (args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim')
+                                        and args.valuenet_backend == 'torch'):
+            sys.exit('--%s applies to the search loop that runs in Python: ValueSim, ValueSimLP, ValueSimC and DistValueSim under '
+                     '--valuenet_backend torch (the native loop of the hip back ends asks only for what it needs already)' % flag)
+    if args.evaluator_pure and not args.dense_requests and args.agent_type == 'ValueSim':
+        sys.exit('--evaluator_pure needs --dense_requests with ValueSim (a leaf answered from the per-observation cache keeps its slot)')
     from importlib import import_module
     from pyTetris import Tetris                       # the reference's own two import lines (play.py:1,81-82)
     _agent_module = import_module('agents.' + args.agent_type)
@@ -111,6 +123,10 @@ def main(argv=None):
         extra['validation_backend'] = args.validation_backend
     elif args.fit_backend != 'torch':
         sys.exit('--fit_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
+    if args.dense_requests:
+        extra['dense_requests'] = True
+    if args.evaluator_pure:
+        extra['evaluator_pure'] = True
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     agent.update_root(game)

@@ -48,6 +48,9 @@ SYMBOLS = {
     "tm_sims_owing": [C.POINTER(TmStore), vp, vp, vp],
     "tm_gc_step": [C.POINTER(TmStore), vp],
     "tm_eval_render": [C.POINTER(TmStore), vp, vp],
+    "tm_eval_gather": [C.POINTER(TmStore), i32, i32, vp, vp, vp, vp],
+    "tm_eval_scatter": [C.POINTER(TmStore), vp, vp, vp, vp, vp],
+    "tm_eval_scatter_dist": [C.POINTER(TmStore), vp, vp, vp, i32, vp],
     "tm_root_stats": [C.POINTER(TmStore), vp, vp, vp],
     "tm_export_game": [C.POINTER(TmStore), i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "tm_core_select_trace_obs": [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp],

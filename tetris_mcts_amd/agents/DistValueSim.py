@@ -87,14 +87,24 @@ class DistValueSim(OnlineFit, TreeAgent):
         if self.evaluator is None and self.model.backend in HIP_BACKENDS:
             self.model.inference_requests(s)                              # nodes rendered inside the convolution kernel
             return
-        states = s.render_eval()                                          # int8 [G, 200]; all zero where nothing is asked
+        if self.dense_requests:
+            states, _, n = s.gather_eval(self.dense_pad)                  # int8 [m, 200]: the pending leaves, then zero boards
+            if n == 0:
+                return
+        else:
+            states = s.render_eval()                                      # int8 [G, 200]; all zero where nothing is asked
+        rows = states.shape[0]
         if self.evaluator is not None:
             d = torch.as_tensor(np.asarray(self.evaluator(states.cpu().numpy().reshape(-1, 20, 10)), np.float32), device=s.device)
         else:
-            x = torch.zeros(self.n_games, 1, 22, 10, dtype=torch.float32, device=s.device)
-            x[:, 0, 2:, :] = states.view(self.n_games, 20, 10).float()   # the reference's net sees 22 rows (model_distributional.py:27)
+            x = torch.zeros(rows, 1, 22, 10, dtype=torch.float32, device=s.device)
+            x[:, 0, 2:, :] = states.view(rows, 20, 10).float()           # the reference's net sees 22 rows (model_distributional.py:27)
             d = self.model.model(x)
-        s.t["eval_dist"][:, :self.atoms].copy_(d.reshape(self.n_games, self.atoms))
+        d = d.reshape(rows, self.atoms)
+        if self.dense_requests:
+            s.scatter_eval_dist(d)
+        else:
+            s.t["eval_dist"][:, :self.atoms].copy_(d)
 
     def get_value(self, node=None):
         """(mean, variance) of the root's distribution (DistValueSimOnline.py:100-109: mean_variance of node_dist)."""

@@ -19,7 +19,9 @@ class ValueSim(OnlineFit, TreeAgent):
         "hip_bf16x3", the split-precision kernels; "torch"), `valuenet_fc1` its fc1 ("fp32", the default; "bf16x3": fc1 split
         as well, with "hip_bf16x3" only - Model_VV refuses any other pairing).  `fit_backend`: how the online fits take their gradients
         (train.train_data: "torch", the default, or "hip", csrc/valuenet_fit.hip).  `validation_backend`: how they validate
-        ("torch", the default, or "hip": the same kernels' forward over the held-out rows; it needs fit_backend="hip")."""
+        ("torch", the default, or "hip": the same kernels' forward over the held-out rows; it needs fit_backend="hip").
+        `evaluator`: a callable, int8 device tensor [B, 200] -> (v[B], var[B]); B is every slot of every game, or, under TreeAgent's
+        `dense_requests`, the posted requests padded to a multiple of `dense_pad`."""
         if fit_backend not in ("torch", "hip"):
             raise ValueError("fit_backend must be 'torch' or 'hip', not %r ('hip_dist' is DistValueSim's)" % (fit_backend,))
         if validation_backend not in ("torch", "hip"):

@@ -39,10 +39,25 @@ class TreeAgent(Agent):
     def __init__(self, sims=100, max_nodes=500000, env=None, env_args=None, node_saver=None, projection=True,
                  min_visits=30, n_games=None, gamma=0.999, online=False, min_visits_to_store=10, replay_cap=0,
                  max_trace=1024, nq_size=1 << 20, reset_on_pool_exhaustion=True, n_sub=1, ev_every=0,
-                 gc_slice_cycles=150000, gc_spec_nodes=None, gc_cost_units=0, gc_collectors=0, **kwargs):
+                 gc_slice_cycles=150000, gc_spec_nodes=None, gc_cost_units=0, gc_collectors=0, dense_requests=False,
+                 dense_pad=256, evaluator_pure=False, **kwargs):
+        """The last three are for the evaluators the engine does not own - a callable, the torch back ends - which the Python loop
+        below drives (where the native loop runs they are accepted and change nothing: it asks only for what it needs already).
+        `dense_requests`: the evaluator is handed the posted requests only, as a dense batch padded to a multiple of `dense_pad`
+        rows with zero boards (store.gather_eval / scatter_eval), instead of every slot of every game.  `evaluator_pure`: the
+        caller's promise that the outputs are a function of the state and of the weights alone; the loop then posts only the
+        requests the backup will use (TM_SIM_EVAL_NEEDED) - tell evaluator_changed() when a callable's weights change."""
         super().__init__(**kwargs)
         if not projection:
             raise NotImplementedError("projection=False is broken in the reference itself (ValueSim.py:73-74)")
+        single_leaf = self.kind in (st.KIND_VALUESIM, st.KIND_CPPAGENT)
+        if evaluator_pure and self.kind in (st.KIND_VANILLA, st.KIND_VANILLA_C):
+            raise ValueError("evaluator_pure: the Vanilla agents have no evaluator (their leaves are rollouts inside the tree kernel)")
+        if int(dense_pad) < 1:
+            raise ValueError("dense_pad must be at least 1")
+        self.dense_requests, self.dense_pad, self.evaluator_pure = bool(dense_requests), int(dense_pad), bool(evaluator_pure)
+        self._epoch_cache = single_leaf        # the kinds whose store keeps obs_eval
+        self._evaluator_epoch = None
         self.sims = sims
         self.max_nodes = max_nodes
         self.env, self.env_args = env, env_args or ((20, 10), 1, 0, 0)
@@ -77,8 +92,30 @@ class TreeAgent(Agent):
         """Evaluate the store's pending leaf requests into eval_v / eval_var.  Default: render the observations
         to int8 [B,200] and call evaluate(); agents with the HIP value net override this with the fused path."""
         s = self.store
+        if self.dense_requests:
+            states, _, n = s.gather_eval(self.dense_pad)
+            if n == 0:
+                return
+            v, var = s.dense_outputs(states.shape[0])
+            self.evaluate(states, v, var)
+            s.scatter_eval(v, var)
+            return
         states = s.render_eval()
         self.evaluate(states, s.t["eval_v"], s.t["eval_var"])
+
+    def evaluator_changed(self):
+        """evaluator_pure with a callable: its outputs are no longer the ones it gave before (new weights): what the tree engine
+        filed per observation is not used again"""
+        from ..model import next_weights_epoch
+        self._evaluator_epoch = next_weights_epoch()
+
+    def _eval_epoch(self):
+        """the version of the evaluator's weights: the built-in model's, or this agent's own count for a callable"""
+        if getattr(self, "evaluator", None) is None and hasattr(getattr(self, "model", None), "weights_epoch"):
+            return int(self.model.weights_epoch)
+        if self._evaluator_epoch is None:
+            self.evaluator_changed()
+        return self._evaluator_epoch
 
     def search_model(self):
         """The model whose HIP value net the native launch loop (search.hip) evaluates leaves with; False = this agent's
@@ -95,6 +132,15 @@ class TreeAgent(Agent):
             s.search(sims, model, n_sub=self.n_sub, ev_every=self.ev_every)
             return
         both = st.SIM_BACKUP | st.SIM_FRONT
+        if self.evaluator_pure:
+            both |= st.SIM_EVAL_NEEDED
+            if self._epoch_cache:
+                if not self.dense_requests:
+                    # a leaf answered from the per-observation cache has its outputs put into its slot by the tree kernel; the
+                    # padded path writes every slot, that one too
+                    raise ValueError("evaluator_pure on a single-leaf agent needs dense_requests=True where the Python loop runs "
+                                     "(the padded path overwrites the slot of a leaf answered from the per-observation cache)")
+                s.s.eval_epoch = self._eval_epoch()
         s.move_begin(sims)
         s.sim_step(both)
         todo, first = sims, True

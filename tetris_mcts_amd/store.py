@@ -122,6 +122,7 @@ class TreeStore:
         self.eval_states = torch.zeros(G * eval_slots, 200, dtype=torch.int8, device=dev)
         self._rem = torch.zeros(2, dtype=torch.int32, device=dev)
         self._search = {}
+        self._dense, self._dense_n = None, 0
         _lib.check(self.L.tm_pool_init(C.byref(s), _stream()), "tm_pool_init")
 
     def __del__(self):
@@ -223,6 +224,53 @@ class TreeStore:
     def render_eval(self):
         _lib.check(self.L.tm_eval_render(C.byref(self.s), _p(self.eval_states), _stream()), "tm_eval_render")
         return self.eval_states
+
+    # ---- dense requests for an evaluator the engine does not own (csrc/eval_requests.hip) ----
+    def _dense_buffers(self):
+        """allocated once, at the first gather, for every slot of the store"""
+        if self._dense is None:
+            cap, dev = self.n_games * self.eval_slots, self.device
+            self._dense = dict(states=torch.zeros(cap, 200, dtype=torch.int8, device=dev),
+                               slots=torch.zeros(cap, dtype=torch.int32, device=dev),
+                               count=torch.zeros(2, dtype=torch.int32, device=dev),
+                               v=torch.zeros(cap, dtype=torch.float32, device=dev),
+                               var=torch.zeros(cap, dtype=torch.float32, device=dev))
+        return self._dense
+
+    def gather_eval(self, pad=256):
+        """The pending requests (eval_obs != 0, ascending slot) as a dense batch: (states int8 [m,200], slots int32 [cap], n) -
+        rows [0, n) are the requests' observations, rows [n, m) zero boards with slot -1, m = n rounded up to a multiple of
+        `pad` (at most every slot).  Reading n back is the one host synchronisation of the dense path."""
+        d = self._dense_buffers()
+        cap = d["slots"].numel()
+        _lib.check(self.L.tm_eval_gather(C.byref(self.s), cap, int(pad), _p(d["states"]), _p(d["slots"]), _p(d["count"]),
+                                         _stream()), "tm_eval_gather")
+        n = self._dense_n = int(d["count"].tolist()[1])
+        m = min(cap, -(-n // int(pad)) * int(pad))
+        return d["states"][:m], d["slots"], n
+
+    def dense_outputs(self, m):
+        """two float32 device buffers of m rows for the evaluator's outputs on gather_eval's batch (what scatter_eval takes)"""
+        d = self._dense_buffers()
+        return d["v"][:m], d["var"][:m]
+
+    def scatter_eval(self, v, var):
+        """v, var: float32 device tensors, a row per row of the last gather_eval -> eval_v / eval_var of the requests' slots"""
+        d = self._dense_buffers()
+        v, var = v.contiguous(), var.contiguous()
+        assert v.dtype == var.dtype == torch.float32 and v.is_cuda and var.is_cuda
+        assert min(v.numel(), var.numel()) >= self._dense_n, "the evaluator returned fewer rows than it was given"
+        _lib.check(self.L.tm_eval_scatter(C.byref(self.s), _p(d["slots"]), _p(d["count"]), _p(v), _p(var), _stream()),
+                   "tm_eval_scatter")
+
+    def scatter_eval_dist(self, dist):
+        """dist: float32 device tensor [rows, >= dist_bins], a row per row of the last gather_eval -> eval_dist (TM_KIND_DIST)"""
+        d = self._dense_buffers()
+        dist = dist.contiguous()
+        assert dist.dtype == torch.float32 and dist.is_cuda and dist.dim() == 2
+        assert dist.shape[0] >= self._dense_n, "the evaluator returned fewer rows than it was given"
+        _lib.check(self.L.tm_eval_scatter_dist(C.byref(self.s), _p(d["slots"]), _p(d["count"]), _p(dist), int(dist.shape[1]),
+                                               _stream()), "tm_eval_scatter_dist")
 
     def root_stats(self):
         _lib.check(self.L.tm_root_stats(C.byref(self.s), _p(self.stats_buf), _p(self.action_buf), _stream()),
