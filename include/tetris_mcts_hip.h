@@ -430,6 +430,17 @@ long long tm_valuenet_fit_workspace(int batch);
 int tm_valuenet_fit_grad(const float *params, const float *out_bounds, const int8_t *states, const float *value,
                          const float *variance, const float *weight, const int64_t *idx, int batch, int weighted,
                          float variance_clip, float *grad, float *loss, float *workspace, void *stream);
+/* tm_valuenet_fit_grad on PACKED rows: obs is uint32 [rows][12], 4-byte aligned, the 48-byte observations of ENGINE_SPEC section 7 as the engine
+ * harvests them (words 0..9: two board rows of 16 bits each, bit c of a row its column c; word 10: the four cell codes 10 r + c of
+ * the falling piece; word 11: its low byte non-zero when the game has ended, which leaves no piece).  A cell is -1 where a code
+ * names it, else its locked bit, exactly engine.h obs_cell; the kernels are those of tm_valuenet_fit_grad with the cell read through another
+ * template argument and every later statement unchanged, so the outputs are bit-identical to tm_valuenet_fit_grad's on the rendered rows.
+ * Any 48 bytes are safe to read: nothing taken out of an observation is used as an address - a code is only compared (codes >= 200
+ * name no cell) and bits 10..15 of a row are ignored.  Every other argument, the workspace (tm_valuenet_fit_workspace, unchanged), the
+ * argument checks and the return codes are the int8 twin's; a misaligned obs is hipErrorInvalidValue too. */
+int tm_valuenet_fit_grad_packed(const float *params, const float *out_bounds, const uint32_t *obs, const float *value,
+                                const float *variance, const float *weight, const int64_t *idx, int batch, int weighted,
+                                float variance_clip, float *grad, float *loss, float *workspace, void *stream);
 /* The gradient step of the distributional head's online fit (csrc/distnet_fit.hip): forward of model_distributional.Net,
  * Model_Dist.loss and the gradient of its MEAN with respect to the eight learnable tensors, for the minibatch rows idx[0 .. batch)
  * (idx NULL: rows 0 .. batch-1; repeats allowed; every entry must be a valid row - the caller checks).  params / grad:
@@ -447,6 +458,17 @@ long long tm_distnet_fit_workspace(int batch, int atoms);
 int tm_distnet_fit_grad(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
                         const int64_t *idx, int batch, int atoms, int weighted, float *grad, float *loss, float *workspace,
                         void *stream);
+/* tm_distnet_fit_grad on PACKED rows: obs is uint32 [rows][12], 4-byte aligned, the 48-byte observations of ENGINE_SPEC section 7 as the engine
+ * harvests them (words 0..9: two board rows of 16 bits each, bit c of a row its column c; word 10: the four cell codes 10 r + c of
+ * the falling piece; word 11: its low byte non-zero when the game has ended, which leaves no piece).  A cell is -1 where a code
+ * names it, else its locked bit, exactly engine.h obs_cell; the kernels are those of tm_distnet_fit_grad with the cell read through another
+ * template argument and every later statement unchanged, so the outputs are bit-identical to tm_distnet_fit_grad's on the rendered rows.
+ * Any 48 bytes are safe to read: nothing taken out of an observation is used as an address - a code is only compared (codes >= 200
+ * name no cell) and bits 10..15 of a row are ignored.  Every other argument, the workspace (tm_distnet_fit_workspace, unchanged), the
+ * argument checks and the return codes are the int8 twin's; a misaligned obs is hipErrorInvalidValue too. */
+int tm_distnet_fit_grad_packed(const float *params, const uint32_t *obs, const float *target, int target_stride,
+                               const float *weight, const int64_t *idx, int batch, int atoms, int weighted, float *grad,
+                               float *loss, float *workspace, void *stream);
 /* The validation pass of the value net's online fit (csrc/valuenet_fit.hip): the forward and the per-sample losses of
  * tm_valuenet_fit_grad (the same kernels with idx NULL, the same statements for the loss) over the n held-out rows, reduced per chunk
  * of `chunk` rows to what train.validation_loss collects: rows_out[c] = {w, mean, std} in double for the rows c*chunk up to
@@ -464,6 +486,12 @@ long long tm_valuenet_fit_validate_workspace(int slab);
 int tm_valuenet_fit_validate(const float *params, const float *out_bounds, const int8_t *states, const float *value,
                              const float *variance, const float *weight, long long n, int chunk, int slab, int weighted,
                              float variance_clip, double *rows_out, float *workspace, void *stream);
+/* tm_valuenet_fit_validate on packed rows (obs uint32 [n][12], 4-byte aligned): as tm_valuenet_fit_grad_packed is to its twin - the
+ * same kernels reading the cell from the observation, rows_out bit-identical to the int8 call's on the rendered rows, any 48 bytes
+ * safe to read, every other argument, check and return code unchanged, workspace tm_valuenet_fit_validate_workspace(slab). */
+int tm_valuenet_fit_validate_packed(const float *params, const float *out_bounds, const uint32_t *obs, const float *value,
+                                    const float *variance, const float *weight, long long n, int chunk, int slab, int weighted,
+                                    float variance_clip, double *rows_out, float *workspace, void *stream);
 /* The validation pass of the distributional head's online fit (csrc/distnet_fit.hip): as the value net's above, with the forward and
  * the per-sample losses of tm_distnet_fit_grad.  rows_out[c] = {w, mean, std}: std is the sample standard deviation (n - 1; NaN for
  * a chunk of one row, as torch.std_mean - train's host loop maps it to 0).  params (16-byte aligned), states, target, target_stride,
@@ -474,6 +502,13 @@ long long tm_distnet_fit_validate_workspace(int slab, int atoms);
 int tm_distnet_fit_validate(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
                             long long n, int chunk, int slab, int atoms, int weighted, double *rows_out, float *workspace,
                             void *stream);
+/* tm_distnet_fit_validate on packed rows (obs uint32 [n][12], 4-byte aligned): as tm_distnet_fit_grad_packed is to its twin - the
+ * same kernels reading the cell from the observation, rows_out bit-identical to the int8 call's on the rendered rows (the NaN of a
+ * one-row chunk included), any 48 bytes safe to read, every other argument, check and return code unchanged, workspace
+ * tm_distnet_fit_validate_workspace(slab, atoms). */
+int tm_distnet_fit_validate_packed(const float *params, const uint32_t *obs, const float *target, int target_stride,
+                                   const float *weight, long long n, int chunk, int slab, int atoms, int weighted,
+                                   double *rows_out, float *workspace, void *stream);
 /* value network forward (model/model_vv.py:13-52; Model_VV.inference 210-217): states int8 [n][200] -> v[n], var[n].
  * params: 478342 floats in PyTorch state_dict layouts (order as in oracle/valuenet_oracle.c).
  * It runs in one of three modes (backend, fc1), checked by tm_valuenet_check_mode (host arithmetic only: 0, or

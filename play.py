@@ -56,6 +56,9 @@ def build_parser():
         'of ValueSim, ValueSimLP and ValueSimC, hip_dist for the distributional head of DistValueSim')
     add('--validation_backend', default='torch', choices=('torch', 'hip'), help='[new] online mode: validation of the fits through '
         'PyTorch (torch) or the forward of the same gfx950 kernels (hip: needs --fit_backend hip or hip_dist)')
+    add('--fit_states', default='dense', choices=('dense', 'packed'), help='[new] online mode: what the fits are fed - the harvested '
+        'observations rendered to float boards (dense) or the 48-byte packed observations themselves, read by the gfx950 kernels '
+        '(packed: needs --fit_backend hip or hip_dist and --validation_backend hip)')
     add('--dense_requests', default=False, action='store_true', help='[new] with --valuenet_backend torch: hand the evaluator the '
         'posted leaf requests as a dense batch instead of every slot of every game')
     add('--evaluator_pure', default=False, action='store_true', help='[new] with --valuenet_backend torch: the evaluator is a '
@@ -92,6 +95,9 @@ def main(argv=None):
         sys.exit('--fit_backend hip_dist applies to DistValueSim only')
     if args.validation_backend == 'hip' and args.fit_backend == 'torch':
         sys.exit('--validation_backend hip reads the parameters of a HIP fit: it needs --fit_backend hip or hip_dist')
+    if args.fit_states == 'packed' and not (args.fit_backend != 'torch' and args.validation_backend == 'hip'):
+        sys.exit('--fit_states packed is read by the HIP fit and the HIP validation: it needs --fit_backend hip or hip_dist and '
+                 '--validation_backend hip')
     if args.valuenet_fc1 != 'fp32':
         if args.agent_type not in ('ValueSim', 'ValueSimLP', 'ValueSimC'):
             sys.exit('--valuenet_fc1 applies to ValueSim, ValueSimLP and ValueSimC only (the distributional head has no such option)')
@@ -121,6 +127,8 @@ def main(argv=None):
     if args.agent_type in ('ValueSim', 'ValueSimLP', 'ValueSimC', 'DistValueSim'):
         extra['fit_backend'] = args.fit_backend      # (DistValueSim refuses 'hip' itself)
         extra['validation_backend'] = args.validation_backend
+        if args.fit_states != 'dense':
+            extra['fit_states'] = args.fit_states
     elif args.fit_backend != 'torch':
         sys.exit('--fit_backend applies to ValueSim, ValueSimLP, ValueSimC and DistValueSim only')
     if args.dense_requests:

@@ -33,7 +33,10 @@ ap.add_argument("--load", default=None, help="start from this checkpoint instead
 ap.add_argument("--no-train", action="store_true", help="play only (with --load: the checkpoint's play strength): no harvest, no fits")
 ap.add_argument("--fit_backend", default="torch", choices=("torch", "hip", "hip_dist"), help="gradients of the fits: PyTorch autograd, the HIP kernels of csrc/valuenet_fit.hip (hip: the value net) or of csrc/distnet_fit.hip (hip_dist: --agent DistValueSim only)")
 ap.add_argument("--validation_backend", default="torch", choices=("torch", "hip"), help="validation of the fits: PyTorch, or the forward of the same HIP kernels (hip: needs --fit_backend hip or hip_dist)")
+ap.add_argument("--fit_states", default="dense", choices=("dense", "packed"), help="what the fits are fed: rendered float boards, or the packed observations themselves (packed: needs --fit_backend hip or hip_dist and --validation_backend hip)")
 args = ap.parse_args()
+if args.fit_states == "packed" and not (args.fit_backend != "torch" and args.validation_backend == "hip"):
+    sys.exit("--fit_states packed needs --fit_backend hip or hip_dist and --validation_backend hip")
 if args.validation_backend == "hip" and args.fit_backend == "torch":
     sys.exit("--validation_backend hip needs --fit_backend hip or hip_dist")
 if args.fit_backend == "hip_dist" and not args.agent.startswith("Dist"):
@@ -49,6 +52,8 @@ if args.fit_backend != "torch":
     extra["fit_backend"] = args.fit_backend      # (DistValueSim refuses "hip")
 if args.validation_backend != "torch":
     extra["validation_backend"] = args.validation_backend
+if args.fit_states != "dense":
+    extra["fit_states"] = args.fit_states
 if args.agent.startswith("Dist"):
     from tetris_mcts_amd.model_distributional import Model_Dist
     model = Model_Dist(atoms=50, seed=0, backend="hip")

@@ -62,12 +62,16 @@ SYMBOLS = {
     "tm_adam_step": [vp, vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, f64, i32, vp],
     "tm_distnet_fit_workspace": [i32, i32],  # (returns long long: restype set in lib())
     "tm_distnet_fit_grad": [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "tm_distnet_fit_grad_packed": [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "tm_valuenet_fit_workspace": [i32],      # (returns long long: restype set in lib())
     "tm_valuenet_fit_grad": [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp],
+    "tm_valuenet_fit_grad_packed": [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, vp, vp, vp, vp],
     "tm_valuenet_fit_validate_workspace": [i32],         # (returns long long: restype set in lib())
     "tm_valuenet_fit_validate": [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, C.c_float, vp, vp, vp],
+    "tm_valuenet_fit_validate_packed": [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, C.c_float, vp, vp, vp],
     "tm_distnet_fit_validate_workspace": [i32, i32],     # (returns long long: restype set in lib())
     "tm_distnet_fit_validate": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
+    "tm_distnet_fit_validate_packed": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
     "tm_valuenet_check_mode": [i32, i32],
     "tm_valuenet_prepare": [vp, vp, i32, i32, vp],
     "tm_valuenet_forward": [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],

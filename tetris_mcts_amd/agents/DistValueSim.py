@@ -27,12 +27,14 @@ class DistValueSim(OnlineFit, TreeAgent):
 
     def __init__(self, atoms=50, vmin=0, vmax=5000, max_nodes=100000, model=None, evaluator=None, online=False,
                  min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, valuenet_backend=None, fit_backend="torch",
-                 validation_backend="torch", **kwargs):
+                 validation_backend="torch", fit_states="dense", **kwargs):
         """fit_backend: how train_nodes takes the gradients of the head's fits - "torch" (autograd, torch.optim.Adam) or
         "hip_dist" (csrc/distnet_fit.hip and the fused Adam).  "hip" names the value net's step (csrc/valuenet_fit.hip: the
         Gaussian loss, not this head's) and is refused here.
         validation_backend: how those fits validate - "torch" or "hip" (the same kernels' forward over the held-out rows; it
         needs fit_backend="hip_dist").
+        fit_states: what those fits are fed - "dense" (the harvested observations rendered to [n,1,22,10] floats) or "packed" (the
+        48-byte observations themselves, read by the kernels; it needs fit_backend="hip_dist" and validation_backend="hip").
         valuenet_backend: the Model_Dist backend of the model the agent builds when `model` is None (None: Model_Dist's
         default; "hip", "hip_bf16x3" - the split-precision kernels - or "torch").
         online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
@@ -47,6 +49,7 @@ class DistValueSim(OnlineFit, TreeAgent):
         if validation_backend == "hip" and fit_backend != "hip_dist":
             raise ValueError("DistValueSim: validation_backend='hip' needs fit_backend='hip_dist'")
         self.fit_backend, self.validation_backend = fit_backend, validation_backend
+        self.check_fit_states(fit_states, "hip_dist")
         kwargs.pop("min_visit", None)
         kwargs.pop("gamma", None)                      # the distributional backup does not discount
         self.atoms, self.vrange = int(atoms), (float(vmin), float(vmax))
@@ -137,7 +140,11 @@ class DistValueSim(OnlineFit, TreeAgent):
         from .. import dist as tdist
         return tdist.all_gather_rows(rows[0].view(torch.int32), *rows[1:])
 
-    def _training_set(self, rows):
+    def _packed_set(self, rows):
+        keys, dists, visits = rows
+        return [keys, dists[:, :self.atoms].contiguous(), visits.reshape(-1, 1)]
+
+    def _dense_set(self, rows):
         from .. import dist as tdist
         keys, dists, visits = rows
         states = torch.zeros(keys.shape[0], 1, 22, 10, dtype=torch.float32, device=keys.device)

@@ -14,12 +14,14 @@ class ValueSim(OnlineFit, TreeAgent):
 
     def __init__(self, online=True, memory_size=500000, min_visits_to_store=10, gamma=0.999, memory_growth_rate=5000,
                  max_nodes=100000, model=None, evaluator=None, valuenet_backend="hip", fit_backend="torch",
-                 validation_backend="torch", valuenet_fc1="fp32", **kwargs):
+                 validation_backend="torch", valuenet_fc1="fp32", fit_states="dense", **kwargs):
         """`valuenet_backend`: the Model_VV backend of the model the agent builds when `model` is None ("hip", the default;
         "hip_bf16x3", the split-precision kernels; "torch"), `valuenet_fc1` its fc1 ("fp32", the default; "bf16x3": fc1 split
         as well, with "hip_bf16x3" only - Model_VV refuses any other pairing).  `fit_backend`: how the online fits take their gradients
         (train.train_data: "torch", the default, or "hip", csrc/valuenet_fit.hip).  `validation_backend`: how they validate
         ("torch", the default, or "hip": the same kernels' forward over the held-out rows; it needs fit_backend="hip").
+        `fit_states`: what the fits are fed ("dense", the default: the harvested observations rendered to [n,1,20,10] floats;
+        "packed": the 48-byte observations themselves, read by the kernels - it needs fit_backend="hip" and validation_backend="hip").
         `evaluator`: a callable, int8 device tensor [B, 200] -> (v[B], var[B]); B is every slot of every game, or, under TreeAgent's
         `dense_requests`, the posted requests padded to a multiple of `dense_pad`."""
         if fit_backend not in ("torch", "hip"):
@@ -29,6 +31,7 @@ class ValueSim(OnlineFit, TreeAgent):
         if validation_backend == "hip" and fit_backend != "hip":
             raise ValueError("validation_backend='hip' needs fit_backend='hip'")
         self.fit_backend, self.validation_backend = fit_backend, validation_backend
+        self.check_fit_states(fit_states, "hip")
         kwargs.pop("min_visit", None)  # play.py:89 forwards it; the reference ValueSim ignores it too
         benchmark = kwargs.get("benchmark", False)
         # device-side harvest buffer per game (64 B per tuple); a GC at a 100 000-entry pool frees a few thousand
@@ -95,9 +98,13 @@ class ValueSim(OnlineFit, TreeAgent):
         from .. import dist as tdist
         return tdist.all_gather_tuples(rows[0].view(torch.int32), rows[1])
 
-    def _training_set(self, rows):
+    def _dense_set(self, rows):
         from .. import dist as tdist
         return list(tdist.training_arrays(*rows))
+
+    def _packed_set(self, rows):
+        from .. import dist as tdist
+        return [rows[0]] + list(tdist.training_targets(rows[1]))
 
     def _dump(self, path, data):
         self.dump_training_set(path, *data)

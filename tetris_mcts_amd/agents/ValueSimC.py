@@ -56,7 +56,10 @@ class ValueSimC(ValueSim):
         out = self.memory.absorb(keys, stats, episode, log=lambda msg: print(msg, file=stderr, flush=True))
         if out is None:
             return None
-        state, value, variance, visit = tdist.training_arrays(*out)
+        if self.fit_states == "packed" and self._train_hook is None:      # (a hook is handed rendered states, as ever)
+            state, (value, variance, visit) = out[0], tdist.training_targets(out[1])
+        else:
+            state, value, variance, visit = tdist.training_arrays(*out)
         d_size = int(state.shape[0])
         if self._train_hook is not None:
             res = self._train_hook(state, value, variance, visit, d_size)
@@ -69,10 +72,16 @@ class ValueSimC(ValueSim):
 
     def training(self, state, value, variance, visit, d_size, **train_kwargs):
         """ValueSimC.py:6-14: dump the training set in the reference's np.savez layout, fit, back to inference mode."""
+        import torch
+        from .. import dist as tdist
+        packed = state.dtype == torch.int32      # fit_states="packed": the observations themselves (rendered for the dump alone)
         if self.dump_path:
-            self.dump_training_set(self.dump_path, state[:d_size], value[:d_size], variance[:d_size], visit[:d_size])
+            dense = tdist.render_observations(state[:d_size]) if packed else state[:d_size]
+            self.dump_training_set(self.dump_path, dense, value[:d_size], variance[:d_size], visit[:d_size])
         opts = dict(iters_per_val=100, batch_size=512, max_iters=50000, sample_replacement=True, oversampling=False,
                     fit_backend=self.fit_backend, validation_backend=self.validation_backend)
+        if packed:
+            opts["state_format"] = "packed"
         opts.update(train_kwargs)
         res = self.model.train_data([state[:d_size], value[:d_size], variance[:d_size], visit[:d_size]], **opts)
         self.model.training(False)

@@ -288,14 +288,33 @@ class OnlineFit:
       _drain()             this rank's tuples harvested since the last drain as a tuple of tensors with one row a tuple (the
                            packed observations first); the device buffers are emptied
       _gather(rows)        the rows of all ranks
-      _training_set(rows)  the job's rows -> the list model.train_data takes
-      _dump(path, data)    that list in the agent's np.savez layout (rank 0 writes)
+      _dense_set(rows)     the job's rows -> the list model.train_data takes, the states rendered (dist.render_observations)
+      _packed_set(rows)    the same list with the packed observations as they are in place of the states
+      _dump(path, data)    the dense list in the agent's np.savez layout (rank 0 writes)
     and DUMP_PATH, online, evaluator, model, fit_backend, validation_backend, memory_size, memory_growth_rate, n_trains = 0 and
-    _memory = None (the rows carried over between two looks)."""
+    _memory = None (the rows carried over between two looks).
+
+    fit_states (check_fit_states, called by the agent's constructor): "dense", the default, renders the job's rows before the
+    fit; "packed" hands train_data the gathered observations themselves (state_format="packed": the HIP kernels read the cell
+    out of the 48 bytes), and only a dump renders."""
     # Whether the rows an earlier look moved into _memory ("not enough training data") count towards train_if_collected's
     # min_tuples.  ValueSim counts them, DistValueSim does not: a difference of behaviour between the two agents that is kept
     # as it is.
     COUNT_HELD = False
+    fit_states = "dense"
+
+    def check_fit_states(self, fit_states, hip_fit):
+        """keep `fit_states`; ValueError unless it is "dense", or "packed" with the HIP fit (`hip_fit`: its fit_backend's name)
+        and the HIP validation - what train_data(state_format="packed") needs (fit_backend and validation_backend are set)"""
+        if fit_states not in ("dense", "packed"):
+            raise ValueError("fit_states must be 'dense' or 'packed', not %r" % (fit_states,))
+        if fit_states == "packed" and not (self.fit_backend == hip_fit and self.validation_backend == "hip"):
+            raise ValueError("fit_states='packed' needs fit_backend=%r and validation_backend='hip' (the torch fit and the torch "
+                             "validation read rendered states)" % (hip_fit,))
+        self.fit_states = fit_states
+
+    def _training_set(self, rows):
+        return self._packed_set(rows) if self.fit_states == "packed" else self._dense_set(rows)
 
     def train_if_collected(self, every=1, min_tuples=1, **kwargs):
         """train_nodes() if garbage collections have harvested tuples since the last fit (the reference's remove_nodes ->
@@ -341,11 +360,13 @@ class OnlineFit:
             return None
         print("Enough training data ({} >= {}), proceed to training.".format(d_size, m_size), file=stderr, flush=True)
         data = self._training_set(rows_all)
-        if dump_data:
-            self._dump(dump_path or self.DUMP_PATH, data)
+        if dump_data:      # (the dump keeps its layout: with packed rows the states are rendered for it alone)
+            self._dump(dump_path or self.DUMP_PATH, data if self.fit_states == "dense" else self._dense_set(rows_all))
         self.n_trains += 1
         opts = dict(iters_per_val=100, batch_size=1024, max_iters=50000, fit_backend=self.fit_backend,     # DistValueSimOnline.py:165
                     validation_backend=self.validation_backend)
+        if self.fit_states != "dense":
+            opts["state_format"] = self.fit_states
         opts.update(train_kwargs)
         res = self.model.train_data(data, **opts)
         self.model.training(False)

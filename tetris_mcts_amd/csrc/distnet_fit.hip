@@ -26,6 +26,9 @@
 // The validation pass (tm_distnet_fit_validate) is the same forward (forward(): the same kernels and instantiations, idx NULL) over
 // the held-out rows, a slab at a time, k_df_head<false> for the per-sample losses and k_fit_val_moments<1> for each chunk's
 // {w, mean, n - 1 std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
+//
+// The states come as int8 [rows][200] or as packed observations, uint32 [rows][12] (tm_distnet_fit_grad_packed,
+// tm_distnet_fit_validate_packed), through the template argument SRC of conv1's two kernels, as in valuenet_fit.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -74,11 +77,12 @@ __host__ inline Layout layout(int B) {
 }
 
 // ---- forward convolution 4 x 4: z[co][b, p] = bias[co] + sum_k W[co][k] in[b][ci][(y + ky) IW + x + kx], LeakyReLU ----
-// M = 32 output channels, N = B * OP positions, K = CIN * 16.  CIN == 1: the input is the int8 state of row idx[b] under two
-// empty rows.  ISTR / OSTR: the channel strides of the input and the output.
-template <int CIN, int IH, int IW, int ISTR, int OSTR, int NT>
+// M = 32 output channels, N = B * OP positions, K = CIN * 16.  CIN == 1: the input is the state of row idx[b] under two empty
+// rows, read through SRC (fit_mma.h: int8 cells or a packed observation); a lane's two quads are the board rows ny + half - 2 and
+// ny + half, one strip that it keeps per tile.  ISTR / OSTR: the channel strides of the input and the output.
+template <int CIN, int IH, int IW, int ISTR, int OSTR, int NT, typename SRC = DenseStates>
 __global__ __launch_bounds__(256) void k_df_conv_fwd(const float* __restrict__ W, const float* __restrict__ bias,
-                                                     const float* __restrict__ in, const int8_t* __restrict__ states,
+                                                     const float* __restrict__ in, const typename SRC::elem* __restrict__ states,
                                                      const int64_t* __restrict__ idx, int B, float* __restrict__ out) {
     constexpr int OW = IW - 3, OP = (IH - 3) * OW, K = CIN * 16, KQ = K / 8;
     const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
@@ -87,6 +91,8 @@ __global__ __launch_bounds__(256) void k_df_conv_fwd(const float* __restrict__ W
     bool ok[NT];
     int nb[NT], np[NT], ny[NT], nx[NT];
     size_t base[NT];
+    typename SRC::Strip cells[NT];
+    static_assert(CIN != 1 || K == 16, "CIN == 1: two quads, the rows ny + half - 2 and ny + half of one strip");
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int n = n0 + 32 * t + l31;
@@ -96,7 +102,8 @@ __global__ __launch_bounds__(256) void k_df_conv_fwd(const float* __restrict__ W
         np[t] = p;
         ny[t] = p / OW;
         nx[t] = p - ny[t] * OW;
-        base[t] = CIN == 1 ? row_of(idx, b) * 200 : (size_t)b * (CIN * ISTR) + ny[t] * IW + nx[t];
+        base[t] = (size_t)b * (CIN * ISTR) + ny[t] * IW + nx[t];
+        if constexpr (CIN == 1) cells[t] = SRC::strip(SRC::row(states, row_of(idx, b)), ny[t] + half - 2);
     }
     f32x16 tot[NT], acc[NT];
 #pragma unroll
@@ -118,9 +125,8 @@ __global__ __launch_bounds__(256) void k_df_conv_fwd(const float* __restrict__ W
                 if (CIN == 1) {
                     const int yy = ny[t] + ky - 2;      // row of the 20 visible ones; the two above them are empty
                     if (ok[t] && yy >= 0) {
-                        const int8_t* s = states + base[t] + yy * 10 + nx[t];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = (float)s[r];
+                        for (int r = 0; r < 4; ++r) v[r] = SRC::cell(cells[t], yy, nx[t] + r);
                     }
                 } else if (ok[t]) {
                     const float* s = in + base[t] + ci * ISTR + ky * IW;
@@ -319,10 +325,13 @@ __global__ __launch_bounds__(256) void k_df_conv_bwd_data(const float* __restric
 // ---- convolution weight gradient: part[chunk][co][n = (ci,ky,kx)] = sum over the chunk's SPW samples and the OP positions of
 // dzo[b][co][p] in[b][ci][(y + ky) IW + x + kx].  M = 32, N = CIN * 16 (NT tiles per wave), K = (sample, position); the
 // gradient's channel stride OSTR is a multiple of 8 and holds zeros beyond OP ----
-template <int CIN, int IW, int ISTR, int OW, int OP, int OSTR, int NT>
+// CIN == 1: ain is the state of row idx[b] under two empty rows, read through SRC.  A lane's tap is fixed and the loop walks the
+// positions, so the strip is built per quad of positions (four positions lie in two rows at most) from the row the lane keeps
+// per sample.
+template <int CIN, int IW, int ISTR, int OW, int OP, int OSTR, int NT, typename SRC = DenseStates>
 __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dzo, const float* __restrict__ ain,
-                                                    const int8_t* __restrict__ states, const int64_t* __restrict__ idx, int B,
-                                                    float* __restrict__ part) {
+                                                    const typename SRC::elem* __restrict__ states,
+                                                    const int64_t* __restrict__ idx, int B, float* __restrict__ part) {
     constexpr int KW = CIN * 16, NG = (KW + 32 * NT - 1) / (32 * NT), KQ = OSTR / 8;
     static_assert(OSTR % 8 == 0, "a quad of K stays inside one sample");
     const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
@@ -344,7 +353,9 @@ __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dz
     vf_zero<NT>(tot);
     for (int b = b0; b < b1; ++b) {
         const float* arow = dzo + (size_t)b * (32 * OSTR) + l31 * OSTR + 4 * half;
-        const size_t ibase = CIN == 1 ? row_of(idx, b) * 200 : (size_t)b * (CIN * ISTR);
+        const size_t ibase = (size_t)b * (CIN * ISTR);
+        typename SRC::Row srow;
+        if constexpr (CIN == 1) srow = SRC::row(states, row_of(idx, b));
 #pragma unroll 1
         for (int qc = 0; qc < KQ; qc += CHUNK_QUADS) {
             vf_zero<NT>(acc);
@@ -354,6 +365,12 @@ __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dz
                 if (q < KQ) {
                     const float4 a = *reinterpret_cast<const float4*>(arow + 8 * q);
                     float bv[NT][4];
+                    typename SRC::Strip cells[NT];
+                    if constexpr (CIN == 1) {
+                        static_assert(CIN != 1 || OW >= 4, "a quad of positions lies in two rows at most");
+#pragma unroll
+                        for (int t = 0; t < NT; ++t) cells[t] = SRC::strip(srow, (8 * q + 4 * half) / OW + nky[t] - 2);
+                    }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int p = 8 * q + 4 * half + r, y = p / OW, x = p - y * OW;
@@ -364,7 +381,7 @@ __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dz
                             if (nok[t] && pin) {
                                 if (CIN == 1) {
                                     const int yy = y + nky[t] - 2;      // row of the 20 visible ones
-                                    if (yy >= 0) v = (float)states[ibase + yy * 10 + x + nkx[t]];
+                                    if (yy >= 0) v = SRC::cell(cells[t], yy, x + nkx[t]);
                                 } else {
                                     v = ain[ibase + nci[t] * ISTR + (y + nky[t]) * IW + x + nkx[t]];
                                 }
@@ -406,10 +423,12 @@ __global__ __launch_bounds__(64) void k_df_conv_bias_part(const float* __restric
     cb[(size_t)b * 64 + i] = s;
 }
 
-// the forward of B rows (states: int8 [.][200], row idx[b], or row b when idx is NULL) into a1, a2, h: the launches of the
-// gradient step and of the validation pass
-static void forward(const float* P, const int8_t* states, const int64_t* idx, int B, float* a1, float* a2, float* h, hipStream_t st) {
-    hipLaunchKernelGGL((k_df_conv_fwd<1, 22, 10, 0, S1, 3>), dim3(blocks_for_waves((tiles((long long)B * P1) + 2) / 3)), dim3(256), 0, st,
+// the forward of B rows (states: SRC's rows, int8 [.][200] or packed [.][12]; row idx[b], or row b when idx is NULL) into a1, a2,
+// h: the launches of the gradient step and of the validation pass
+template <typename SRC>
+static void forward(const float* P, const typename SRC::elem* states, const int64_t* idx, int B, float* a1, float* a2, float* h,
+                    hipStream_t st) {
+    hipLaunchKernelGGL((k_df_conv_fwd<1, 22, 10, 0, S1, 3, SRC>), dim3(blocks_for_waves((tiles((long long)B * P1) + 2) / 3)), dim3(256), 0, st,
                        P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
     hipLaunchKernelGGL((k_df_conv_fwd<32, 19, 7, S1, P2, 2>), dim3(blocks_for_waves((tiles((long long)B * P2) + 1) / 2)), dim3(256), 0, st,
                        P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
@@ -431,19 +450,11 @@ __host__ inline ValLayout val_layout(int slab) {
     return L;
 }
 
-}  // namespace tmcts_df
-
-extern "C" {
-
-long long tm_distnet_fit_workspace(int batch, int atoms) {
-    if (batch < 1 || batch > tmcts_df::MAX_BATCH || atoms < 1 || atoms > tmcts_df::ROW) return -1;
-    return tmcts_df::layout(batch).total;
-}
-
-int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* target, int target_stride, const float* weight,
-                        const int64_t* idx, int batch, int atoms, int weighted, float* grad, float* loss, float* workspace,
-                        void* stream_) {
-    using namespace tmcts_df;
+// the gradient step on either kind of rows: tm_distnet_fit_grad (DenseStates) and tm_distnet_fit_grad_packed (PackedStates)
+template <typename SRC>
+static int fit_grad(const float* params, const typename SRC::elem* states, const float* target, int target_stride,
+                    const float* weight, const int64_t* idx, int batch, int atoms, int weighted, float* grad, float* loss,
+                    float* workspace, void* stream_) {
     if (!params || !states || !target || !weight || !grad || !loss || !workspace) return (int)hipErrorInvalidValue;
     if (batch < 1 || batch > MAX_BATCH || atoms < 1 || atoms > ROW || target_stride < atoms) return (int)hipErrorInvalidValue;
     if (((uintptr_t)workspace & 15) || ((uintptr_t)params & 15)) return (int)hipErrorInvalidValue;
@@ -457,7 +468,7 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
     const float* P = params;
     const int OFF_FVB = OFF_FVW + atoms * HID;
     // ---- forward ----
-    forward(P, states, idx, B, a1, a2, h, st);
+    forward<SRC>(P, states, idx, B, a1, a2, h, st);
     // ---- output layer, loss, and the bias sums of the two FC layers ----
     hipLaunchKernelGGL(k_df_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P + OFF_FVW, P + OFF_FVB, h, target, target_stride, weight, idx,
                        B, atoms, weighted, dzv, per, dh);
@@ -478,7 +489,7 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
                        (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw2);
     hipLaunchKernelGGL((k_df_conv_bwd_data<2>), dim3(blocks_for_waves((tiles((long long)B * S1) + 1) / 2)), dim3(256), 0, st, P + OFF_C2W,
                        dz2, a1, B, dz1);
-    hipLaunchKernelGGL((k_df_conv_dw<1, 10, 0, 7, P1, S1, 1>), dim3(blocks_for_waves(L.chunks)), dim3(256), 0, st, dz1,
+    hipLaunchKernelGGL((k_df_conv_dw<1, 10, 0, 7, P1, S1, 1, SRC>), dim3(blocks_for_waves(L.chunks)), dim3(256), 0, st, dz1,
                        (const float*)nullptr, states, idx, B, pw1);
     hipLaunchKernelGGL(k_df_conv_bias_part, dim3(B), dim3(64), 0, st, dz1, dz2, B, cb);
     // ---- second stages of the convolutions' sums ----
@@ -489,15 +500,11 @@ int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* 
     return (int)hipGetLastError();
 }
 
-long long tm_distnet_fit_validate_workspace(int slab, int atoms) {
-    if (slab < 1 || slab > tmcts_df::MAX_BATCH || atoms < 1 || atoms > tmcts_df::ROW) return -1;
-    return tmcts_df::val_layout(slab).total;
-}
-
-int tm_distnet_fit_validate(const float* params, const int8_t* states, const float* target, int target_stride, const float* weight,
-                            long long n, int chunk, int slab, int atoms, int weighted, double* rows_out, float* workspace,
-                            void* stream_) {
-    using namespace tmcts_df;
+// the validation pass on either kind of rows
+template <typename SRC>
+static int fit_validate(const float* params, const typename SRC::elem* states, const float* target, int target_stride,
+                        const float* weight, long long n, int chunk, int slab, int atoms, int weighted, double* rows_out,
+                        float* workspace, void* stream_) {
     if (!params || !states || !target || !weight || !rows_out || !workspace) return (int)hipErrorInvalidValue;
     if (n < 1 || chunk < 1 || slab < chunk || slab > MAX_BATCH || slab % chunk) return (int)hipErrorInvalidValue;
     if (atoms < 1 || atoms > ROW || target_stride < atoms) return (int)hipErrorInvalidValue;
@@ -510,7 +517,7 @@ int tm_distnet_fit_validate(const float* params, const int8_t* states, const flo
     // slab by slab on the one stream: a slab's kernels have read the workspace before the next slab's overwrite it
     for (long long r0 = 0; r0 < n; r0 += slab) {
         const int B = (int)(n - r0 < slab ? n - r0 : slab);
-        forward(params, states + r0 * 200, (const int64_t*)nullptr, B, a1, a2, h, st);
+        forward<SRC>(params, states + r0 * SRC::STRIDE, (const int64_t*)nullptr, B, a1, a2, h, st);
         hipLaunchKernelGGL(k_df_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params + OFF_FVW, params + OFF_FVB, h,
                            target + r0 * target_stride, target_stride, weight + r0, (const int64_t*)nullptr, B, atoms, weighted,
                            (float*)nullptr, per, (float*)nullptr);
@@ -518,6 +525,50 @@ int tm_distnet_fit_validate(const float* params, const int8_t* states, const flo
                            rows_out + 3 * (r0 / chunk));
     }
     return (int)hipGetLastError();
+}
+
+}  // namespace tmcts_df
+
+extern "C" {
+
+long long tm_distnet_fit_workspace(int batch, int atoms) {
+    if (batch < 1 || batch > tmcts_df::MAX_BATCH || atoms < 1 || atoms > tmcts_df::ROW) return -1;
+    return tmcts_df::layout(batch).total;
+}
+
+int tm_distnet_fit_grad(const float* params, const int8_t* states, const float* target, int target_stride, const float* weight,
+                        const int64_t* idx, int batch, int atoms, int weighted, float* grad, float* loss, float* workspace,
+                        void* stream) {
+    return tmcts_df::fit_grad<tmcts_fit::DenseStates>(params, states, target, target_stride, weight, idx, batch, atoms, weighted,
+                                                      grad, loss, workspace, stream);
+}
+
+int tm_distnet_fit_grad_packed(const float* params, const uint32_t* obs, const float* target, int target_stride,
+                               const float* weight, const int64_t* idx, int batch, int atoms, int weighted, float* grad,
+                               float* loss, float* workspace, void* stream) {
+    if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
+    return tmcts_df::fit_grad<tmcts_fit::PackedStates>(params, obs, target, target_stride, weight, idx, batch, atoms, weighted,
+                                                       grad, loss, workspace, stream);
+}
+
+long long tm_distnet_fit_validate_workspace(int slab, int atoms) {
+    if (slab < 1 || slab > tmcts_df::MAX_BATCH || atoms < 1 || atoms > tmcts_df::ROW) return -1;
+    return tmcts_df::val_layout(slab).total;
+}
+
+int tm_distnet_fit_validate(const float* params, const int8_t* states, const float* target, int target_stride, const float* weight,
+                            long long n, int chunk, int slab, int atoms, int weighted, double* rows_out, float* workspace,
+                            void* stream) {
+    return tmcts_df::fit_validate<tmcts_fit::DenseStates>(params, states, target, target_stride, weight, n, chunk, slab, atoms,
+                                                          weighted, rows_out, workspace, stream);
+}
+
+int tm_distnet_fit_validate_packed(const float* params, const uint32_t* obs, const float* target, int target_stride,
+                                   const float* weight, long long n, int chunk, int slab, int atoms, int weighted,
+                                   double* rows_out, float* workspace, void* stream) {
+    if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
+    return tmcts_df::fit_validate<tmcts_fit::PackedStates>(params, obs, target, target_stride, weight, n, chunk, slab, atoms,
+                                                           weighted, rows_out, workspace, stream);
 }
 
 }  // extern "C"

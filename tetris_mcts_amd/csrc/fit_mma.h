@@ -3,7 +3,8 @@
 // block sums of the second stages and the moments of the per-sample losses.  Kernels that are the same statements in both nets
 // up to constants and the activation: fc1's forward and data gradient (k_fit_fc1_fwd, k_fit_fc1_bwd_data), the second stage of
 // every batch sum (k_fit_reduce), the loss of a gradient step and the chunks of a validation pass (k_fit_loss,
-// k_fit_val_moments).  The host helpers of the launch shapes (up4, blocks_for_waves, tiles).  A template is instantiated in the
+// k_fit_val_moments).  The two sources of a training row's cells, int8 or a packed observation (DenseStates, PackedStates).  The
+// host helpers of the launch shapes (up4, blocks_for_waves, tiles).  A template is instantiated in the
 // object of each file that launches it.  The convolutions, the output layers and the two FC weight gradients stay in their files.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,6 +47,49 @@ __device__ __forceinline__ void vf_add(f32x16 (&tot)[NT], const f32x16 (&acc)[NT
 }
 
 __device__ __forceinline__ size_t row_of(const int64_t* __restrict__ idx, int b) { return idx ? (size_t)idx[b] : (size_t)b; }
+
+// ---- where a CIN == 1 kernel reads its input cells: the state of training row i as int8 [200] (DenseStates) or as the packed
+// observation of ENGINE_SPEC section 7, twelve dwords (PackedStates).  row(): what a lane keeps per sample.  strip(row, r): what
+// it keeps for the board rows r, r + 1, r + 2 (r may be negative or past the board: rows outside 0..19 are never asked for).
+// cell(strip, r, c): the value of cell (r, c) as the float the matrix core is fed, 0 empty, 1 locked, -1 the falling piece.
+// Both sources give the same float for the same board, so everything a kernel does with it is the same bits. ----
+struct DenseStates {
+    typedef int8_t elem;
+    static constexpr int STRIDE = 200;      // elements per training row
+    struct Row { const int8_t* p; };
+    typedef Row Strip;
+    static __device__ __forceinline__ Row row(const elem* __restrict__ s, size_t i) { return Row{s + i * STRIDE}; }
+    static __device__ __forceinline__ Strip strip(const Row& w, int) { return w; }
+    static __device__ __forceinline__ float cell(const Strip& s, int r, int c) { return (float)s.p[r * 10 + c]; }
+};
+
+// engine.h obs_cell's semantics: the locked bit of cell (r, c) is bit 16 (r & 1) + c of word r >> 1; the cell is -1 where one
+// of the four cell codes of word 10 equals 10 r + c and the low byte of word 11 (ended) is 0; the piece wins over a locked bit.
+// Nothing read out of an observation is used as an address or a shift: a code is only compared (codes >= 200 match no cell, an
+// ended row's codes are replaced by 255), and a row's bits 10..15 are never looked at, so any 48 bytes are safe to read.
+// A row keeps words 10 and 11, loaded once per (lane, sample); a strip the two words of the four rows from the even row at or
+// below r, loaded once where it is built (the word index is clamped to the ten board words).
+struct PackedStates {
+    typedef uint32_t elem;
+    static constexpr int STRIDE = 12;
+    struct Row { const uint32_t* o; uint32_t codes; };
+    struct Strip { uint64_t bits; uint32_t codes; int r0; };
+    static __device__ __forceinline__ Row row(const elem* __restrict__ s, size_t i) {
+        const uint32_t* o = s + i * STRIDE;
+        return Row{o, (o[11] & 0xFFu) ? 0xFFFFFFFFu : o[10]};
+    }
+    static __device__ __forceinline__ Strip strip(const Row& w, int r) {
+        const int a = r >> 1;       // (arithmetic: -1 for the two rows above the board)
+        const uint32_t lo = (a >= 0 && a <= 9) ? w.o[a] : 0u, hi = (a >= -1 && a <= 8) ? w.o[a + 1] : 0u;
+        return Strip{(uint64_t)lo | ((uint64_t)hi << 32), w.codes, 2 * a};
+    }
+    static __device__ __forceinline__ float cell(const Strip& s, int r, int c) {
+        const uint32_t i = (uint32_t)(r * 10 + c), k = s.codes;
+        const bool piece = ((k & 0xFFu) == i) | (((k >> 8) & 0xFFu) == i) | (((k >> 16) & 0xFFu) == i) | ((k >> 24) == i);
+        const uint32_t locked = (uint32_t)(s.bits >> (16 * (r - s.r0) + c)) & 1u;
+        return piece ? -1.0f : (float)locked;
+    }
+};
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

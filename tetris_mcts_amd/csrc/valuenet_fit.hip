@@ -25,6 +25,11 @@
 // The validation pass (tm_valuenet_fit_validate) is the same forward (forward(): the same kernels and instantiations, idx NULL)
 // over the held-out rows, a slab at a time, k_vf_head<false> for the per-sample losses and k_fit_val_moments<0> for each chunk's
 // {w, mean, population std}: what a row's loss is, and the order in which losses are added, are the gradient step's.
+//
+// The training rows' states come as int8 [rows][200] or as the packed observations of the engine, uint32 [rows][12]
+// (tm_valuenet_fit_grad_packed, tm_valuenet_fit_validate_packed): the two kernels that read them (conv1's forward and weight
+// gradient) take fit_mma.h's DenseStates or PackedStates as a template argument and get a cell's value from it; every statement
+// after that is one text, so the packed calls write the bits of the int8 calls on the rendered rows.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -75,18 +80,20 @@ __host__ inline Layout layout(int B) {
 }
 
 // ---- forward convolution: z[co][b, p] = bias[co] + sum_k W[co][k] in[b][ci][(y + ky) IW + x + kx], ReLU ----
-// M = 32 output channels, N = B * OP positions, K = CIN * 9.  CIN == 1: the input is the int8 state of row idx[b].
-template <int CIN, int IH, int IW, int NT>
+// M = 32 output channels, N = B * OP positions, K = CIN * 9.  CIN == 1: the input is the state of row idx[b], read through SRC
+// (fit_mma.h: int8 cells or a packed observation); a lane keeps the strip of its position's three rows per tile.
+template <int CIN, int IH, int IW, int NT, typename SRC = DenseStates>
 __global__ __launch_bounds__(256) void k_vf_conv_fwd(const float* __restrict__ W, const float* __restrict__ bias,
-                                                     const float* __restrict__ in, const int8_t* __restrict__ states,
+                                                     const float* __restrict__ in, const typename SRC::elem* __restrict__ states,
                                                      const int64_t* __restrict__ idx, int B, float* __restrict__ out) {
     constexpr int OW = IW - 2, OP = (IH - 2) * OW, IP = IH * IW, K = CIN * 9, KQ = (K + 7) / 8;
     const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
     const int n0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NT * 32, N = B * OP;
     if (n0 >= N) return;
     bool ok[NT];
-    int nb[NT], np[NT];
+    int nb[NT], np[NT], ny[NT], nx[NT];
     size_t base[NT];
+    typename SRC::Strip cells[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int n = n0 + 32 * t + l31;
@@ -94,7 +101,10 @@ __global__ __launch_bounds__(256) void k_vf_conv_fwd(const float* __restrict__ W
         const int nn = ok[t] ? n : 0, b = nn / OP, p = nn - b * OP, y = p / OW, x = p - y * OW;
         nb[t] = b;
         np[t] = p;
-        base[t] = (CIN == 1 ? row_of(idx, b) * 200 : (size_t)b * (CIN * IP)) + y * IW + x;
+        ny[t] = y;
+        nx[t] = x;
+        base[t] = (size_t)b * (CIN * IP) + y * IW + x;
+        if constexpr (CIN == 1) cells[t] = SRC::strip(SRC::row(states, row_of(idx, b)), y);
     }
     f32x16 tot[NT], acc[NT];
 #pragma unroll
@@ -118,7 +128,7 @@ __global__ __launch_bounds__(256) void k_vf_conv_fwd(const float* __restrict__ W
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     float v = 0.0f;
-                    if (kin && ok[t]) v = (CIN == 1) ? (float)states[base[t] + koff] : in[base[t] + koff];
+                    if (kin && ok[t]) v = (CIN == 1) ? SRC::cell(cells[t], ny[t] + ky, nx[t] + kx) : in[base[t] + koff];
                     bv[t][r] = v;
                 }
             }
@@ -309,10 +319,12 @@ __global__ __launch_bounds__(256) void k_vf_conv_bwd_data(const float* __restric
 
 // ---- convolution weight gradient: part[chunk][co][n = (ci,ky,kx)] = sum over the chunk's SPW samples and the OP positions of
 // dzo[b][co][p] ain[b][ci][(y + ky) IW + x + kx].  M = 32, N = CIN * 9 (NT tiles per wave), K = (sample, position) ----
-template <int CIN, int IH, int IW, int NT>
+// CIN == 1: ain is the state of row idx[b], read through SRC.  A lane's tap is fixed and the loop walks the positions, so the
+// strip is built per quad of positions (with OW == 8 a quad lies in one row) from the row the lane keeps per sample.
+template <int CIN, int IH, int IW, int NT, typename SRC = DenseStates>
 __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dzo, const float* __restrict__ ain,
-                                                    const int8_t* __restrict__ states, const int64_t* __restrict__ idx, int B,
-                                                    float* __restrict__ part) {
+                                                    const typename SRC::elem* __restrict__ states,
+                                                    const int64_t* __restrict__ idx, int B, float* __restrict__ part) {
     constexpr int OW = IW - 2, OP = (IH - 2) * OW, IP = IH * IW, KW = CIN * 9, NG = (KW + 32 * NT - 1) / (32 * NT);
     static_assert(OP % 8 == 0, "a quad of K stays inside one sample");
     const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
@@ -320,13 +332,15 @@ __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dz
     const int b0 = chunk * SPW, b1 = min(B, b0 + SPW);
     if (b0 >= B) return;
     bool nok[NT];
-    int noff[NT];
+    int noff[NT], nky[NT], nkx[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const int n = (ng * NT + t) * 32 + l31;
         nok[t] = n < KW;
         const int nn = nok[t] ? n : 0, ci = nn / 9, rr = nn - 9 * ci, ky = rr / 3, kx = rr - 3 * ky;
         noff[t] = ci * IP + ky * IW + kx;
+        nky[t] = ky;
+        nkx[t] = kx;
     }
     f32x16 acc[NT];
 #pragma unroll
@@ -335,18 +349,26 @@ __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dz
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
     for (int b = b0; b < b1; ++b) {
         const float* arow = dzo + (size_t)b * (32 * OP) + l31 * OP + 4 * half;
-        const size_t ibase = CIN == 1 ? row_of(idx, b) * 200 : (size_t)b * (CIN * IP);
+        const size_t ibase = (size_t)b * (CIN * IP);
+        typename SRC::Row srow;
+        if constexpr (CIN == 1) srow = SRC::row(states, row_of(idx, b));
 #pragma unroll 2
         for (int q = 0; q < OP / 8; ++q) {
             const float4 a = *reinterpret_cast<const float4*>(arow + 8 * q);
             float bv[NT][4];
+            typename SRC::Strip cells[NT];
+            if constexpr (CIN == 1) {
+                static_assert(CIN != 1 || OW == 8, "a quad of positions lies in one row of the output");
+#pragma unroll
+                for (int t = 0; t < NT; ++t) cells[t] = SRC::strip(srow, q + nky[t]);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int p = 8 * q + 4 * half + r, y = p / OW, x = p - y * OW, poff = y * IW + x;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     float v = 0.0f;
-                    if (nok[t]) v = (CIN == 1) ? (float)states[ibase + noff[t] + poff] : ain[ibase + noff[t] + poff];
+                    if (nok[t]) v = (CIN == 1) ? SRC::cell(cells[t], y + nky[t], x + nkx[t]) : ain[ibase + noff[t] + poff];
                     bv[t][r] = v;
                 }
             }
@@ -381,11 +403,12 @@ __global__ __launch_bounds__(128) void k_vf_conv_bias_part(const float* __restri
     cb[(size_t)b * 96 + i] = s;
 }
 
-// the forward of B rows (states: int8 [.][200], row idx[b], or row b when idx is NULL) into a1, a2, a3, h: the launches of the
-// gradient step and of the validation pass
-static void forward(const float* P, const int8_t* states, const int64_t* idx, int B, float* a1, float* a2, float* a3, float* h,
-                    hipStream_t st) {
-    hipLaunchKernelGGL((k_vf_conv_fwd<1, 20, 10, 3>), dim3(blocks_for_waves((tiles((long long)B * 144) + 2) / 3)), dim3(256), 0, st,
+// the forward of B rows (states: SRC's rows, int8 [.][200] or packed [.][12]; row idx[b], or row b when idx is NULL) into a1, a2,
+// a3, h: the launches of the gradient step and of the validation pass
+template <typename SRC>
+static void forward(const float* P, const typename SRC::elem* states, const int64_t* idx, int B, float* a1, float* a2, float* a3,
+                    float* h, hipStream_t st) {
+    hipLaunchKernelGGL((k_vf_conv_fwd<1, 20, 10, 3, SRC>), dim3(blocks_for_waves((tiles((long long)B * 144) + 2) / 3)), dim3(256), 0, st,
                        P + OFF_C1W, P + OFF_C1B, (const float*)nullptr, states, idx, B, a1);
     hipLaunchKernelGGL((k_vf_conv_fwd<32, 18, 8, 3>), dim3(blocks_for_waves((tiles((long long)B * 96) + 2) / 3)), dim3(256), 0, st,
                        P + OFF_C2W, P + OFF_C2B, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, a2);
@@ -410,19 +433,11 @@ __host__ inline ValLayout val_layout(int slab) {
     return L;
 }
 
-}  // namespace tmcts_vf
-
-extern "C" {
-
-long long tm_valuenet_fit_workspace(int batch) {
-    if (batch < 1 || batch > tmcts_vf::MAX_BATCH) return -1;
-    return tmcts_vf::layout(batch).total;
-}
-
-int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int8_t* states, const float* value,
-                         const float* variance, const float* weight, const int64_t* idx, int batch, int weighted,
-                         float variance_clip, float* grad, float* loss, float* workspace, void* stream_) {
-    using namespace tmcts_vf;
+// the gradient step on either kind of rows: tm_valuenet_fit_grad (DenseStates) and tm_valuenet_fit_grad_packed (PackedStates)
+template <typename SRC>
+static int fit_grad(const float* params, const float* out_bounds, const typename SRC::elem* states, const float* value,
+                    const float* variance, const float* weight, const int64_t* idx, int batch, int weighted,
+                    float variance_clip, float* grad, float* loss, float* workspace, void* stream_) {
     if (!params || !out_bounds || !states || !value || !variance || !weight || !grad || !loss || !workspace)
         return (int)hipErrorInvalidValue;
     if (batch < 1 || batch > MAX_BATCH || ((uintptr_t)workspace & 15)) return (int)hipErrorInvalidValue;
@@ -436,7 +451,7 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
     double* per = reinterpret_cast<double*>(ws + L.per);
     const float* P = params;
     // ---- forward ----
-    forward(P, states, idx, B, a1, a2, a3, h, st);
+    forward<SRC>(P, states, idx, B, a1, a2, a3, h, st);
     // ---- output layer, loss, and the small batch sums ----
     hipLaunchKernelGGL(k_vf_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P, out_bounds, h, value, variance, weight, idx, B, weighted,
                        variance_clip, dzo, per, dh);
@@ -458,7 +473,7 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
                        (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw2);
     hipLaunchKernelGGL((k_vf_conv_bwd_data<18, 8, 3>), dim3(blocks_for_waves((tiles((long long)B * 144) + 2) / 3)), dim3(256), 0, st,
                        P + OFF_C2W, dz2, a1, B, dz1);
-    hipLaunchKernelGGL((k_vf_conv_dw<1, 20, 10, 1>), dim3(blocks_for_waves(L.chunks)), dim3(256), 0, st, dz1, (const float*)nullptr,
+    hipLaunchKernelGGL((k_vf_conv_dw<1, 20, 10, 1, SRC>), dim3(blocks_for_waves(L.chunks)), dim3(256), 0, st, dz1, (const float*)nullptr,
                        states, idx, B, pw1);
     hipLaunchKernelGGL(k_vf_conv_bias_part, dim3(B), dim3(128), 0, st, dz1, dz2, dz3, B, cb);
     // ---- second stages of the convolutions' sums ----
@@ -471,15 +486,11 @@ int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int
     return (int)hipGetLastError();
 }
 
-long long tm_valuenet_fit_validate_workspace(int slab) {
-    if (slab < 1 || slab > tmcts_vf::MAX_BATCH) return -1;
-    return tmcts_vf::val_layout(slab).total;
-}
-
-int tm_valuenet_fit_validate(const float* params, const float* out_bounds, const int8_t* states, const float* value,
-                             const float* variance, const float* weight, long long n, int chunk, int slab, int weighted,
-                             float variance_clip, double* rows_out, float* workspace, void* stream_) {
-    using namespace tmcts_vf;
+// the validation pass on either kind of rows
+template <typename SRC>
+static int fit_validate(const float* params, const float* out_bounds, const typename SRC::elem* states, const float* value,
+                        const float* variance, const float* weight, long long n, int chunk, int slab, int weighted,
+                        float variance_clip, double* rows_out, float* workspace, void* stream_) {
     if (!params || !out_bounds || !states || !value || !variance || !weight || !rows_out || !workspace)
         return (int)hipErrorInvalidValue;
     if (n < 1 || chunk < 1 || slab < chunk || slab > MAX_BATCH || slab % chunk) return (int)hipErrorInvalidValue;
@@ -491,13 +502,57 @@ int tm_valuenet_fit_validate(const float* params, const float* out_bounds, const
     // slab by slab on the one stream: a slab's kernels have read the workspace before the next slab's overwrite it
     for (long long r0 = 0; r0 < n; r0 += slab) {
         const int B = (int)(n - r0 < slab ? n - r0 : slab);
-        forward(params, states + r0 * 200, (const int64_t*)nullptr, B, a1, a2, a3, h, st);
+        forward<SRC>(params, states + r0 * SRC::STRIDE, (const int64_t*)nullptr, B, a1, a2, a3, h, st);
         hipLaunchKernelGGL(k_vf_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params, out_bounds, h, value + r0, variance + r0,
                            weight + r0, (const int64_t*)nullptr, B, weighted, variance_clip, (float*)nullptr, per, (float*)nullptr);
         hipLaunchKernelGGL(k_fit_val_moments<0>, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
                            rows_out + 3 * (r0 / chunk));
     }
     return (int)hipGetLastError();
+}
+
+}  // namespace tmcts_vf
+
+extern "C" {
+
+long long tm_valuenet_fit_workspace(int batch) {
+    if (batch < 1 || batch > tmcts_vf::MAX_BATCH) return -1;
+    return tmcts_vf::layout(batch).total;
+}
+
+int tm_valuenet_fit_grad(const float* params, const float* out_bounds, const int8_t* states, const float* value,
+                         const float* variance, const float* weight, const int64_t* idx, int batch, int weighted,
+                         float variance_clip, float* grad, float* loss, float* workspace, void* stream) {
+    return tmcts_vf::fit_grad<tmcts_fit::DenseStates>(params, out_bounds, states, value, variance, weight, idx, batch, weighted,
+                                                      variance_clip, grad, loss, workspace, stream);
+}
+
+int tm_valuenet_fit_grad_packed(const float* params, const float* out_bounds, const uint32_t* obs, const float* value,
+                                const float* variance, const float* weight, const int64_t* idx, int batch, int weighted,
+                                float variance_clip, float* grad, float* loss, float* workspace, void* stream) {
+    if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
+    return tmcts_vf::fit_grad<tmcts_fit::PackedStates>(params, out_bounds, obs, value, variance, weight, idx, batch, weighted,
+                                                       variance_clip, grad, loss, workspace, stream);
+}
+
+long long tm_valuenet_fit_validate_workspace(int slab) {
+    if (slab < 1 || slab > tmcts_vf::MAX_BATCH) return -1;
+    return tmcts_vf::val_layout(slab).total;
+}
+
+int tm_valuenet_fit_validate(const float* params, const float* out_bounds, const int8_t* states, const float* value,
+                             const float* variance, const float* weight, long long n, int chunk, int slab, int weighted,
+                             float variance_clip, double* rows_out, float* workspace, void* stream) {
+    return tmcts_vf::fit_validate<tmcts_fit::DenseStates>(params, out_bounds, states, value, variance, weight, n, chunk, slab,
+                                                          weighted, variance_clip, rows_out, workspace, stream);
+}
+
+int tm_valuenet_fit_validate_packed(const float* params, const float* out_bounds, const uint32_t* obs, const float* value,
+                                    const float* variance, const float* weight, long long n, int chunk, int slab, int weighted,
+                                    float variance_clip, double* rows_out, float* workspace, void* stream) {
+    if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
+    return tmcts_vf::fit_validate<tmcts_fit::PackedStates>(params, out_bounds, obs, value, variance, weight, n, chunk, slab,
+                                                           weighted, variance_clip, rows_out, workspace, stream);
 }
 
 }  // extern "C"

@@ -144,6 +144,11 @@ def render_observations(obs_keys):
     return flat.reshape(n, 1, 20, 10)
 
 
+def training_targets(stats):
+    """(values [n,1], variance [n,1], weights [n,1]) as ValueSim.memory holds them."""
+    return stats[:, 0:1].clone(), stats[:, 1:2].clone(), stats[:, 2:3].clone()
+
+
 def training_arrays(obs_keys, stats):
     """(states [n,1,20,10], values [n,1], variance [n,1], weights [n,1]) as ValueSim.memory holds them."""
-    return render_observations(obs_keys), stats[:, 0:1].clone(), stats[:, 1:2].clone(), stats[:, 2:3].clone()
+    return (render_observations(obs_keys),) + training_targets(stats)

@@ -163,16 +163,20 @@ class Model_VV(_HipHead):
         return self.optimizer
 
     def train_data(self, data, **kwargs):
-        """data: [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (numpy or tensors); fit_backend and
-        validation_backend as train.train_data describes them."""
+        """data: [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (numpy or tensors); fit_backend,
+        validation_backend and state_format as train.train_data describes them (state_format="packed": data[0] holds the packed
+        observations, int32 [n,12] on the GPU, and is passed on as it is)."""
         from . import train as T
         dev = self.device
+        packed = kwargs.get("state_format", "dense") == "packed"
+        T.check_state_format(kwargs.get("state_format", "dense"), kwargs.get("fit_backend", "torch"),
+                             kwargs.get("validation_backend", "torch"), kwargs.get("validation_fraction", 0.1), data)
         if kwargs.get("fit_backend") == "hip_dist":
             raise ValueError("Model_VV.train_data: fit_backend='hip_dist' is the distributional head's gradient step "
                              "('hip' is the value net's)")
         if kwargs.get("validation_backend", "torch") == "hip" and kwargs.get("fit_backend", "torch") != "hip":
             raise ValueError("Model_VV.train_data: validation_backend='hip' needs fit_backend='hip'")
-        data = [torch.as_tensor(d, dtype=torch.float32, device=dev) for d in data]
+        data = [d if packed and i == 0 else torch.as_tensor(d, dtype=torch.float32, device=dev) for i, d in enumerate(data)]
         with torch.no_grad():
             self.model.out_ubound.copy_(torch.stack([data[1].max(), data[2].max()]))   # model_vv.py:228-229
         best = {}

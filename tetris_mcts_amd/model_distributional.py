@@ -156,7 +156,8 @@ class Model_Dist(_HipHead):
         this class's loss; data-parallel over the ranks as train.train_data describes.  fit_backend: "torch" (the default:
         autograd and the model's optimiser as it stands) or "hip_dist" (csrc/distnet_fit.hip's gradient step and the fused Adam;
         train.HipDistFit lists what it needs); "hip" names the value net's step and is refused.  validation_backend (in kwargs): "torch"
-        or "hip" (csrc/distnet_fit.hip's validation pass; it needs fit_backend="hip_dist")."""
+        or "hip" (csrc/distnet_fit.hip's validation pass; it needs fit_backend="hip_dist").  state_format (in kwargs): "dense" or
+        "packed" (data[0] holds the packed observations, int32 [n,12] on the GPU, and is passed on as it is; train.train_data)."""
         from . import train as T
         if fit_backend not in ("torch", "hip_dist"):
             raise ValueError("Model_Dist.train_data: fit_backend must be 'torch' or 'hip_dist', not %r" % (fit_backend,))
@@ -164,7 +165,10 @@ class Model_Dist(_HipHead):
             raise ValueError("Model_Dist.train_data: validation_backend must be 'torch' or 'hip', not %r" % (kwargs["validation_backend"],))
         if kwargs.get("validation_backend", "torch") == "hip" and fit_backend != "hip_dist":
             raise ValueError("Model_Dist.train_data: validation_backend='hip' needs fit_backend='hip_dist'")
-        data = [torch.as_tensor(d, dtype=torch.float32, device=self.device) for d in data]
+        packed = kwargs.get("state_format", "dense") == "packed"
+        T.check_state_format(kwargs.get("state_format", "dense"), fit_backend, kwargs.get("validation_backend", "torch"),
+                             kwargs.get("validation_fraction", 0.1), data)
+        data = [d if packed and i == 0 else torch.as_tensor(d, dtype=torch.float32, device=self.device) for i, d in enumerate(data)]
         best = {}
 
         def save():

@@ -312,17 +312,57 @@ def _validation_slab(rows, chunk, slab):
     return min(slab, (rows + chunk - 1) // chunk * chunk)
 
 
+def _packed_states_fault(states):
+    """why `states` is not what state_format='packed' reads (None when it is): the observations as the engine harvests them,
+    int32 [n,12] on the GPU (ENGINE_SPEC section 7)"""
+    if not isinstance(states, torch.Tensor) or states.dtype != torch.int32:
+        return "int32 observations, got %s" % (getattr(states, "dtype", type(states).__name__),)
+    if states.dim() != 2 or states.shape[1] != 12:
+        return "observations of 12 words a row, got shape %s" % (tuple(states.shape),)
+    if not states.is_cuda:
+        return "the observations on the GPU (they are on %s)" % (states.device,)
+    return None
+
+
+def check_state_format(state_format, fit_backend, validation_backend, validation_fraction, data):
+    """The refusals of train_data's `state_format`, a ValueError that names the option, raised before the model, the optimiser
+    or a sampling stream is touched (train_data and the models' train_data call it first)."""
+    if state_format not in ("dense", "packed"):
+        raise ValueError("state_format must be 'dense' or 'packed', not %r" % (state_format,))
+    if state_format == "dense":
+        return
+    if fit_backend not in ("hip", "hip_dist"):
+        raise ValueError("state_format='packed': only the HIP gradient steps read packed observations, it needs fit_backend='hip' "
+                         "or 'hip_dist', not %r" % (fit_backend,))
+    rows = len(data[0]) if hasattr(data[0], "__len__") else 0
+    if validation_backend != "hip" and int(rows * validation_fraction) > 0:
+        raise ValueError("state_format='packed': the torch validation does not read packed observations, it needs "
+                         "validation_backend='hip' or a validation_fraction that holds no rows out")
+    fault = _packed_states_fault(data[0])
+    if fault:
+        raise ValueError("state_format='packed' needs " + fault)
+
+
 class _HipFitBase:
     """What the per-fit states of fit_backend="hip" and "hip_dist" share: the order of the checks (once per fit, everything that
     can refuse before the optimiser is flattened), the workspaces of the gradient step and of the validation pass, the index
     check and the two calls.  A subclass names its backend (`BACKEND`, for the messages), checks the net, the optimiser and one
     list of rows (`_check`, `_check_rows`, `_check_flat`), keeps its copies of the rows (`_keep`) and makes the C calls
-    (`_workspace`, `_grad`, `_validate`)."""
+    (`_workspace`, `_grad`, `_validate`).
+
+    state_format="packed": the first array of `train` and of `val` holds the packed observations (int32 [rows,12]) in place
+    of rendered states.  The kernels give every bit pattern a meaning, so the rows' check is of dtype, shape and device alone,
+    the rows are kept as they are (a contiguous view: no copy of contiguous rows), and the calls are the `_packed` entry points,
+    whose outputs are the bits of the int8 ones on the rendered rows."""
     BACKEND = None
 
-    def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB):
+    def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB,
+                 state_format="dense"):
         from . import _lib
         self._lib = _lib
+        if state_format not in ("dense", "packed"):
+            raise ValueError("state_format must be 'dense' or 'packed', not %r" % (state_format,))
+        self.packed = state_format == "packed"
         L, V = "fit_backend='%s'" % self.BACKEND, "validation_backend='hip'"
         rows = self._check(net, optimizer, train, L)
         if val is not None:      # validation_backend="hip": the same checks on the held-out rows, before the optimiser is touched
@@ -358,6 +398,18 @@ class _HipFitBase:
         self._validate(int(bool(weighted)), torch.cuda.current_stream(self.dev).cuda_stream)
         return self.val_out.cpu().tolist()
 
+    def _check_packed(self, data, L, what):
+        """the first array of `data` as packed observations: dtype, shape and device (no sweep over the contents)"""
+        fault = _packed_states_fault(data[0]) if len(data) else "a list of arrays"
+        if fault:
+            raise ValueError(L + " with state_format='packed' needs " + fault + " as the " + what + "'s states")
+        if data[0].shape[0] < 1:
+            raise ValueError(L + " with state_format='packed' needs at least one row of " + what)
+
+    def _fn(self, name):
+        """the entry point `name` for this fit's kind of rows"""
+        return getattr(self._lib.lib(), name + ("_packed" if self.packed else ""))
+
     def check_idx(self, idx):
         """ValueError unless every index names a training row (a host synchronisation: not inside a graph capture)"""
         lo, hi = int(idx.min()), int(idx.max())
@@ -387,6 +439,14 @@ class HipFit(_HipFitBase):
 
     def _check_rows(self, data, L, what):
         """the checks of one list of rows (`what`: "data", the training rows, or "validation data"); the number of rows"""
+        if self.packed:
+            self._check_packed(data, L, what)
+            rows = data[0].shape[0]
+            if len(data) != 4 or not all(d.is_cuda and d.dtype == torch.float32 for d in data[1:]):
+                raise ValueError(L + " needs %s = [observations, values, variances, weights], the last three float32 CUDA tensors" % what)
+            if any(t.shape[0] != rows or t.numel() != rows for t in data[1:]):
+                raise ValueError(L + " needs one value, variance and weight a row")
+            return rows
         rows = data[0].shape[0]
         if len(data) != 4 or rows < 1 or data[0].numel() != rows * 200:
             if what != "data":
@@ -418,7 +478,7 @@ class HipFit(_HipFitBase):
             raise ValueError(L + ": the optimizer's flat buffers are not the net's learnable tensors in model.PARAM_ORDER")
 
     def _keep(self, data, rows, pre):
-        setattr(self, pre + "states", data[0].reshape(rows, 200).to(torch.int8).contiguous())
+        setattr(self, pre + "states", data[0].contiguous() if self.packed else data[0].reshape(rows, 200).to(torch.int8).contiguous())
         for name, t in zip(("value", "variance", "weight"), data[1:]):
             setattr(self, pre + name, t.reshape(rows).contiguous())
 
@@ -426,14 +486,14 @@ class HipFit(_HipFitBase):
         return self._lib.lib().tm_valuenet_fit_validate_workspace(n) if validation else self._lib.lib().tm_valuenet_fit_workspace(n)
 
     def _validate(self, weighted, stream):
-        self._lib.check(self._lib.lib().tm_valuenet_fit_validate(
+        self._lib.check(self._fn("tm_valuenet_fit_validate")(
             self.F["p"].data_ptr(), self.bounds.data_ptr(), self.val_states.data_ptr(), self.val_value.data_ptr(),
             self.val_variance.data_ptr(), self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab, weighted,
             float(variance_bound), self.val_out.data_ptr(), self.val_ws.data_ptr(), stream), "tm_valuenet_fit_validate")
 
     def _grad(self, idx, weighted, stream):
         F = self.F
-        self._lib.check(self._lib.lib().tm_valuenet_fit_grad(
+        self._lib.check(self._fn("tm_valuenet_fit_grad")(
             F["p"].data_ptr(), self.bounds.data_ptr(), self.states.data_ptr(), self.value.data_ptr(), self.variance.data_ptr(),
             self.weight.data_ptr(), idx.data_ptr(), self.batch, weighted, float(variance_bound), F["g"].data_ptr(),
             self.loss.data_ptr(), self.ws.data_ptr(), stream), "tm_valuenet_fit_grad")
@@ -479,8 +539,12 @@ class HipDistFit(_HipFitBase):
 
     def _check_rows(self, data, L, what):
         """the checks of one list of rows (`what`: "data", the training rows, or "validation data"); the number of rows"""
+        if self.packed:      # (20 board rows a row: the kernels supply the two empty rows on top, which holds the dense rule by construction)
+            self._check_packed(data, L, what)
+            if len(data) != 3:
+                raise ValueError(L + " needs %s = [observations, targets, weights]" % what)
         rows, atoms = data[0].shape[0], self.atoms
-        if len(data) != 3 or rows < 1 or data[0].numel() != rows * 220:
+        if not self.packed and (len(data) != 3 or rows < 1 or data[0].numel() != rows * 220):
             if what != "data":
                 raise ValueError(L + " needs validation data = [states of 22 x 10 cells a row, targets, weights]")
             if len(data) != 3:
@@ -492,14 +556,15 @@ class HipDistFit(_HipFitBase):
                              % (rows, atoms, " as the net's atoms" if what == "data" else "", tuple(target.shape)))
         if weight.shape[0] != rows or weight.numel() != rows:
             raise ValueError(L + " needs one weight a row")
-        s3 = states.reshape(rows, 22, 10)
-        if not bool(((s3 == s3.round()) & (s3.abs() <= 127)).all()):
-            raise ValueError(L + " reads the states as int8: they must be integers in [-127, 127]")
-        if not bool((s3[:, :2] == 0).all()):
-            raise ValueError(L + " supplies the two top rows of the 22 itself: they must be all zero in the data")
+        if not self.packed:
+            s3 = states.reshape(rows, 22, 10)
+            if not bool(((s3 == s3.round()) & (s3.abs() <= 127)).all()):
+                raise ValueError(L + " reads the states as int8: they must be integers in [-127, 127]")
+            if not bool((s3[:, :2] == 0).all()):
+                raise ValueError(L + " supplies the two top rows of the 22 itself: they must be all zero in the data")
         if not bool((torch.isfinite(target) & (target >= 0)).all()):
             raise ValueError(L + " needs finite targets >= 0")
-        if not all(d.is_cuda and d.dtype == torch.float32 for d in data):
+        if not all(d.is_cuda and d.dtype == torch.float32 for d in data[1 if self.packed else 0:]):
             raise ValueError(L + " needs float32 CUDA tensors (the %s is %s on %s)" % (what, states.dtype, states.device))
         return rows
 
@@ -526,7 +591,8 @@ class HipDistFit(_HipFitBase):
             raise ValueError(L + ": %d flat parameters on %s, expected %d on %s" % (F["n"], F["p"].device, want, dev))
 
     def _keep(self, data, rows, pre):
-        setattr(self, pre + "states", data[0].reshape(rows, 22, 10)[:, 2:].reshape(rows, 200).to(torch.int8).contiguous())
+        setattr(self, pre + "states", data[0].contiguous() if self.packed else
+                data[0].reshape(rows, 22, 10)[:, 2:].reshape(rows, 200).to(torch.int8).contiguous())
         setattr(self, pre + "target", data[1].contiguous())
         setattr(self, pre + "weight", data[2].reshape(rows).contiguous())
 
@@ -535,14 +601,14 @@ class HipDistFit(_HipFitBase):
         return lib.tm_distnet_fit_validate_workspace(n, self.atoms) if validation else lib.tm_distnet_fit_workspace(n, self.atoms)
 
     def _validate(self, weighted, stream):
-        self._lib.check(self._lib.lib().tm_distnet_fit_validate(
+        self._lib.check(self._fn("tm_distnet_fit_validate")(
             self.F["p"].data_ptr(), self.val_states.data_ptr(), self.val_target.data_ptr(), self.val_target.stride(0),
             self.val_weight.data_ptr(), self.val_rows, self.val_chunk, self.val_slab, self.atoms, weighted,
             self.val_out.data_ptr(), self.val_ws.data_ptr(), stream), "tm_distnet_fit_validate")
 
     def _grad(self, idx, weighted, stream):
         F = self.F
-        self._lib.check(self._lib.lib().tm_distnet_fit_grad(
+        self._lib.check(self._fn("tm_distnet_fit_grad")(
             F["p"].data_ptr(), self.states.data_ptr(), self.target.data_ptr(), self.target.stride(0), self.weight.data_ptr(),
             idx.data_ptr(), self.batch, self.atoms, weighted, F["g"].data_ptr(), self.loss.data_ptr(), self.ws.data_ptr(), stream),
             "tm_distnet_fit_grad")
@@ -552,7 +618,7 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
                sample_replacement=True, oversampling=False, weighted=True, early_stopping=True, early_stopping_patience=10,
                early_stopping_threshold=1.0, shuffle=False, max_iters=100000, grad_clip=0.0, save=None, load=None,
                generator=None, log=True, data_parallel=True, group=None, loss_fn=None, fit_backend="torch",
-               validation_backend="torch"):
+               validation_backend="torch", state_format="dense"):
     """data = [states f32 [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (device tensors); with `loss_fn`
     (net, batch, weighted) -> (mean, std) any list of arrays whose LAST one holds the sample weights (Model.train_data is
     generic in the reference too, model/model.py:176-249: the model class supplies `_loss`).
@@ -580,8 +646,16 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     step's own forward and per-sample losses over the held-out rows, reduced per chunk of 1 024 on the device) and one .cpu()
     of the chunks' rows, which feed the same host combination (combine_chunk_rows).  It reads the optimiser's flat parameter
     buffer as it stands, so it needs fit_backend "hip" or "hip_dist" and refuses anything else with a ValueError before the
-    model, the optimiser or a sampling stream is touched; with validation_fraction 0 it is accepted and does nothing."""
+    model, the optimiser or a sampling stream is touched; with validation_fraction 0 it is accepted and does nothing.
+
+    `state_format`: "dense" (the default) takes data[0] as rendered states; "packed" takes it as the observations the engine
+    harvests, int32 [n,12] on the GPU (dist.render_observations' input), and hands them to the HIP kernels as they are: no
+    rendered copy exists at any point, and the fit computes the bits of the dense one on the rendered rows.  The shuffle, the
+    split, the index draws and the graph capture treat the keys as they treat dense rows.  It needs fit_backend "hip" or
+    "hip_dist", and validation_backend "hip" unless no rows are held out; anything else is a ValueError raised before the model,
+    the optimiser or a sampling stream is touched (check_state_format)."""
     import torch.distributed as tdist
+    check_state_format(state_format, fit_backend, validation_backend, validation_fraction, data)
     if fit_backend not in ("torch", "hip", "hip_dist"):
         raise ValueError("fit_backend must be 'torch', 'hip' or 'hip_dist', not %r" % (fit_backend,))
     if validation_backend not in ("torch", "hip"):
@@ -626,8 +700,9 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     net.train()
     # the one-kernel optimiser step (Yogi on the GPU): parameters and gradients are views of flat buffers from here on
     hip_val = val if validation_backend == "hip" else None
-    hip = (HipFit(net, optimizer, train, batch_size // world, val=hip_val) if fit_backend == "hip" else
-           HipDistFit(net, optimizer, train, batch_size // world, val=hip_val) if fit_backend == "hip_dist" else None)
+    hip = (HipFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format) if fit_backend == "hip" else
+           HipDistFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format)
+           if fit_backend == "hip_dist" else None)
     if hip is not None and hip.rows != n - n_val:      # every draw below is an index into [0, n - n_val): the rows the kernels hold
         raise ValueError("fit_backend=%r: %d training rows, but the index draws cover %d" % (fit_backend, hip.rows, n - n_val))
     flat_g = optimizer.flat_grad() if hasattr(optimizer, "flat_grad") else None
