@@ -314,6 +314,42 @@ int tm_eval_scatter(const tm_store *s, const int32_t *slots, const int32_t *coun
 int tm_eval_scatter_dist(const tm_store *s, const int32_t *slots, const int32_t *count, const float *dist, int dist_stride,
                          void *stream);
 
+/* Self-play records on the device (episodes.hip): what the reference's DataSaver.add collects through getters every move
+ * (util/Data.py:14-26,63-96; play.py:131-132), written by the device into rows that are the file's rows, plus a log of the
+ * episodes that end.  A State row, TM_EPISODE_ROW_BYTES, little-endian:
+ *     0 episode i4 | 4 cycle i4 | 8 slot i4 (game index) | 12 move i4 (0-based index of the row within its episode) |
+ *    16 combo i4 | 20 lines i4 | 24 score i4 (the fields of the info call above, before the action) | 28 line_stats i4[4] |
+ *    44 value f4 | 48 variance f4 (the root observation's: TreeAgent.get_value_and_variance()) |
+ *    52 child_stats f4[3][7] (the caller's root statistics buffer, copied) |
+ *   136 policy f4[7]: child_stats[0][a] / (the seven visits added in index order), fp32 IEEE division; no visit: NaN |
+ *   164 board i1[20][10] (the render call's bytes for that game) | 364 action i1 | 365 three pad bytes, written as 0
+ * An episode row, TM_EPISODE_DONE_BYTES: episode, cycle, slot, moves (the State rows of the episode), score, lines,
+ * line_stats[4], all i4, the last three FINAL: taken after the action that ended the game.
+ * Per-slot state slot_state: int32 [G][TM_EPISODE_SLOT_DW] = episode_id, move_idx, live, one spare; counters: int32 [2] =
+ * next_id, n_done.
+ * tm_episode_init: episode_id[g] = first_id + g, move_idx = live = 0, next_id = first_id + G, n_done = 0.
+ * tm_episode_record, after the search and before the action is applied, writes exactly G rows (rows: [G][368], 4-byte aligned):
+ * for a game that has not ended the row above, and live = 1; for one that has (a slot the caller did not reset) episode = -1 and
+ * every other byte 0, live untouched.  env: the games (env_game, env_line_stats, n_games); tree: the agent's store or NULL
+ * (value = variance = 0); stats [G][3][7] and action [G] as the root statistics call left them (or what is actually played).
+ * tm_episode_advance, after the action is applied and before ended games are reset: a slot with live set whose game has now
+ * ended is finished - its episode row goes to done[n_done + r], episode_id = next_id + r, move_idx = 0, r its rank among the
+ * slots that finish in this call IN ASCENDING SLOT ORDER; a live slot whose game goes on gets move_idx += 1; live is cleared
+ * everywhere; next_id and n_done advance by the number finished.  done rows at or beyond cap are not written, n_done advances all
+ * the same: the caller sees the overflow in the count.  (With one game the ids are the reference's ngames counter; with G games
+ * the first G episodes are the slots, later ids follow play.py's Episode: lines - by move, then by slot.)
+ * All three enqueue on stream; they do not allocate, synchronise or read anything back, use no atomics, are deterministic and
+ * write nothing outside the arrays named.  hipErrorInvalidValue, nothing launched, for a NULL pointer (tree excepted),
+ * n_games < 1, cap < 1, first_id < 0, a misaligned rows / done or a tree of another n_games: checked before the first HIP call,
+ * so these answer on a machine without a GPU. */
+#define TM_EPISODE_ROW_BYTES 368
+#define TM_EPISODE_DONE_BYTES 40
+#define TM_EPISODE_SLOT_DW 4
+int tm_episode_init(int n_games, int first_id, int32_t *slot_state, int32_t *counters, void *stream);
+int tm_episode_record(const tm_store *env, const tm_store *tree, const float *stats, const int32_t *action, int cycle,
+                      int32_t *slot_state, void *rows, void *stream);
+int tm_episode_advance(const tm_store *env, int cycle, int32_t *slot_state, int32_t *counters, void *done, int cap, void *stream);
+
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel
  * workgroup's games; the groups of TM_GS_GC_ACTIVE4): hipErrorInvalidValue otherwise. */

@@ -2,8 +2,9 @@
 """play.py — self-play driver with the command line of the reference's play.py (flags: play.py:46-70), running
 on the MI355X engine.  `python play.py --agent_type ValueSimLP --mcts_sims 500 --ngames 10` behaves like the
 reference (same per-game log lines, play.py:25-37,164); `--n_games N` plays N games concurrently on the GPU
-(new, optional).  Only the hot path is reimplemented: --save/--save_tree (PyTables episode files, util/Data.py),
---gui and --interactive belong to the reference's storage / UI layers and are refused with a clear message.
+(new, optional).  `--save` writes the reference's self-play rows (util/Data.py State), recorded on the device, as numbered
+.npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5).  --save_tree, --gui and --interactive belong to
+the reference's storage / UI layers and are refused with a clear message.
 """
 import argparse
 import sys
@@ -85,10 +86,13 @@ class Scoreboard:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    for flag in ('save', 'save_tree', 'gui', 'interactive'):
+    for flag in ('save_tree', 'gui', 'interactive'):
         if getattr(args, flag):
-            sys.exit('--%s is part of the reference\'s storage / UI layer (util/Data.py: PyTables / HDF5 episode files - neither '
-                     'PyTables nor h5py nor libhdf5 exists in this image; util/gui.py), which this engine does not reimplement' % flag)
+            sys.exit('--%s is part of the reference\'s storage / UI layer (util/Data.py: PyTables / HDF5 files of expanded tree '
+                     'nodes; util/gui.py), which this engine does not reimplement' % flag)
+    if args.save and not args.agent_type:
+        sys.exit('--save records what an agent plays (its root statistics, value and policy beside the board): it needs '
+                 '--agent_type (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     if not args.agent_type:
         sys.exit('--agent_type is required (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     if args.fit_backend == 'hip_dist' and args.agent_type != 'DistValueSim':
@@ -138,6 +142,10 @@ def main(argv=None):
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     agent.update_root(game)
+    rec = None
+    if args.save:
+        from tetris_mcts_amd.episodes import EpisodeRecorder
+        rec = EpisodeRecorder(args.save_dir, args.save_file, args.cycle, G)
 
     board_file = open('board_output', 'wb') if args.print_board_to_file else None
     if args.realtime_status:
@@ -150,6 +158,8 @@ def main(argv=None):
         if args.printboard:
             game.printState()
         action = agent.play()
+        if rec is not None:
+            rec.add(agent, game)
         if board_file is not None or args.realtime_status:
             st = game.getState().reshape(-1, 20, 10)[0]
             if board_file is not None:
@@ -164,6 +174,8 @@ def main(argv=None):
                 mm['score'][:] = np.atleast_1d(game.score)[0]
                 mm['line_stats'][:] = np.asarray(game.line_stats).reshape(-1, 4)[0]
         game.play(action)
+        if rec is not None:
+            rec.advance(game)
         agent.update_root(game)
         moves += 1
         if args.online and not args.benchmark and hasattr(agent, 'train_if_collected'):
@@ -191,6 +203,8 @@ def main(argv=None):
         if args.max_moves and moves >= args.max_moves:
             break
     print(flush=True)
+    if rec is not None:
+        rec.close()
     agent.close()
 
 

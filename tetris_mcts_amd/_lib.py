@@ -52,6 +52,9 @@ SYMBOLS = {
     "tm_eval_scatter": [C.POINTER(TmStore), vp, vp, vp, vp, vp],
     "tm_eval_scatter_dist": [C.POINTER(TmStore), vp, vp, vp, i32, vp],
     "tm_root_stats": [C.POINTER(TmStore), vp, vp, vp],
+    "tm_episode_init": [i32, i32, vp, vp, vp],
+    "tm_episode_record": [C.POINTER(TmStore), C.POINTER(TmStore), vp, vp, i32, vp, vp, vp],
+    "tm_episode_advance": [C.POINTER(TmStore), i32, vp, vp, vp, i32, vp],
     "tm_export_game": [C.POINTER(TmStore), i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "tm_core_select_trace_obs": [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp],
     "tm_core_backup_trace_obs": [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f64, vp],

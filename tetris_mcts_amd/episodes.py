@@ -1,0 +1,260 @@
+"""Self-play records: the reference's `DataSaver` / `DataLoader` (util/Data.py:42-183) for a batch of games.
+
+The reference writes one `State` row per move through the agent's and the game's getters into a PyTables file.  Here the rows
+are written ON THE DEVICE (csrc/episodes.hip: tm_episode_record, tm_episode_advance) into a ring that is copied to pinned host
+memory when it is full, and the host turns a copy into files later, when it needs that buffer again.  The container is numpy's
+`.npy` (a table of fixed-size records), NOT HDF5: neither PyTables nor h5py is a dependency.  Where PyTables exists,
+`table.append(rows[list(State.columns)])` converts a shard.
+
+Files of `EpisodeRecorder(save_dir, save_file, cycle, ...)`, with stem = save_dir + save_file + str(cycle) (the reference's file
+name; `.r<rank>` is appended under torch.distributed with more than one rank, and episode ids are then rank-local):
+    <stem>.part00000.npy, .part00001.npy, ...             STATE_DTYPE rows, move-major, slot-minor
+    <stem>.episodes.part00000.npy, ...                    EPISODE_DTYPE rows: the episodes that ended, with their FINAL score
+Opening over existing parts continues their numbering and the episode ids (the reference's mode='a').
+"""
+import ctypes as C
+import glob
+import os
+import re
+
+import numpy as np
+
+ROW_BYTES, DONE_BYTES, SLOT_DW = 368, 40, 4       # TM_EPISODE_ROW_BYTES, TM_EPISODE_DONE_BYTES, TM_EPISODE_SLOT_DW
+N_ACTIONS = 7
+
+# the reference's State columns (util/Data.py:14-26) plus slot and move; the order is the device row's, readers go by name
+STATE_DTYPE = np.dtype({
+    "names": ["episode", "cycle", "slot", "move", "combo", "lines", "score", "line_stats", "value", "variance", "child_stats",
+              "policy", "board", "action"],
+    "formats": ["<i4", "<i4", "<i4", "<i4", "<i4", "<i4", "<i4", ("<i4", (4,)), "<f4", "<f4", ("<f4", (3, N_ACTIONS)),
+                ("<f4", (N_ACTIONS,)), ("i1", (20, 10)), "i1"],
+    "offsets": [0, 4, 8, 12, 16, 20, 24, 28, 44, 48, 52, 136, 164, 364],
+    "itemsize": ROW_BYTES})
+EPISODE_DTYPE = np.dtype({
+    "names": ["episode", "cycle", "slot", "moves", "score", "lines", "line_stats"],
+    "formats": ["<i4", "<i4", "<i4", "<i4", "<i4", "<i4", ("<i4", (4,))],
+    "offsets": [0, 4, 8, 12, 16, 20, 24],
+    "itemsize": DONE_BYTES})
+
+_PART = re.compile(r"\.part(\d{5})\.npy$")
+
+
+def _parts(stem, episodes=False):
+    """the existing part files of a stem in the order of their numbers"""
+    found = glob.glob(glob.escape(stem) + (".episodes" if episodes else "") + ".part[0-9][0-9][0-9][0-9][0-9].npy")
+    return sorted(found, key=lambda f: int(_PART.search(f).group(1)))
+
+
+class ShardWriter:
+    """The host half of the recorder: numbered shards of a stem.  `write(rows, episodes, n_done, cap)` takes a flush as the
+    device left it - STATE_DTYPE rows with episode == -1 where a game had ended, the `done` buffer of `cap` EPISODE_DTYPE rows
+    of which the first n_done are valid - drops the -1 rows and writes the next part of both tables."""
+
+    def __init__(self, save_dir, save_file, cycle, rank=None):
+        self.stem = "%s%s%s" % (save_dir, save_file, cycle)
+        if rank is not None:
+            self.stem += ".r%d" % rank
+        d = os.path.dirname(self.stem)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        have, have_ep = _parts(self.stem), _parts(self.stem, episodes=True)
+        self.part = 1 + max([int(_PART.search(f).group(1)) for f in have + have_ep], default=-1)
+        # the ids already given: the episodes that ended, and the ones under way in the last rows written
+        ids = [int(t["episode"].max()) for t in (np.load(f, mmap_mode="r") for f in have_ep) if len(t)]
+        if have:
+            last = np.load(have[-1], mmap_mode="r")
+            if len(last):
+                ids.append(int(last["episode"].max()))
+        self.next_id = 1 + max(ids, default=-1)
+
+    def write(self, rows, episodes, n_done, cap):
+        n_done = int(n_done)
+        if n_done > int(cap) or n_done > len(episodes):
+            raise RuntimeError("episode log overflow: %d episodes ended since the last flush, the buffer holds %d - their rows "
+                               "are lost; flush more often (ring_moves)" % (n_done, min(int(cap), len(episodes))))
+        # (whole rows as bytes: the pad bytes stay what the device wrote)
+        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(len(rows), ROW_BYTES)[rows["episode"] != -1].view(STATE_DTYPE).reshape(-1)
+        names = ("%s.part%05d.npy" % (self.stem, self.part), "%s.episodes.part%05d.npy" % (self.stem, self.part))
+        np.save(names[0], rows)
+        np.save(names[1], np.ascontiguousarray(episodes[:n_done]))
+        self.part += 1
+        return names
+
+
+class EpisodeRecorder:
+    """DataSaver for a batch: add(agent, game) right after agent.play(), advance(game) right after game.play(action) and
+    before game.reset('ended'), close() at the end.
+
+    Device: a ring of ring_moves x G State rows, a `done` buffer of ring_moves x G episode rows (a slot ends at most once a move,
+    so it cannot overflow between two flushes), the per-slot state and the counters.  add() and advance() are one kernel launch
+    each.  When the ring is full (and at close()) a FLUSH copies ring, done buffer and counters into one of two pinned host
+    buffers with stream-ordered asynchronous copies followed by an event, and clears n_done on the device; nothing waits.  The
+    host makes files of a pinned buffer only when it needs that buffer again, two flushes later, or at close(); the event's
+    synchronize() is then the only wait there is, on work enqueued 2 x ring_moves moves before."""
+
+    def __init__(self, save_dir, save_file, cycle, n_games, ring_moves=64, device="cuda"):
+        import torch
+        from . import _lib
+        if int(n_games) < 1 or int(ring_moves) < 1:
+            raise ValueError("n_games and ring_moves must be at least 1")
+        self.L = _lib.lib()
+        self.torch, self._check = torch, _lib.check
+        self.cycle, self.G, self.ring_moves = int(cycle), int(n_games), int(ring_moves)
+        self.device = torch.device(device)
+        rank = None
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            rank = torch.distributed.get_rank()
+        self.writer = ShardWriter(save_dir, save_file, cycle, rank)
+        self.cap = self.ring_moves * self.G
+        dev = self.device
+        self.ring = torch.zeros(self.cap * ROW_BYTES, dtype=torch.uint8, device=dev)
+        self.done = torch.zeros(self.cap * DONE_BYTES, dtype=torch.uint8, device=dev)
+        self.slot_state = torch.zeros(self.G, SLOT_DW, dtype=torch.int32, device=dev)
+        self.counters = torch.zeros(2, dtype=torch.int32, device=dev)
+        self._act = torch.zeros(self.G, dtype=torch.int32, device=dev)
+        # a pinned buffer: the ring, the done buffer, then the counters
+        self._off_done = self.cap * ROW_BYTES
+        self._off_cnt = self._off_done + self.cap * DONE_BYTES
+        self._host = [torch.zeros(self._off_cnt + 8, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._pending = [None, None]         # per pinned buffer: (event, moves held)
+        self._flushes, self._pos, self.closed = 0, 0, False
+        self.files = []
+        self._check(self.L.tm_episode_init(self.G, self.writer.next_id, self._p(self.slot_state), self._p(self.counters),
+                                           self._stream()), "tm_episode_init")
+
+    def _stream(self):
+        return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
+
+    @staticmethod
+    def _p(t, offset=0):
+        return C.c_void_p(t.data_ptr() + offset)
+
+    def add(self, agent=None, game=None, action=None):
+        """Record this move of every game: call after agent.play() (the statistics are the store's root_stats buffers as the
+        last get_action() left them) and before game.play().  `action`: what is actually played where that is not the agent's
+        choice (an int, an array or a tensor of n_games)."""
+        store = getattr(agent, "store", None)
+        if store is None or game is None:
+            raise TypeError("EpisodeRecorder.add needs a TreeAgent (with its store built) and the game")
+        torch = self.torch
+        if store.n_games != self.G or game.n_games != self.G:
+            raise ValueError("the recorder was made for %d games" % self.G)
+        if self._pos == self.ring_moves:
+            self._flush()
+        act = store.action_buf
+        if action is not None:
+            if torch.is_tensor(action):
+                self._act.copy_(action.to(torch.int32).reshape(-1), non_blocking=True)
+            else:
+                self._act.copy_(torch.from_numpy(np.array(np.broadcast_to(np.asarray(action, np.int32).reshape(-1), (self.G,)))))
+            act = self._act
+        self._check(self.L.tm_episode_record(C.byref(game.s), C.byref(store.s), self._p(store.stats_buf), self._p(act), self.cycle,
+                                             self._p(self.slot_state), self._p(self.ring, self._pos * self.G * ROW_BYTES),
+                                             self._stream()), "tm_episode_record")
+        self._pos += 1
+
+    def advance(self, game):
+        """Number the episodes: call after game.play(action) and before ended games are reset."""
+        self._check(self.L.tm_episode_advance(C.byref(game.s), self.cycle, self._p(self.slot_state), self._p(self.counters),
+                                              self._p(self.done), self.cap, self._stream()), "tm_episode_advance")
+        if self._pos == self.ring_moves:
+            self._flush()
+
+    def _flush(self):
+        k = self._flushes % 2
+        self._drain(k)                       # the buffer's earlier contents become files first
+        host, n = self._host[k], self._pos * self.G * ROW_BYTES
+        host[:n].copy_(self.ring[:n], non_blocking=True)
+        host[self._off_done:self._off_cnt].copy_(self.done, non_blocking=True)
+        host[self._off_cnt:].copy_(self.counters.view(self.torch.uint8), non_blocking=True)
+        self.counters[1:].zero_()            # the done buffer starts over (stream-ordered, after the copy)
+        ev = self.torch.cuda.Event()
+        ev.record()
+        self._pending[k] = (ev, self._pos)
+        self._flushes += 1
+        self._pos = 0
+
+    def _drain(self, k):
+        if self._pending[k] is None:
+            return
+        ev, moves = self._pending[k]
+        self._pending[k] = None
+        ev.synchronize()
+        buf = self._host[k].numpy()
+        rows = buf[:moves * self.G * ROW_BYTES].view(STATE_DTYPE)
+        episodes = buf[self._off_done:self._off_cnt].view(EPISODE_DTYPE)
+        n_done = int(buf[self._off_cnt:].view(np.int32)[1])
+        self.files.append(self.writer.write(rows, episodes, n_done, self.cap))
+
+    def close(self):
+        """flush the partial ring and write every copy that is still held"""
+        if self.closed:
+            return
+        self.closed = True
+        if self._pos:
+            self._flush()
+        for k in (self._flushes % 2, (self._flushes + 1) % 2):      # the older copy first: parts are in the order of the moves
+            self._drain(k)
+
+
+def _concat(tables, dtype):
+    """the tables one after the other IN `dtype` (np.concatenate would pack the fields and lose the row's layout)"""
+    for t in tables:
+        if t.dtype != dtype:
+            raise ValueError("a shard of another layout: %s" % (t.dtype,))
+    raw = [np.ascontiguousarray(t).view(np.uint8).reshape(len(t), dtype.itemsize) for t in tables]
+    return np.concatenate(raw + [np.zeros((0, dtype.itemsize), np.uint8)]).view(dtype).reshape(-1)
+
+
+def _expand(list_of_files):
+    """state shards named directly, or through a stem; in the order (stem, part)"""
+    if isinstance(list_of_files, (str, os.PathLike)):
+        list_of_files = [list_of_files]
+    out = []
+    for f in map(str, list_of_files):
+        if ".episodes.part" in f:
+            continue
+        out.extend([f] if _PART.search(f) else _parts(f))
+    key = lambda f: (_PART.sub("", f), int(_PART.search(f).group(1)))  # noqa: E731
+    return sorted(dict.fromkeys(out), key=key)
+
+
+class EpisodeLoader:
+    """The reference's DataLoader (util/Data.py:135-183) over shards: every column a concatenated attribute, `length`, the get*
+    accessors; `.episodes` the table of ended episodes that goes with the shards.  list_of_files: state shards or stems.
+    by_episode: rows stable-sorted by (cycle, episode, move), so that an episode's rows are contiguous and in order, as the
+    reference's consumers assume; False: the order of the files (move-major, slot-minor)."""
+
+    def __init__(self, list_of_files, by_episode=True):
+        self.files = _expand(list_of_files)
+        rows = _concat([np.load(f) for f in self.files], STATE_DTYPE)
+        if by_episode:
+            order = np.lexsort((rows["move"], rows["episode"], rows["cycle"]))           # (lexsort is stable)
+            rows = rows.view(np.uint8).reshape(len(rows), ROW_BYTES)[order].view(STATE_DTYPE).reshape(-1)
+        self.rows = rows
+        for c in STATE_DTYPE.names:
+            setattr(self, c, np.ascontiguousarray(rows[c]))
+        self.length = len(rows)
+        ep_files = [f for f in (_PART.sub(lambda m: ".episodes" + m.group(0), s) for s in self.files) if os.path.exists(f)]
+        self.episodes = _concat([np.load(f) for f in ep_files], EPISODE_DTYPE)
+
+    def bound_index(self, index):
+        return min(max(index, 0), self.length - 1)
+
+    def getBoard(self, index):
+        return self.board[self.bound_index(index)]
+
+    def getPolicy(self, index):
+        return self.policy[self.bound_index(index)]
+
+    def getCycle(self, index):
+        return self.cycle[self.bound_index(index)]
+
+    def getScore(self, index):
+        return self.score[self.bound_index(index)]
+
+    def getLines(self, index):
+        return self.lines[self.bound_index(index)]
+
+    def getCombo(self, index):
+        return self.combo[self.bound_index(index)]
