@@ -350,6 +350,38 @@ int tm_episode_record(const tm_store *env, const tm_store *tree, const float *st
                       int32_t *slot_state, void *rows, void *stream);
 int tm_episode_advance(const tm_store *env, int cycle, int32_t *slot_state, int32_t *counters, void *done, int cap, void *stream);
 
+/* Training targets from recorded episodes (episode_targets.hip; the reference's train.py:81-131).  rows: n_rows State rows on the
+ * device in ANY order (file order - move-major, slot-minor - is the normal case; they are read in place, 4-byte aligned).
+ * order: int32 [n_rows]; seg: int32 [n_seg + 1]: segment e is the sorted positions seg[e] .. seg[e+1]-1, and rows[order[j]] over
+ * them is one episode in ascending move order.  Per segment a tail: tail_kind u8 (1: one virtual element (tail_score, tail_value)
+ * follows the episode's last row - an episode that ended, its FINAL score, value 0; 0: nothing follows), tail_score i32,
+ * tail_value f32.  Outputs by sorted position j: value[j], variance[j], weight[j], float32.
+ * With s_k the row's score (int) and v_k its value column over the series k = 0 .. (the tail included if there is one):
+ *   mode 0 (Monte Carlo): value_i = s_end - s_i, s_end the tail's score, without a tail the last row's; integer arithmetic,
+ *       converted to float once.
+ *   mode 1 (lambda-return): value_i = sum_k lambda^k (s_{i+k} + v_{i+k} - s_i) / sum_k lambda^k over k = 0 .. end of the series,
+ *       accumulated in fp64 (N_i = v_i + lambda (N_{i+1} + B_{i+1} (s_{i+1} - s_i)), B_i = 1 + lambda B_{i+1}, value_i = N_i / B_i)
+ *       and rounded to fp32 once; lambda = 0 gives v_i, lambda = 1 the plain mean.
+ *   mode 2: value_i = v_i, the bits copied.
+ * variance[j]: the row's variance column, the bits copied, in every mode.  weight[j] by weight_mode: 0: 1; 1: 1.0f / (variance +
+ * eps), IEEE fp32; 2: the seven visits child_stats[0][a] added in index order; 3: that sum / (variance + eps).  Nothing is
+ * normalised (the fit divides the weights by their mean).
+ * An order[j] outside [0, n_rows) is never made an address: position j gets value = variance = weight = 0, *fault = 1 (a device
+ * int32 the caller cleared; a plain store), and the position is left out of its episode's series.  seg entries outside
+ * [0, n_rows] are clamped and set *fault as well.
+ * tm_episode_gather_states: out float32 [n][200] (16-byte aligned) = the board cells of rows[idx[k]], the int8 values the row
+ * holds; an idx[k] outside [0, n_rows) gives a board of zeros and *fault = 1.
+ * Both enqueue one kernel on stream and make no other HIP call; they write nothing outside their outputs and *fault, use no
+ * atomics and are deterministic.  hipErrorInvalidValue, nothing launched, for n_rows < 0, n_seg < 0, n < 0, a mode outside 0..2,
+ * a weight_mode outside 0..3, a lambda outside [0, 1] (a NaN included), and - when there is work - a NULL pointer or a misaligned
+ * rows / out; n_rows == 0, n_seg == 0 or n == 0 returns 0 and launches nothing.  All checked before the first HIP call.
+ * Run on an MI355X against a numpy statement of these definitions and an exact oracle (tests/test_gpu_offline.py) and timed there
+ * (profiles/offline_targets_timing.json); a table of more than 2^31 - 64 rows is refused and has not been run. */
+int tm_episode_targets(const void *rows, int n_rows, const int32_t *order, const int32_t *seg, int n_seg, const uint8_t *tail_kind,
+                       const int32_t *tail_score, const float *tail_value, int mode, double lambda, int weight_mode, float eps,
+                       float *value, float *variance, float *weight, int32_t *fault, void *stream);
+int tm_episode_gather_states(const void *rows, int n_rows, const int32_t *idx, int n, float *out, int32_t *fault, void *stream);
+
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel
  * workgroup's games; the groups of TM_GS_GC_ACTIVE4): hipErrorInvalidValue otherwise. */

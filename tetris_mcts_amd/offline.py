@@ -1,0 +1,371 @@
+"""Offline training from recorded episodes: the middle of the reference's play-then-train cycle (train.py:64-176, cycle.sh).
+
+`play.py --save` leaves State rows in FILE order - move-major, slot-minor, an episode's rows n_games rows apart - and a table of
+the episodes that ended (episodes.py).  This module turns them into what `Model_VV.train_data` takes, [states, values, variances,
+weights], with the targets that only episodes can give: the realised return and the lambda-return along the moves played.
+
+The rows go to the device once, as they are.  `episode_index` finds the episodes from the int columns alone (two stable sorts of
+int64 keys; the 368-byte rows never move), `episode_targets` computes value / variance / weight per sorted position
+(csrc/episode_targets.hip: tm_episode_targets), and `training_set` gathers the 200 board bytes of the rows that will train
+(tm_episode_gather_states).  With CPU tensors `episode_index` runs the same torch statements on the host, and
+`episode_targets(..., device="cpu")` is a numpy statement of the same definitions in fp64 - one backward pass, all episodes at
+once.  That statement is the specification: tests/test_offline.py holds it to exact rationals, tests/test_gpu_offline.py holds
+the kernel to it.
+
+The three target rules are the reference's (train.py:81-131):
+    mode 0  not --td              value_i = s_end - s_i                       (Monte Carlo; integer arithmetic)
+    mode 1  --td with a trace     value_i = sum_k lam^k (s_{i+k} + v_{i+k} - s_i) / sum_k lam^k       (the lambda-return)
+    mode 2  --td                  value_i = v_i                               (the search's own estimate)
+Where the reference's `_v` is sum(n q) / sum(n) over a child_stats row that does not exist, v is the recorded root value.
+`terminal="final"` appends to an episode that ended one virtual element (its FINAL score from the episode table, value 0): the
+State rows carry the score before the last action, so without it the last action's points are lost.  `terminal="rows"` is the
+reference's rule - no such element anywhere, the last row is the end.  An episode without a row in the episode table was cut off
+by the end of the run: it is CENSORED.  In mode 1 it has no tail and its last row's value bootstraps the rest; in mode 0
+`censored="drop"` leaves its rows out and `censored="keep"` takes its last row as the end (the reference's rule).
+Weights: the reference applies --weighted only to mode 2; here the four rules apply in every mode.  weight_mode of the C call =
+0 without --weighted, else --weighted_mode + 1.  The reference divides the visits by their mean; `train_data` divides whatever
+weights it is given by their mean, so nothing here normalises.
+"""
+import ctypes as C
+import glob
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .episodes import EPISODE_DTYPE, ROW_BYTES, STATE_DTYPE, _PART, _concat, _parts
+
+EPS = 0.001                    # train.py:10
+ROW_DW = ROW_BYTES // 4
+COL = dict(episode=0, cycle=1, move=3, board=41)      # dword offsets of a row (include/tetris_mcts_hip.h)
+
+EpisodeIndex = namedtuple("EpisodeIndex", "order seg ended final_score stem cycle episode")
+EpisodeIndex.__doc__ = """order int32 [n]: rows[order[j]] is sorted by (stem, cycle, episode, move); seg int32 [n_seg + 1]: episode e is
+the sorted positions seg[e] .. seg[e+1]-1; ended bool [n_seg]: the episode table has a row for it; final_score int32 [n_seg]: that
+row's score (0 where censored); stem, cycle, episode int32 [n_seg]: the episode's key.  Tensors on the rows' device."""
+
+
+def rows_tensor(rows, device=None):
+    """State rows as a uint8 tensor [n, 368]: a numpy STATE_DTYPE table (one copy, to `device`) or such a tensor already."""
+    if torch.is_tensor(rows):
+        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != ROW_BYTES or not rows.is_contiguous():
+            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % ROW_BYTES)
+        return rows if device is None else rows.to(device)
+    rows = np.asarray(rows)
+    if rows.dtype != STATE_DTYPE:
+        raise ValueError("rows: a table of STATE_DTYPE, not %s" % (rows.dtype,))
+    t = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(len(rows), ROW_BYTES))
+    return t if device is None else t.to(device)
+
+
+def _unsigned(x):
+    """an int32 column as an int64 in [0, 2^32) that sorts as the int32 does"""
+    return x.to(torch.int64) + (1 << 31)
+
+
+def episode_index(rows, stem_rows=None, episodes=None, episode_stems=None):
+    """Find the episodes.  rows: uint8 tensor [n, 368] on any device, in any order (rows_tensor).  stem_rows: how many rows each
+    stem contributed, in the order they were concatenated (None: one stem) - ids under `.r<rank>` stems are rank-local, so the
+    stem's number is part of the key (stem, cycle, episode, move).  episodes: the EPISODE_DTYPE table of the episodes that ended
+    (numpy, host), episode_stems: the stem number of each of its rows (None: stem 0)."""
+    dev, n = rows.device, rows.shape[0]
+    if n > (1 << 31) - 64:
+        raise ValueError("at most 2^31 - 64 rows")
+    cols = rows.view(torch.int32).view(n, ROW_DW)
+    stem_rows = [n] if stem_rows is None else [int(c) for c in stem_rows]
+    if sum(stem_rows) != n or min(stem_rows, default=0) < 0:
+        raise ValueError("stem_rows must add up to the %d rows" % n)
+    stem = torch.repeat_interleave(torch.arange(len(stem_rows), dtype=torch.int64, device=dev),
+                                   torch.tensor(stem_rows, dtype=torch.int64, device=dev), output_size=n)
+    lo = (_unsigned(cols[:, COL["episode"]]) << 32) | _unsigned(cols[:, COL["move"]])
+    hi = (stem << 32) | _unsigned(cols[:, COL["cycle"]])
+    o1 = torch.sort(lo, stable=True).indices
+    order = o1[torch.sort(hi[o1], stable=True).indices]
+    key = torch.stack([stem[order], cols[:, COL["cycle"]][order].to(torch.int64), cols[:, COL["episode"]][order].to(torch.int64)], 1)
+    first = torch.ones(n, dtype=torch.bool, device=dev)
+    if n > 1:
+        first[1:] = (key[1:] != key[:-1]).any(1)
+    starts = torch.nonzero(first).flatten()
+    seg = torch.cat([starts, torch.tensor([n], dtype=torch.int64, device=dev)]).to(torch.int32)
+    seg_key = key[starts]
+    n_seg = seg_key.shape[0]
+    ended = torch.zeros(n_seg, dtype=torch.bool, device=dev)
+    final = torch.zeros(n_seg, dtype=torch.int32, device=dev)
+    if episodes is not None and len(episodes) and n_seg:
+        if episodes.dtype != EPISODE_DTYPE:
+            raise ValueError("episodes: a table of EPISODE_DTYPE, not %s" % (episodes.dtype,))
+        es = np.zeros(len(episodes), np.int64) if episode_stems is None else np.asarray(episode_stems, np.int64)
+        tab = torch.from_numpy(np.stack([es, episodes["cycle"].astype(np.int64), episodes["episode"].astype(np.int64)], 1)).to(dev)
+        score = torch.from_numpy(np.ascontiguousarray(episodes["score"]).astype(np.int32)).to(dev)
+        # one id per distinct (stem, cycle, episode) over both lists; the table's score filed under its id
+        ids = torch.unique(torch.cat([seg_key, tab]), dim=0, return_inverse=True)[1]
+        n_ids = int(ids.max().item()) + 1
+        have = torch.zeros(n_ids, dtype=torch.bool, device=dev)
+        by_id = torch.zeros(n_ids, dtype=torch.int32, device=dev)
+        have[ids[n_seg:]] = True
+        by_id[ids[n_seg:]] = score
+        ended, final = have[ids[:n_seg]], by_id[ids[:n_seg]]
+    return EpisodeIndex(order.to(torch.int32), seg, ended, final, seg_key[:, 0].to(torch.int32), seg_key[:, 1].to(torch.int32),
+                        seg_key[:, 2].to(torch.int32))
+
+
+def target_mode(td, lam):
+    """(mode, lambda) of tm_episode_targets for the command line's --td / --td_lambda"""
+    if not td:
+        return 0, 0.0
+    if lam is None:
+        return 2, 0.0
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lam (--td_lambda) is in [0, 1], not %r" % (lam,))
+    return 1, lam
+
+
+def weight_mode(weighted, weighted_mode):
+    if not weighted:
+        return 0
+    if weighted_mode not in (0, 1, 2):
+        raise ValueError("weighted_mode: 0 inverse of variance, 1 number of visits, 2 both; not %r" % (weighted_mode,))
+    return int(weighted_mode) + 1
+
+
+def targets_numpy(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam, wmode, eps=EPS):
+    """The specification of tm_episode_targets in numpy (include/tetris_mcts_hip.h): fp64, ONE backward pass in which step t
+    handles the t-th row from the end of every episode that has one.  rows: STATE_DTYPE table.  Returns value, variance, weight
+    (float32, by sorted position) and fault (0 / 1)."""
+    n_rows, n = len(rows), len(order)
+    order, seg = np.asarray(order, np.int64), np.clip(np.asarray(seg, np.int64), 0, n_rows)
+    fault = int((np.asarray(seg) != seg).any())
+    ok = (order >= 0) & (order < n_rows)
+    covered = np.zeros(n, bool)
+    for a, b in zip(seg[:-1], seg[1:]):
+        covered[a:b] = True
+    fault |= int((~ok & covered).any())
+    safe = np.where(ok, order, 0)
+    zero = np.float32(0)
+    s = np.where(ok, rows["score"][safe].astype(np.int64), 0) if n_rows else np.zeros(n, np.int64)
+    v32 = np.where(ok, rows["value"][safe], zero) if n_rows else np.zeros(n, np.float32)
+    variance = np.where(ok, rows["variance"][safe], zero).astype(np.float32) if n_rows else np.zeros(n, np.float32)
+    value = np.zeros(n, np.float32)
+    first, last = seg[:-1], seg[1:]
+    tail = np.asarray(tail_kind) == 1
+    if mode == 2:
+        value = v32.astype(np.float32)
+    else:
+        lam = float(lam)
+        N = np.where(tail, np.asarray(tail_value, np.float64), 0.0)
+        B = np.where(tail, 1.0, 0.0)
+        s_next = np.where(tail, np.asarray(tail_score, np.int64), 0)          # the score of the next element that exists ...
+        has = tail.copy()                                                     # ... if there is one (mode 0: the end is known)
+        for t in range(int((last - first).max(initial=0))):
+            live = np.nonzero(last - first > t)[0]
+            j = last[live] - 1 - t
+            good = ok[j]
+            e, j = live[good], j[good]
+            if mode == 0:
+                s_next[e] = np.where(has[e], s_next[e], s[j])                 # without a tail the last row that exists is the end
+                has[e] = True
+                value[j] = (s_next[e] - s[j]).astype(np.float32)
+            else:
+                d = np.where(has[e], s_next[e] - s[j], 0).astype(np.float64)
+                Ne = v32[j].astype(np.float64) + lam * (N[e] + B[e] * d)
+                Be = 1.0 + lam * B[e]
+                value[j] = (Ne / Be).astype(np.float32)
+                N[e], B[e], s_next[e], has[e] = Ne, Be, s[j], True
+    one = np.float32(1)
+    if wmode >= 2:
+        st = rows["child_stats"][safe][:, 0, :] if n_rows else np.zeros((n, 7), np.float32)
+        weight = st[:, 0].astype(np.float32)
+        for a in range(1, 7):
+            weight = weight + st[:, a]
+    else:
+        weight = np.full(n, one, np.float32)
+    if wmode in (1, 3):
+        with np.errstate(all="ignore"):
+            weight = weight / (variance + np.float32(eps))
+    value, weight = np.where(ok, value, zero), np.where(ok, weight, zero)
+    value[~covered], variance[~covered], weight[~covered] = 0, 0, 0          # (the call leaves them alone: callers cover every row)
+    return value.astype(np.float32), variance, weight.astype(np.float32), fault
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def targets_device(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam, wmode, eps=EPS):
+    """tm_episode_targets on the rows' device, on the current stream; returns value, variance, weight and the fault word
+    (device tensors: nothing is read back here)."""
+    from . import _lib
+    dev, n = rows.device, order.shape[0]
+    value, variance, weight = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(3))
+    fault = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().tm_episode_targets(
+            _ptr(rows), rows.shape[0], _ptr(order), _ptr(seg), seg.shape[0] - 1, _ptr(tail_kind), _ptr(tail_score), _ptr(tail_value),
+            int(mode), float(lam), int(wmode), float(eps), _ptr(value), _ptr(variance), _ptr(weight), _ptr(fault),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tm_episode_targets")
+    return value, variance, weight, fault
+
+
+def gather_states(rows, idx):
+    """float32 [n, 1, 20, 10]: the boards of rows[idx] (tm_episode_gather_states on a GPU, numpy indexing on the host)"""
+    n = idx.shape[0]
+    if not rows.is_cuda:
+        board = rows[:, 4 * COL["board"]:4 * COL["board"] + 200].view(torch.int8)
+        return board[idx.to(torch.int64)].to(torch.float32).reshape(n, 1, 20, 10)
+    from . import _lib
+    idx = idx.to(torch.int32).contiguous()
+    out = torch.empty(n, 1, 20, 10, dtype=torch.float32, device=rows.device)
+    fault = torch.zeros(1, dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.lib().tm_episode_gather_states(_ptr(rows), rows.shape[0], _ptr(idx), n, _ptr(out), _ptr(fault),
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "tm_episode_gather_states")
+    if int(fault.item()):
+        raise RuntimeError("tm_episode_gather_states: an index outside the %d rows" % rows.shape[0])
+    return out
+
+
+def episode_targets(rows, index, td=False, lam=None, weighted=False, weighted_mode=0, terminal="final", censored="drop",
+                    device=None, eps=EPS):
+    """value, variance, weight (float32 tensors by SORTED position j, i.e. of rows[index.order[j]]) and `keep` (bool: False for
+    the rows `censored="drop"` leaves out).  td / lam / weighted / weighted_mode: the command line's (module docstring).
+    device: None - where the rows are; "cpu" - the numpy statement, whatever the rows' device."""
+    if terminal not in ("final", "rows"):
+        raise ValueError("terminal is 'final' or 'rows', not %r" % (terminal,))
+    if censored not in ("drop", "keep"):
+        raise ValueError("censored is 'drop' or 'keep', not %r" % (censored,))
+    mode, lam = target_mode(td, lam)
+    wmode = weight_mode(weighted, weighted_mode)
+    rows = rows_tensor(rows)
+    on = rows.device if device is None else torch.device(device)
+    n, n_seg = index.order.shape[0], index.ended.shape[0]
+    tail_kind = (index.ended if terminal == "final" else torch.zeros_like(index.ended)).to(torch.uint8)
+    tail_value = torch.zeros(n_seg, dtype=torch.float32, device=tail_kind.device)
+    if on.type == "cpu":
+        table = rows.cpu().numpy().reshape(-1).view(STATE_DTYPE)
+        value, variance, weight, fault = targets_numpy(table, index.order.cpu().numpy(), index.seg.cpu().numpy(), tail_kind.cpu().numpy(),
+                                                       index.final_score.cpu().numpy(), tail_value.cpu().numpy(), mode, lam, wmode, eps)
+        value, variance, weight = (torch.from_numpy(x) for x in (value, variance, weight))
+    else:
+        rows, order, seg, tail_kind, final, tail_value = (t.to(on).contiguous() for t in (rows, index.order, index.seg, tail_kind,
+                                                                                         index.final_score, tail_value))
+        value, variance, weight, fault = targets_device(rows, order, seg, tail_kind, final, tail_value, mode, lam, wmode, eps)
+        fault = int(fault.item())
+    if fault:
+        raise RuntimeError("episode_targets: the index names rows outside the %d given" % rows.shape[0])
+    keep = torch.ones(n, dtype=torch.bool, device=value.device)
+    if mode == 0 and censored == "drop" and n_seg:
+        length = (index.seg[1:] - index.seg[:-1]).to(torch.int64)
+        keep = torch.repeat_interleave(index.ended, length, output_size=n).to(value.device)
+    return value, variance, weight, keep
+
+
+def choose_stems(paths, last_nfiles=1):
+    """train.py:68-77 over stems: every path is a glob pattern (or a stem, or a directory of shards); what it matches is mapped to
+    stems - one "file" is one stem, whatever the number of its parts - which are ordered by the time their newest State shard was
+    written; the last `last_nfiles` are kept (<= 0: all)."""
+    if isinstance(paths, (str, os.PathLike)):
+        paths = [paths]
+    shard = ".part[0-9][0-9][0-9][0-9][0-9].npy"
+    stems = []
+    for p in map(str, paths):
+        found = []
+        for f in glob.glob(p) or glob.glob(glob.escape(p) + shard):
+            found += glob.glob(os.path.join(glob.escape(f), "*" + shard)) if os.path.isdir(f) else [f]
+        stems += [_PART.sub("", f).removesuffix(".episodes") for f in found if _PART.search(f)]
+    stems = [s for s in dict.fromkeys(stems) if _parts(s)]
+    stems.sort(key=lambda s: (max(os.path.getmtime(f) for f in _parts(s)), s))
+    if last_nfiles > 0:
+        stems = stems[-last_nfiles:]
+    if not stems:
+        raise RuntimeError("list_of_data is empty.")
+    return stems
+
+
+def load_stems(stems):
+    """the State rows of the stems one after the other in file order, how many each has, their episode tables as one and the stem
+    number of each of its rows"""
+    tables = [[np.load(f) for f in _parts(s)] for s in stems]
+    ep = [_concat([np.load(f) for f in _parts(s, episodes=True)], EPISODE_DTYPE) for s in stems]
+    rows = _concat([t for ts in tables for t in ts], STATE_DTYPE)
+    return (rows, [sum(len(t) for t in ts) for ts in tables], _concat(ep, EPISODE_DTYPE),
+            np.concatenate([np.full(len(e), i, np.int64) for i, e in enumerate(ep)] + [np.zeros(0, np.int64)]))
+
+
+def validation_fraction(n, n_val):
+    """a fraction for which train_data's own split, int(n * fraction), is n_val exactly"""
+    if n_val == 0 or n == 0:
+        return 0.0
+    f = (n_val + 0.5) / n
+    assert int(n * f) == n_val, (n, n_val)
+    return f
+
+
+def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, terminal="final", censored="drop", last_nfiles=1,
+                 validation=False, val_mode=0, val_episodes=0, val_set_size=0.05, val_set_size_max=-1, generator=None,
+                 device="cuda", eps=EPS):
+    """data = [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (float32 on `device`), training rows first and
+    the held-out rows last - the layout train_data splits - and a dict with n_val, validation_fraction (train_data's
+    int(n * fraction) is n_val exactly), n_train, the stems and the row counts.  Files as train.py --data_paths / --last_nfiles
+    chooses them (choose_stems).  validation: train.py:148-174 - val_mode 0 holds out a random int(n * val_set_size) rows (at most
+    val_set_size_max if that is positive; `generator`: a torch.Generator for the draw), val_mode 1 whole episodes with
+    episode < val_episodes + 1 (a random val_set_size_max of their rows if that is positive)."""
+    stems = choose_stems(paths, last_nfiles)
+    table, stem_rows, episodes, episode_stems = load_stems(stems)
+    dev = torch.device(device)
+    rows = rows_tensor(table, dev)
+    index = episode_index(rows, stem_rows, episodes, episode_stems)
+    value, variance, weight, keep = episode_targets(rows, index, td=td, lam=lam, weighted=weighted, weighted_mode=weighted_mode,
+                                                    terminal=terminal, censored=censored, eps=eps)
+    n_all = keep.shape[0]
+    held = torch.zeros(n_all, dtype=torch.bool, device=dev)
+    if validation and val_mode == 1 and val_episodes > 0:
+        length = (index.seg[1:] - index.seg[:-1]).to(torch.int64)
+        held = torch.repeat_interleave(index.episode < val_episodes + 1, length, output_size=n_all) & keep
+    pos = torch.nonzero(keep & ~held).flatten()
+    val = torch.nonzero(held).flatten()
+
+    def draw(k):
+        g = generator.device if generator is not None else dev
+        return torch.randperm(k, generator=generator, device=g).to(dev)
+    if validation and val_mode == 0:
+        n = pos.shape[0]
+        n_val = 0 if val_set_size <= 0 else n if val_set_size >= 1 else int(n * val_set_size)
+        if val_set_size_max > 0 and 0 < val_set_size < 1:
+            n_val = min(n_val, val_set_size_max)
+        chosen = torch.zeros(n, dtype=torch.bool, device=dev)
+        chosen[draw(n)[:n_val]] = True
+        pos, val = pos[~chosen], pos[chosen]
+    elif validation and val_mode == 1:
+        if val_set_size_max > 0 and val.shape[0] > val_set_size_max:
+            val = val[torch.sort(draw(val.shape[0])[:val_set_size_max]).values]
+    elif validation:
+        raise ValueError("val_mode: 0 random, 1 episodic; not %r" % (val_mode,))
+    sel = torch.cat([pos, val])
+    n, n_val = int(sel.shape[0]), int(val.shape[0])
+    if n == 0:
+        raise RuntimeError("no rows to train on: every episode of %s is censored (censored='keep' takes them as they are)" % (stems,))
+    states = gather_states(rows, index.order[sel])
+    data = [states] + [x[sel].reshape(n, 1) for x in (value, variance, weight)]
+    return data, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
+                      rows=n_all, episodes=int(index.ended.shape[0]), censored_episodes=int((~index.ended).sum().item()))
+
+
+def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
+                 early_stopping_patience=10, fit_backend="torch", validation_backend="torch", **options):
+    """training_set(paths, **options) on the model's device, then model.train_data on it; returns what train_data returns.
+    max_iters and iters_per_val may be functions of the number of training rows (train.py computes its iterations from it)."""
+    from .model import Model_VV
+    if not isinstance(model, Model_VV):
+        raise TypeError("fit_episodes fits a Model_VV: the reference has no episode target for a distribution (%s)"
+                        % type(model).__name__)
+    data, info = training_set(paths, device=model.device, **options)
+    iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
+    extra = {}
+    if iters_per_val is not None:
+        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    return model.train_data(data, batch_size=batch_size, max_iters=iters, validation_fraction=info["validation_fraction"],
+                            shuffle=False, early_stopping=early_stopping, early_stopping_patience=early_stopping_patience,
+                            fit_backend=fit_backend, validation_backend=validation_backend, **extra)

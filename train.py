@@ -1,0 +1,118 @@
+#!/usr/bin/env python
+"""train.py — the offline fit with the command line of the reference's train.py (flags: train.py:15-39), on the MI355X engine:
+the middle of cycle.sh's loop.  `play.py --save` writes a cycle's episodes, this fits the value net to them
+(tetris_mcts_amd/offline.py: targets on the device from the rows as recorded, csrc/episode_targets.hip) and writes
+pytorch_model/model_checkpoint, which the next play.py loads.
+
+The reference's script does not run as committed (`backend`, `eligibility_trace` and `eligibility_trace_lambda` are undefined and
+it reads row 3 of a 3-row child_stats), so what is kept is its intent: its flags, its file choice, its three target rules, its
+validation split and its iteration count.  `--td_lambda` stands for its eligibility trace: without it `--td` fits the recorded
+root values, with it the lambda-return.  --ewc and --save_loss are refused with a message.
+"""
+import argparse
+import sys
+
+
+def build_parser():
+    p = argparse.ArgumentParser()
+    add = p.add_argument
+    add('--batch_size', default=32, type=int, help='Batch size (default:32)')
+    add('--cycle', default=-1, type=int, help='Cycle (default:-1)')
+    add('--data_paths', default=[], nargs='*', help='Training data paths (default: empty list)')
+    add('--early_stopping', default=False, help='Use early stopping', action='store_true')
+    add('--early_stopping_patience', default=10, type=int, help='Early stopping patience (default:10)')
+    add('--epochs', default=10, type=int, help='Training epochs (default:10)')
+    add('--ewc', default=False, help='Elastic weight consolidation (default:False)', action='store_true')
+    add('--last_nfiles', default=1, type=int, help='Use last n files in training only (default:1, -1 for all)')
+    add('--min_iters', default=-1, type=int, help='Min training iterations (default:-1, negative for unlimited)')
+    add('--max_iters', default=-1, type=int, help='Max training iterations (default:-1, negative for unlimited)')
+    add('--new', default=False, help='Create a new model instead of training the old one', action='store_true')
+    add('--validation', default=False, help='Validation set (default:False)', action='store_true')
+    add('--val_episodes', default=0, type=float, help='Number of validation episodes (default:0)')
+    add('--val_mode', default=0, type=int, help='Validation mode (0: random, 1:episodic, default:0)')
+    add('--val_set_size', default=0.05, type=float, help='Validation set size (fraction of total) (default:0.05)')
+    add('--val_set_size_max', default=-1, type=int, help='Maximum validation set size (default:-1, negative for unlimited)')
+    add('--val_total', default=25, type=int, help='Total number of validations (default:25)')
+    add('--save_loss', default=False, help='Save loss history', action='store_true')
+    add('--td', default=False, help='Temporal difference update', action='store_true')
+    add('--weighted', default=False, help='Weighted loss', action='store_true')
+    add('--weighted_mode', default=0, type=int, help='0: inverse of variance, 1: number of visits, 2: both')
+    # extensions (not in the reference)
+    add('--td_lambda', default=None, type=float, help='[new] with --td: fit the lambda-return along the moves played (the '
+        'reference\'s eligibility trace), lambda in [0, 1]; without it --td fits the recorded root values')
+    add('--terminal', default='final', choices=('final', 'rows'), help='[new] final: an episode that ended ends with its FINAL '
+        'score from the episode table (value 0); rows: the reference\'s rule, the last recorded row is the end')
+    add('--censored', default='drop', choices=('drop', 'keep'), help='[new] without --td: the episodes the run cut off are left '
+        'out (drop) or end at their last row (keep, the reference\'s rule)')
+    add('--fit_backend', default='hip', choices=('torch', 'hip'), help='[new] gradients through PyTorch autograd (torch) or the '
+        'hand-written gfx950 forward / loss / backward kernels (hip)')
+    add('--validation_backend', default=None, choices=('torch', 'hip'), help='[new] validation through PyTorch (torch) or the '
+        'forward of the same gfx950 kernels (hip: needs --fit_backend hip); default: as --fit_backend')
+    return p
+
+
+def check_args(args):
+    """the refusals, before anything is imported or read"""
+    if args.ewc:
+        sys.exit('--ewc needs a Fisher pass over the training data (the reference\'s Model.compute_fisher), which this engine does '
+                 'not have: no elastic weight consolidation')
+    if args.save_loss:
+        sys.exit('--save_loss writes the reference\'s HDF5 loss table (util/Data.py LossSaver: PyTables), which this engine does '
+                 'not reimplement; the fit logs its losses to stderr')
+    if args.td_lambda is not None and not args.td:
+        sys.exit('--td_lambda is the trace of --td: it needs --td')
+    if args.td_lambda is not None and not 0.0 <= args.td_lambda <= 1.0:
+        sys.exit('--td_lambda is in [0, 1]')
+    if args.weighted_mode not in (0, 1, 2):
+        sys.exit('--weighted_mode: 0 inverse of variance, 1 number of visits, 2 both')
+    args.validation_backend = args.validation_backend or args.fit_backend
+    if args.validation_backend == 'hip' and args.fit_backend != 'hip':
+        sys.exit('--validation_backend hip reads the parameters of a HIP fit: it needs --fit_backend hip')
+    if args.early_stopping and not args.validation:
+        sys.exit('Early stopping without validation?')
+    if not args.data_paths:
+        sys.exit('list_of_data is empty: give --data_paths (what play.py --save wrote, e.g. data/self1/data*)')
+
+
+def iterations(args, n_data):
+    """train.py:193-203: (iterations, iterations between two validations)"""
+    iters_per_epoch = n_data // args.batch_size
+    iters = int(args.epochs * iters_per_epoch)
+    if args.max_iters >= 0:
+        iters = int(min(iters, args.max_iters))
+    if args.min_iters >= 0:
+        iters = int(max(iters, args.min_iters))
+    if args.early_stopping:
+        # the reference's early-stopping loop validates once an epoch until its patience runs out (train.py:246-277);
+        # --max_iters still bounds it here
+        return (args.max_iters if args.max_iters >= 0 else 100000), max(1, iters_per_epoch)
+    return iters, iters // args.val_total + 1
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    check_args(args)
+    from tetris_mcts_amd.model import Model_VV
+    from tetris_mcts_amd.offline import fit_episodes
+    model = Model_VV(backend='hip')
+    if not args.new:
+        model.load()
+    plan = {}
+
+    def max_iters(n_train):
+        plan['iters'], plan['val'] = iterations(args, n_train)
+        return plan['iters']
+    res = fit_episodes(model, args.data_paths, batch_size=args.batch_size, max_iters=max_iters, iters_per_val=lambda _: plan['val'],
+                       early_stopping=args.early_stopping, early_stopping_patience=args.early_stopping_patience,
+                       fit_backend=args.fit_backend, validation_backend=args.validation_backend,
+                       td=args.td, lam=args.td_lambda, weighted=args.weighted, weighted_mode=args.weighted_mode,
+                       terminal=args.terminal, censored=args.censored, last_nfiles=args.last_nfiles, validation=args.validation,
+                       val_mode=args.val_mode, val_episodes=args.val_episodes, val_set_size=args.val_set_size,
+                       val_set_size_max=args.val_set_size_max)
+    print('iters:%d/%d' % (res['iters'], plan['iters'])
+          + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
+    model.save()
+
+
+if __name__ == '__main__':
+    main()
