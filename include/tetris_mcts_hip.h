@@ -77,6 +77,10 @@ enum {
     TM_GS_LOW_NODE = 26, TM_GS_LOW_OBS,  /* lowest node / observation index ever allocated (GC skips untouched entries) */
     TM_GS_FIRST_MISS = 28, /* levels of the last walk that were taken over from the walk before it (verified in parallel, tree.hip) */
     TM_GS_PREFIX_SUM,      /* sum of TM_GS_FIRST_MISS over all simulations */
+    TM_GS_EVAL_ENTRY,      /* under a request cap (tm_store::eval_cap), TM_GS_PENDING == TM_PENDING_POSTED: the pending request's entry
+                              within its segment of the dense list, held against eval_served by the next launch */
+    TM_GS_N_EVAL_DEFERRED, /* requests posted again because the evaluator's launch left them out (TM_GS_N_EVAL counts a request once,
+                              when it is first posted) */
     /* garbage collection by the collector workgroups of tm_sim_step (a game that collects does not simulate; tree.hip) */
     TM_GS_GC_PHASE = 32, /* 0 none; (launch << 4) | 1 requested; 2 marking, 3 counting + re-inserting the kept nodes, 4 writing the free
                             lists + re-inserting the kept observations; (launch << 4) | 7 complete (the game resumes in a later
@@ -124,6 +128,9 @@ enum {
     TM_GS_GC_IDLE_TURNS        /* turns of that loop that found nothing flagged */
 };
 #define TM_GC_FLAG_WORDS 4
+/* TM_GS_PENDING: 0 no simulation under way; 1 the leaf is expanded, its requests posted, the backup is due; 2 suspended in the
+   expansion (a collection under way); TM_PENDING_POSTED as 1, under a request cap: the evaluator may have left the request out */
+#define TM_PENDING_POSTED 3
 /* error bits in TM_GS_ERR */
 #define TM_ERR_POOL 1      /* node pool exhausted even after reclaiming unreachable nodes */
 #define TM_ERR_TRACE 2     /* trace longer than max_trace */
@@ -232,6 +239,15 @@ typedef struct tm_store {
                               on; 0: the default (13).  More units serve more collections per launch and make the launch longer. */
     int32_t gc_collectors; /* collector workgroups per tm_sim_step launch (half for the bounded steps, half for the marking); 0: the
                               default (128), at most 128.  A collection must be continued by launches with the same number. */
+    /* the request cap (single-leaf kinds, eval_slots == 1, the built-in value net; tm_search_set_request_cap): the evaluator serves
+       the first eval_cap dense positions of a launch's list, counted through the segments cyclically from segment eval_rot (the
+       caller advances it every launch, so that no segment stands last every time), and writes eval_served[s] = the entries of
+       segment s among them.  The game of a request left out posts it again in the next tm_sim_step launch, does not back up and
+       owes a launch (tm_sims_owing).  eval_cap == 0: every request is served; eval_served == NULL: a store without the cap.
+       eval_cap changes between moves only (no request is pending there): launches under a cap run a kernel of their own. */
+    int32_t eval_cap;
+    int32_t eval_rot;      /* in [0, TM_EVAL_SEGS(n_games)) */
+    int32_t *eval_served;  /* [G] (segment s of the games of *this at [s]) */
 } tm_store;
 #define TM_EVAL_SEGS(n_games) ((n_games) < 64 ? (n_games) : 64)
 
@@ -413,6 +429,19 @@ int tm_search_set_epoch(tm_search *h, int epoch);
  * hipErrorInvalidValue, and nothing changed, for any other pair (tm_valuenet_check_mode).  The caller gives every mode's outputs
  * an epoch of their own (tm_search_set_epoch): obs_eval must not mix them (TM_KIND_DIST keeps no obs_eval). */
 int tm_search_set_valuenet(tm_search *h, int backend, int fc1);
+/* The request cap of tm_search_run (tm_store::eval_cap): the value net's two kernels step up in cost where a launch holds more
+ * requests than the convolution has resident waves, so the requests beyond that wait for the next launch and their games catch
+ * up at the end of the move like games that collected garbage.  A change of schedule only: every game's results are what they
+ * are without the cap.  cap = -1: off; 0: automatic (the default); > 0: that cap for every move (hipErrorInvalidValue where
+ * the store cannot carry one).  Automatic mode acts on a store of a single-leaf kind with eval_slots == 1, the built-in value
+ * net and n_sub == 1: cap = tm_valuenet_resident_states(), in force for a move when the move before it posted between
+ * TM_REQUEST_CAP_LOW x cap and TM_REQUEST_CAP_T x cap requests per simulation; the first move of a handle and the first move
+ * under other weights (tm_search_set_epoch) run without.  tm_search_stats: out[2], the catch-up launches, counts the launches
+ * the deferred games needed as well, out[11] the moves that ran under a cap. */
+int tm_search_set_request_cap(tm_search *h, int cap);
+#define TM_REQUEST_CAP_T 1.32   /* 1 + (cost of the value net's second round) / (cost of a full step): DESIGN.md section 3.6 */
+#define TM_REQUEST_CAP_LOW 0.95 /* below this many times cap no launch of the next move reaches the cap, and the capped tree kernel
+                                   costs a microsecond a launch over the other one: DESIGN.md section 3.6 */
 int tm_root_stats(const tm_store *s, float *stats /* [G][3][7] */, int32_t *action /* [G] */, void *stream);
 /* one game's tree in the reference's array layout (agents/agent.py:58-88), for inspection and tests */
 int tm_export_game(const tm_store *s, int game, int32_t *child /* [N][7] */, float *score, int32_t *n_to_o,
@@ -610,6 +639,15 @@ int tm_valuenet_forward_plain(const float *params, const int8_t *states, int n, 
  * round robin); workgroup b of `grid` takes items b, b + grid, ...  Writes the workgroup's (tile, part) pairs to
  * items[0 .. 2 * cap) and returns how many it takes (possibly more than cap); -1 on arguments that make no grid. */
 int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t *items, int cap);
+/* the states k_vn_conv takes in one round: its resident waves (two workgroups of four waves a compute unit); <= 0: no device */
+int tm_valuenet_resident_states(void);
+/* The request cap's arithmetic (host only, callable without a GPU; the kernels use the same formulas).  counts[segs] = the
+ * entries of the dense list's segments; a launch serves the first min(sum, cap) dense positions (cap == 0: all), counted
+ * through the segments cyclically from segment rot.  tm_request_served: served[s] = the entries of segment s among them
+ * (what k_vn_conv writes to tm_store::eval_served); returns their number.  tm_request_at: dense position p -> out = (segment,
+ * entry within it, index into eval_list at `slots` request slots a game); returns 0.  -1 on arguments that make no list. */
+int tm_request_served(const int32_t *counts, int segs, int rot, int cap, int32_t *served);
+int tm_request_at(const int32_t *counts, int segs, int rot, int slots, int p, int32_t *out);
 
 /* distributional value head (model/model_distributional.py:18-57 `Net`, Model_Dist.inference :100-107), the leaf evaluator
  * of TM_KIND_DIST: states int8 [n][200] (the 20 visible rows; the net's two extra rows on top are empty) -> softmax over

@@ -26,6 +26,7 @@ class TmStore(C.Structure):
         ("gc_spec_nodes", i32),
         ("eval_list", vp), ("eval_cnt", vp), ("obs_eval", vp), ("eval_parity", i32), ("eval_epoch", i32),
         ("replay_dist", vp), ("game_list", vp), ("n_listed", i32), ("gc_cost_units", i32), ("gc_collectors", i32),
+        ("eval_cap", i32), ("eval_rot", i32), ("eval_served", vp),
     ]
 
 
@@ -96,6 +97,10 @@ SYMBOLS = {
     "tm_search_stats": [vp, vp, i32, i32],
     "tm_search_set_epoch": [vp, i32],
     "tm_search_set_valuenet": [vp, i32, i32],
+    "tm_search_set_request_cap": [vp, i32],
+    "tm_valuenet_resident_states": [],
+    "tm_request_served": [vp, i32, i32, i32, vp],
+    "tm_request_at": [vp, i32, i32, i32, i32, vp],
 }
 
 _lib = None

@@ -44,9 +44,35 @@ struct tm_search {
     double tree_ms, nn_ms;
     long long n_timed, n_runs, extra_launches, launches, gc_launches;
     int vn_backend = TM_VALUENET_FP32, vn_fc1 = TM_VALUENET_FC1_FP32;   // tm_search_set_valuenet
+    // the request cap (tm_search_set_request_cap): -1 off, 0 automatic, > 0 that cap.  Automatic mode decides move by move from the
+    // requests the move before posted per regular launch (< 0: no move yet): the sum of TM_GS_N_EVAL over the games, read once
+    // at the end of every move
+    int cap_mode = 0;
+    long long capped_runs = 0;       // moves that ran under a cap (tm_search_stats)
+    double prev_requests = -1.0;
+    long long posted_before = -1;
+    unsigned long long* posted_dev = nullptr;
+    unsigned long long* posted_host = nullptr;
 };
 
+// sum of the games' TM_GS_N_EVAL (requests posted, each counted once) into *out (zeroed by the caller)
+static __global__ void k_posted_sum(tm_store S, unsigned long long* out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long v = g < S.n_games ? (unsigned long long)(unsigned)S.gs[(size_t)g * TM_GS_DW + TM_GS_N_EVAL] : 0ull;
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
+}
+
 #define TM_TRY(x) do { int e_ = (int)(x); if (e_ != 0) return e_; } while (0)
+
+// *h->posted_host = the games' requests posted so far (waits for the stream)
+static int posted_total(tm_search* h, hipStream_t stream) {
+    TM_TRY(hipMemsetAsync(h->posted_dev, 0, sizeof(unsigned long long), stream));
+    hipLaunchKernelGGL(k_posted_sum, dim3((h->full.n_games + 255) / 256), dim3(256), 0, stream, h->full, h->posted_dev);
+    TM_TRY(hipGetLastError());
+    TM_TRY(hipMemcpyAsync(h->posted_host, h->posted_dev, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+    return (int)hipStreamSynchronize(stream);
+}
 
 extern "C" {
 
@@ -85,6 +111,7 @@ int tm_store_slice(const tm_store* s, int first, int n, tm_store* out) {
     if (t.mt_state && (s->kind == TM_KIND_VANILLA || s->kind == TM_KIND_VANILLA_C)) t.mt_state += f * 625;
     t.eval_list += f * (size_t)s->eval_slots * 2;
     t.eval_cnt += f * 2;
+    if (t.eval_served) t.eval_served += f;
     if (t.obs_eval) t.obs_eval += f * N * 4;
     if (t.replay_dist) t.replay_dist += f * (size_t)s->replay_cap * TM_DIST_ROW;
     *out = t;
@@ -142,6 +169,10 @@ int tm_search_create(tm_search** out, const tm_store* s, int n_sub, int ev_every
     if (e != hipSuccess) return fail((int)e);
     e = hipMalloc(&h->owing_dev, sizeof(int32_t) * (size_t)(G > 0 ? G : 1));
     if (e != hipSuccess) return fail((int)e);
+    e = hipMalloc(&h->posted_dev, sizeof(unsigned long long));
+    if (e != hipSuccess) return fail((int)e);
+    e = hipHostMalloc(&h->posted_host, sizeof(unsigned long long), hipHostMallocDefault);
+    if (e != hipSuccess) return fail((int)e);
     *out = h;
     return 0;
 }
@@ -157,6 +188,8 @@ void tm_search_destroy(tm_search* h) {
     if (h->rem_dev) (void)hipFree(h->rem_dev);
     if (h->owing_dev) (void)hipFree(h->owing_dev);
     if (h->rem_host) (void)hipHostFree(h->rem_host);
+    if (h->posted_dev) (void)hipFree(h->posted_dev);
+    if (h->posted_host) (void)hipHostFree(h->posted_host);
     delete h;
 }
 
@@ -166,6 +199,31 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
                   void* stream_) {
     hipStream_t caller = (hipStream_t)stream_;
     const int K = h->n_sub;
+    // The request cap (include/tetris_mcts_hip.h, tm_search_set_request_cap): what the value net's launch leaves out waits for the
+    // next one, and the catch-up loop below picks the games up as it does those that collected garbage.  A store that can carry
+    // one: a single-leaf kind with one slot a game and the list's served counts, the built-in value net, one sub-batch.
+    const int kind = h->full.kind;
+    const bool can_cap = vn_params && K == 1 && h->full.eval_served && h->full.eval_slots == 1 &&
+                         (kind == TM_KIND_VALUESIM || kind == TM_KIND_CPPAGENT);
+    const bool watch = can_cap && h->cap_mode == 0;      // automatic mode: this move's requests decide for the next one
+    int cap = 0;
+    if (h->cap_mode > 0) {
+        if (!can_cap) return (int)hipErrorInvalidValue;
+        cap = h->cap_mode;
+    } else if (watch) {
+        const int resident = tm_valuenet_resident_states();
+        // (in force only where it can matter: a capped launch of the tree kernel looks at eval_served before anything else, a
+        //  microsecond that a move whose launches stay well under the cap would pay for nothing)
+        if (resident > 0 && h->prev_requests >= TM_REQUEST_CAP_LOW * resident && h->prev_requests < TM_REQUEST_CAP_T * resident)
+            cap = resident;
+    }
+    for (int k = 0; k < K; ++k) { h->sub[k].eval_cap = cap; h->sub[k].eval_rot = 0; }
+    h->capped_runs += cap > 0 ? 1 : 0;
+    if (watch && h->posted_before < 0) {
+        // the first move the handle watches: where the count stands before it (one more wait of the host, this once)
+        TM_TRY(posted_total(h, caller));
+        h->posted_before = (long long)*h->posted_host;
+    }
     TM_TRY(tm_move_begin(&h->full, sims, caller));
     std::vector<hipStream_t> st(K);
     for (int k = 0; k < K; ++k) st[k] = h->own_streams ? h->streams[k] : caller;
@@ -178,6 +236,8 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
         if (h->sub[k].n_games == 0) return 0;
         h->launches += 1;
         h->sub[k].eval_parity ^= 1;      // the dense request list: every launch appends under the other parity (tm_store::eval_list)
+        // (under a cap the evaluator counts from another segment every launch: no segment's games stand last every time)
+        if (cap > 0) h->sub[k].eval_rot = (h->sub[k].eval_rot + 1) % TM_EVAL_SEGS(h->sub[k].n_games);
         h->sub[k].game_list = owing > 0 ? h->owing_dev + h->first[k] : nullptr;
         h->sub[k].n_listed = owing;
         // the evaluator is the built-in net, a function of the observation: only the requests whose outputs the backup uses
@@ -264,6 +324,20 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
         float ms = 0;
         if (hipEventElapsedTime(&ms, h->ev_loop0, h->ev_loop1) == hipSuccess) { h->loop_ms += ms; h->loop_sims += sims; }
     }
+    if (watch) {
+        // The requests this move posted (each counted once, whichever launch served it) over `sims`: what a regular launch of
+        // the move holds without a cap, the catch-up launches' share included - the figure the next move's decision needs.  Read
+        // once, after the last round.  (A game whose tree was re-initialised starts its count again: a total that fell says
+        // nothing about this move, and the few requests of a reset game that a total which did not fall hides are 1 / n_games each.)
+        TM_TRY(posted_total(h, st[0]));
+        const long long posted = (long long)*h->posted_host;
+        h->prev_requests = (h->posted_before >= 0 && posted >= h->posted_before && sims > 0)
+                               ? (double)(posted - h->posted_before) / (double)sims : -1.0;
+        h->posted_before = posted;
+    } else {
+        h->prev_requests = -1.0;
+        h->posted_before = -1;
+    }
     h->n_runs += 1;
     return 0;
 }
@@ -271,6 +345,9 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
 // The weights of the built-in evaluator changed (or are another model's): outputs filed under another epoch are not used
 // (tm_store::obs_eval, TM_SIM_EVAL_NEEDED).  The handle holds its own copy of the store description.
 int tm_search_set_epoch(tm_search* h, int epoch) {
+    // (other weights: nothing filed per observation answers a leaf any more, the next move posts far more requests than the last
+    //  one did - the automatic request cap sits that move out)
+    if (epoch != h->full.eval_epoch) h->prev_requests = -1.0;
     h->full.eval_epoch = epoch;
     for (auto& t : h->sub) t.eval_epoch = epoch;
     return 0;
@@ -287,19 +364,32 @@ int tm_search_set_valuenet(tm_search* h, int backend, int fc1) {
     return 0;
 }
 
-// out[0..10] = runs, tree-kernel launches, catch-up launches, timed samples, sum of tree-kernel ms, sum of value-net ms,
+// The request cap of the runs that follow (include/tetris_mcts_hip.h): -1 off, 0 automatic, > 0 that cap for every move.
+int tm_search_set_request_cap(tm_search* h, int cap) {
+    if (cap < -1) return (int)hipErrorInvalidValue;
+    if (cap > 0 && !(h->n_sub == 1 && h->full.eval_served && h->full.eval_slots == 1 &&
+                     (h->full.kind == TM_KIND_VALUESIM || h->full.kind == TM_KIND_CPPAGENT)))
+        return (int)hipErrorInvalidValue;
+    h->cap_mode = cap;
+    h->prev_requests = -1.0;
+    h->posted_before = -1;
+    return 0;
+}
+
+// out[0..11] = runs, tree-kernel launches, catch-up launches, timed samples, sum of tree-kernel ms, sum of value-net ms,
 // sub-batches, collector-only launches, sum of the regular launch loops' ms (HIP events around sims x (value net, tree
 // kernel) of sub-batch 0's stream), simulations in those loops, simulation waves of the catch-up launches (each runs over the
-// games that owe only); the per-kernel sums are over the timed samples (sub-batch 0, every ev_every-th simulation)
+// games that owe only), moves that ran under a request cap; the per-kernel sums are over the timed samples (sub-batch 0, every ev_every-th simulation)
 int tm_search_stats(tm_search* h, double* out, int n, int reset) {
-    double v[11] = {(double)h->n_runs, (double)h->launches, (double)h->extra_launches, (double)h->n_timed, h->tree_ms,
-                    h->nn_ms, (double)h->n_sub, (double)h->gc_launches, h->loop_ms, (double)h->loop_sims, (double)h->extra_waves};
-    for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
+    double v[12] = {(double)h->n_runs, (double)h->launches, (double)h->extra_launches, (double)h->n_timed, h->tree_ms,
+                    h->nn_ms, (double)h->n_sub, (double)h->gc_launches, h->loop_ms, (double)h->loop_sims, (double)h->extra_waves,
+                    (double)h->capped_runs};
+    for (int i = 0; i < n && i < 12; ++i) out[i] = v[i];
     if (reset) {
         h->tree_ms = h->nn_ms = h->loop_ms = 0;
-        h->n_timed = h->n_runs = h->extra_launches = h->launches = h->gc_launches = h->loop_sims = h->extra_waves = 0;
+        h->n_timed = h->n_runs = h->extra_launches = h->launches = h->gc_launches = h->loop_sims = h->extra_waves = h->capped_runs = 0;
     }
-    return 11;
+    return 12;
 }
 
 }  // extern "C"

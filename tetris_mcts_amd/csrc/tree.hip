@@ -834,7 +834,9 @@ __device__ __forceinline__ void wave_sim_back(const tm_store& S, const GP& P, Wa
 // second stage of the front half: expansion of the leaf and the evaluation requests.  Runs right after the
 // walk, or again from the control block when the expansion had to wait for a collection.
 // ---------------------------------------------------------------------------------------------------
-template <bool VANILLA>
+// (CAPPED: the launch runs under a request cap, tm_store::eval_cap > 0 - k_sim_step_capped; everything about the cap is behind it,
+//  so that the code of the other launches is what it is without the cap)
+template <bool VANILLA, bool CAPPED = false>
 __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P, WaveLds& L, int g, int lane, int leaf,
                                                   int leaf_end, uint32_t self_o, uint32_t self_sc, int gsv, int gc_req_word,
                                                   int eflags) {
@@ -842,6 +844,7 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
     const int kind = S.kind;
     int k_eval = 0;                 // what the backup finds in TM_GS_K_EVAL: the leaf's unique children (leaf-parallel kinds), else requests posted
     int n_post = 0, n_skip = 0, n_cached = 0;
+    int entry = 0;                  // CAPPED: the request's entry within its segment of the dense list
     bool post = false;              // this lane's request slot carries a request
     uint32_t post_obs = 0;
     // single-leaf kinds under TM_SIM_EVAL_NEEDED: what the evaluator returned for this observation when it was a leaf before
@@ -897,6 +900,7 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
             int base = 0;
             if (lane == 0) base = atomicAdd(&S.eval_cnt[(size_t)seg * 2 + S.eval_parity], n_post);
             base = (int)rl_u32((uint32_t)base, 0);
+            if (CAPPED) entry = base;
             const uint64_t pm = __ballot(post);
             if (post) {
                 const int d = base + __popcll(pm & ((1ull << lane) - 1ull));
@@ -914,7 +918,10 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
     if (lane == 0) {
         int32_t* gs = P.gs();
         gs[TM_GS_CYC_EXPAND] = (int)((long long)__builtin_readcyclecounter() - tc0);
-        gs[TM_GS_PENDING] = 1;
+        // under a request cap (tm_store::eval_cap: single-leaf kinds) the evaluator may leave the request for a later launch:
+        // the game remembers where on the list it stands and looks at eval_served before it backs up (k_sim_step)
+        if (CAPPED && n_post > 0) { gs[TM_GS_PENDING] = TM_PENDING_POSTED; gs[TM_GS_EVAL_ENTRY] = entry; }
+        else gs[TM_GS_PENDING] = 1;
         gs[TM_GS_GC_RETRY] = 0;
         gs[TM_GS_K_EVAL] = k_eval;
         gs[TM_GS_N_EVAL] = GSV(gsv, TM_GS_N_EVAL) + n_post;
@@ -933,7 +940,7 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
 // ---------------------------------------------------------------------------------------------------
 // the front half: select_trace_obs (core.h:167-224), then expansion and evaluation requests
 // ---------------------------------------------------------------------------------------------------
-template <bool VANILLA>
+template <bool VANILLA, bool CAPPED = false>
 __device__ __forceinline__ void wave_sim_front(const tm_store& S, const GP& P, WaveLds& L, MtLds* M, int g, int lane, int gsv,
                                                int gc_req_word, int eflags) {
     const long long tc_start = __builtin_readcyclecounter();
@@ -1234,7 +1241,7 @@ __device__ __forceinline__ void wave_sim_front(const tm_store& S, const GP& P, W
         if (lane < 32) S.rng[(size_t)g * 32 + lane] = rng_keep;
         if (lane == 0) P.gs()[TM_GS_RNG_POS] = rng_pos;
     }
-    wave_front_finish<VANILLA>(S, P, L, g, lane, leaf, leaf_end | (overflow ? 1 : 0), self_o, self_sc, gsv, gc_req_word, eflags);
+    wave_front_finish<VANILLA, CAPPED>(S, P, L, g, lane, leaf, leaf_end | (overflow ? 1 : 0), self_o, self_sc, gsv, gc_req_word, eflags);
 }
 
 __device__ __forceinline__ bool bit_test_set(uint8_t* bm, uint32_t i) {
@@ -2847,102 +2854,13 @@ __host__ inline size_t sim_lds_bytes(const tm_store& S, bool vanilla) {
 }
 template <bool VANILLA>
 __global__ __launch_bounds__(64 * WPB, 5) void k_sim_step(tm_store S, int flags) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sim_lds[];
-    WaveLds* lds = reinterpret_cast<WaveLds*>(sim_lds);
-    MtLds* mt_lds = reinterpret_cast<MtLds*>(sim_lds + WPB * sizeof(WaveLds));   // WPB entries, only in the VANILLA instantiation
-    // the wave index is uniform by construction: say so, and every per-game base pointer lives in scalar registers
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    // The first workgroups of the grid are collectors: each looks after the garbage collections of a range of games, in
-    // slices of S.gc_slice_cycles per launch (catch-up launches pass TM_SIM_GC_FULL: to completion), beside the
-    // simulation workgroups - they are dispatched first and share the CUs with them (a k_sim_step wave needs 70 registers).
-    const int n_gc = gc_blocks(S);
-    if ((int)blockIdx.x < n_gc) {
-        // the dense request list: this launch appends under S.eval_parity; the other set of counters (the list the evaluator
-        // drew from before this launch) is cleared for the next one
-        if (blockIdx.x == 0 && (flags & TM_SIM_FRONT) && (int)threadIdx.x < TM_EVAL_SEGS(S.n_games))
-            S.eval_cnt[(size_t)threadIdx.x * 2 + (S.eval_parity ^ 1)] = 0;
-        // (a collector wave shares its SIMD with four simulation waves and is the one a blocked game waits for: it goes first)
-        __builtin_amdgcn_s_setprio(3);
-#ifdef TM_TIMELINE   // (measurement builds, scripts/launch_timeline.py: when this workgroup started and ended, 100 MHz ticks)
-        const unsigned tl0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
-        gc_collector_block(S, flags, n_gc, *reinterpret_cast<GcLds*>(sim_lds));
-#ifdef TM_TIMELINE
-        if (lane == 0 && (flags & TM_SIM_FRONT) && !(flags & TM_SIM_GC_FULL) && !S.game_list && (int)blockIdx.x + 6 * n_gc < S.n_games) {
-            // collector b: the spare word 35 of game b's block (start), of game n_gc + b's (end), of game 2 n_gc + b's (the
-            // launch); odd launches 3 n_gc further on
-            const size_t row = (size_t)blockIdx.x + ((((unsigned)flags >> 8) & 1) ? 3 * n_gc : 0);
-            if (w == 0) S.gs[row * TM_GS_DW + TM_GS_GC_RSV1] = (int)tl0;
-            if (w == 0) S.gs[(row + 2 * n_gc) * TM_GS_DW + TM_GS_GC_RSV1] = (int)((unsigned)flags >> 8);
-            // (the end as launch << 16 | ticks since the start, the largest over the workgroup's waves: grows from launch to launch
-            // whatever the 32-bit clock does - good for 65 535 launches)
-            const unsigned dt = (unsigned)__builtin_amdgcn_s_memrealtime() - tl0;
-            atomicMax(reinterpret_cast<unsigned*>(S.gs + (row + n_gc) * TM_GS_DW + TM_GS_GC_RSV1), ((((unsigned)flags >> 8) & 0xFFFFu) << 16) | (dt < 0xFFFFu ? dt : 0xFFFFu));
-        }
-#endif
-        return;
-    }
-    // simulation wave i takes game i, or - a launch over some of the games: the catch-up launches - game_list[i]
-    const int slot = ((int)blockIdx.x - n_gc) * WPB + w;
-    if (slot >= (S.game_list ? S.n_listed : S.n_games)) return;
-    const int g = S.game_list ? __builtin_amdgcn_readfirstlane(S.game_list[slot]) : slot;
-    GP P = game_ptrs(S, g);
-    WaveLds& L = lds[w];
-    int32_t* gs = P.gs();
-#ifdef TM_TIMELINE
-    const unsigned tl0 = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
-    // The game's control block (64 words) in one coalesced load: word i in lane i, read with v_readlane.  A word is read
-    // from the snapshot only before this launch writes it (the halves below write each word once, from lane 0).
-    int gsv = gs[lane];
-    int gc_req_word = (int)(((unsigned)flags >> 8) << 4) | GC_REQ;
-    {
-        // a collection requested, in progress, or completed in THIS launch: the game does not simulate (what a collector
-        // workgroup of this launch writes is not ordered with this wave's reads); completed in an earlier launch: resume;
-        // a speculative marking (GC_SPEC_*): the game simulates, with the write barrier once the marking is under way
-        const int gcw = GSV(gsv, TM_GS_GC_PHASE), gph = gcw & 15;
-        if (gph == GC_SPEC_MARK) gc_req_word = (gc_req_word & ~15) | GC_REQ_SPEC;
-        else if (gph == GC_SPEC_REQ) gc_req_word = (gc_req_word & ~15) | GC_REQ_OVER;
-        else if (gcw != 0) {
-            if (gph != GC_DONE || (gcw >> 4) == (int)((unsigned)flags >> 8)) return;
-            if (lane == 0) { gs[TM_GS_GC_PHASE] = 0; gc_active_clear(P); }
-            gsv = lane == TM_GS_GC_PHASE ? 0 : gsv;       // (the snapshot's phase word is what the finish stage tests)
-        }
-    }
-    const int pend = GSV(gsv, TM_GS_PENDING);
-    if (pend == 2) {
-        // the simulation suspended in its expansion: redo the expansion of its leaf, post the evaluation requests
-        const int leaf = GSV(gsv, TM_GS_LEAF);
-        const uint32_t self_o = P.rec()[(size_t)leaf * TM_REC_DW + TM_REC_OBS];
-        const uint32_t self_sc = P.rec()[(size_t)leaf * TM_REC_DW + TM_REC_SCORE];
-        wave_front_finish<VANILLA>(S, P, L, g, lane, leaf, 0, self_o, self_sc, gsv, gc_req_word, flags);
-        return;
-    }
-    const bool dist = !VANILLA && S.kind == TM_KIND_DIST;
-    const long long t0 = __builtin_readcyclecounter();
-    if ((flags & TM_SIM_BACKUP) && pend == 1) {
-        if (dist) wave_dist_back(S, P, L, g, lane, gsv);
-        else wave_sim_back(S, P, L, lane, gsv, flags);
-        __threadfence_block();
-    }
-    const long long t1 = __builtin_readcyclecounter();
-#ifndef TM_TIMELINE
-    if (lane == 0) gs[TM_GS_CYC_BACK] = (int)(t1 - t0);
-#endif
-    // the per-move quota (tm_move_begin): games that lost launches to a collection catch up in extra launches
-    if ((flags & TM_SIM_FRONT) && GSV(gsv, TM_GS_SIM_STARTED) < GSV(gsv, TM_GS_SIM_TARGET)) {
-        if (dist) wave_dist_front<VANILLA>(S, P, L, g, lane, gsv, gc_req_word, flags);
-        else wave_sim_front<VANILLA>(S, P, L, VANILLA ? &mt_lds[w] : nullptr, g, lane, gsv, gc_req_word, flags);
-    }
-    else if (lane < S.eval_slots) P.eval_obs()[lane] = 0;   // nothing started: no request (the evaluator skips empty slots)
-#ifdef TM_TIMELINE
-    if (lane == 0 && (flags & TM_SIM_FRONT) && !(flags & TM_SIM_GC_FULL) && !S.game_list &&
-        GSV(gsv, TM_GS_SIM_STARTED) < GSV(gsv, TM_GS_SIM_TARGET)) {      // (the move's regular launches: all games; a simulation was started)
-        gs[TM_GS_CYC_BACK] = (int)tl0;            // (in place of the phase cycles, which nothing on the device reads)
-        gs[TM_GS_CYC_SELECT] = (int)__builtin_amdgcn_s_memrealtime();
-        gs[TM_GS_CYC_EXPAND] = (int)((unsigned)flags >> 8);
-    }
-#endif
+    constexpr bool CAPPED = false;
+#include "sim_step_body.inc"
+}
+// the launches under a request cap (single-leaf kinds, never the rollout kinds)
+__global__ __launch_bounds__(64 * WPB, 5) void k_sim_step_capped(tm_store S, int flags) {
+    constexpr bool VANILLA = false, CAPPED = true;
+#include "sim_step_body.inc"
 }
 
 // per-move simulation quota (TreeAgent.play: self.mcts(self.root, self.sims), agents/agent.py:147-150)
@@ -3369,6 +3287,11 @@ int tm_tree_remove_nodes(const tm_store* s, const uint8_t* mask, void* stream) {
 int tm_sim_step(const tm_store* s, int flags, void* stream) {
     if (!s->eval_list || !s->eval_cnt) return (int)hipErrorInvalidValue;      // (a tm_store of an older header: no request list)
     if (s->game_list && (s->n_listed < 0 || s->n_listed > s->n_games)) return (int)hipErrorInvalidValue;
+    // the request cap: single-leaf kinds with the built-in value net, launches that back up and start simulations in one
+    if (s->eval_cap != 0 && (s->eval_cap < 0 || !s->eval_served || s->eval_slots != 1 ||
+                             (s->kind != TM_KIND_VALUESIM && s->kind != TM_KIND_CPPAGENT) ||
+                             (flags & (TM_SIM_BACKUP | TM_SIM_FRONT)) != (TM_SIM_BACKUP | TM_SIM_FRONT)))
+        return (int)hipErrorInvalidValue;
     // the launch number (bits 8.. of the kernel's flags): what orders a game's wave and its collector workgroup, which
     // only ever hand over at kernel boundaries.  Any two launches that touch the same game differ in it.
     flags = (flags & 0xFF) | (int)(((tm_launch_seq.fetch_add(1) + 1u) & 0x7FFFFu) << 8) | gc_mem_marks_flag();
@@ -3376,6 +3299,8 @@ int tm_sim_step(const tm_store* s, int flags, void* stream) {
     const dim3 grid((n_waves + WPB - 1) / WPB + gc_blocks(*s)), block(64 * WPB);
     if (s->kind == TM_KIND_VANILLA || s->kind == TM_KIND_VANILLA_C)
         hipLaunchKernelGGL(k_sim_step<true>, grid, block, sim_lds_bytes(*s, true), (hipStream_t)stream, *s, flags);
+    else if (s->eval_cap > 0)
+        hipLaunchKernelGGL(k_sim_step_capped, grid, block, sim_lds_bytes(*s, false), (hipStream_t)stream, *s, flags);
     else
         hipLaunchKernelGGL(k_sim_step<false>, grid, block, sim_lds_bytes(*s, false), (hipStream_t)stream, *s, flags);
     return TM_LAUNCH_CHECK();

@@ -170,24 +170,43 @@ struct ReqList {
     const int2* list;
     const int32_t* cnt;
     int parity, segs, slots;
+    // the request cap (tm_store::eval_cap): a launch serves the first `cap` dense positions only (0: all of them), counted through
+    // the segments cyclically from segment `rot`; block 0 of the convolution kernel writes served[s] = how many entries of
+    // segment s that is (with cap == 0: the segment's count) for the tree kernel's next launch.  served == nullptr: nobody asks.
+    int cap, rot;
+    int32_t* served;
 };
-// lane i: inclusive prefix of the segments' counts; total = the number of requests
+// The cap's arithmetic, host and device (tm_request_served / tm_request_at export it for tests/test_request_cap.py): the i-th
+// segment of the rotated order; how many of a segment's `count` entries lie inside the first `cap` dense positions when `before`
+// entries precede it in that order; where entry d of segment sg lives in the list.
+__host__ __device__ constexpr int req_segment(int i, int rot, int segs) { return i + rot >= segs ? i + rot - segs : i + rot; }
+__host__ __device__ constexpr int req_served(int before, int count, int cap) {
+    return cap <= 0 || cap - before >= count ? count : cap - before > 0 ? cap - before : 0;
+}
+__host__ __device__ constexpr int req_entry(int sg, int d, int segs, int slots) { return (sg + segs * (d / slots)) * slots + d % slots; }
+// lane i: inclusive prefix of the counts of the first i + 1 segments of the rotated order; total = the requests this launch serves
 __device__ __forceinline__ int req_prefix(const ReqList& rq, int lane, int& total) {
-    int incl = lane < rq.segs ? rq.cnt[lane * 2 + rq.parity] : 0;
+    int incl = lane < rq.segs ? rq.cnt[req_segment(lane, rq.rot, rq.segs) * 2 + rq.parity] : 0;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const int t = __shfl_up(incl, d, 64);
         if (lane >= d) incl += t;
     }
     total = __shfl(incl, 63, 64);
+    if (rq.cap > 0) total = min(total, rq.cap);
     return incl;
+}
+// what the launch serves of every segment, for the tree kernel (one wave of the launch calls it, every lane of the wave)
+__device__ __forceinline__ void req_publish_served(const ReqList& rq, int incl, int lane) {
+    const int up = __shfl_up(incl, 1, 64), before = lane > 0 ? up : 0;
+    if (rq.served && lane < rq.segs) rq.served[req_segment(lane, rq.rot, rq.segs)] = req_served(before, incl - before, rq.cap);
 }
 // index into rq.list of dense position p (wave-uniform, p < total; every lane of the wave calls it)
 __device__ __forceinline__ int req_at(const ReqList& rq, int incl, int p, int lane) {
-    const int sg = __popcll(__ballot(lane < rq.segs && incl <= p));     // the first segment whose inclusive prefix exceeds p
+    const int sg = __popcll(__ballot(lane < rq.segs && incl <= p));     // the first segment (rotated order) whose inclusive prefix exceeds p
     const int before = __shfl(incl, sg > 0 ? sg - 1 : 0, 64);
     const int d = p - (sg > 0 ? before : 0);
-    return (sg + rq.segs * (d / rq.slots)) * rq.slots + d % rq.slots;
+    return req_entry(req_segment(sg, rq.rot, rq.segs), d, rq.segs, rq.slots);
 }
 // The request-list render as functions, for k_vn_conv_x3 (valuenet_x3.inc).  k_vn_conv keeps its own inline copy of the same
 // statements: calling these from it changes its machine code (measured on the code object), and the fp32 kernel stays as it is.
@@ -321,7 +340,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 4
             for (int k = 0; k < rq.segs; ++k) sg += __builtin_amdgcn_readlane(incl, k) <= p ? 1 : 0;     // first segment whose inclusive prefix exceeds p
             const int before = __shfl(incl, sg > 0 ? sg - 1 : 0, 64);
             const int d = p - (sg > 0 ? before : 0);
-            my_slot = rq.list[(sg + rq.segs * (d / rq.slots)) * rq.slots + d % rq.slots].x;
+            my_slot = rq.list[req_entry(req_segment(sg, rq.rot, rq.segs), d, rq.segs, rq.slots)].x;
         }
     }
     const int ht = part * HT + (w % HT);             // 16-row hidden tile 0..15
@@ -661,7 +680,7 @@ static int vn_forward_impl(const float* P, const float* prepared, int backend, i
 // matrix-core path; prepared: tm_valuenet_prepare's output for this mode or a larger one; scratch: n x TM_VALUENET_SCRATCH_MFMA floats
 int tm_valuenet_forward(const float* P, const float* prepared, int backend, int fc1, const int8_t* states, int n, float* v,
                         float* var, float* scratch, void* stream_) {
-    return vn_forward_impl(P, prepared, backend, fc1, states, nullptr, ReqList{nullptr, nullptr, 0, 0, 1}, 0, n, v, var, scratch,
+    return vn_forward_impl(P, prepared, backend, fc1, states, nullptr, ReqList{nullptr, nullptr, 0, 0, 1, 0, 0, nullptr}, 0, n, v, var, scratch,
                            (hipStream_t)stream_);
 }
 
@@ -669,7 +688,12 @@ int tm_valuenet_forward(const float* P, const float* prepared, int backend, int 
 int tm_valuenet_forward_requests(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
                                  void* stream_) {
     // the requests of the last tm_sim_step launch, drawn from its dense list (s->eval_parity = that launch's)
-    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, TM_EVAL_SEGS(s->n_games), s->eval_slots};
+    // (s->eval_cap / eval_rot / eval_served: the request cap, tm_search_set_request_cap; a store without it serves every request)
+    const int segs = TM_EVAL_SEGS(s->n_games);
+    const bool capped = s->eval_served != nullptr;
+    if (capped && (s->eval_cap < 0 || s->eval_rot < 0 || s->eval_rot >= segs)) return (int)hipErrorInvalidValue;
+    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, segs, s->eval_slots,
+                     capped ? s->eval_cap : 0, capped ? s->eval_rot : 0, capped ? s->eval_served : nullptr};
     return vn_forward_impl(P, prepared, backend, fc1, nullptr, s->obs_key, rq, s->max_nodes, s->n_games * s->eval_slots,
                            s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
 }
@@ -686,6 +710,42 @@ int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t* ite
         if (items && k < cap) { items[2 * k] = it.tile; items[2 * k + 1] = it.part; }
     }
     return k;
+}
+
+// k_vn_conv's resident waves, one state each: the cap of the native loop's automatic mode (search.hip)
+int tm_valuenet_resident_states(void) {
+    const int cus = vn_compute_units();      // (the launch's grid stops at 256 compute units' worth of workgroups: vn_forward_impl)
+    return cus > 0 ? (cus < 256 ? cus : 256) * CONV_WG_PER_CU * 4 : 0;
+}
+// The request cap's arithmetic (host only: callable without a GPU).  counts[segs] = the segments' entries; the launch serves the
+// first min(sum, cap) dense positions (cap == 0: all) counted from segment `rot` cyclically.  tm_request_served: served[s] = the
+// entries of segment s among them; returns their number, -1 on arguments that make no list.
+int tm_request_served(const int32_t* counts, int segs, int rot, int cap, int32_t* served) {
+    if (!counts || !served || segs <= 0 || rot < 0 || rot >= segs || cap < 0) return -1;
+    int before = 0, n = 0;
+    for (int i = 0; i < segs; ++i) {
+        const int sg = req_segment(i, rot, segs);
+        if (counts[sg] < 0) return -1;
+        served[sg] = req_served(before, counts[sg], cap);
+        n += served[sg];
+        before += counts[sg];
+    }
+    return n;
+}
+// tm_request_at: dense position p -> out[0] = its segment, out[1] = its entry within the segment, out[2] = its index in the list of
+// `slots` request slots a game; returns 0, -1 when p is not a position of the list
+int tm_request_at(const int32_t* counts, int segs, int rot, int slots, int p, int32_t* out) {
+    if (!counts || !out || segs <= 0 || rot < 0 || rot >= segs || slots <= 0 || p < 0) return -1;
+    int incl = 0;
+    for (int i = 0; i < segs; ++i) {          // the first segment of the rotated order whose inclusive prefix exceeds p
+        const int sg = req_segment(i, rot, segs), before = incl;
+        incl += counts[sg];
+        if (incl > p) {
+            out[0] = sg; out[1] = p - before; out[2] = req_entry(sg, p - before, segs, slots);
+            return 0;
+        }
+    }
+    return -1;
 }
 
 }  // extern "C"

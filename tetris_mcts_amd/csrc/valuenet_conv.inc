@@ -66,7 +66,9 @@ __global__ __launch_bounds__(256, CONV_WAVES_PER_SIMD) void k_vn_conv(const floa
     const int stride = gridDim.x * 4;
     int s = blockIdx.x * 4 + w;
     int incl = 0;
-    if (!states) incl = req_prefix(rq, lane, n);          // n = the requests posted by the last tree launch
+    if (!states) incl = req_prefix(rq, lane, n);          // n = the requests this launch serves: those the last tree launch posted, up to the cap
+    // the tree kernel's next launch learns from these which requests were served (a request past the cap is posted again)
+    if (!states && blockIdx.x == 0 && w == 0) req_publish_served(rq, incl, lane);
     auto key_of = [&](int p) -> uint32_t {               // lane < 12: word `lane` of the packed observation of request p
         if (p >= n) return 0u;
         const int2 e = rq.list[req_at(rq, incl, p, lane)];

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 4
             for (int k = 0; k < rq.segs; ++k) sg += __builtin_amdgcn_readlane(incl, k) <= p ? 1 : 0;
             const int before = __shfl(incl, sg > 0 ? sg - 1 : 0, 64);
             const int d = p - (sg > 0 ? before : 0);
-            my_slot = rq.list[(sg + rq.segs * (d / rq.slots)) * rq.slots + d % rq.slots].x;
+            my_slot = rq.list[req_entry(req_segment(sg, rq.rot, rq.segs), d, rq.segs, rq.slots)].x;
         }
     }
     const int ht = part * HT + (w % HT);             // 16-row hidden tile 0..15

@@ -116,6 +116,7 @@ __global__ __launch_bounds__(256, 1) void k_vn_conv_x3(const float* __restrict__
     int s = blockIdx.x * 4 + w;
     int incl = 0;
     if (!states) incl = req_prefix(rq, lane, n);
+    if (!states && blockIdx.x == 0 && w == 0) req_publish_served(rq, incl, lane);      // (as k_vn_conv does)
     uint32_t kw_next = states ? 0u : req_obs_word(rq, incl, obs_key, max_nodes, n, s, lane);
     for (; s < n; s += stride) {
         const uint32_t kw = kw_next;

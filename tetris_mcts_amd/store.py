@@ -15,7 +15,7 @@ KIND_VALUESIM, KIND_VALUESIM_LP, KIND_CPPAGENT_LP, KIND_CPPAGENT, KIND_VANILLA, 
 GS = dict(ROOT=0, EPISODE=1, NFREE_NODE=2, NFREE_OBS=3, TRACE_LEN=4, PENDING=5, ERR=6, N_EXPAND=7, N_SIMS=8, N_GC=9,
           RNG_POS=10, N_NQ_FALLBACK=11, LEAF=12, LEAF_END=13, K_EVAL=14, LEAF_SCORE=15, TRACE_SUM=16, N_EVAL=17, N_POOL_RESET=18, MAX_TRACE=19, N_DROPPED=25,
           CYC_BACK=20, CYC_SELECT=21, CYC_EXPAND=22, CYC_GC16=23, GC_REACHABLE=24, GC_PHASE=32, GC_ACTIVE4=34, GC_WORK=36, GC_MARK_LAUNCHES=37, GC_SLICES=38,
-          SIM_TARGET=40, SIM_STARTED=41, CYC_VERIFY=42, FIRST_MISS=28, PREFIX_SUM=29, N_WALK_MISS=43, POOL_FULL=44, GC_IN_MOVE=45, GC_REQ_AT=46,
+          SIM_TARGET=40, SIM_STARTED=41, CYC_VERIFY=42, FIRST_MISS=28, PREFIX_SUM=29, EVAL_ENTRY=30, N_EVAL_DEFERRED=31, N_WALK_MISS=43, POOL_FULL=44, GC_IN_MOVE=45, GC_REQ_AT=46,
           LEAF_OBS=47, N_EVAL_SKIP=48, N_EVAL_CACHED=49, GC_NGC=50, GC_BLOCKS=51, GC_ITERS=52, GC_MARK_CYC=53, GC_FLAGS=54, GC_MARK_PARTS=58, GC_MARK_SHARED=59, GC_CYC_LOAD=60, GC_CYC_ROUNDS=61, GC_CYC_WAVES=62, GC_IDLE_TURNS=63)
 
 _nq_cache = {}
@@ -91,6 +91,7 @@ class TreeStore:
         # per observation - include/tetris_mcts_hip.h tm_store::eval_list / obs_eval
         self.t["eval_list"] = z(G * eval_slots, 2)
         self.t["eval_cnt"] = z(G, 2)
+        self.t["eval_served"] = z(G)     # (the request cap, tm_store::eval_cap: what the evaluator's last launch served of every segment)
         self.t["obs_eval"] = z(G, N, 4, dtype=torch.float32) if kind in (KIND_VALUESIM, KIND_CPPAGENT) else None
         # the distributional agent's harvest (DistValueSimOnline.store_nodes): the freed nodes' distributions
         self.t["replay_dist"] = z(G, replay_cap, 64, dtype=torch.float32) if (kind == KIND_DIST and online and replay_cap > 0) else None
@@ -116,6 +117,7 @@ class TreeStore:
                 setattr(s, name, self.t[name].data_ptr() if self.t[name] is not None else None)
         s.dist_bins, s.dist_vmin, s.dist_vmax = int(dist_bins), float(dist_range[0]), float(dist_range[1])
         s.eval_parity, s.eval_epoch, s.n_listed, s.gc_cost_units, s.gc_collectors = 0, 0, 0, int(gc_cost_units or 0), int(gc_collectors or 0)
+        s.eval_cap, s.eval_rot = 0, 0    # (the native loop sets them in its own copy, move by move: set_request_cap)
         self.s = s
         self.stats_buf = torch.zeros(G, 3, 7, dtype=torch.float32, device=dev)
         self.action_buf = torch.zeros(G, dtype=torch.int32, device=dev)
@@ -184,15 +186,24 @@ class TreeStore:
         """One step of every garbage collection under way (collector workgroups only)."""
         _lib.check(self.L.tm_gc_step(C.byref(self.s), _stream()), "tm_gc_step")
 
-    def search(self, sims, model=None, n_sub=1, ev_every=0):
-        """One move's search through the native launch loop (search.hip): `sims` simulations of every game, the leaf
-        evaluator = the HIP value net of `model` (None: no evaluator, the Vanilla kind).  Returns when complete."""
+    def _search_handle(self, n_sub, ev_every):
         key = (int(n_sub), int(ev_every))
         h = self._search.get(key)
         if h is None:
             h = C.c_void_p()
             _lib.check(self.L.tm_search_create(C.byref(h), C.byref(self.s), key[0], key[1]), "tm_search_create")
             self._search[key] = h
+        return h
+
+    def set_request_cap(self, cap, n_sub=1, ev_every=0):
+        """The request cap of the native loop of (n_sub, ev_every) (tm_search_set_request_cap): -1 off, 0 automatic (the
+        default), > 0 that many requests a launch of the value net - a change of schedule, never of a result."""
+        _lib.check(self.L.tm_search_set_request_cap(self._search_handle(n_sub, ev_every), int(cap)), "tm_search_set_request_cap")
+
+    def search(self, sims, model=None, n_sub=1, ev_every=0):
+        """One move's search through the native launch loop (search.hip): `sims` simulations of every game, the leaf
+        evaluator = the HIP value net of `model` (None: no evaluator, the Vanilla kind).  Returns when complete."""
+        h = self._search_handle(n_sub, ev_every)
         if model is None:
             P = prep = scr = C.c_void_p(0)
         else:
@@ -210,10 +221,10 @@ class TreeStore:
         h = self._search.get((int(n_sub), int(ev_every)))
         if h is None:
             return None
-        out = (C.c_double * 11)()
-        self.L.tm_search_stats(h, out, 11, int(bool(reset)))
+        out = (C.c_double * 12)()
+        self.L.tm_search_stats(h, out, 12, int(bool(reset)))
         keys = ("runs", "tree_launches", "catchup_launches", "timed", "tree_ms_sum", "nn_ms_sum", "n_sub", "gc_launches",
-                "loop_ms_sum", "loop_sims", "catchup_waves")
+                "loop_ms_sum", "loop_sims", "catchup_waves", "capped_runs")
         return dict(zip(keys, list(out)))
 
     def sim_step(self, flags):
