@@ -39,7 +39,11 @@ extern "C" {
 #define TM_VALUENET_SCRATCH 9728       /* floats of scratch per state, tm_valuenet_forward_plain */
 #define TM_VALUENET_SCRATCH_MFMA 2064  /* floats of scratch per state, tm_valuenet_forward / _requests in every mode; no initial contents
                                           required (the kernels keep a counter per tile of 32 or 64 states in the rows' padding: every
-                                          evaluation clears them first) */
+                                          evaluation clears them first).  The 16 pad words of a tile's first row: word 0 fc1's arrival
+                                          counter; words 14 and 15 k_vn_conv_fc1's ready counters of evaluations under list parity 0
+                                          and 1 (a launch clears the other parity's; the library clears a launch's own first unless the caller
+                                          proves that the launch before it did: tm_valuenet_forward_requests_run); words
+                                          1 .. 14 the measurement builds' time stamps (TM_FC1_TIMELINE: they keep the two kernels) */
 /* the parts of tm_valuenet_prepare's buffer, in its order */
 #define TM_VALUENET_PREPARED 477184    /* floats: conv2 + conv3 + fc1 operand streams (every mode) */
 #define TM_VALUENET_PREPARED_X3 27648  /* floats (55 296 bf16): conv2 + conv3 weights as bf16 hi / mid / lo planes (TM_VALUENET_BF16X3) */
@@ -639,6 +643,29 @@ int tm_valuenet_forward_plain(const float *params, const int8_t *states, int n, 
  * round robin); workgroup b of `grid` takes items b, b + grid, ...  Writes the workgroup's (tile, part) pairs to
  * items[0 .. 2 * cap) and returns how many it takes (possibly more than cap); -1 on arguments that make no grid. */
 int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t *items, int cap);
+/* The fp32 mode's requests at the single-leaf shape (fewer than 8 192 request slots) run as ONE launch, k_vn_conv_fc1: the
+ * convolutions, then fc1 on the same resident workgroups, a tile of 32 states handed over through a ready counter in the scratch
+ * rows' padding (TM_VALUENET_SCRATCH_MFMA).  The two kernels remain for everything else, where the chip refuses the launch's LDS
+ * or residency, and under TM_VALUENET_FUSED=0 in the environment (read once; 1 asks for the one launch; for A/B runs and tests).
+ * A poller's wait is bounded (10 ms): when it runs out the kernel sets a sticky error word and leaves.
+ * tm_fused_tile_rows: host arithmetic only - the count tile `tile`'s poller waits for at `requests` requests (32, the remainder
+ * in the last tile, 0 past it; -1 on negative arguments).
+ * tm_valuenet_forward_requests_grid: tm_valuenet_forward_requests with the path named, for tests - grid > 0: k_vn_conv_fc1 on
+ * `grid` workgroups (hipErrorInvalidValue above what is resident, or where the launch does not serve), 0: on its own grid, < 0: the
+ * two kernels.
+ * tm_valuenet_forward_requests_run: tm_valuenet_forward_requests for a caller that issues a run of evaluations on one scratch and
+ * stream with nothing else writing the scratch in between (tm_search_run within a move): *run = -1 before the first, the library
+ * keeps it.  It spares the clear of the launch's ready words that every other call puts in front of the one launch.
+ * tm_valuenet_fused_error: the sticky error word, one a process whatever the handle or device, to be read after a synchronisation:
+ * tm_search_run reads it at every synchronisation of a move and fails with hipErrorLaunchTimeOut; a caller of
+ * tm_valuenet_forward_requests reads it itself once the stream is idle, before it uses eval_v / eval_var (Model_VV.inference_requests
+ * leaves that to its caller as well).  reset != 0 clears it. */
+int tm_fused_tile_rows(int requests, int tile);
+int tm_valuenet_forward_requests_grid(const float *params, const float *prepared, int backend, int fc1, const tm_store *s,
+                                      float *scratch, void *stream, int grid);
+int tm_valuenet_forward_requests_run(const float *params, const float *prepared, int backend, int fc1, const tm_store *s,
+                                     float *scratch, void *stream, int32_t *run);
+int tm_valuenet_fused_error(int reset);
 /* the states k_vn_conv takes in one round: its resident waves (two workgroups of four waves a compute unit); <= 0: no device */
 int tm_valuenet_resident_states(void);
 /* The request cap's arithmetic (host only, callable without a GPU; the kernels use the same formulas).  counts[segs] = the

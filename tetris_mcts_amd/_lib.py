@@ -99,6 +99,10 @@ SYMBOLS = {
     "tm_search_set_valuenet": [vp, i32, i32],
     "tm_search_set_request_cap": [vp, i32],
     "tm_valuenet_resident_states": [],
+    "tm_fused_tile_rows": [i32, i32],
+    "tm_valuenet_forward_requests_grid": [vp, vp, i32, i32, C.POINTER(TmStore), vp, vp, i32],
+    "tm_valuenet_forward_requests_run": [vp, vp, i32, i32, C.POINTER(TmStore), vp, vp, vp],
+    "tm_valuenet_fused_error": [i32],
     "tm_request_served": [vp, i32, i32, i32, vp],
     "tm_request_at": [vp, i32, i32, i32, i32, vp],
 }

@@ -246,14 +246,17 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
         h->sub[k].n_listed = 0;
         return e;
     };
+    // the value net's launches of this move on a sub-batch's scratch and stream are an unbroken run (tm_valuenet_forward_requests_run)
+    std::vector<int32_t> vn_run(K, -1);
     auto nn = [&](int k) -> int {
         if (!vn_params || h->sub[k].n_games == 0) return 0;
         // vn_prepared: one buffer, the fp32 operand streams and behind them the planes the mode names (tm_search_set_valuenet)
         if (h->full.kind == TM_KIND_DIST)      // the distributional head (distnet.hip): eval_obs names the leaf node
             return tm_distnet_forward_requests(vn_params, vn_prepared, h->vn_backend, &h->sub[k],
                                                vn_scratch + (size_t)h->first[k] * TM_DISTNET_SCRATCH, st[k]);
-        return tm_valuenet_forward_requests(vn_params, vn_prepared, h->vn_backend, h->vn_fc1, &h->sub[k],
-                                            vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA, st[k]);
+        return tm_valuenet_forward_requests_run(vn_params, vn_prepared, h->vn_backend, h->vn_fc1, &h->sub[k],
+                                                vn_scratch + (size_t)h->first[k] * h->full.eval_slots * TM_VALUENET_SCRATCH_MFMA, st[k],
+                                                &vn_run[k]);
     };
     h->ev_used = 0;
     TM_TRY(hipEventRecord(h->ev_loop0, st[0]));
@@ -293,6 +296,9 @@ int tm_search_run(tm_search* h, int sims, const float* vn_params, const float* v
             TM_TRY(hipMemcpyAsync(h->rem_host + 3 * k, h->rem_dev + 3 * k, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st[k]));
         }
         for (int k = 0; k < K; ++k) TM_TRY(hipStreamSynchronize(st[k]));
+        // (every stream is idle) a poller of the value net's one-launch form whose bounded wait ran out: no result, and nothing
+        // more is launched on top of it
+        if (vn_params && h->full.kind != TM_KIND_DIST && tm_valuenet_fused_error(1)) return (int)hipErrorLaunchTimeOut;
         int r = 0, collecting = 0;
         for (int k = 0; k < K; ++k) { r = h->rem_host[3 * k] > r ? h->rem_host[3 * k] : r; collecting += h->rem_host[3 * k + 1]; }
         if (r == 0) break;

@@ -300,244 +300,29 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(RT == 4 ? 4
                                                 float* __restrict__ hout, int hstride,
                                                 ReqList rq, int32_t* __restrict__ cnt, int cnt_stride,
                                                 float* __restrict__ v_out, float* __restrict__ var_out) {
-    constexpr int ROWS = 16 * RT, PITCH = KC + 4, HS_PITCH = HID + 4;
-    constexpr int UNITS = HID / NY, HT = UNITS / 16, SG = 8 / HT, NST = RT / SG;      // hidden tiles per workgroup, groups of state tiles, state tiles per wave
-    static_assert(HT * SG == 8 && NST * SG == RT && NST >= 1 && ROWS <= 64, "eight waves = hidden tiles x groups of state tiles; one lane per row");
-    constexpr int BT = ROWS * PITCH > (ROWS * HS_PITCH + 1) / 2 ? ROWS * PITCH : (ROWS * HS_PITCH + 1) / 2;     // floats per staging buffer
-    __shared__ __attribute__((aligned(16))) float bt[2][BT];
-    __shared__ int row_slot[ROWS];        // request mode: where row j of the tile delivers its outputs
-    __shared__ int last_flag;
-    // the output layer's operands - its 2 x 256 weights, two biases and the four affine constants, 518 consecutive parameters -
-    // fetched by every workgroup under the K loop's last chunk, so that the tile's last workgroup runs its chains on LDS alone
-    constexpr int WO = 2 * HID + 6;
-    static_assert(OFF_FOB == OFF_FOW + 2 * HID && OFF_UB == OFF_FOB + 2 && OFF_LB == OFF_UB + 2, "the output layer's parameters are consecutive");
-    __shared__ __attribute__((aligned(16))) float wo[(WO + 3) / 4 * 4];
-    const int lane = threadIdx.x & 63;
-    // rows = dense positions of the request list: its length decides how many items there are (a fixed trip count from here on; a
-    // workgroup past the last item leaves before it has asked the memory system for anything else)
-    int incl = 0;
-    if (rq.list) {
-        incl = req_prefix(rq, lane, n);
-        n = __builtin_amdgcn_readfirstlane(n);      // (the same in every lane: say so, or the items' tile, part and s0 are vector arithmetic)
+    // (the shape's constants and the item loop: valuenet_fc1_body.inc, the text k_vn_conv_fc1 runs as its second phase)
+#define FC1_LDS() \
+    __shared__ __attribute__((aligned(16))) float bt[2][BT]; \
+    __shared__ int row_slot[ROWS];        /* request mode: where row j of the tile delivers its outputs */ \
+    __shared__ int last_flag; \
+    __shared__ __attribute__((aligned(16))) float wo[(WO + 3) / 4 * 4]
+#define FC1_ROWS() \
+    const int lane = threadIdx.x & 63; \
+    int incl = 0; \
+    if (rq.list) { \
+        incl = req_prefix(rq, lane, n); \
+        n = __builtin_amdgcn_readfirstlane(n);      /* (the same in every lane: say so, or the items' tile, part and s0 are vector arithmetic) */ \
     }
-    const int n_items = fc1_item_count(n, ROWS, NY);
-    for (int item = fc1_item_index(blockIdx.x, gridDim.x, 0), kth = 0; item < n_items; item = fc1_item_index(blockIdx.x, gridDim.x, ++kth)) {
-    // (the thread's index behind an empty asm: nothing derived from it is loop-invariant for the compiler, which otherwise keeps
-    //  some seventy registers of hoisted addresses alive across the items - 233 registers against 163 for the single-leaf shape,
-    //  172 against 106 for the other, which then no longer fits two workgroups a CU)
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int w = tid >> 6, lane = tid & 63, kk = lane >> 4, l15 = lane & 15;     // (`lane` shadows the one above on purpose)
-    const Fc1Item it = fc1_item(item, n, ROWS, NY);
-    const int tile = it.tile, part = it.part, s0 = tile * ROWS;
-    int my_slot = 0;
-    FC1_STAMP(0);
-    if (rq.list) {
-        if (w == 0) {
-            // lane j resolves row j (all list entries in flight together; the slot is needed after the K loop only)
-            const int p = min(s0 + (lane & (ROWS - 1)), n - 1);
-            int sg = 0;
-            for (int k = 0; k < rq.segs; ++k) sg += __builtin_amdgcn_readlane(incl, k) <= p ? 1 : 0;     // first segment whose inclusive prefix exceeds p
-            const int before = __shfl(incl, sg > 0 ? sg - 1 : 0, 64);
-            const int d = p - (sg > 0 ? before : 0);
-            my_slot = rq.list[req_entry(req_segment(sg, rq.rot, rq.segs), d, rq.segs, rq.slots)].x;
-        }
-    }
-    const int ht = part * HT + (w % HT);             // 16-row hidden tile 0..15
-    const int st0 = (w / HT) * NST;                   // this wave's first 16-state tile
-    const float4* W = reinterpret_cast<const float4*>(prep + PREP_W1) + (size_t)ht * 112 * 64 + lane;
-    f32x4 acc[NST];
-#pragma unroll
-    for (int t = 0; t < NST; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[t][r] = P[OFF_F1B + 16 * ht + kk * 4 + r];
-    constexpr int NCH = A3 / KC;          // chunks of KC k = KC/4 MFMA steps
-    // a group = GRP MFMA steps (per state tile) = GRP/4 weight quads; weights: a ring of WRING groups, the group WRING - 1 ahead
-    // requested while a group is multiplied (measured, r04 calls C-E per launch of ~60 32-state tiles: chunk-deep weights without
-    // the LDS pipeline 45 us, with it 35 us; a ring of three groups 45 us again - the weights need the longer lead when nothing
-    // else is resident to cover it)
-    constexpr int GRP = 16 / NST, QPG = GRP / 4, NGRP = KC / 4 / GRP;
-    static_assert(A3 % KC == 0 && NCH >= 2 && (KC / 4) % GRP == 0, "chunking");
-    float4 wring[WRING][QPG];
-    auto wload = [&](int G) {          // G = chunk * NGRP + group
-#pragma unroll
-        for (int q = 0; q < QPG; ++q) wring[G % WRING][q] = W[((size_t)G * QPG + q) * 64];
-    };
-    // The first weights (and the biases above) are requested BEFORE the activations: a wave's loads return in order, and the first
-    // MFMA needs both.  (Which weights is a matter of the item's part, and the item numbering needs the number of tiles: they
-    // cannot go out before the request list's counters are back.  On the former grid of slots, where blockIdx.y was the part,
-    // every workgroup asking before it read the counters measured 34.4 us against 31.5.)
-#pragma unroll
-    for (int G0 = 0; G0 < WRING - 1; ++G0) wload(G0);
-    // staging: ROWS rows x KC floats per chunk, KC/4 threads per row, 16-byte pieces
-    constexpr int TPR = KC / 4, RPP = 512 / TPR, NPASS = ROWS / RPP;
-    const int row0 = tid / TPR, c4 = (tid % TPR) * 4;
-    // The activations of chunk c + 2 are requested while chunk c is multiplied (two register sets): a tile's rows were written
-    // by convolution waves all over the chip, so they come from beyond this XCD's L2, and one chunk of MFMAs (under 2 us) does
-    // not cover that round trip.  (Kept as a select: a plain 16-byte copy into the array sent the whole array to scratch
-    // memory - tests/test_abi.py holds every hot kernel to a private segment of 0.)
-    // r06 (scripts/fc1_timeline.py, the kernel's stations in time): PF register sets = PF chunks in flight, the request for chunk
-    // c + PF issued at the START of chunk c's MFMAs (until then it went out after them: one chunk of cover, not two), and the
-    // first weights requested before the first activations (a wave's loads return in order).  1 867 states, entry to outputs:
-    // 34.2 us before; PF = 2 / 3 / 4 / 7 (the whole tile up front): 28.9 / 29.6 / 30.2 / 32.6 - the more is asked for at once, the
-    // later the first chunk is there (4.5 ... 9.4 us), and the K loop does not shorten (18 - 19 us for 12 of matrix time).
-    float4 st[PF][NPASS];
-    auto gload = [&](int chunk) {
-#pragma unroll
-        for (int i = 0; i < NPASS; ++i) {
-            const int sa = s0 + row0 + RPP * i;
-            st[chunk % PF][i] = (sa < n) ? *reinterpret_cast<const float4*>(a3 + (size_t)sa * a3stride + chunk * KC + c4)
-                                         : make_float4(0, 0, 0, 0);
-        }
-    };
-    auto lstore = [&](int chunk) {
-#pragma unroll
-        for (int i = 0; i < NPASS; ++i)
-            *reinterpret_cast<float4*>(&bt[chunk & 1][(row0 + RPP * i) * PITCH + c4]) = st[chunk % PF][i];
-    };
-    static_assert(PF >= 2 && PF <= A3 / KC, "chunks in flight");
-    float wo_r[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < PF; ++c) gload(c);
-    FC1_STAMP(1);
-    lstore(0);
-    __syncthreads();
-    FC1_STAMP(2);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        if (c + PF < NCH) gload(c + PF);         // into the register set chunk c's staging has left (lstore(c): before the last barrier)
-        if (c == NCH - 1 && tid < (WO + 3) / 4) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (4 * tid + r < WO) wo_r[r] = P[OFF_FOW + 4 * tid + r];
-        }
-        const float* b0 = &bt[c & 1][(16 * st0 + l15) * PITCH + kk];
-        // The B operands (LDS) of the next group of MFMA steps are requested while this group's MFMAs issue (r03 - r04 call C:
-        // the compiler's own order was read, wait for it, two MFMAs, read ...: an LDS round trip per pair of MFMAs, 45 us per
-        // launch whatever the number of tiles, against 12 us of matrix-core time).
-        float bb[2][NST][GRP];
-        auto load_b = [&](int grp, int buf) {
-#pragma unroll
-            for (int t = 0; t < NST; ++t)
-#pragma unroll
-                for (int i = 0; i < GRP; ++i) bb[buf][t][i] = b0[16 * t * PITCH + 4 * (GRP * grp + i)];
-        };
-        load_b(0, 0);
-#pragma unroll
-        for (int gq = 0; gq < NGRP; ++gq) {
-            const int G = c * NGRP + gq;
-            if (G + WRING - 1 < NCH * NGRP) wload(G + WRING - 1);
-            if (gq + 1 < NGRP) load_b(gq + 1, (gq + 1) & 1);
-#pragma unroll
-            for (int i = 0; i < GRP; ++i) {
-                const float4 w4 = wring[G % WRING][i / 4];
-                const int r = i & 3;
-                const float a = (r == 0) ? w4.x : (r == 1) ? w4.y : (r == 2) ? w4.z : w4.w;
-#pragma unroll
-                for (int t = 0; t < NST; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bb[gq & 1][t][i], acc[t], 0, 0, 0);
-            }
-            // issue order inside the group: an LDS read behind every other MFMA (the reads pair up into ds_read2_b32)
-#pragma unroll
-            for (int i = 0; i < NST * GRP / 2; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);      // the next group's reads stay in this group's region: a whole group ahead of their use
-        }
-        if (c + 1 < NCH) lstore(c + 1);          // (requested PF - 1 chunks ago)
-        __syncthreads();
-        if (c == NCH - 1) FC1_STAMP(3);
-    }
-    // D[i = kk*4 + r][j = l15]: four consecutive hidden units of one state per lane -> one 16-byte write-through store,
-    // and a copy into LDS (hs[state][hidden unit], the layout the output layer below reads)
-    const int i0 = 16 * ht + kk * 4;
-    float* hs = &bt[0][0];                      // ROWS x HS_PITCH floats: the K loop is over, its staging buffers are free
-    static_assert(ROWS * HS_PITCH <= 2 * BT, "hidden tile fits the staging buffers");
-#pragma unroll
-    for (int t = 0; t < NST; ++t) {
-        f32x4v o0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o0[r] = acc[t][r] > 0.f ? acc[t][r] : 0.f;
-        const int row = 16 * (st0 + t) + l15;
-        if (s0 + row < n) {
-            float* dst = hout + (size_t)(s0 + row) * hstride + i0;
-            asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst), "v"(o0) : "memory");
-        }
-        *reinterpret_cast<f32x4v*>(&hs[row * HS_PITCH + i0]) = o0;
-    }
-    if (rq.list && w == 0 && lane < ROWS) row_slot[lane] = my_slot;      // (the list entry has had the whole K loop to arrive)
-    if (tid < (WO + 3) / 4) *reinterpret_cast<float4*>(&wo[4 * tid]) = make_float4(wo_r[0], wo_r[1], wo_r[2], wo_r[3]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    FC1_STAMP(4);
-    if (tid == 0) {
-        // (relaxed on purpose: the hand-off is carried by the write-through sc1 stores + s_waitcnt before the arrival and the sc1
-        // loads after it - MI355X_MICROARCH.md's measured form.  With __ATOMIC_ACQ_REL here the compiler adds buffer_wbl2 sc1 /
-        // buffer_inv sc1 around the atomic: 33.4 -> 35.8 us per launch, r04; tests/test_gpu_valuenet.py holds the folded output
-        // layer to the oracle's bits on every run)
-        const int old = __hip_atomic_fetch_add(&cnt[(size_t)tile * cnt_stride], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = old;
-        if (old == NY - 1) __hip_atomic_store(&cnt[(size_t)tile * cnt_stride], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // for the next launch
-    }
-    __syncthreads();
-    FC1_STAMP(5);
-    if (last_flag == NY - 1) {
-    // ---- this workgroup arrived last: the other parts of h past the caches (ROWS states x (256 - UNITS) units) ----
-    {
-        // all of a thread's 16-byte loads in flight together, one wait (the memory clobbers keep the LDS stores behind it)
-        constexpr int OQ = (HID - UNITS) / 4, CNT = ROWS * OQ / 512;      // 16-byte pieces per row of the other parts; per thread
-        static_assert(ROWS * OQ % 512 == 0, "whole passes");
-        f32x4v wv[CNT];
-#pragma unroll
-        for (int i = 0; i < CNT; ++i) {
-            const int e = i * 512 + tid, row = e / OQ, c = (e % OQ) * 4;
-            const int col = c < part * UNITS ? c : c + UNITS;      // skipping this workgroup's own units
-            const float* src = hout + (size_t)(s0 + (s0 + row < n ? row : 0)) * hstride + col;
-            asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(wv[i]) : "v"(src) : "memory");
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < CNT; ++i) {
-            const int e = i * 512 + tid, row = e / OQ, c = (e % OQ) * 4;
-            const int col = c < part * UNITS ? c : c + UNITS;
-            f32x4v t = wv[i];
-            asm volatile("" : "+v"(t));          // (a use the compiler cannot hoist above the wait)
-            if (s0 + row < n) *reinterpret_cast<f32x4v*>(&hs[row * HS_PITCH + col]) = t;
-        }
-    }
-    __syncthreads();
-    FC1_STAMP(6);
-    if (tid < 2 * ROWS) {
-        // one chain per lane: state j = t >> 1, output o = t & 1 (k_fc_out's thread t = 2 s + o); fma over the 256 hidden units
-        // in order
-        const int j = tid >> 1, o = tid & 1;
-        int sidx = s0 + j;
-        const bool live = sidx < n;
-        if (rq.list) sidx = row_slot[j];          // (written by wave 0 before the barrier above)
-        if (live) {
-            float a = wo[2 * HID + o];
-            // the same chain in the same order, its operands fetched four at a time (r06, scripts/fc1_timeline.py: this loop was
-            // 4.5 us of the tile's last workgroup - a scalar LDS read and a scalar global read in front of every fma)
-            const float4* x4 = reinterpret_cast<const float4*>(&hs[j * HS_PITCH]);
-            const float4* w4 = reinterpret_cast<const float4*>(&wo[o * HID]);
-#pragma unroll 8
-            for (int i = 0; i < HID / 4; ++i) {
-                const float4 xv = x4[i], wv = w4[i];
-                a = fmaf(xv.x, wv.x, a); a = fmaf(xv.y, wv.y, a); a = fmaf(xv.z, wv.z, a); a = fmaf(xv.w, wv.w, a);
-            }
-            const float sg = fc1_sigmoid(a);
-            const float tt = sg * wo[2 * HID + 2 + o];
-            const float res = tt + wo[2 * HID + 4 + o];
-            if (o == 0) v_out[sidx] = res; else var_out[sidx] = res;
-        }
-    }
-    FC1_STAMP(7);
-    }   // (arrived last)
-    // a further item stages into bt[] and resolves into row_slot[]: not before the output layer above has read them
-    if (fc1_item_index(blockIdx.x, gridDim.x, kth + 1) < n_items) __syncthreads();
-    }   // (items)
+#define FC1_A3_LOAD(row, k, c) (*reinterpret_cast<const float4*>(a3 + (size_t)(row) * a3stride + (k) + (c)))
+#define FC1_TILE_WAIT() do { } while (0)
+#include "valuenet_fc1_body.inc"
+#undef FC1_LDS
+#undef FC1_ROWS
+#undef FC1_A3_LOAD
+#undef FC1_TILE_WAIT
 }
+
+#include "valuenet_fused.inc"
 
 #include "valuenet_x3.inc"
 #include "valuenet_fc1_x3.inc"
@@ -602,6 +387,85 @@ static int vn_fc1_x3_launch(const float* P, const __bf16* fc1_planes, const ReqL
     return vn_fc1_x3_launch_shape<2, 4, 128, 6, 2, 1>(P, fc1_planes, rq, n, v, var, scratch, stream, cus);
 }
 
+// ---- k_vn_conv_fc1 (valuenet_fused.inc): the host side ----
+#ifndef TM_FC1_TIMELINE
+constexpr bool VN_FUSED_DEFAULT = true;      // what TM_VALUENET_FUSED unset means
+// TM_VALUENET_FUSED (read once): 0 forces the two kernels, 1 asks for the one launch - for A/B runs and the tests, not a user feature
+static bool vn_fused_wanted() {
+    static std::once_flag once;
+    static bool on = VN_FUSED_DEFAULT;
+    std::call_once(once, [&] {
+        const char* e = getenv("TM_VALUENET_FUSED");
+        if (e && e[0] && !e[1] && (e[0] == '0' || e[0] == '1')) on = e[0] == '1';
+    });
+    return on;
+}
+// the launch's grid, asked once: one workgroup a CU up to 256, or 0 - the two-kernel path for good - when the LDS is refused or
+// the chip does not hold that many workgroups at once (a poller must never wait for a workgroup that is not resident)
+static int vn_fused_grid() {
+    static std::once_flag once;
+    static int grid = 0;
+    std::call_once(once, [&] {
+        const int cus = vn_compute_units(), lds = FUSED_LDS_FLOATS * (int)sizeof(float);
+        int per_cu = 0;
+        if (cus <= 0 || max_dynamic_lds<k_vn_conv_fc1>(lds) != 0) return;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_vn_conv_fc1, 512, (size_t)lds) != hipSuccess || per_cu < 1) {
+            (void)hipGetLastError();
+            return;
+        }
+        grid = cus < 256 ? cus : 256;
+    });
+    return grid;
+}
+// the sticky error word (mapped host memory: a poller that gave up writes it, the host reads it after any synchronisation)
+static int32_t* vn_fused_err_host = nullptr;
+static int32_t* vn_fused_err() {
+    static std::once_flag once;
+    static int32_t* dev = nullptr;
+    std::call_once(once, [&] {
+        void* h = nullptr;
+        void* d = nullptr;
+        if (hipHostMalloc(&h, 64, hipHostMallocDefault) != hipSuccess) return;
+        *static_cast<int32_t*>(h) = 0;
+        if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) { (void)hipHostFree(h); return; }
+        vn_fused_err_host = static_cast<int32_t*>(h);
+        dev = static_cast<int32_t*>(d);
+    });
+    return dev;
+}
+// the case the one launch serves: fp32, request mode, the single-leaf shape
+static bool vn_fused_serves(int backend, int fc1, const int8_t* states, const ReqList& rq, int n) {
+    return backend == TM_VALUENET_FP32 && fc1 == TM_VALUENET_FC1_FP32 && !states && rq.list && n > 0 && n < 8192;
+}
+// grid 0: the launch's own grid.  `run`: the caller's proof that the launch's ready words are clear (valuenet_fused.inc) - *run is
+// the list parity of the launch before this one in an unbroken run of one-launch evaluations on this scratch and stream, which
+// cleared this launch's words, or -1; nullptr, -1 or the same parity again: the words are cleared here first
+static int vn_fused_launch(const float* P, const float* prepared, const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n,
+                           float* v, float* var, float* scratch, hipStream_t stream, int grid, int32_t* run) {
+    constexpr int SS = TM_VALUENET_SCRATCH_MFMA;
+    const int resident = vn_fused_grid(), parity = rq.parity & 1;
+    int32_t* err = vn_fused_err();
+    if (resident <= 0 || !err || grid < 0 || grid > resident) return (int)hipErrorInvalidValue;
+    if (!run || *run != (parity ^ 1)) {
+        const int tiles = (n + 31) / 32;
+        hipLaunchKernelGGL(k_vn_ready_clear, dim3((tiles + 255) / 256), dim3(256), 0, stream,
+                           reinterpret_cast<int32_t*>(scratch + A3 + HID), tiles, 32 * SS, FUSED_READY_WORD + parity);
+    }
+    if (run) *run = parity;
+    hipLaunchKernelGGL(k_vn_conv_fc1, dim3(grid > 0 ? grid : resident), dim3(512), FUSED_LDS_FLOATS * sizeof(float), stream, P,
+                       prepared, obs_key, rq, max_nodes, n, scratch, SS, v, var, err);
+    return (int)hipGetLastError();
+}
+#else
+static bool vn_fused_wanted() { return false; }
+static int vn_fused_grid() { return 0; }
+static int32_t* vn_fused_err_host = nullptr;
+static bool vn_fused_serves(int, int, const int8_t*, const ReqList&, int) { return false; }
+static int vn_fused_launch(const float*, const float*, const uint32_t*, const ReqList&, int, int, float*, float*, float*, hipStream_t, int, int32_t*) {
+    return (int)hipErrorInvalidValue;
+}
+#endif
+
 extern "C" {
 
 // the one check of the value net's mode: (FP32, FC1_FP32), (BF16X3, FC1_FP32), (BF16X3, FC1_BF16X3).  Host arithmetic only.
@@ -649,14 +513,10 @@ int tm_valuenet_forward_plain(const float* P, const int8_t* states, int n, float
 
 // backend BF16X3: the convolutions of the split-precision backend (k_vn_conv_x3) on the planes behind prepared's streams, fc1 and
 // the output layer as always - unless fc1 is FC1_BF16X3: k_vn_fc1_x3 on fc1's planes behind those
-static int vn_forward_impl(const float* P, const float* prepared, int backend, int fc1, const int8_t* states,
-                           const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n, float* v, float* var,
-                           float* scratch, hipStream_t stream) {
-    if (const int e = tm_valuenet_check_mode(backend, fc1)) return e;
-    if (n <= 0) return 0;
-    if (backend == TM_VALUENET_BF16X3 && !prepared) return (int)hipErrorInvalidValue;
-    constexpr int SS = TM_VALUENET_SCRATCH_MFMA;   // a3 (1792) + hidden (256) + 16 pad words (word 0 of a tile's first row: its arrival counter)
-    static_assert(SS >= A3 + HID + 1 && SS % 4 == 0, "scratch row");
+static int vn_forward_two(const float* P, const float* prepared, int backend, int fc1, const int8_t* states,
+                          const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n, float* v, float* var,
+                          float* scratch, hipStream_t stream) {
+    constexpr int SS = TM_VALUENET_SCRATCH_MFMA;
     if (backend == TM_VALUENET_BF16X3) {
         const int lds = 4 * X3_WAVE_BYTES;
         if (const int e = max_dynamic_lds<k_vn_conv_x3>(lds)) return e;
@@ -677,6 +537,20 @@ static int vn_forward_impl(const float* P, const float* prepared, int backend, i
     return vn_fc1_launch(P, prepared, rq, n, v, var, scratch, stream);
 }
 
+static int vn_forward_impl(const float* P, const float* prepared, int backend, int fc1, const int8_t* states,
+                           const uint32_t* obs_key, const ReqList& rq, int max_nodes, int n, float* v, float* var,
+                           float* scratch, hipStream_t stream, int32_t* run = nullptr) {
+    if (const int e = tm_valuenet_check_mode(backend, fc1)) return e;
+    if (n <= 0) return 0;
+    if (backend == TM_VALUENET_BF16X3 && !prepared) return (int)hipErrorInvalidValue;
+    constexpr int SS = TM_VALUENET_SCRATCH_MFMA;   // a3 (1792) + hidden (256) + 16 pad words (word 0 of a tile's first row: its arrival counter)
+    static_assert(SS >= A3 + HID + 1 && SS % 4 == 0, "scratch row");
+    // one launch for the convolutions and fc1 where it serves (valuenet_fused.inc); the two kernels otherwise
+    if (vn_fused_wanted() && vn_fused_serves(backend, fc1, states, rq, n) && vn_fused_grid() > 0)
+        return vn_fused_launch(P, prepared, obs_key, rq, max_nodes, n, v, var, scratch, stream, 0, run);
+    return vn_forward_two(P, prepared, backend, fc1, states, obs_key, rq, max_nodes, n, v, var, scratch, stream);
+}
+
 // matrix-core path; prepared: tm_valuenet_prepare's output for this mode or a larger one; scratch: n x TM_VALUENET_SCRATCH_MFMA floats
 int tm_valuenet_forward(const float* P, const float* prepared, int backend, int fc1, const int8_t* states, int n, float* v,
                         float* var, float* scratch, void* stream_) {
@@ -685,8 +559,8 @@ int tm_valuenet_forward(const float* P, const float* prepared, int backend, int 
 }
 
 // the tree engine's evaluation requests, rendered inside the first kernel: v/var -> s->eval_v / s->eval_var
-int tm_valuenet_forward_requests(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
-                                 void* stream_) {
+static int vn_forward_requests(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
+                               void* stream_, int32_t* run) {
     // the requests of the last tm_sim_step launch, drawn from its dense list (s->eval_parity = that launch's)
     // (s->eval_cap / eval_rot / eval_served: the request cap, tm_search_set_request_cap; a store without it serves every request)
     const int segs = TM_EVAL_SEGS(s->n_games);
@@ -695,7 +569,16 @@ int tm_valuenet_forward_requests(const float* P, const float* prepared, int back
     const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, segs, s->eval_slots,
                      capped ? s->eval_cap : 0, capped ? s->eval_rot : 0, capped ? s->eval_served : nullptr};
     return vn_forward_impl(P, prepared, backend, fc1, nullptr, s->obs_key, rq, s->max_nodes, s->n_games * s->eval_slots,
-                           s->eval_v, s->eval_var, scratch, (hipStream_t)stream_);
+                           s->eval_v, s->eval_var, scratch, (hipStream_t)stream_, run);
+}
+int tm_valuenet_forward_requests(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
+                                 void* stream_) {
+    return vn_forward_requests(P, prepared, backend, fc1, s, scratch, stream_, nullptr);
+}
+// the same for a caller that issues a run of evaluations (search.hip): *run = -1 before the first; the library keeps it
+int tm_valuenet_forward_requests_run(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
+                                     void* stream_, int32_t* run) {
+    return vn_forward_requests(P, prepared, backend, fc1, s, scratch, stream_, run);
 }
 
 // k_vn_fc1's item dealing (host arithmetic only: callable without a GPU): the items of workgroup b of a grid of `grid` workgroups
@@ -710,6 +593,39 @@ int tm_fc1_deal(int requests, int rows, int parts, int grid, int b, int32_t* ite
         if (items && k < cap) { items[2 * k] = it.tile; items[2 * k + 1] = it.part; }
     }
     return k;
+}
+
+// the count a tile's poller waits for in k_vn_conv_fc1 (host arithmetic only): the rows of tile `tile` of 32 at `requests` requests
+int tm_fused_tile_rows(int requests, int tile) {
+    if (requests < 0 || tile < 0) return -1;
+    const int left = requests - 32 * tile;
+    return left <= 0 ? 0 : left < 32 ? left : 32;
+}
+// tm_valuenet_forward_requests with the path named (a test entry): grid > 0: k_vn_conv_fc1 on `grid` workgroups (at most the
+// resident ones), 0: on its own grid, < 0: the two kernels.  hipErrorInvalidValue where the one launch does not serve.
+int tm_valuenet_forward_requests_grid(const float* P, const float* prepared, int backend, int fc1, const tm_store* s, float* scratch,
+                                      void* stream_, int grid) {
+    if (const int e = tm_valuenet_check_mode(backend, fc1)) return e;
+    const int segs = TM_EVAL_SEGS(s->n_games);
+    const bool capped = s->eval_served != nullptr;
+    if (capped && (s->eval_cap < 0 || s->eval_rot < 0 || s->eval_rot >= segs)) return (int)hipErrorInvalidValue;
+    const ReqList rq{reinterpret_cast<const int2*>(s->eval_list), s->eval_cnt, s->eval_parity, segs, s->eval_slots,
+                     capped ? s->eval_cap : 0, capped ? s->eval_rot : 0, capped ? s->eval_served : nullptr};
+    const int n = s->n_games * s->eval_slots;
+    if (n <= 0) return 0;
+    if (grid < 0)
+        return vn_forward_two(P, prepared, backend, fc1, nullptr, s->obs_key, rq, s->max_nodes, n, s->eval_v, s->eval_var, scratch,
+                              (hipStream_t)stream_);
+    if (!vn_fused_serves(backend, fc1, nullptr, rq, n)) return (int)hipErrorInvalidValue;
+    return vn_fused_launch(P, prepared, s->obs_key, rq, s->max_nodes, n, s->eval_v, s->eval_var, scratch, (hipStream_t)stream_, grid, nullptr);
+}
+// k_vn_conv_fc1's sticky error word, one a process: nonzero once a poller's bounded wait ran out in any launch of any handle or
+// device (read it after a synchronisation).  reset != 0: clears it
+int tm_valuenet_fused_error(int reset) {
+    if (!vn_fused_err_host) return 0;
+    const int e = __atomic_load_n(vn_fused_err_host, __ATOMIC_RELAXED);
+    if (reset && e) __atomic_store_n(vn_fused_err_host, 0, __ATOMIC_RELAXED);
+    return e;
 }
 
 // k_vn_conv's resident waves, one state each: the cap of the native loop's automatic mode (search.hip)

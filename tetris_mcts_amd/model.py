@@ -243,10 +243,17 @@ class Model_VV(_HipHead):
 
     @torch.no_grad()
     def inference_requests(self, store):
-        """Evaluate a TreeStore's pending leaf requests in place (fused render + forward, HIP back ends only)."""
+        """Evaluate a TreeStore's pending leaf requests in place (fused render + forward, HIP back ends only).  Enqueues only; the
+        fp32 mode's one-launch kernel reports a wait that ran out in a sticky word (fused_wait_failed, after a synchronisation)."""
         P, prep, scr = self.hip_buffers(store.n_games * store.eval_slots)
         _lib.check(_lib.lib().tm_valuenet_forward_requests(P, prep, *self._mode(), C.byref(store.s), scr, _stream()),
                    "tm_valuenet_forward_requests")
+
+    @staticmethod
+    def fused_wait_failed(reset=True):
+        """True once a launch of the one-launch kernel gave up its bounded wait (tm_valuenet_fused_error): what it left in eval_v /
+        eval_var is not an evaluation.  Call when the stream is idle."""
+        return _lib.lib().tm_valuenet_fused_error(int(bool(reset))) != 0
 
     def inference(self, batch):
         """Reference signature (model_vv.py:210-217): float array [B,1,20,10] -> [v[B,1], var[B,1]] numpy."""
