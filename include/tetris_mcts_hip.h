@@ -402,6 +402,28 @@ int tm_episode_targets(const void *rows, int n_rows, const int32_t *order, const
                        float *value, float *variance, float *weight, int32_t *fault, void *stream);
 int tm_episode_gather_states(const void *rows, int n_rows, const int32_t *idx, int n, float *out, int32_t *fault, void *stream);
 
+/* tm_episode_targets with a discount per move and, optionally, another source for the values.  Everything not named here is
+ * tm_episode_targets' own: the rows read in place, order / seg / the tails, the outputs by sorted position, variance[j] and
+ * weight[j] (always from the ROW's variance and visits), the bounds rules, one kernel on stream and no other HIP call, no
+ * atomics, deterministic, nothing written outside the three outputs and *fault.
+ * v_rows: NULL, or float32 [n_rows] BY TABLE ROW (4-byte aligned): v_k of a row is then v_rows[order[.]] instead of the row's value
+ * column; the tail's value stays tail_value.  With r_k = s_{k+1} - s_k (integers) over the series, the tail included:
+ *   mode 0: value_i = sum_{k >= i} gamma^(k-i) r_k; without a tail the last row is the end (value 0).  gamma == 1.0 takes
+ *       tm_episode_targets' integer statement; otherwise D_i = r_i + gamma D_{i+1} in fp64, rounded to fp32 once.
+ *   mode 1: value_i = sum_k lambda^k T_{i,k} / sum_k lambda^k, T_{i,k} = sum_{j<k} gamma^j r_{i+j} + gamma^k v_{i+k}, k to the end
+ *       of the series: N_i = v_i + lambda (gamma N_{i+1} + B_{i+1} r_i), B_i = 1 + lambda B_{i+1}, value_i = N_i / B_i, in
+ *       fp64, rounded to fp32 once.
+ *   mode 2: value_i = v_i, the bits copied from v_rows or from the row.
+ * At gamma == 1.0 and v_rows == NULL the three outputs and *fault are tm_episode_targets' bit for bit in every mode and weight
+ * mode (tests/test_gpu_offline_discount.py).  A non-finite v_rows[k] is not an error: it propagates by IEEE rules into the values
+ * of its episode.
+ * hipErrorInvalidValue, nothing launched, checked before the first HIP call: everything tm_episode_targets refuses; a gamma
+ * outside (0, 1] (a NaN included); v_rows given with mode 0 (mode 0 reads no value); a misaligned v_rows. */
+int tm_episode_targets_discounted(const void *rows, int n_rows, const int32_t *order, const int32_t *seg, int n_seg,
+                                  const uint8_t *tail_kind, const int32_t *tail_score, const float *tail_value,
+                                  const float *v_rows, int mode, double lambda, double gamma, int weight_mode, float eps,
+                                  float *value, float *variance, float *weight, int32_t *fault, void *stream);
+
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel
  * workgroup's games; the groups of TM_GS_GC_ACTIVE4): hipErrorInvalidValue otherwise. */

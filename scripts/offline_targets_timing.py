@@ -10,7 +10,16 @@ episode table's lookup), tm_episode_targets in mode 1 (lambda = 0.9, visit weigh
 over every row; the kernel again on the segments longer than 64 rows alone and on the others alone (long episodes run their
 chunks one after the other: how much of the launch is theirs).  On the host, the median of 3: EpisodeLoader's sort and copy
 (np.lexsort and the fancy index of the 368-byte table) and offline.targets_numpy.  Peak device memory is torch's.
-Needs a GPU: there is no fall-back."""
+Needs a GPU: there is no fall-back.
+
+    python scripts/offline_targets_timing.py --discounted [--json FILE]      (profiles/offline_targets_discounted_timing.json)
+
+The same table, mode 1, lambda = 0.9, visit weights over variance: tm_episode_targets against tm_episode_targets_discounted at
+gamma = 0.999 without and with v_rows, in one process, ALTERNATING - `--repeats` passes, each timing every side once as the median
+of 20 single calls between two events (the way the figure above was taken) and once as 200 calls back to back between two events
+(a window long enough that the events' own cost does not count).  The spread is that of a side's passes.  Then predict_rows over
+the table under a seeded Model_VV: host clock around the call up to a synchronise, the median of 5, and the same loop with the
+gathers alone.  The values of the discounted call are compared with offline.targets_numpy in ulp."""
 import argparse
 import json
 import os
@@ -82,17 +91,99 @@ def host_ms(fn, calls=3):
     return dict(median_ms=statistics.median(out), min_ms=min(out), max_ms=max(out), calls=calls)
 
 
+def batch_ms(fn, calls=200, warm=3):
+    """one call's share of `calls` calls back to back between two events"""
+    import torch
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(calls):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / calls
+
+
+def discounted(a):
+    import torch
+    from tetris_mcts_amd import offline as O
+    from tetris_mcts_amd.model import Model_VV
+    rows, ep = make_table(a.slots, a.moves)
+    n = len(rows)
+    rows_d = O.rows_tensor(rows, "cuda")
+    index = O.episode_index(rows_d, None, ep, None)
+    kind = index.ended.to(torch.uint8)
+    tval = torch.zeros(kind.shape[0], dtype=torch.float32, device="cuda")
+    v_rows = torch.from_numpy(np.random.default_rng(1).uniform(0, 200, n).astype(np.float32)).cuda()
+    head = (rows_d, index.order, index.seg, kind, index.final_score, tval, 1, 0.9, 3)
+    sides = {"tm_episode_targets": lambda: O.targets_device(*head),
+             "discounted_gamma_0.999": lambda: O.targets_device(*head, gamma=0.999),
+             "discounted_gamma_0.999_v_rows": lambda: O.targets_device(*head, gamma=0.999, v_rows=v_rows)}
+    single, batched = {k: [] for k in sides}, {k: [] for k in sides}
+    for _ in range(a.repeats):
+        for k, fn in sides.items():
+            single[k].append(device_ms(fn)["median_ms"])
+        for k, fn in sides.items():
+            batched[k].append(batch_ms(fn))
+
+    def spread(x):
+        return dict(median_ms=statistics.median(x), min_ms=min(x), max_ms=max(x), passes=len(x))
+    res = dict(slots=a.slots, moves=a.moves, rows=n, segments=int(kind.shape[0]), device=torch.cuda.get_device_name(0),
+               mode=1, lam=0.9, gamma=0.999, weight_mode=3,
+               single_call_median_of_20={k: spread(v) for k, v in single.items()},
+               per_call_of_200_back_to_back={k: spread(v) for k, v in batched.items()})
+    base = res["per_call_of_200_back_to_back"]["tm_episode_targets"]
+    for k in ("discounted_gamma_0.999", "discounted_gamma_0.999_v_rows"):
+        r = res["per_call_of_200_back_to_back"][k]
+        res[k + "_over_tm_episode_targets"] = r["median_ms"] / base["median_ms"]
+    # (each call above also allocates and clears its three outputs: both sides alike)
+    order_h, seg_h = index.order.cpu().numpy(), index.seg.cpu().numpy()
+    tail_h = (kind.cpu().numpy(), index.final_score.cpu().numpy(), tval.cpu().numpy())
+    same = {}
+    for name, v in (("discounted_gamma_0.999", None), ("discounted_gamma_0.999_v_rows", v_rows)):
+        got = [x.cpu().numpy() for x in O.targets_device(*head, gamma=0.999, v_rows=v)[:3]]
+        want = O.targets_numpy(rows, order_h, seg_h, *tail_h, 1, 0.9, 3, gamma=0.999, v_rows=None if v is None else v.cpu().numpy())
+        same[name] = dict(value_max_ulp=int(np.abs(got[0].view(np.int32).astype(np.int64) - want[0].view(np.int32).astype(np.int64)).max()),
+                          variance_bits=got[1].tobytes() == want[1].tobytes(), weight_bits=got[2].tobytes() == want[2].tobytes())
+    res["same_results"] = same
+    model = Model_VV(backend="hip", seed=0)
+
+    def gathers(chunk=65536):
+        for lo in range(0, n, chunk):
+            O.gather_states(rows_d, torch.arange(lo, min(n, lo + chunk), dtype=torch.int32, device="cuda"))
+
+    def synced(fn):
+        def run():
+            fn()
+            torch.cuda.synchronize()
+        return run
+    O.predict_rows(model, rows_d)
+    total = host_ms(synced(lambda: O.predict_rows(model, rows_d)), calls=5)
+    gather = host_ms(synced(gathers), calls=5)
+    res["predict_rows"] = dict(chunk=65536, total=total, gathers_alone=gather, gather_share=gather["median_ms"] / total["median_ms"])
+    print(json.dumps(res))
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--slots", type=int, default=4096)
     ap.add_argument("--moves", type=int, default=200)
+    ap.add_argument("--discounted", action="store_true", help="time tm_episode_targets_discounted against tm_episode_targets")
+    ap.add_argument("--repeats", type=int, default=7, help="--discounted: alternating passes over the sides")
     a = ap.parse_args()
     import torch
     from tetris_mcts_amd import offline as O
     from tetris_mcts_amd.episodes import ROW_BYTES, STATE_DTYPE
     if not torch.cuda.is_available():
         sys.exit("offline_targets_timing.py measures the device route: it needs a GPU")
+    if a.discounted:
+        return discounted(a)
     rows, ep = make_table(a.slots, a.moves)
     n = len(rows)
     t = time.perf_counter()

@@ -17,6 +17,16 @@
 // fault[0] = 1 (a plain store), and it is LEFT OUT of its episode's series - the identity map, and d_i of the row before it
 // looks past it to the next row that exists.  seg entries are clamped to [0, n_rows] the same way.
 //
+// k_episode_targets_discounted (tm_episode_targets_discounted) is the same body with a discount gamma per move and, optionally,
+// the values taken from an array by table row instead of the rows' value column.  Mode 1 becomes
+//     N_i = v_i + lambda (gamma N_{i+1} + B_{i+1} r_i),   B_i = 1 + lambda B_{i+1},   r_i = s_{i+1} - s_i:
+// row i is (N, B) -> (v_i + a N + b B, 1 + aB B) with a = lambda gamma, b = lambda r_i, aB = lambda.  The composed maps carry FIVE
+// doubles (a, b, oN, oB, aB): a = (lambda gamma)^span and aB = lambda^span are different powers, and a span is not the lane
+// distance where rows were left out.  At gamma = 1 a and aB hold the same bits at every step, so every statement is the old
+// kernel's.  Mode 0 with gamma < 1 is D_i = r_i + gamma D_{i+1}: the maps D -> o + a D, two doubles, the same scan; with
+// gamma = 1 it is the integer statement.  Both kernels include episode_targets_body.inc; k_episode_targets compiles to the
+// instructions it had before that file existed (scripts/compare_device_code.py).
+//
 // k_episode_gather: a thread per dword of a board - four cells - one float4 store each, so a wave stores 1 KiB contiguously.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -46,18 +56,34 @@ struct TargetArgs {
     int n_rows, n_seg, mode, weight_mode;
 };
 
-// (N, B) -> (oN + a N + b B, oB + a B)
+struct TargetArgsDiscounted : TargetArgs {
+    double gamma;
+    const float* v_rows;                                        // by TABLE row, or nullptr: the rows' value column
+};
+
+// (N, B) -> (oN + a N + b B, oB + aB B); without a discount aB is a
+template <bool DISC>
 struct Map {
     double a, b, oN, oB;
+    __device__ __forceinline__ double aB() const { return a; }
+    __device__ __forceinline__ void set_aB(double) {}
+};
+template <>
+struct Map<true> {
+    double a, b, oN, oB, aB_;
+    __device__ __forceinline__ double aB() const { return aB_; }
+    __device__ __forceinline__ void set_aB(double x) { aB_ = x; }
 };
 
 // first g, then f
-__device__ __forceinline__ Map compose(const Map& f, const Map& g) {
-    Map h;
+template <bool DISC>
+__device__ __forceinline__ Map<DISC> compose(const Map<DISC>& f, const Map<DISC>& g) {
+    Map<DISC> h;
     h.a = f.a * g.a;
-    h.b = f.a * g.b + f.b * g.a;
+    h.b = f.a * g.b + f.b * g.aB();
     h.oN = f.oN + (f.a * g.oN + f.b * g.oB);
-    h.oB = f.oB + f.a * g.oB;
+    h.oB = f.oB + f.aB() * g.oB;
+    h.set_aB(f.aB() * g.aB());
     return h;
 }
 
@@ -74,94 +100,15 @@ __device__ __forceinline__ double lane0_f64(double x) {
 }
 
 __global__ __launch_bounds__(ET_THREADS) void k_episode_targets(TargetArgs A) {
-    const int lane = threadIdx.x & 63;
-    const int e = blockIdx.x * ET_WAVES + (threadIdx.x >> 6);
-    if (e >= A.n_seg) return;                                   // (wave-uniform: no barrier follows)
-    int first = A.seg[e], last = A.seg[e + 1];
-    if (first < 0 || last > A.n_rows) {
-        if (lane == 0) A.fault[0] = 1;
-        first = first < 0 ? 0 : first;
-        last = last > A.n_rows ? A.n_rows : last;
-    }
-    if (first >= last) return;
-    const bool tail = A.tail_kind[e] == 1;
-    // the carry: what lies behind the chunk in hand (wave-uniform)
-    double cN = tail ? (double)A.tail_value[e] : 0.0, cB = tail ? 1.0 : 0.0;
-    int cs = tail ? A.tail_score[e] : 0;                        // the score of the next element that exists ...
-    bool c_has = tail;                                          // ... if there is one
-    int s_end = cs;                                             // mode 0: the tail's score, or the last row's
-    bool end_has = tail;
+#define ET_DISCOUNTED 0
+#include "episode_targets_body.inc"
+#undef ET_DISCOUNTED
+}
 
-    for (int base = first + ((last - first - 1) / 64) * 64; base >= first; base -= 64) {
-        const int j = base + lane;
-        const bool in = j < last;
-        const int r = in ? A.order[j] : -1;
-        const bool ok = in && r >= 0 && r < A.n_rows;
-        if (in && !ok) A.fault[0] = 1;
-        const uint32_t* row = A.rows + (size_t)(ok ? r : 0) * ET_ROW_DW;
-        const int s = ok ? (int)row[ET_SCORE] : 0;
-        const uint32_t v_bits = ok ? row[ET_VALUE] : 0u, var_bits = ok ? row[ET_VARIANCE] : 0u;
-        const float v = __uint_as_float(v_bits), var = __uint_as_float(var_bits);
-
-        float out = 0.0f;
-        if (A.mode == 2) {
-            out = v;
-        } else if (A.mode == 0) {
-            if (!end_has) {
-                const uint64_t have = __ballot(ok);
-                if (have) {
-                    s_end = __shfl(s, 63 - __builtin_clzll(have));
-                    end_has = true;
-                }
-            }
-            out = (float)((long long)s_end - (long long)s);
-        } else {
-            // the score of the next row that exists, looking past the ones that do not: first inside the chunk ...
-            int s_here = s;
-            bool has = ok;
-#pragma unroll
-            for (int k = 1; k < 64; k <<= 1) {
-                const int t = __shfl_down(s_here, k);
-                const int th = __shfl_down((int)has, k);
-                if (!has && lane + k < 64 && th) { s_here = t; has = true; }
-            }
-            int s_next = __shfl_down(s_here, 1);
-            int next_has = __shfl_down((int)has, 1);
-            if (lane == 63 || !next_has) { s_next = cs; next_has = c_has; }       // ... then behind it
-            const double d = next_has ? (double)((long long)s_next - (long long)s) : 0.0;
-            Map m;
-            if (ok) { m.a = A.lambda; m.b = A.lambda * d; m.oN = (double)v; m.oB = 1.0; }
-            else { m.a = 1.0; m.b = 0.0; m.oN = 0.0; m.oB = 0.0; }
-#pragma unroll
-            for (int k = 1; k < 64; k <<= 1) {
-                Map g;
-                g.a = shfl_down_f64(m.a, k); g.b = shfl_down_f64(m.b, k);
-                g.oN = shfl_down_f64(m.oN, k); g.oB = shfl_down_f64(m.oB, k);
-                if (lane + k < 64) m = compose(m, g);
-            }
-            const double N = m.oN + (m.a * cN + m.b * cB), B = m.oB + m.a * cB;
-            out = (float)(N / B);
-            cN = lane0_f64(N);
-            cB = lane0_f64(B);
-            const int h0 = __shfl((int)has, 0), s0 = __shfl(s_here, 0);
-            if (h0) { cs = s0; c_has = true; }
-        }
-
-        float w = 1.0f;
-        if (A.weight_mode >= 2) {
-            const float* st = reinterpret_cast<const float*>(row + ET_VISITS);
-            float sum = ok ? st[0] : 0.0f;
-#pragma unroll
-            for (int a = 1; a < 7; ++a) sum = sum + (ok ? st[a] : 0.0f);
-            w = sum;
-        }
-        if (A.weight_mode == 1 || A.weight_mode == 3) w = w / (var + A.eps);
-        if (in) {
-            A.value[j] = ok ? out : 0.0f;
-            A.variance[j] = __uint_as_float(var_bits);
-            A.weight[j] = ok ? w : 0.0f;
-        }
-    }
+__global__ __launch_bounds__(ET_THREADS) void k_episode_targets_discounted(TargetArgsDiscounted A) {
+#define ET_DISCOUNTED 1
+#include "episode_targets_body.inc"
+#undef ET_DISCOUNTED
 }
 
 __global__ __launch_bounds__(ET_THREADS) void k_episode_gather(const uint32_t* __restrict__ rows, int n_rows,
@@ -188,9 +135,11 @@ using namespace tmcts;
 
 extern "C" {
 
-int tm_episode_targets(const void* rows, int n_rows, const int32_t* order, const int32_t* seg, int n_seg, const uint8_t* tail_kind,
-                       const int32_t* tail_score, const float* tail_value, int mode, double lambda, int weight_mode, float eps,
-                       float* value, float* variance, float* weight, int32_t* fault, void* stream) {
+// what both target calls refuse (hipErrorInvalidValue); 0 with *work = false: nothing to do
+static int check_targets(const void* rows, int n_rows, const int32_t* order, const int32_t* seg, int n_seg, const uint8_t* tail_kind,
+                         const int32_t* tail_score, const float* tail_value, int mode, double lambda, int weight_mode,
+                         const float* value, const float* variance, const float* weight, const int32_t* fault, bool* work) {
+    *work = false;
     if (n_rows < 0 || n_seg < 0 || mode < 0 || mode > 2 || weight_mode < 0 || weight_mode > 3) return (int)hipErrorInvalidValue;
     if (n_rows > 0x7FFFFFFF - 64) return (int)hipErrorInvalidValue;                            // a chunk's positions stay ints
     if (!(lambda >= 0.0 && lambda <= 1.0)) return (int)hipErrorInvalidValue;                   // (a NaN is refused too)
@@ -198,14 +147,52 @@ int tm_episode_targets(const void* rows, int n_rows, const int32_t* order, const
     if (!rows || !order || !seg || !tail_kind || !tail_score || !tail_value || !value || !variance || !weight || !fault)
         return (int)hipErrorInvalidValue;
     if ((reinterpret_cast<uintptr_t>(rows) & 3) != 0) return (int)hipErrorInvalidValue;         // rows are read as dwords
-    TargetArgs A;
+    *work = true;
+    return 0;
+}
+
+static void fill_targets(TargetArgs& A, const void* rows, int n_rows, const int32_t* order, const int32_t* seg, int n_seg,
+                         const uint8_t* tail_kind, const int32_t* tail_score, const float* tail_value, int mode, double lambda,
+                         int weight_mode, float eps, float* value, float* variance, float* weight, int32_t* fault) {
     A.rows = reinterpret_cast<const uint32_t*>(rows);
     A.order = order; A.seg = seg;
     A.tail_kind = tail_kind; A.tail_score = tail_score; A.tail_value = tail_value;
     A.value = value; A.variance = variance; A.weight = weight; A.fault = fault;
     A.lambda = lambda; A.eps = eps;
     A.n_rows = n_rows; A.n_seg = n_seg; A.mode = mode; A.weight_mode = weight_mode;
+}
+
+int tm_episode_targets(const void* rows, int n_rows, const int32_t* order, const int32_t* seg, int n_seg, const uint8_t* tail_kind,
+                       const int32_t* tail_score, const float* tail_value, int mode, double lambda, int weight_mode, float eps,
+                       float* value, float* variance, float* weight, int32_t* fault, void* stream) {
+    bool work;
+    const int rc = check_targets(rows, n_rows, order, seg, n_seg, tail_kind, tail_score, tail_value, mode, lambda, weight_mode, value,
+                                 variance, weight, fault, &work);
+    if (!work) return rc;
+    TargetArgs A;
+    fill_targets(A, rows, n_rows, order, seg, n_seg, tail_kind, tail_score, tail_value, mode, lambda, weight_mode, eps, value, variance,
+                 weight, fault);
     hipLaunchKernelGGL(k_episode_targets, dim3((n_seg + ET_WAVES - 1) / ET_WAVES), dim3(ET_THREADS), 0, (hipStream_t)stream, A);
+    return (int)hipGetLastError();
+}
+
+int tm_episode_targets_discounted(const void* rows, int n_rows, const int32_t* order, const int32_t* seg, int n_seg,
+                                  const uint8_t* tail_kind, const int32_t* tail_score, const float* tail_value, const float* v_rows,
+                                  int mode, double lambda, double gamma, int weight_mode, float eps, float* value, float* variance,
+                                  float* weight, int32_t* fault, void* stream) {
+    if (!(gamma > 0.0 && gamma <= 1.0)) return (int)hipErrorInvalidValue;                      // (a NaN is refused too)
+    if (v_rows && mode == 0) return (int)hipErrorInvalidValue;                                 // mode 0 reads no value
+    if ((reinterpret_cast<uintptr_t>(v_rows) & 3) != 0) return (int)hipErrorInvalidValue;
+    bool work;
+    const int rc = check_targets(rows, n_rows, order, seg, n_seg, tail_kind, tail_score, tail_value, mode, lambda, weight_mode, value,
+                                 variance, weight, fault, &work);
+    if (!work) return rc;
+    TargetArgsDiscounted A;
+    fill_targets(A, rows, n_rows, order, seg, n_seg, tail_kind, tail_score, tail_value, mode, lambda, weight_mode, eps, value, variance,
+                 weight, fault);
+    A.gamma = gamma; A.v_rows = v_rows;
+    hipLaunchKernelGGL(k_episode_targets_discounted, dim3((n_seg + ET_WAVES - 1) / ET_WAVES), dim3(ET_THREADS), 0,
+                       (hipStream_t)stream, A);
     return (int)hipGetLastError();
 }
 

@@ -25,6 +25,16 @@ by the end of the run: it is CENSORED.  In mode 1 it has no tail and its last ro
 Weights: the reference applies --weighted only to mode 2; here the four rules apply in every mode.  weight_mode of the C call =
 0 without --weighted, else --weighted_mode + 1.  The reference divides the visits by their mean; `train_data` divides whatever
 weights it is given by their mean, so nothing here normalises.
+
+Two options go beyond the reference's rules (tm_episode_targets_discounted); their defaults reproduce the rules above bit for bit:
+    gamma     the discount per move.  With r_k = s_{k+1} - s_k:
+              mode 0  value_i = sum_k gamma^k r_{i+k}                         (D_i = r_i + gamma D_{i+1})
+              mode 1  value_i = sum_k lam^k T_{i,k} / sum_k lam^k,  T_{i,k} = sum_{j<k} gamma^j r_{i+j} + gamma^k v_{i+k}
+                      (N_i = v_i + lam (gamma N_{i+1} + B_{i+1} r_i), B_i = 1 + lam B_{i+1}, value_i = N_i / B_i)
+              The search backs up score difference + gamma * value' with gamma = 0.999 (ValueSim(gamma=0.999), tm_store.gamma), so
+              0.999 is the choice under which the fitted net answers the question the search asks it; 1.0 is the reference's.
+    v_rows    float32 by TABLE row: the v_k of the rows, instead of their value column (mode 1 and 2).  `predict_rows` fills it
+              from the net being fitted, and fit_episodes(bootstrap="net") refreshes it before every round of the fit.
 """
 import ctypes as C
 import glob
@@ -130,11 +140,27 @@ def weight_mode(weighted, weighted_mode):
     return int(weighted_mode) + 1
 
 
-def targets_numpy(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam, wmode, eps=EPS):
-    """The specification of tm_episode_targets in numpy (include/tetris_mcts_hip.h): fp64, ONE backward pass in which step t
-    handles the t-th row from the end of every episode that has one.  rows: STATE_DTYPE table.  Returns value, variance, weight
-    (float32, by sorted position) and fault (0 / 1)."""
+def _check_discount(mode, gamma, v_rows):
+    gamma = float(gamma)
+    if not 0.0 < gamma <= 1.0:
+        raise ValueError("gamma is in (0, 1], not %r" % (gamma,))
+    if v_rows is not None and mode == 0:
+        raise ValueError("v_rows replaces the rows' values, and mode 0 (not --td) reads none")
+    return gamma
+
+
+def targets_numpy(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam, wmode, eps=EPS, gamma=1.0, v_rows=None):
+    """The specification of tm_episode_targets and tm_episode_targets_discounted in numpy (include/tetris_mcts_hip.h): fp64, ONE
+    backward pass in which step t handles the t-th row from the end of every episode that has one.  rows: STATE_DTYPE table.
+    gamma, v_rows (float32 [n_rows] by table row): the module docstring; at their defaults every statement computes what it
+    computed without them (gamma * N is exact at 1.0).  Returns value, variance, weight (float32, by sorted position) and fault
+    (0 / 1)."""
+    gamma = _check_discount(mode, gamma, v_rows)
     n_rows, n = len(rows), len(order)
+    if v_rows is not None:
+        v_rows = np.asarray(v_rows)
+        if v_rows.dtype != np.float32 or v_rows.shape != (n_rows,):
+            raise ValueError("v_rows: float32 [%d], one value per table row" % n_rows)
     order, seg = np.asarray(order, np.int64), np.clip(np.asarray(seg, np.int64), 0, n_rows)
     fault = int((np.asarray(seg) != seg).any())
     ok = (order >= 0) & (order < n_rows)
@@ -145,7 +171,7 @@ def targets_numpy(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam
     safe = np.where(ok, order, 0)
     zero = np.float32(0)
     s = np.where(ok, rows["score"][safe].astype(np.int64), 0) if n_rows else np.zeros(n, np.int64)
-    v32 = np.where(ok, rows["value"][safe], zero) if n_rows else np.zeros(n, np.float32)
+    v32 = np.where(ok, (rows["value"] if v_rows is None else v_rows)[safe], zero) if n_rows else np.zeros(n, np.float32)
     variance = np.where(ok, rows["variance"][safe], zero).astype(np.float32) if n_rows else np.zeros(n, np.float32)
     value = np.zeros(n, np.float32)
     first, last = seg[:-1], seg[1:]
@@ -156,6 +182,7 @@ def targets_numpy(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam
         lam = float(lam)
         N = np.where(tail, np.asarray(tail_value, np.float64), 0.0)
         B = np.where(tail, 1.0, 0.0)
+        D = np.zeros(len(tail))                                               # mode 0 with a discount: D_i = r_i + gamma D_{i+1}
         s_next = np.where(tail, np.asarray(tail_score, np.int64), 0)          # the score of the next element that exists ...
         has = tail.copy()                                                     # ... if there is one (mode 0: the end is known)
         for t in range(int((last - first).max(initial=0))):
@@ -163,13 +190,18 @@ def targets_numpy(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam
             j = last[live] - 1 - t
             good = ok[j]
             e, j = live[good], j[good]
-            if mode == 0:
+            if mode == 0 and gamma == 1.0:
                 s_next[e] = np.where(has[e], s_next[e], s[j])                 # without a tail the last row that exists is the end
                 has[e] = True
                 value[j] = (s_next[e] - s[j]).astype(np.float32)
+            elif mode == 0:
+                d = np.where(has[e], s_next[e] - s[j], 0).astype(np.float64)
+                D[e] = d + gamma * D[e]
+                value[j] = D[e].astype(np.float32)
+                s_next[e], has[e] = s[j], True
             else:
                 d = np.where(has[e], s_next[e] - s[j], 0).astype(np.float64)
-                Ne = v32[j].astype(np.float64) + lam * (N[e] + B[e] * d)
+                Ne = v32[j].astype(np.float64) + lam * (gamma * N[e] + B[e] * d)
                 Be = 1.0 + lam * B[e]
                 value[j] = (Ne / Be).astype(np.float32)
                 N[e], B[e], s_next[e], has[e] = Ne, Be, s[j], True
@@ -193,18 +225,29 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
-def targets_device(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam, wmode, eps=EPS):
+def targets_device(rows, order, seg, tail_kind, tail_score, tail_value, mode, lam, wmode, eps=EPS, gamma=1.0, v_rows=None):
     """tm_episode_targets on the rows' device, on the current stream; returns value, variance, weight and the fault word
-    (device tensors: nothing is read back here)."""
+    (device tensors: nothing is read back here).  tm_episode_targets_discounted is called only when gamma or v_rows (a
+    contiguous float32 tensor [n_rows] on that device) is off its default: with the defaults this is the call it always was."""
     from . import _lib
+    gamma = _check_discount(mode, gamma, v_rows)
     dev, n = rows.device, order.shape[0]
+    if v_rows is not None and (v_rows.dtype != torch.float32 or v_rows.shape != (rows.shape[0],) or v_rows.device != dev
+                               or not v_rows.is_contiguous()):
+        raise ValueError("v_rows: a contiguous float32 tensor [%d] on %s, one value per table row" % (rows.shape[0], dev))
     value, variance, weight = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(3))
     fault = torch.zeros(1, dtype=torch.int32, device=dev)
+    head = (_ptr(rows), rows.shape[0], _ptr(order), _ptr(seg), seg.shape[0] - 1, _ptr(tail_kind), _ptr(tail_score), _ptr(tail_value))
+    out = (_ptr(value), _ptr(variance), _ptr(weight), _ptr(fault))
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().tm_episode_targets(
-            _ptr(rows), rows.shape[0], _ptr(order), _ptr(seg), seg.shape[0] - 1, _ptr(tail_kind), _ptr(tail_score), _ptr(tail_value),
-            int(mode), float(lam), int(wmode), float(eps), _ptr(value), _ptr(variance), _ptr(weight), _ptr(fault),
-            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tm_episode_targets")
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if gamma == 1.0 and v_rows is None:
+            _lib.check(_lib.lib().tm_episode_targets(*head, int(mode), float(lam), int(wmode), float(eps), *out, stream),
+                       "tm_episode_targets")
+        else:
+            _lib.check(_lib.lib().tm_episode_targets_discounted(
+                *head, C.c_void_p(0) if v_rows is None else _ptr(v_rows), int(mode), float(lam), gamma, int(wmode), float(eps), *out,
+                stream), "tm_episode_targets_discounted")
     return value, variance, weight, fault
 
 
@@ -227,10 +270,27 @@ def gather_states(rows, idx):
     return out
 
 
+def predict_rows(model, rows, chunk=65536):
+    """float32 [n_rows] value and variance of every table row's board under `model` (a Model_VV), in table order: `chunk` rows at a
+    time through tm_episode_gather_states and Model_VV.inference_device - the kernels the search asks, which is what a bootstrap
+    should come from.  rows: the uint8 tensor [n, 368] on the model's device.  No host synchronisation beyond those calls' own
+    (gather_states reads its fault word)."""
+    if chunk < 1:
+        raise ValueError("chunk: at least one row, not %r" % (chunk,))
+    n = rows.shape[0]
+    value, variance = (torch.empty(n, dtype=torch.float32, device=rows.device) for _ in range(2))
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        boards = gather_states(rows, torch.arange(a, b, dtype=torch.int32, device=rows.device))
+        model.inference_device(boards.reshape(b - a, 200).to(torch.int8), value[a:b], variance[a:b])
+    return value, variance
+
+
 def episode_targets(rows, index, td=False, lam=None, weighted=False, weighted_mode=0, terminal="final", censored="drop",
-                    device=None, eps=EPS):
+                    device=None, eps=EPS, gamma=1.0, v_rows=None):
     """value, variance, weight (float32 tensors by SORTED position j, i.e. of rows[index.order[j]]) and `keep` (bool: False for
     the rows `censored="drop"` leaves out).  td / lam / weighted / weighted_mode: the command line's (module docstring).
+    gamma, v_rows (a float32 tensor by table row on the rows' device): the module docstring.
     device: None - where the rows are; "cpu" - the numpy statement, whatever the rows' device."""
     if terminal not in ("final", "rows"):
         raise ValueError("terminal is 'final' or 'rows', not %r" % (terminal,))
@@ -246,12 +306,14 @@ def episode_targets(rows, index, td=False, lam=None, weighted=False, weighted_mo
     if on.type == "cpu":
         table = rows.cpu().numpy().reshape(-1).view(STATE_DTYPE)
         value, variance, weight, fault = targets_numpy(table, index.order.cpu().numpy(), index.seg.cpu().numpy(), tail_kind.cpu().numpy(),
-                                                       index.final_score.cpu().numpy(), tail_value.cpu().numpy(), mode, lam, wmode, eps)
+                                                       index.final_score.cpu().numpy(), tail_value.cpu().numpy(), mode, lam, wmode, eps,
+                                                       gamma, None if v_rows is None else v_rows.cpu().numpy())
         value, variance, weight = (torch.from_numpy(x) for x in (value, variance, weight))
     else:
         rows, order, seg, tail_kind, final, tail_value = (t.to(on).contiguous() for t in (rows, index.order, index.seg, tail_kind,
                                                                                          index.final_score, tail_value))
-        value, variance, weight, fault = targets_device(rows, order, seg, tail_kind, final, tail_value, mode, lam, wmode, eps)
+        value, variance, weight, fault = targets_device(rows, order, seg, tail_kind, final, tail_value, mode, lam, wmode, eps, gamma,
+                                                        None if v_rows is None else v_rows.to(on).contiguous())
         fault = int(fault.item())
     if fault:
         raise RuntimeError("episode_targets: the index names rows outside the %d given" % rows.shape[0])
@@ -305,10 +367,12 @@ def validation_fraction(n, n_val):
 
 def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, terminal="final", censored="drop", last_nfiles=1,
                  validation=False, val_mode=0, val_episodes=0, val_set_size=0.05, val_set_size_max=-1, generator=None,
-                 device="cuda", eps=EPS):
+                 device="cuda", eps=EPS, gamma=1.0, v_rows=None):
     """data = [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (float32 on `device`), training rows first and
     the held-out rows last - the layout train_data splits - and a dict with n_val, validation_fraction (train_data's
-    int(n * fraction) is n_val exactly), n_train, the stems and the row counts.  Files as train.py --data_paths / --last_nfiles
+    int(n * fraction) is n_val exactly), n_train, the stems and the row counts, and what a refresh of the values needs without
+    reading the files again: `rows` (the table on `device`), `index` (episode_index of it) and `sel` (the sorted positions of the
+    n rows of `data`, in its order).  gamma, v_rows: episode_targets'.  Files as train.py --data_paths / --last_nfiles
     chooses them (choose_stems).  validation: train.py:148-174 - val_mode 0 holds out a random int(n * val_set_size) rows (at most
     val_set_size_max if that is positive; `generator`: a torch.Generator for the draw), val_mode 1 whole episodes with
     episode < val_episodes + 1 (a random val_set_size_max of their rows if that is positive)."""
@@ -318,7 +382,7 @@ def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, ter
     rows = rows_tensor(table, dev)
     index = episode_index(rows, stem_rows, episodes, episode_stems)
     value, variance, weight, keep = episode_targets(rows, index, td=td, lam=lam, weighted=weighted, weighted_mode=weighted_mode,
-                                                    terminal=terminal, censored=censored, eps=eps)
+                                                    terminal=terminal, censored=censored, eps=eps, gamma=gamma, v_rows=v_rows)
     n_all = keep.shape[0]
     held = torch.zeros(n_all, dtype=torch.bool, device=dev)
     if validation and val_mode == 1 and val_episodes > 0:
@@ -350,22 +414,64 @@ def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, ter
     states = gather_states(rows, index.order[sel])
     data = [states] + [x[sel].reshape(n, 1) for x in (value, variance, weight)]
     return data, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
-                      rows=n_all, episodes=int(index.ended.shape[0]), censored_episodes=int((~index.ended).sum().item()))
+                      n_rows=n_all, episodes=int(index.ended.shape[0]), censored_episodes=int((~index.ended).sum().item()),
+                      rows=rows, index=index, sel=sel)
 
 
 def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
-                 early_stopping_patience=10, fit_backend="torch", validation_backend="torch", **options):
-    """training_set(paths, **options) on the model's device, then model.train_data on it; returns what train_data returns.
-    max_iters and iters_per_val may be functions of the number of training rows (train.py computes its iterations from it)."""
+                 early_stopping_patience=10, fit_backend="torch", validation_backend="torch", gamma=1.0, bootstrap="recorded",
+                 bootstrap_rounds=1, on_round=None, **options):
+    """training_set(paths, gamma=gamma, **options) on the model's device, then model.train_data on it; returns what train_data
+    returns plus `rounds`: one dict per round with iters, best_validation and graph_replay.
+    max_iters and iters_per_val may be functions of the number of training rows (train.py computes its iterations from it).
+
+    bootstrap="recorded" (one round): the v_k of the lambda-return are the recorded root values - one training_set, one
+    train_data.  bootstrap="net" (needs td=True and a lam: mode 2 would fit the net to its own output, and mode 0 bootstraps
+    nothing) takes them from `model` itself and refreshes them: the iterations are split into `bootstrap_rounds` parts
+    (iters // R each, the remainder to the last), and before each part the values of ALL selected rows, held-out rows included,
+    are recomputed - predict_rows under the model as it stands, episode_targets with those v_rows - and written into the same
+    data[1] tensor.  The split, the variances and the weights are computed once.  Early stopping and the best-weights reload act
+    within a round; the optimiser's state persists across rounds, as it does across online fits.  A prediction that is not
+    finite raises RuntimeError before a target is computed from it (one .item() a round).
+    on_round(r, data, v_rows), r = 0 .. R-1, is called before each round's train_data with the tensors in use (v_rows: None
+    with bootstrap="recorded")."""
     from .model import Model_VV
     if not isinstance(model, Model_VV):
         raise TypeError("fit_episodes fits a Model_VV: the reference has no episode target for a distribution (%s)"
                         % type(model).__name__)
-    data, info = training_set(paths, device=model.device, **options)
+    rounds = int(bootstrap_rounds)
+    if bootstrap not in ("recorded", "net"):
+        raise ValueError("bootstrap is 'recorded' or 'net', not %r" % (bootstrap,))
+    if rounds < 1:
+        raise ValueError("bootstrap_rounds: at least 1, not %r" % (bootstrap_rounds,))
+    if bootstrap == "net" and (not options.get("td") or options.get("lam") is None):
+        raise ValueError("bootstrap='net' refreshes the v of the lambda-return: it needs td=True and a lam")
+    if bootstrap == "recorded" and rounds > 1:
+        raise ValueError("bootstrap='recorded' with %d rounds: nothing would change between them" % rounds)
+    _check_discount(target_mode(options.get("td", False), options.get("lam"))[0], gamma, None)
+    data, info = training_set(paths, device=model.device, gamma=gamma, **options)
     iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
     extra = {}
     if iters_per_val is not None:
         extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
-    return model.train_data(data, batch_size=batch_size, max_iters=iters, validation_fraction=info["validation_fraction"],
-                            shuffle=False, early_stopping=early_stopping, early_stopping_patience=early_stopping_patience,
-                            fit_backend=fit_backend, validation_backend=validation_backend, **extra)
+    if rounds > 1 and iters < rounds:
+        raise ValueError("%d iterations do not make %d rounds" % (iters, rounds))
+    targets = {k: options[k] for k in ("td", "lam", "weighted", "weighted_mode", "terminal", "censored", "eps") if k in options}
+    done = []
+    for r in range(rounds):
+        v_rows = None
+        if bootstrap == "net":
+            model.training(False)
+            v_rows = predict_rows(model, info["rows"])[0]
+            if not bool(torch.isfinite(v_rows).all().item()):
+                raise RuntimeError("fit_episodes: round %d: the net's values of the recorded boards are not all finite" % r)
+            value = episode_targets(info["rows"], info["index"], gamma=gamma, v_rows=v_rows, **targets)[0]
+            data[1].copy_(value[info["sel"]].reshape(-1, 1))
+        if on_round is not None:
+            on_round(r, data, v_rows)
+        res = model.train_data(data, batch_size=batch_size, max_iters=iters // rounds + (iters % rounds if r == rounds - 1 else 0),
+                               validation_fraction=info["validation_fraction"], shuffle=False, early_stopping=early_stopping,
+                               early_stopping_patience=early_stopping_patience, fit_backend=fit_backend,
+                               validation_backend=validation_backend, **extra)
+        done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
+    return dict(res, rounds=done)

@@ -8,6 +8,10 @@ The reference's script does not run as committed (`backend`, `eligibility_trace`
 it reads row 3 of a 3-row child_stats), so what is kept is its intent: its flags, its file choice, its three target rules, its
 validation split and its iteration count.  `--td_lambda` stands for its eligibility trace: without it `--td` fits the recorded
 root values, with it the lambda-return.  --ewc and --save_loss are refused with a message.
+
+Beyond the reference: --target_gamma discounts the targets per move (0.999 is the search's discount; the default 1.0 is the
+reference's undiscounted rule), and --bootstrap net takes the values inside the lambda-return from the net being fitted, refreshed
+before each of --bootstrap_rounds parts of the fit, instead of the values the playing net recorded.
 """
 import argparse
 import sys
@@ -44,6 +48,12 @@ def build_parser():
         'score from the episode table (value 0); rows: the reference\'s rule, the last recorded row is the end')
     add('--censored', default='drop', choices=('drop', 'keep'), help='[new] without --td: the episodes the run cut off are left '
         'out (drop) or end at their last row (keep, the reference\'s rule)')
+    add('--target_gamma', default=1.0, type=float, help='[new] the discount per move of the targets, in (0, 1]: 0.999 is the '
+        'search\'s discount (the value it adds to discounted score differences); default 1.0, the reference\'s undiscounted rule')
+    add('--bootstrap', default='recorded', choices=('recorded', 'net'), help='[new] with --td --td_lambda: the values inside the '
+        'lambda-return are the recorded root values (recorded) or the fitted net\'s own, refreshed every round (net)')
+    add('--bootstrap_rounds', default=1, type=int, help='[new] with --bootstrap net: the iterations are split into this many '
+        'parts and the targets recomputed from the net before each (default:1)')
     add('--fit_backend', default='hip', choices=('torch', 'hip'), help='[new] gradients through PyTorch autograd (torch) or the '
         'hand-written gfx950 forward / loss / backward kernels (hip)')
     add('--validation_backend', default=None, choices=('torch', 'hip'), help='[new] validation through PyTorch (torch) or the '
@@ -63,6 +73,16 @@ def check_args(args):
         sys.exit('--td_lambda is the trace of --td: it needs --td')
     if args.td_lambda is not None and not 0.0 <= args.td_lambda <= 1.0:
         sys.exit('--td_lambda is in [0, 1]')
+    if not 0.0 < args.target_gamma <= 1.0:
+        sys.exit('--target_gamma is in (0, 1]')
+    if args.bootstrap == 'net' and not (args.td and args.td_lambda is not None):
+        sys.exit('--bootstrap net refreshes the values inside the lambda-return: it needs --td --td_lambda')
+    if args.bootstrap == 'net' and args.new:
+        sys.exit('--bootstrap net with --new: the values of a random net are noise')
+    if args.bootstrap_rounds < 1:
+        sys.exit('--bootstrap_rounds is at least 1')
+    if args.bootstrap_rounds > 1 and args.bootstrap == 'recorded':
+        sys.exit('--bootstrap_rounds above 1 needs --bootstrap net: recorded values do not change between rounds')
     if args.weighted_mode not in (0, 1, 2):
         sys.exit('--weighted_mode: 0 inverse of variance, 1 number of visits, 2 both')
     args.validation_backend = args.validation_backend or args.fit_backend
@@ -108,8 +128,9 @@ def main(argv=None):
                        td=args.td, lam=args.td_lambda, weighted=args.weighted, weighted_mode=args.weighted_mode,
                        terminal=args.terminal, censored=args.censored, last_nfiles=args.last_nfiles, validation=args.validation,
                        val_mode=args.val_mode, val_episodes=args.val_episodes, val_set_size=args.val_set_size,
-                       val_set_size_max=args.val_set_size_max)
-    print('iters:%d/%d' % (res['iters'], plan['iters'])
+                       val_set_size_max=args.val_set_size_max, gamma=args.target_gamma, bootstrap=args.bootstrap,
+                       bootstrap_rounds=args.bootstrap_rounds)
+    print('iters:%d/%d' % (sum(r['iters'] for r in res['rounds']), plan['iters'])
           + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
     model.save()
 
