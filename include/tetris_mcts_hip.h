@@ -424,6 +424,39 @@ int tm_episode_targets_discounted(const void *rows, int n_rows, const int32_t *o
                                   const float *v_rows, int mode, double lambda, double gamma, int weight_mode, float eps,
                                   float *value, float *variance, float *weight, int32_t *fault, void *stream);
 
+/* Categorical targets for the distributional head from the same rows (episode_dist_targets.hip): the search's distributional
+ * backup (shift by the score gained, mix) along the moves played.  rows, order, seg, tail_kind and tail_score are
+ * tm_episode_targets' (seg does not fall: a position finds its segment by bisection); there is no tail value: the tail element is
+ * tail_score with ALL MASS IN ATOM 0, the search's v_dummy of a finished game.  atoms K in 1 .. TM_DIST_ROW over [vmin, vmax),
+ * delta = (vmax - vmin) / K in double.
+ * The shift S_c(p) by an integer score difference c >= 0 is tm_distpy_shift's rule: bs = (double)c / delta, n = floor(bs),
+ * f = bs - n; source atom a gives p[a] (1 - f) to lb = min(a + n, K-1) and p[a] f to min(lb + 1, K-1); mass that reaches the top
+ * atom stays there.  The series of an episode is its rows in move order, then the tail element where tail_kind == 1.
+ *   mode 0 (Monte Carlo): target_i = S_{s_end - s_i}(e_0), e_0 = all mass in atom 0, s_end the tail's score, without a tail the last
+ *       row's: atom lb gets (float)(1 - f), atom lb + 1 (float)f, and 1 where the two are the top atom; no distribution is read.
+ *   mode 1 (truncated lambda-return): target_i = sum_{k=0..m} lambda^k S_{s_{i+k} - s_i}(P_{i+k}) / sum_{k=0..m} lambda^k with
+ *       m = min(horizon, elements after i); P of a row = p_rows[row] (float32 [n_rows][p_stride] BY TABLE ROW, atoms first; the
+ *       padding is never read), P of the tail = e_0.  Per atom in fp64 in ascending k (the weight by repeated multiplication; a
+ *       term in gather form, out[b] = p[b-n] (1 - f) + p[b-n-1] f, the top atom = the fp64 sum p[K-1] + p[K-2] + .. down to atom
+ *       max(K-1-n, 0), added in that order, + p[K-2-n] f), divided once and rounded to fp32 once.  lambda == 0 copies P_i.
+ * There is no discount (the distributional backup has none) and no mode 2 (no distribution is recorded).
+ * Outputs by sorted position j: target[j * target_stride + b] for b < atoms ONLY, weight[j] by tm_episode_targets' four
+ * weight_mode rules from the row's visits and variance.  *fault (a device int32 the caller cleared): bit 0 - an order[j] outside
+ * [0, n_rows) (never made an address: a zero target row, weight 0, left out of its episode's series) or a seg entry outside
+ * [0, n_rows] (clamped); bit 1 - a negative score difference, taken as 0.
+ * Enqueues two kernels on stream (the weights and the bounds first; the second stores bit 1 into the word as the first left it)
+ * and makes no other HIP call: no allocation, no synchronisation, no read-back, no atomics, deterministic, nothing written outside
+ * target[:, :atoms], weight and *fault.  hipErrorInvalidValue, nothing launched, checked before the first HIP call: everything
+ * tm_episode_targets refuses (its value pointers excepted: there are none); atoms outside 1 .. 64; target_stride < atoms, and
+ * p_stride < atoms in mode 1; vmax <= vmin or a bound that is not finite; horizon < 0; a mode outside 0 .. 1; p_rows == NULL in
+ * mode 1 when there is work; a p_rows or target that is not 4-byte aligned.  n_rows == 0 or n_seg == 0 returns 0.
+ * Held on an MI355X to a numpy statement of these definitions and to an exact rational oracle (tests/test_gpu_offline_dist.py);
+ * timed there (profiles/offline_dist_targets_timing.json). */
+int tm_episode_dist_targets(const void *rows, int n_rows, const int32_t *order, const int32_t *seg, int n_seg,
+                            const uint8_t *tail_kind, const int32_t *tail_score, const float *p_rows, int p_stride, int atoms,
+                            double vmin, double vmax, int mode, double lambda, int horizon, int weight_mode, float eps,
+                            float *target, int target_stride, float *weight, int32_t *fault, void *stream);
+
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel
  * workgroup's games; the groups of TM_GS_GC_ACTIVE4): hipErrorInvalidValue otherwise. */

@@ -36,7 +36,9 @@ class DistValueSim(OnlineFit, TreeAgent):
         fit_states: what those fits are fed - "dense" (the harvested observations rendered to [n,1,22,10] floats) or "packed" (the
         48-byte observations themselves, read by the kernels; it needs fit_backend="hip_dist" and validation_backend="hip").
         valuenet_backend: the Model_Dist backend of the model the agent builds when `model` is None (None: Model_Dist's
-        default; "hip", "hip_bf16x3" - the split-precision kernels - or "torch").
+        default; "hip", "hip_bf16x3" - the split-precision kernels - or "torch").  That model loads
+        pytorch_model/model_checkpoint_dist (train.py --head dist) when the file exists; a checkpoint of another atom count is
+        refused.
         online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
         least `min_visits_to_store` visits whose seven children have all been visited (its commented store_nodes, default 50)
         as (board, distribution, visits) tuples, train_nodes fits the head on them (memory_size / memory_growth_rate as
@@ -61,7 +63,13 @@ class DistValueSim(OnlineFit, TreeAgent):
         super().__init__(max_nodes=max_nodes, online=self.online, min_visits_to_store=min_visits_to_store, **kwargs)
         if evaluator is None:
             from ..model_distributional import Model_Dist
-            self.model = model if model is not None else Model_Dist(atoms=self.atoms, backend=valuenet_backend)
+            if model is None:
+                model = Model_Dist(atoms=self.atoms, backend=valuenet_backend)
+                import os
+                from ..model_distributional import CHECKPOINT
+                if os.path.isfile(CHECKPOINT):         # what train.py --head dist wrote; without the file nothing is touched
+                    model.load(verbose=False)
+            self.model = model
             if int(getattr(self.model, "atoms", self.atoms)) != self.atoms:
                 # the head's parameter blob is indexed with the store's atom count (tm_distnet_forward_requests): another
                 # count reads fc_v out of bounds

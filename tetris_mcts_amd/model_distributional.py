@@ -13,6 +13,7 @@ model_distributional.py:27).  Same module names, so `state_dict`s are interchang
   * "torch"      - PyTorch-ROCm ops (MIOpen / rocBLAS): training (`loss`) and a cross-check.
 The distribution arithmetic around it is in csrc/tree.hip (wave_dist_front / wave_dist_back)."""
 import ctypes as C
+import os
 from collections import OrderedDict
 
 import torch
@@ -20,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .model import VALUENET_BACKEND, _HipHead
+from .model import EXP_PATH, VALUENET_BACKEND, _HipHead
 from .store import _p, _stream
 
 PARAM_ORDER = ["seq.conv1.weight", "seq.conv1.bias", "seq.conv2.weight", "seq.conv2.bias", "seq.fc1.weight", "seq.fc1.bias",
@@ -30,6 +31,7 @@ PREPARED_X3 = 24576     # TM_DISTNET_PREPARED_X3: conv2's bf16 planes behind the
 HIP_BACKENDS = ("hip", "hip_bf16x3")    # the backends the native search loop (search.hip) runs
 SCRATCH = 2048          # TM_DISTNET_SCRATCH
 ROW = 64                # TM_DIST_ROW
+CHECKPOINT = EXP_PATH + "model_checkpoint_dist"     # beside Model_VV's model_checkpoint
 
 
 def _conv_out(shape, k, stride):
@@ -134,6 +136,39 @@ class Model_Dist(_HipHead):
             # Model_Dist.__init__ (model_distributional.py:66): what the class ends up with (its _init_model's Yogi is overwritten)
             self.optimizer = torch.optim.Adam(self.model.parameters(), lr=1e-4, eps=1e-5, amsgrad=True)
         return self.optimizer
+
+    def load(self, filename=CHECKPOINT, verbose=True):
+        """Model_VV.load for this head: the same dictionary keys in a file of its own.  A checkpoint with another number of atoms
+        is refused (fc_v would not fit, and the search indexes the parameter blob with the store's atom count); an optimiser state
+        that does not fit the optimiser restarts it with a warning.  Without the file nothing changes."""
+        if os.path.isfile(filename):
+            if verbose:
+                print("Loading model...", flush=True)
+            ck = torch.load(filename, map_location=self.device)
+            state = ck["model_state_dict"]
+            atoms = int(state["seq.fc_v.weight"].shape[0])
+            if atoms != self.atoms:
+                raise ValueError("%s holds a head of %d atoms, this Model_Dist has %d" % (filename, atoms, self.atoms))
+            self.model.load_state_dict(state)
+            if ck.get("optimizer_state_dict"):
+                try:
+                    (getattr(self, "optimizer", None) or self._optimizer()).load_state_dict(ck["optimizer_state_dict"])
+                except (ValueError, KeyError) as e:
+                    from sys import stderr
+                    print("WARNING: optimizer state of %s not loaded (%s): the optimiser restarts with fresh moments"
+                          % (filename, e), file=stderr, flush=True)
+        elif verbose:
+            print("Checkpoint not found, using default model", flush=True)
+        self.weights_changed()
+
+    def save(self, filename=CHECKPOINT, verbose=True):
+        """model_state_dict and optimizer_state_dict, as Model_VV.save writes them; a fused Adam's state dict is torch.optim.Adam's
+        (train._FlatBuffers.state_dict), so either optimiser loads what the other wrote."""
+        if verbose:
+            print("Saving model...", flush=True)
+        os.makedirs(os.path.dirname(filename) or ".", exist_ok=True)
+        opt = getattr(self, "optimizer", None) or self._optimizer()
+        torch.save({"model_state_dict": self.model.state_dict(), "optimizer_state_dict": opt.state_dict()}, filename)
 
     def _fused_optimizer(self, commit=True):
         """the model's optimiser as a train.FusedAdam (one HIP kernel a step, a flat gradient buffer), the state of the Adam it

@@ -35,6 +35,10 @@ Two options go beyond the reference's rules (tm_episode_targets_discounted); the
               0.999 is the choice under which the fitted net answers the question the search asks it; 1.0 is the reference's.
     v_rows    float32 by TABLE row: the v_k of the rows, instead of their value column (mode 1 and 2).  `predict_rows` fills it
               from the net being fitted, and fit_episodes(bootstrap="net") refreshes it before every round of the fit.
+
+The distributional head has the same route with categorical targets (the second half of this file): dist_targets_numpy is the
+specification, dist_targets_device the call (csrc/episode_dist_targets.hip: tm_episode_dist_targets), episode_dist_targets,
+predict_rows_dist and fit_episodes_dist what episode_targets, predict_rows and fit_episodes are to the value net.
 """
 import ctypes as C
 import glob
@@ -365,24 +369,9 @@ def validation_fraction(n, n_val):
     return f
 
 
-def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, terminal="final", censored="drop", last_nfiles=1,
-                 validation=False, val_mode=0, val_episodes=0, val_set_size=0.05, val_set_size_max=-1, generator=None,
-                 device="cuda", eps=EPS, gamma=1.0, v_rows=None):
-    """data = [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (float32 on `device`), training rows first and
-    the held-out rows last - the layout train_data splits - and a dict with n_val, validation_fraction (train_data's
-    int(n * fraction) is n_val exactly), n_train, the stems and the row counts, and what a refresh of the values needs without
-    reading the files again: `rows` (the table on `device`), `index` (episode_index of it) and `sel` (the sorted positions of the
-    n rows of `data`, in its order).  gamma, v_rows: episode_targets'.  Files as train.py --data_paths / --last_nfiles
-    chooses them (choose_stems).  validation: train.py:148-174 - val_mode 0 holds out a random int(n * val_set_size) rows (at most
-    val_set_size_max if that is positive; `generator`: a torch.Generator for the draw), val_mode 1 whole episodes with
-    episode < val_episodes + 1 (a random val_set_size_max of their rows if that is positive)."""
-    stems = choose_stems(paths, last_nfiles)
-    table, stem_rows, episodes, episode_stems = load_stems(stems)
-    dev = torch.device(device)
-    rows = rows_tensor(table, dev)
-    index = episode_index(rows, stem_rows, episodes, episode_stems)
-    value, variance, weight, keep = episode_targets(rows, index, td=td, lam=lam, weighted=weighted, weighted_mode=weighted_mode,
-                                                    terminal=terminal, censored=censored, eps=eps, gamma=gamma, v_rows=v_rows)
+def _split(index, keep, validation, val_mode, val_episodes, val_set_size, val_set_size_max, generator, dev):
+    """training_set's split (train.py:148-174): the sorted positions that train followed by the ones held out, and how many the
+    latter are.  keep: bool by sorted position, the rows that take part at all."""
     n_all = keep.shape[0]
     held = torch.zeros(n_all, dtype=torch.bool, device=dev)
     if validation and val_mode == 1 and val_episodes > 0:
@@ -407,8 +396,30 @@ def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, ter
             val = val[torch.sort(draw(val.shape[0])[:val_set_size_max]).values]
     elif validation:
         raise ValueError("val_mode: 0 random, 1 episodic; not %r" % (val_mode,))
-    sel = torch.cat([pos, val])
-    n, n_val = int(sel.shape[0]), int(val.shape[0])
+    return torch.cat([pos, val]), int(val.shape[0])
+
+
+def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, terminal="final", censored="drop", last_nfiles=1,
+                 validation=False, val_mode=0, val_episodes=0, val_set_size=0.05, val_set_size_max=-1, generator=None,
+                 device="cuda", eps=EPS, gamma=1.0, v_rows=None):
+    """data = [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (float32 on `device`), training rows first and
+    the held-out rows last - the layout train_data splits - and a dict with n_val, validation_fraction (train_data's
+    int(n * fraction) is n_val exactly), n_train, the stems and the row counts, and what a refresh of the values needs without
+    reading the files again: `rows` (the table on `device`), `index` (episode_index of it) and `sel` (the sorted positions of the
+    n rows of `data`, in its order).  gamma, v_rows: episode_targets'.  Files as train.py --data_paths / --last_nfiles
+    chooses them (choose_stems).  validation: train.py:148-174 - val_mode 0 holds out a random int(n * val_set_size) rows (at most
+    val_set_size_max if that is positive; `generator`: a torch.Generator for the draw), val_mode 1 whole episodes with
+    episode < val_episodes + 1 (a random val_set_size_max of their rows if that is positive)."""
+    stems = choose_stems(paths, last_nfiles)
+    table, stem_rows, episodes, episode_stems = load_stems(stems)
+    dev = torch.device(device)
+    rows = rows_tensor(table, dev)
+    index = episode_index(rows, stem_rows, episodes, episode_stems)
+    value, variance, weight, keep = episode_targets(rows, index, td=td, lam=lam, weighted=weighted, weighted_mode=weighted_mode,
+                                                    terminal=terminal, censored=censored, eps=eps, gamma=gamma, v_rows=v_rows)
+    n_all = keep.shape[0]
+    sel, n_val = _split(index, keep, validation, val_mode, val_episodes, val_set_size, val_set_size_max, generator, dev)
+    n = int(sel.shape[0])
     if n == 0:
         raise RuntimeError("no rows to train on: every episode of %s is censored (censored='keep' takes them as they are)" % (stems,))
     states = gather_states(rows, index.order[sel])
@@ -473,5 +484,297 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
                                validation_fraction=info["validation_fraction"], shuffle=False, early_stopping=early_stopping,
                                early_stopping_patience=early_stopping_patience, fit_backend=fit_backend,
                                validation_backend=validation_backend, **extra)
+        done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
+    return dict(res, rounds=done)
+
+
+# ---- the distributional head: categorical targets (csrc/episode_dist_targets.hip: tm_episode_dist_targets) ----------------------
+#
+# What the search's distributional backup does along a trace - shift a distribution by the score gained, mix it into the node
+# above - done along the moves played.  atoms K over [vmin, vmax), delta = (vmax - vmin) / K in double.  The shift S_c(p) by an
+# integer score difference c >= 0 (tm_distpy_shift's rule): bs = c / delta, n = floor(bs), f = bs - n; source atom a gives
+# p[a] (1 - f) to lb = min(a + n, K-1) and p[a] f to min(lb + 1, K-1).  An episode's series is its rows in move order and, where it
+# ended (terminal="final"), one tail element: its final score with all mass in atom 0, the search's v_dummy.
+#     mode 0  not --td                 target_i = S_{s_end - s_i}(e_0)                                       (Monte Carlo)
+#     mode 1  --td --td_lambda L       target_i = sum_{k<=m} L^k S_{s_{i+k} - s_i}(P_{i+k}) / sum_{k<=m} L^k,  m = min(horizon, what follows i)
+# P comes from `p_rows`, float32 [n_rows, >= K] by TABLE row: the head's own output (predict_rows_dist).  There is no mode 2 (no
+# distribution is recorded) and no discount (the distributional backup has none).  Two interpolating shifts composed are not the
+# shift by the sum, so nothing is carried from one target to the next: every term is one exact shift over a bounded horizon.
+
+def dist_target_mode(td, lam):
+    """(mode, lambda) of tm_episode_dist_targets for the command line's --td / --td_lambda"""
+    if not td:
+        return 0, 0.0
+    if lam is None:
+        raise ValueError("td without a lam: the rows record no distribution to fit (the value net's mode 2 has no counterpart)")
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lam (--td_lambda) is in [0, 1], not %r" % (lam,))
+    return 1, lam
+
+
+def _check_dist(atoms, vmin, vmax, mode, horizon, p_rows, n_rows):
+    atoms, vmin, vmax = int(atoms), float(vmin), float(vmax)
+    if not 1 <= atoms <= 64:
+        raise ValueError("atoms: 1 .. 64, not %r" % (atoms,))
+    if not (np.isfinite(vmin) and np.isfinite(vmax) and vmax > vmin and np.isfinite(vmax - vmin)):
+        raise ValueError("[vmin, vmax): two finite bounds with vmin < vmax, not %r, %r" % (vmin, vmax))
+    if mode not in (0, 1):
+        raise ValueError("mode: 0 Monte Carlo, 1 the truncated lambda-return; not %r" % (mode,))
+    if int(horizon) < 0:
+        raise ValueError("horizon: at least 0, not %r" % (horizon,))
+    if mode == 1 and (p_rows is None or p_rows.dtype not in (np.float32, torch.float32) or len(p_rows.shape) != 2
+                      or p_rows.shape[0] != n_rows or p_rows.shape[1] < atoms):
+        raise ValueError("p_rows: float32 [%d, >= %d], one distribution per table row" % (n_rows, atoms))
+    return atoms, (vmax - vmin) / atoms
+
+
+def _shift_terms(P, suf, el, n, f, K):
+    """S(P[el]) in gather form, fp64 [len(el), K]: atom b < K-1 = P[b-n] (1-f) + P[b-n-1] f, the top atom = suf[max(K-1-n, 0)] +
+    P[K-2-n] f.  P: [., K+1] with a last column of zeros (what a source below atom 0 reads), suf: [., K] its sums from the top."""
+    b = np.arange(K - 1)
+    src = b[None, :] - n[:, None]
+    row = el[:, None]
+    t = np.empty((len(el), K))
+    t[:, :K - 1] = P[row, np.where(src >= 0, src, K)] * (1.0 - f)[:, None] + P[row, np.where(src >= 1, src - 1, K)] * f[:, None]
+    top = K - 1 - n
+    t[:, K - 1] = suf[el, np.maximum(top, 0)] + P[el, np.where(top >= 1, top - 1, K)] * f
+    return t
+
+
+def _shift_of(c, delta, K):
+    """(n, f, a score fell) of int64 score differences; a negative one is taken as 0"""
+    fell = bool((c < 0).any())
+    bs = np.maximum(c, 0).astype(np.float64) / delta
+    fl = np.floor(bs)
+    return np.minimum(fl, K).astype(np.int64), bs - fl, fell
+
+
+def dist_targets_numpy(rows, order, seg, tail_kind, tail_score, atoms, vmin, vmax, mode, lam, horizon, wmode, eps=EPS, p_rows=None):
+    """The specification of tm_episode_dist_targets in numpy (include/tetris_mcts_hip.h): fp64, all targets at once, one pass per
+    k.  rows: STATE_DTYPE table; seg does not fall.  Returns target float32 [n, atoms] and weight float32 [n] by sorted position,
+    and the fault word (bit 0: an order entry that is not a row, or a seg entry outside the table; bit 1: a score that fell)."""
+    n_rows, n = len(rows), len(order)
+    K, delta = _check_dist(atoms, vmin, vmax, mode, horizon, p_rows, n_rows)
+    order, seg0 = np.asarray(order, np.int64), np.asarray(seg, np.int64)
+    seg = np.clip(seg0, 0, n_rows)
+    fault = int((seg0 != seg).any())
+    ok = (order >= 0) & (order < n_rows)
+    n_seg = len(seg) - 1
+    ep = np.full(n, -1, np.int64)
+    for e in range(n_seg):
+        ep[seg[e]:seg[e + 1]] = e
+    covered = ep >= 0
+    fault |= int((~ok & covered).any())
+    safe = np.where(ok, order, 0)
+    zero, one = np.float32(0), np.float32(1)
+    if wmode >= 2:
+        st = rows["child_stats"][safe][:, 0, :] if n_rows else np.zeros((n, 7), np.float32)
+        weight = st[:, 0].astype(np.float32)
+        for a in range(1, 7):
+            weight = weight + st[:, a]
+    else:
+        weight = np.full(n, one, np.float32)
+    if wmode in (1, 3):
+        variance = rows["variance"][safe].astype(np.float32) if n_rows else np.zeros(n, np.float32)
+        with np.errstate(all="ignore"):
+            weight = weight / (variance + np.float32(eps))
+    weight = np.where(ok & covered, weight, zero).astype(np.float32)
+    target = np.zeros((n, K), np.float32)
+    pos = np.nonzero(ok & covered)[0]                                     # ascending: episode by episode, in move order
+    if not len(pos):
+        return target, weight, fault
+    # the series of all episodes one after the other: the rows that exist, then the tail
+    tail = np.asarray(tail_kind)[:n_seg] == 1
+    cnt = np.bincount(ep[pos], minlength=n_seg)
+    off = np.concatenate([[0], np.cumsum(cnt + tail)])
+    first = np.concatenate([[0], np.cumsum(cnt)])[:-1]
+    x = off[ep[pos]] + (np.arange(len(pos)) - first[ep[pos]])             # the element that position is
+    end = off[ep[pos] + 1]                                                # one past its series' last element
+    S = np.zeros(off[-1], np.int64)
+    S[x] = rows["score"][order[pos]].astype(np.int64)
+    S[off[1:][tail] - 1] = np.asarray(tail_score, np.int64)[:n_seg][tail]
+    if mode == 0:
+        has = (cnt + tail) > 0
+        s_end = np.zeros(n_seg, np.int64)
+        s_end[has] = S[off[1:][has] - 1]                                  # the tail's score; without a tail the last row's
+        nn, f, fell = _shift_of(s_end[ep[pos]] - S[x], delta, K)
+        e0 = np.zeros((1, K + 1))
+        e0[0, 0] = 1.0
+        target[pos] = _shift_terms(e0, e0[:, :K], np.zeros(len(pos), np.int64), nn, f, K).astype(np.float32)
+        return target, weight, fault | (2 if fell else 0)
+    P = np.zeros((off[-1], K + 1))
+    P[x, :K] = np.asarray(p_rows)[order[pos], :K].astype(np.float64)      # (the padding atoms are never read)
+    P[off[1:][tail] - 1, 0] = 1.0
+    suf = np.cumsum(P[:, K - 1::-1], axis=1)[:, ::-1]                     # p[K-1] + p[K-2] + .., added in that order
+    lam = float(lam)
+    H = 0 if lam == 0.0 else int(horizon)
+    acc, wsum, w = np.zeros((len(pos), K)), np.zeros(len(pos)), np.ones(len(pos))
+    fell = False
+    for k in range(H + 1):
+        act = np.nonzero(x + k < end)[0]
+        if not len(act):
+            break
+        nn, f, fell_k = _shift_of(S[x[act] + k] - S[x[act]], delta, K)
+        fell |= fell_k
+        acc[act] = acc[act] + w[act][:, None] * _shift_terms(P, suf, x[act] + k, nn, f, K)
+        wsum[act] = wsum[act] + w[act]
+        w[act] = w[act] * lam
+    target[pos] = (acc / wsum[:, None]).astype(np.float32)
+    return target, weight, fault | (2 if fell else 0)
+
+
+def dist_targets_device(rows, order, seg, tail_kind, tail_score, atoms, vmin, vmax, mode, lam, horizon, wmode, eps=EPS, p_rows=None):
+    """tm_episode_dist_targets on the rows' device, on the current stream; returns target (float32 [n, 64]: the atoms first, the
+    padding zero), weight and the fault word (device tensors: nothing is read back here).  p_rows: a float32 tensor [n_rows, >=
+    atoms] on that device with contiguous rows (mode 1)."""
+    from . import _lib
+    dev, n = rows.device, order.shape[0]
+    K, _ = _check_dist(atoms, vmin, vmax, mode, horizon, p_rows, rows.shape[0])
+    if p_rows is not None and mode == 1 and (p_rows.device != dev or p_rows.stride(1) != 1):
+        raise ValueError("p_rows: on %s, its rows contiguous" % (dev,))
+    target = torch.zeros(n, 64, dtype=torch.float32, device=dev)
+    weight = torch.zeros(n, dtype=torch.float32, device=dev)
+    fault = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().tm_episode_dist_targets(
+            _ptr(rows), rows.shape[0], _ptr(order), _ptr(seg), seg.shape[0] - 1, _ptr(tail_kind), _ptr(tail_score),
+            C.c_void_p(0) if mode == 0 else _ptr(p_rows), 0 if mode == 0 else p_rows.stride(0), K, float(vmin), float(vmax), int(mode),
+            float(lam), int(horizon), int(wmode), float(eps), _ptr(target), target.stride(0), _ptr(weight), _ptr(fault),
+            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tm_episode_dist_targets")
+    return target, weight, fault
+
+
+def _kept(index, mode, censored, dev):
+    """bool by sorted position: False for the rows of the censored episodes that mode 0 with censored="drop" leaves out"""
+    n, n_seg = index.order.shape[0], index.ended.shape[0]
+    if mode == 0 and censored == "drop" and n_seg:
+        length = (index.seg[1:] - index.seg[:-1]).to(torch.int64)
+        return torch.repeat_interleave(index.ended, length, output_size=n).to(dev)
+    return torch.ones(n, dtype=torch.bool, device=dev)
+
+
+def episode_dist_targets(rows, index, td=False, lam=None, horizon=64, atoms=50, vmin=0.0, vmax=5000.0, weighted=False,
+                         weighted_mode=0, terminal="final", censored="drop", p_rows=None, device=None, eps=EPS):
+    """target (float32 [n, atoms]), weight (float32 [n]) by SORTED position j, i.e. of rows[index.order[j]], and `keep` (bool:
+    False for the rows `censored="drop"` leaves out).  td / lam: dist_target_mode; horizon: the terms after the row's own that a
+    mode-1 target takes at most; p_rows: the distributions by table row (mode 1), a float32 tensor [n_rows, >= atoms].
+    device: None - where the rows are; "cpu" - the numpy statement, whatever the rows' device.  Raises RuntimeError on a set
+    fault word (one .item())."""
+    if terminal not in ("final", "rows"):
+        raise ValueError("terminal is 'final' or 'rows', not %r" % (terminal,))
+    if censored not in ("drop", "keep"):
+        raise ValueError("censored is 'drop' or 'keep', not %r" % (censored,))
+    mode, lam = dist_target_mode(td, lam)
+    wmode = weight_mode(weighted, weighted_mode)
+    rows = rows_tensor(rows)
+    on = rows.device if device is None else torch.device(device)
+    tail_kind = (index.ended if terminal == "final" else torch.zeros_like(index.ended)).to(torch.uint8)
+    if on.type == "cpu":
+        table = rows.cpu().numpy().reshape(-1).view(STATE_DTYPE)
+        target, weight, fault = dist_targets_numpy(table, index.order.cpu().numpy(), index.seg.cpu().numpy(), tail_kind.cpu().numpy(),
+                                                   index.final_score.cpu().numpy(), atoms, vmin, vmax, mode, lam, horizon, wmode, eps,
+                                                   None if p_rows is None else p_rows.cpu().numpy())
+        target, weight = torch.from_numpy(target), torch.from_numpy(weight)
+    else:
+        rows, order, seg, tail_kind, final = (t.to(on).contiguous() for t in (rows, index.order, index.seg, tail_kind, index.final_score))
+        target, weight, fault = dist_targets_device(rows, order, seg, tail_kind, final, atoms, vmin, vmax, mode, lam, horizon, wmode,
+                                                    eps, None if p_rows is None else p_rows.to(on))
+        target, fault = target[:, :int(atoms)], int(fault.item())
+    if fault & 1:
+        raise RuntimeError("episode_dist_targets: the index names rows outside the %d given" % rows.shape[0])
+    if fault & 2:
+        raise RuntimeError("episode_dist_targets: a score falls inside an episode: these are not recorded rows in move order")
+    return target, weight, _kept(index, mode, censored, target.device)
+
+
+def predict_rows_dist(model, rows, chunk=65536):
+    """float32 [n_rows, 64]: the distribution of every table row's board under `model` (a Model_Dist) in table order, the atoms
+    first - `chunk` rows at a time through tm_episode_gather_states and Model_Dist.inference_device, the kernels the search asks.
+    rows: the uint8 tensor [n, 368] on the model's device."""
+    if chunk < 1:
+        raise ValueError("chunk: at least one row, not %r" % (chunk,))
+    n = rows.shape[0]
+    out = torch.zeros(n, 64, dtype=torch.float32, device=rows.device)
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        boards = gather_states(rows, torch.arange(a, b, dtype=torch.int32, device=rows.device))
+        model.inference_device(boards.reshape(b - a, 200).to(torch.int8), out[a:b])
+    return out
+
+
+def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
+                      early_stopping_patience=10, fit_backend=None, validation_backend="torch", td=False, lam=None, horizon=64,
+                      vmin=0.0, vmax=5000.0, rounds=1, on_round=None, weighted=False, weighted_mode=0, terminal="final",
+                      censored="drop", last_nfiles=1, validation=False, val_mode=0, val_episodes=0, val_set_size=0.05,
+                      val_set_size_max=-1, generator=None, eps=EPS):
+    """fit_episodes for the distributional head: the recorded episodes of `paths` (choose_stems) -> categorical targets over the
+    model's atoms on [vmin, vmax) (episode_dist_targets on the model's device) -> Model_Dist.train_data -> the checkpoint
+    (Model_Dist.save, after every round).  Returns what train_data returns plus `rounds`, as fit_episodes does.
+    Not td: mode 0, the realised return as a distribution; computed once (rounds must be 1).  td with a lam: mode 1; the
+    distributions inside it are the MODEL's own, over every recorded board (predict_rows_dist), refreshed before each of `rounds`
+    parts of the iterations (iters // rounds each, the remainder to the last) - the targets of all selected rows, held-out rows
+    included, are recomputed and written into the same data[1] tensor, as fit_episodes(bootstrap="net") does.  The split
+    (training_set's), the boards and the weights are computed once.  A prediction that is not finite raises RuntimeError before a
+    target is computed from it, and so does a set fault word.
+    fit_backend: None - "hip_dist" on a GPU, "torch" on the host.  max_iters / iters_per_val may be functions, as in fit_episodes.
+    on_round(r, data, p_rows), r = 0 .. rounds-1, is called before each round's train_data with the tensors in use (p_rows: None
+    in mode 0)."""
+    from .model_distributional import Model_Dist
+    if not isinstance(model, Model_Dist):
+        raise TypeError("fit_episodes_dist fits a Model_Dist: the value net's episode targets are fit_episodes' (%s)"
+                        % type(model).__name__)
+    mode, lam_ = dist_target_mode(td, lam)
+    rounds = int(rounds)
+    if rounds < 1:
+        raise ValueError("rounds: at least 1, not %r" % (rounds,))
+    if mode == 0 and rounds > 1:
+        raise ValueError("%d rounds without td: the Monte Carlo targets do not change between them" % rounds)
+    dev = torch.device(model.device)
+    _check_dist(model.atoms, vmin, vmax, 0, horizon, None, 0)
+    if fit_backend is None:
+        fit_backend = "hip_dist" if dev.type == "cuda" else "torch"
+    stems = choose_stems(paths, last_nfiles)
+    table, stem_rows, episodes, episode_stems = load_stems(stems)
+    rows = rows_tensor(table, dev)
+    index = episode_index(rows, stem_rows, episodes, episode_stems)
+    sel, n_val = _split(index, _kept(index, mode, censored, dev), validation, val_mode, val_episodes, val_set_size, val_set_size_max,
+                        generator, dev)
+    n = int(sel.shape[0])
+    if n == 0:
+        raise RuntimeError("no rows to train on: every episode of %s is censored (censored='keep' takes them as they are)" % (stems,))
+    states = torch.zeros(n, 1, 22, 10, dtype=torch.float32, device=dev)
+    states[:, :, 2:, :] = gather_states(rows, index.order[sel])              # the head's 22 rows: two empty ones on top
+    iters = int(max_iters(n - n_val)) if callable(max_iters) else int(max_iters)
+    extra = {}
+    if iters_per_val is not None:
+        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    if rounds > 1 and iters < rounds:
+        raise ValueError("%d iterations do not make %d rounds" % (iters, rounds))
+    options = dict(td=td, lam=lam, horizon=horizon, atoms=model.atoms, vmin=vmin, vmax=vmax, weighted=weighted,
+                   weighted_mode=weighted_mode, terminal=terminal, censored=censored, eps=eps)
+    data, done = None, []
+    for r in range(rounds):
+        p_rows = None
+        if mode == 1:
+            model.training(False)
+            p_rows = predict_rows_dist(model, rows)
+            if not bool(torch.isfinite(p_rows[:, :model.atoms]).all().item()):
+                raise RuntimeError("fit_episodes_dist: round %d: the head's distributions of the recorded boards are not all finite" % r)
+        if data is None or mode == 1:
+            target, weight, _ = episode_dist_targets(rows, index, p_rows=p_rows, **options)
+            if data is None:
+                data = [states, target[sel].contiguous(), weight[sel].reshape(n, 1)]
+            else:
+                data[1].copy_(target[sel])
+        if on_round is not None:
+            on_round(r, data, p_rows)
+        res = model.train_data(data, fit_backend=fit_backend, batch_size=batch_size,
+                               max_iters=iters // rounds + (iters % rounds if r == rounds - 1 else 0),
+                               validation_fraction=validation_fraction(n, n_val), shuffle=False, early_stopping=early_stopping,
+                               early_stopping_patience=early_stopping_patience, validation_backend=validation_backend, **extra)
+        from . import dist as tdist
+        if tdist.rank() == 0:                  # replicas are identical: one checkpoint file, written by rank 0
+            model.save(verbose=False)
         done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
     return dict(res, rounds=done)

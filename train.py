@@ -12,6 +12,13 @@ root values, with it the lambda-return.  --ewc and --save_loss are refused with 
 Beyond the reference: --target_gamma discounts the targets per move (0.999 is the search's discount; the default 1.0 is the
 reference's undiscounted rule), and --bootstrap net takes the values inside the lambda-return from the net being fitted, refreshed
 before each of --bootstrap_rounds parts of the fit, instead of the values the playing net recorded.
+
+--head dist fits the distributional head of DistValueSim instead (offline.fit_episodes_dist: categorical targets over --atoms
+atoms on [--vmin, --vmax), csrc/episode_dist_targets.hip) and writes pytorch_model/model_checkpoint_dist, which a DistValueSim
+that builds its own model loads.  Without --td the target is the realised return as a distribution; --td --td_lambda L
+--bootstrap net is the lambda-return of the head's own distributions over at most --td_horizon moves, refreshed before each of
+--bootstrap_rounds parts.  --fit_backend hip then means the head's gradient step (hip_dist).  The head records no distribution
+and its backup has no discount, so --td alone, --bootstrap recorded with --td and a --target_gamma other than 1 are refused.
 """
 import argparse
 import sys
@@ -58,6 +65,13 @@ def build_parser():
         'hand-written gfx950 forward / loss / backward kernels (hip)')
     add('--validation_backend', default=None, choices=('torch', 'hip'), help='[new] validation through PyTorch (torch) or the '
         'forward of the same gfx950 kernels (hip: needs --fit_backend hip); default: as --fit_backend')
+    add('--head', default='value', choices=('value', 'dist'), help='[new] the net that is fitted: the value net (value) or the '
+        'distributional head of DistValueSim (dist: categorical targets, pytorch_model/model_checkpoint_dist)')
+    add('--atoms', default=50, type=int, help='[new] --head dist: the atoms of the head, 1 .. 64 (default:50)')
+    add('--vmin', default=0.0, type=float, help='[new] --head dist: the lower end of the atoms\' range (default:0)')
+    add('--vmax', default=5000.0, type=float, help='[new] --head dist: the upper end of the atoms\' range (default:5000)')
+    add('--td_horizon', default=64, type=int, help='[new] --head dist with --td: the moves after a row that its target takes in '
+        'at most (default:64)')
     return p
 
 
@@ -71,6 +85,19 @@ def check_args(args):
                  'not reimplement; the fit logs its losses to stderr')
     if args.td_lambda is not None and not args.td:
         sys.exit('--td_lambda is the trace of --td: it needs --td')
+    if args.head == 'dist':
+        if args.td and args.td_lambda is None:
+            sys.exit('--head dist with --td needs --td_lambda: the rows record no distribution to fit')
+        if args.td and args.bootstrap != 'net':
+            sys.exit('--head dist with --td needs --bootstrap net: the distributions inside the target are the head\'s own')
+        if args.target_gamma != 1.0:
+            sys.exit('--head dist takes no --target_gamma other than 1: the distributional backup does not discount')
+        if args.td_horizon < 0:
+            sys.exit('--td_horizon is at least 0')
+        if not 1 <= args.atoms <= 64:
+            sys.exit('--atoms is in 1 .. 64')
+        if not args.vmin < args.vmax:
+            sys.exit('--vmin is below --vmax')
     if args.td_lambda is not None and not 0.0 <= args.td_lambda <= 1.0:
         sys.exit('--td_lambda is in [0, 1]')
     if not 0.0 < args.target_gamma <= 1.0:
@@ -109,9 +136,36 @@ def iterations(args, n_data):
     return iters, iters // args.val_total + 1
 
 
+def main_dist(args):
+    """--head dist: the same files, split and iteration count; categorical targets (offline.fit_episodes_dist)"""
+    from tetris_mcts_amd.model_distributional import Model_Dist
+    from tetris_mcts_amd.offline import fit_episodes_dist
+    model = Model_Dist(atoms=args.atoms, backend='hip')
+    if not args.new:
+        model.load()
+    plan = {}
+
+    def max_iters(n_train):
+        plan['iters'], plan['val'] = iterations(args, n_train)
+        return plan['iters']
+    res = fit_episodes_dist(model, args.data_paths, batch_size=args.batch_size, max_iters=max_iters, iters_per_val=lambda _: plan['val'],
+                            early_stopping=args.early_stopping, early_stopping_patience=args.early_stopping_patience,
+                            fit_backend='hip_dist' if args.fit_backend == 'hip' else 'torch', validation_backend=args.validation_backend,
+                            td=args.td, lam=args.td_lambda, horizon=args.td_horizon, vmin=args.vmin, vmax=args.vmax,
+                            rounds=args.bootstrap_rounds, weighted=args.weighted, weighted_mode=args.weighted_mode,
+                            terminal=args.terminal, censored=args.censored, last_nfiles=args.last_nfiles, validation=args.validation,
+                            val_mode=args.val_mode, val_episodes=args.val_episodes, val_set_size=args.val_set_size,
+                            val_set_size_max=args.val_set_size_max)
+    print('iters:%d/%d' % (sum(r['iters'] for r in res['rounds']), plan['iters'])
+          + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
+    model.save()
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     check_args(args)
+    if args.head == 'dist':
+        return main_dist(args)
     from tetris_mcts_amd.model import Model_VV
     from tetris_mcts_amd.offline import fit_episodes
     model = Model_VV(backend='hip')
