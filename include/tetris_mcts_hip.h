@@ -648,6 +648,38 @@ int tm_valuenet_fit_validate(const float *params, const float *out_bounds, const
 int tm_valuenet_fit_validate_packed(const float *params, const float *out_bounds, const uint32_t *obs, const float *value,
                                     const float *variance, const float *weight, long long n, int chunk, int slab, int weighted,
                                     float variance_clip, double *rows_out, float *workspace, void *stream);
+/* The Fisher pass of the value net's fit (csrc/valuenet_fit.hip): fisher[i] = (1/n) sum_b (d loss_b / d p_i)^2 over the rows idx[0 .. n)
+ * (idx NULL: rows 0 .. n-1; repeats allowed; every entry must be a valid row - the caller checks), loss_b the per-sample loss of
+ * tm_valuenet_fit_grad (the weight multiplied in when weighted != 0), i over the 478338 floats of params: the empirical Fisher diagonal
+ * at the targets the fit used.  The rows are taken `slab` at a time (1 .. 2^20): per slab the gradient step's forward, its output layer
+ * with per-sample scale w (not w / batch) and its data-gradient kernels as they are, and the squared forms of its weight-gradient
+ * kernels (fc1: the product of the squared operands; the convolutions: the square of each sample's sum over positions); the slab's sums
+ * go through the gradient step's second stages into a temporary and from there into a double accumulator, slab after slab in stream
+ * order; after the last slab fisher = (float)(accumulator / n).  No atomics: every sum is in a fixed order that follows from (n, slab)
+ * alone, and a slab >= n gives the bits of slab == n.  fisher is OVERWRITTEN, never read.  workspace: tm_valuenet_fit_fisher_workspace(slab)
+ * floats = tm_valuenet_fit_workspace(slab) + 478340 (the temporary) + 956676 (the accumulator), 16-byte aligned, no initial contents
+ * required.  Everything is enqueued on `stream`: no allocation, no host synchronisation, nothing read back.  hipErrorInvalidValue, and
+ * nothing launched, for a NULL pointer (idx excepted), n < 1, a slab that is refused or a misaligned workspace.
+ * tm_valuenet_fit_fisher_workspace is host arithmetic only (callable without a GPU): -1 for a slab that is refused. */
+long long tm_valuenet_fit_fisher_workspace(int slab);
+int tm_valuenet_fit_fisher(const float *params, const float *out_bounds, const int8_t *states, const float *value,
+                           const float *variance, const float *weight, const int64_t *idx, long long n, int slab, int weighted,
+                           float variance_clip, float *fisher, float *workspace, void *stream);
+/* tm_valuenet_fit_fisher on packed rows (obs uint32 [rows][12], 4-byte aligned): as tm_valuenet_fit_grad_packed is to its twin - fisher
+ * bit-identical to the int8 call's on the rendered rows, any 48 bytes safe to read, a misaligned obs hipErrorInvalidValue. */
+int tm_valuenet_fit_fisher_packed(const float *params, const float *out_bounds, const uint32_t *obs, const float *value,
+                                  const float *variance, const float *weight, const int64_t *idx, long long n, int slab, int weighted,
+                                  float variance_clip, float *fisher, float *workspace, void *stream);
+/* The penalty of elastic weight consolidation over FLAT device buffers of n floats (csrc/yogi.hip): the loss gains
+ * 0.5 lambda sum_i F[i] (p[i] - anchor[i])^2 and the gradient lambda F[i] (p[i] - anchor[i]).  Per element, in float, no contraction,
+ * in this order: d = p - anchor, t = ((float)lambda F) d, grad = grad + t (grad is ADDED to).  loss[0] (one double on the device) =
+ * 0.5 lambda sum F d d in double, F and the float d converted first, summed in two fixed-order stages through the workspace
+ * (tm_ewc_penalty_workspace(n) floats, 16-byte aligned, no initial contents required).  Two launches on `stream`, no atomics, no host
+ * synchronisation: capturable in a HIP graph.  hipErrorInvalidValue, and nothing launched, for a NULL pointer, n < 1, a lambda that is
+ * negative or not finite, a misaligned workspace or loss.  tm_ewc_penalty_workspace is host arithmetic only: -1 for n < 1. */
+long long tm_ewc_penalty_workspace(int n);
+int tm_ewc_penalty(const float *p, const float *anchor, const float *fisher, int n, double lambda, float *grad, double *loss,
+                   float *workspace, void *stream);
 /* The validation pass of the distributional head's online fit (csrc/distnet_fit.hip): as the value net's above, with the forward and
  * the per-sample losses of tm_distnet_fit_grad.  rows_out[c] = {w, mean, std}: std is the sample standard deviation (n - 1; NaN for
  * a chunk of one row, as torch.std_mean - train's host loop maps it to 0).  params (16-byte aligned), states, target, target_stride,

@@ -78,6 +78,11 @@ SYMBOLS = {
     "tm_valuenet_fit_validate_workspace": [i32],         # (returns long long: restype set in lib())
     "tm_valuenet_fit_validate": [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, C.c_float, vp, vp, vp],
     "tm_valuenet_fit_validate_packed": [vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, i32, C.c_float, vp, vp, vp],
+    "tm_valuenet_fit_fisher_workspace": [i32],           # (returns long long: restype set in lib())
+    "tm_valuenet_fit_fisher": [vp, vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, C.c_float, vp, vp, vp],
+    "tm_valuenet_fit_fisher_packed": [vp, vp, vp, vp, vp, vp, vp, C.c_longlong, i32, i32, C.c_float, vp, vp, vp],
+    "tm_ewc_penalty_workspace": [i32],                   # (returns long long: restype set in lib())
+    "tm_ewc_penalty": [vp, vp, vp, i32, f64, vp, vp, vp, vp],
     "tm_distnet_fit_validate_workspace": [i32, i32],     # (returns long long: restype set in lib())
     "tm_distnet_fit_validate": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
     "tm_distnet_fit_validate_packed": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
@@ -131,6 +136,8 @@ def lib():
         L.tm_distnet_fit_workspace.restype = C.c_longlong
         L.tm_valuenet_fit_validate_workspace.restype = C.c_longlong
         L.tm_distnet_fit_validate_workspace.restype = C.c_longlong
+        L.tm_valuenet_fit_fisher_workspace.restype = C.c_longlong
+        L.tm_ewc_penalty_workspace.restype = C.c_longlong
         L.tm_fill_norm_quantile.argtypes, L.tm_fill_norm_quantile.restype = [vp, i32], None
         L.tm_fill_norm_quantile_f64.argtypes, L.tm_fill_norm_quantile_f64.restype = [vp, i32], None
         L.tm_version.argtypes, L.tm_version.restype = [], C.c_char_p

@@ -155,11 +155,13 @@ __global__ __launch_bounds__(256) void k_vf_conv_fwd(const float* __restrict__ W
 // per = log var_p + ((value - v_p)^2 + max(variance, clip)) / var_p - log max(variance, clip) - 1, times the weight;
 // dzo[b][2] = d(mean of per) / d(fc_out pre-activation), dh[b][i] = (dzo . W_out[:, i]) where h > 0.
 // GRAD = false (the validation pass): per alone, by the same statements; dzo and dh are not touched.
+// div: what the per-sample weight is divided by in the gradients - the batch for the gradient of the MEAN (tm_valuenet_fit_grad),
+// 1 for the per-sample gradients of the Fisher pass.
 template <bool GRAD>
 __global__ __launch_bounds__(256) void k_vf_head(const float* __restrict__ P, const float* __restrict__ bounds,
                                                  const float* __restrict__ h, const float* __restrict__ value,
                                                  const float* __restrict__ variance, const float* __restrict__ weight,
-                                                 const int64_t* __restrict__ idx, int B, int weighted, float clip,
+                                                 const int64_t* __restrict__ idx, int B, int weighted, float clip, double div,
                                                  float* __restrict__ dzo, double* __restrict__ per, float* __restrict__ dh) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
@@ -187,7 +189,7 @@ __global__ __launch_bounds__(256) void k_vf_head(const float* __restrict__ P, co
     const double diff = val - vp, num = diff * diff + vt;
     if (lane == 0) per[b] = w * (log(varp) + num / varp - log(vt) - 1.0);
     if (!GRAD) return;
-    const double scale = w / (double)B;
+    const double scale = w / div;
     const double dvp = -2.0 * diff / varp * scale, dvarp = (1.0 / varp - num / (varp * varp)) * scale;
     const double g0 = dvp * (double)bounds[0] * ds[0], g1 = dvarp * (double)bounds[1] * ds[1];
     if (lane == 0) {
@@ -201,15 +203,23 @@ __global__ __launch_bounds__(256) void k_vf_head(const float* __restrict__ P, co
 }
 
 // partial sums over HEAD_CHUNK samples of dW_out = dzo^T h, db_fc1 = sum dh, db_out = sum dzo
+// SQ (the Fisher pass): of the squares of the per-sample terms, dzo^2 h^2, dh^2, dzo^2
+template <bool SQ>
 __global__ __launch_bounds__(256) void k_vf_head_part(const float* __restrict__ dzo, const float* __restrict__ h,
                                                       const float* __restrict__ dh, int B, float* __restrict__ part) {
     const int i = threadIdx.x, b0 = blockIdx.x * HEAD_CHUNK, b1 = min(B, b0 + HEAD_CHUNK);
     float w0 = 0.f, w1 = 0.f, bf = 0.f, bo = 0.f;
     for (int b = b0; b < b1; ++b) {
-        const float g0 = dzo[2 * b], g1 = dzo[2 * b + 1], hv = h[(size_t)b * HID + i];
+        float g0 = dzo[2 * b], g1 = dzo[2 * b + 1], hv = h[(size_t)b * HID + i], d = dh[(size_t)b * HID + i];
+        if constexpr (SQ) {
+            g0 = g0 * g0;
+            g1 = g1 * g1;
+            hv = hv * hv;
+            d = d * d;
+        }
         w0 = fmaf(g0, hv, w0);
         w1 = fmaf(g1, hv, w1);
-        bf += dh[(size_t)b * HID + i];
+        bf += d;
         if (i < 2) bo += i == 0 ? g0 : g1;
     }
     float* dst = part + (size_t)blockIdx.x * HEAD_PART;
@@ -221,7 +231,9 @@ __global__ __launch_bounds__(256) void k_vf_head_part(const float* __restrict__ 
 
 // ---- fc1 weight gradient: part[s][j][k] = sum over the samples of split s of dh[b][j] a3[b][k]; M = 256, N = 1792 ----
 // (a split is ONE chain here and chunks of 32 in distnet_fit.hip's k_df_fc_dw: one kernel for both would change this one's bits)
-template <int NT>
+// SQ (the Fisher pass): both operands are squared as they are loaded - the sum over the samples of the squared outer products
+// (dh[b][j] a3[b][k])^2 is the matrix product of the squared operands.
+template <int NT, bool SQ = false>
 __global__ __launch_bounds__(256) void k_vf_fc1_dw(const float* __restrict__ dh, const float* __restrict__ a3, int B,
                                                    float* __restrict__ part) {
     const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
@@ -247,6 +259,11 @@ __global__ __launch_bounds__(256) void k_vf_fc1_dw(const float* __restrict__ dh,
             av[r] = in ? acol[bb * HID] : 0.0f;
 #pragma unroll
             for (int t = 0; t < NT; ++t) bv[t][r] = in ? bcol[bb * A3 + 32 * t] : 0.0f;
+            if constexpr (SQ) {
+                av[r] = av[r] * av[r];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) bv[t][r] = bv[t][r] * bv[t][r];
+            }
         }
         float4 b4[NT];
 #pragma unroll
@@ -321,7 +338,9 @@ __global__ __launch_bounds__(256) void k_vf_conv_bwd_data(const float* __restric
 // dzo[b][co][p] ain[b][ci][(y + ky) IW + x + kx].  M = 32, N = CIN * 9 (NT tiles per wave), K = (sample, position) ----
 // CIN == 1: ain is the state of row idx[b], read through SRC.  A lane's tap is fixed and the loop walks the positions, so the
 // strip is built per quad of positions (with OW == 8 a quad lies in one row) from the row the lane keeps per sample.
-template <int CIN, int IH, int IW, int NT, typename SRC = DenseStates>
+// SQ (the Fisher pass): after each sample's positions acc holds that sample's gradient; its square is added to a second set of
+// accumulators and acc starts the next sample from zero, so a partial is the sum over its samples of the squared per-sample gradients.
+template <int CIN, int IH, int IW, int NT, typename SRC = DenseStates, bool SQ = false>
 __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dzo, const float* __restrict__ ain,
                                                     const typename SRC::elem* __restrict__ states,
                                                     const int64_t* __restrict__ idx, int B, float* __restrict__ part) {
@@ -343,10 +362,14 @@ __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dz
         nkx[t] = kx;
     }
     f32x16 acc[NT];
+    [[maybe_unused]] f32x16 sq[SQ ? NT : 1];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+        for (int r = 0; r < 16; ++r) {
+            acc[t][r] = 0.0f;
+            if constexpr (SQ) sq[t][r] = 0.0f;
+        }
     for (int b = b0; b < b1; ++b) {
         const float* arow = dzo + (size_t)b * (32 * OP) + l31 * OP + 4 * half;
         const size_t ibase = (size_t)b * (CIN * IP);
@@ -377,6 +400,15 @@ __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dz
             for (int t = 0; t < NT; ++t) b4[t] = make_float4(bv[t][0], bv[t][1], bv[t][2], bv[t][3]);
             vf_quad<NT>(acc, a, b4);
         }
+        if constexpr (SQ) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    sq[t][r] += acc[t][r] * acc[t][r];
+                    acc[t][r] = 0.0f;
+                }
+        }
     }
     float* dst = part + (size_t)chunk * (32 * KW);
 #pragma unroll
@@ -384,11 +416,16 @@ __global__ __launch_bounds__(256) void k_vf_conv_dw(const float* __restrict__ dz
         if (nok[t]) {
             const int n = (ng * NT + t) * 32 + l31;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dst[drow(r, half) * KW + n] = acc[t][r];
+            for (int r = 0; r < 16; ++r) {
+                if constexpr (SQ) dst[drow(r, half) * KW + n] = sq[t][r];
+                else dst[drow(r, half) * KW + n] = acc[t][r];
+            }
         }
 }
 
-// per sample, the sums over positions of dz1 / dz2 / dz3 per channel: cb[b][96] (conv1, conv2, conv3)
+// per sample, the sums over positions of dz1 / dz2 / dz3 per channel: cb[b][96] (conv1, conv2, conv3); SQ (the Fisher pass): their
+// squares
+template <bool SQ>
 __global__ __launch_bounds__(128) void k_vf_conv_bias_part(const float* __restrict__ dz1, const float* __restrict__ dz2,
                                                            const float* __restrict__ dz3, int B, float* __restrict__ cb) {
     const int b = blockIdx.x, i = threadIdx.x;
@@ -400,7 +437,7 @@ __global__ __launch_bounds__(128) void k_vf_conv_bias_part(const float* __restri
         const float4 v = *reinterpret_cast<const float4*>(src + p);
         s += (v.x + v.y) + (v.z + v.w);
     }
-    cb[(size_t)b * 96 + i] = s;
+    cb[(size_t)b * 96 + i] = SQ ? s * s : s;
 }
 
 // the forward of B rows (states: SRC's rows, int8 [.][200] or packed [.][12]; row idx[b], or row b when idx is NULL) into a1, a2,
@@ -454,9 +491,9 @@ static int fit_grad(const float* params, const float* out_bounds, const typename
     forward<SRC>(P, states, idx, B, a1, a2, a3, h, st);
     // ---- output layer, loss, and the small batch sums ----
     hipLaunchKernelGGL(k_vf_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P, out_bounds, h, value, variance, weight, idx, B, weighted,
-                       variance_clip, dzo, per, dh);
+                       variance_clip, (double)B, dzo, per, dh);
     hipLaunchKernelGGL(k_fit_loss<0>, dim3(1), dim3(256), 0, st, per, B, loss);
-    hipLaunchKernelGGL(k_vf_head_part, dim3(L.hchunks), dim3(256), 0, st, dzo, h, dh, B, hp);
+    hipLaunchKernelGGL(k_vf_head_part<false>, dim3(L.hchunks), dim3(256), 0, st, dzo, h, dh, B, hp);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3((512 + 15) / 16), dim3(256), 0, st, hp, L.hchunks, (long long)HEAD_PART, 512, grad + OFF_FOW);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(256 / 16), dim3(256), 0, st, hp + 512, L.hchunks, (long long)HEAD_PART, 256, grad + OFF_F1B);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(1), dim3(256), 0, st, hp + 768, L.hchunks, (long long)HEAD_PART, 2, grad + OFF_FOB);
@@ -475,7 +512,7 @@ static int fit_grad(const float* params, const float* out_bounds, const typename
                        P + OFF_C2W, dz2, a1, B, dz1);
     hipLaunchKernelGGL((k_vf_conv_dw<1, 20, 10, 1, SRC>), dim3(blocks_for_waves(L.chunks)), dim3(256), 0, st, dz1, (const float*)nullptr,
                        states, idx, B, pw1);
-    hipLaunchKernelGGL(k_vf_conv_bias_part, dim3(B), dim3(128), 0, st, dz1, dz2, dz3, B, cb);
+    hipLaunchKernelGGL(k_vf_conv_bias_part<false>, dim3(B), dim3(128), 0, st, dz1, dz2, dz3, B, cb);
     // ---- second stages of the convolutions' sums ----
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw3, L.chunks, 9216LL, 9216, grad + OFF_C3W);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw2, L.chunks, 9216LL, 9216, grad + OFF_C2W);
@@ -504,9 +541,84 @@ static int fit_validate(const float* params, const float* out_bounds, const type
         const int B = (int)(n - r0 < slab ? n - r0 : slab);
         forward<SRC>(params, states + r0 * SRC::STRIDE, (const int64_t*)nullptr, B, a1, a2, a3, h, st);
         hipLaunchKernelGGL(k_vf_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params, out_bounds, h, value + r0, variance + r0,
-                           weight + r0, (const int64_t*)nullptr, B, weighted, variance_clip, (float*)nullptr, per, (float*)nullptr);
+                           weight + r0, (const int64_t*)nullptr, B, weighted, variance_clip, 1.0, (float*)nullptr, per, (float*)nullptr);
         hipLaunchKernelGGL(k_fit_val_moments<0>, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
                            rows_out + 3 * (r0 / chunk));
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- the Fisher pass: F[i] = (1/n) sum_b (d loss_b / d p_i)^2 over n rows, a slab at a time ----
+// A slab is the gradient step's forward, k_vf_head with the divisor 1 (dzo and dh are then PER-SAMPLE gradients) and its data
+// gradients as they are, and the SQ forms of the weight-gradient kernels, whose partials hold sums over samples of squared
+// per-sample gradients; the unchanged second stages add them into a temporary [NPARAM], which k_vf_fisher_add adds to a double
+// accumulator, slab after slab in stream order.  The workspace is the gradient step's of `slab` rows, then the temporary, then
+// the accumulator.
+constexpr long long FISHER_TMP = up4(NPARAM), FISHER_ACC = 2LL * NPARAM;      // floats (the accumulator: NPARAM doubles)
+static_assert(FISHER_ACC % 4 == 0, "every segment starts at a multiple of four floats");
+
+// acc[i] = (first ? 0 : acc[i]) + tmp[i]; after the last slab fisher[i] = (float)(acc[i] / n)
+__global__ __launch_bounds__(256) void k_vf_fisher_add(const float* __restrict__ tmp, double* __restrict__ acc, int first, int last,
+                                                       double n, float* __restrict__ fisher) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= NPARAM) return;
+    const double a = (first ? 0.0 : acc[i]) + (double)tmp[i];
+    acc[i] = a;
+    if (last) fisher[i] = (float)(a / n);
+}
+
+template <typename SRC>
+static int fit_fisher(const float* params, const float* out_bounds, const typename SRC::elem* states, const float* value,
+                      const float* variance, const float* weight, const int64_t* idx, long long n, int slab, int weighted,
+                      float variance_clip, float* fisher, float* workspace, void* stream_) {
+    if (!params || !out_bounds || !states || !value || !variance || !weight || !fisher || !workspace)
+        return (int)hipErrorInvalidValue;
+    if (n < 1 || slab < 1 || slab > MAX_BATCH || ((uintptr_t)workspace & 15)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream_;
+    const Layout L = layout(slab);
+    float* ws = workspace;
+    float *a1 = ws + L.a1, *a2 = ws + L.a2, *a3 = ws + L.a3, *dz1 = ws + L.dz1, *dz2 = ws + L.dz2, *dz3 = ws + L.dz3;
+    float *h = ws + L.h, *dh = ws + L.dh, *dzo = ws + L.dzo, *pf1 = ws + L.pf1, *pw3 = ws + L.pw3, *pw2 = ws + L.pw2;
+    float *pw1 = ws + L.pw1, *cb = ws + L.cb, *hp = ws + L.hp, *tmp = ws + L.total;
+    double *per = reinterpret_cast<double*>(ws + L.per), *acc = reinterpret_cast<double*>(ws + L.total + FISHER_TMP);
+    const float* P = params;
+    // slab by slab on the one stream: a slab's kernels have read the workspace before the next slab's overwrite it
+    for (long long r0 = 0; r0 < n; r0 += slab) {
+        const int B = (int)(n - r0 < slab ? n - r0 : slab);
+        const int s1 = (B + FC1_KC - 1) / FC1_KC, chunks = (B + SPW - 1) / SPW, hchunks = (B + HEAD_CHUNK - 1) / HEAD_CHUNK;
+        // rows idx[r0 + b]; without idx the rows r0 + b
+        const int64_t* ix = idx ? idx + r0 : nullptr;
+        const long long base = idx ? 0 : r0;
+        const typename SRC::elem* S = states + base * SRC::STRIDE;
+        forward<SRC>(P, S, ix, B, a1, a2, a3, h, st);
+        hipLaunchKernelGGL(k_vf_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P, out_bounds, h, value + base, variance + base,
+                           weight + base, ix, B, weighted, variance_clip, 1.0, dzo, per, dh);
+        hipLaunchKernelGGL(k_vf_head_part<true>, dim3(hchunks), dim3(256), 0, st, dzo, h, dh, B, hp);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3((512 + 15) / 16), dim3(256), 0, st, hp, hchunks, (long long)HEAD_PART, 512, tmp + OFF_FOW);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(256 / 16), dim3(256), 0, st, hp + 512, hchunks, (long long)HEAD_PART, 256, tmp + OFF_F1B);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(1), dim3(256), 0, st, hp + 768, hchunks, (long long)HEAD_PART, 2, tmp + OFF_FOB);
+        hipLaunchKernelGGL((k_vf_fc1_dw<2, true>), dim3(blocks_for_waves((long long)s1 * 8 * 28)), dim3(256), 0, st, dh, a3, B, pf1);
+        hipLaunchKernelGGL((k_fit_reduce<4>), dim3(HID * A3 / 64), dim3(256), 0, st, pf1, s1, (long long)HID * A3, HID * A3, tmp + OFF_F1W);
+        hipLaunchKernelGGL((k_fit_fc1_bwd_data<HID, A3, Relu, 2>), dim3(blocks_for_waves(tiles(B) * 28)), dim3(256), 0, st, P + OFF_F1W, dh, a3, B, dz3);
+        hipLaunchKernelGGL((k_vf_conv_dw<32, 16, 6, 3, DenseStates, true>), dim3(blocks_for_waves((long long)chunks * 3)), dim3(256), 0, st, dz3, a2,
+                           (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw3);
+        hipLaunchKernelGGL((k_vf_conv_bwd_data<16, 6, 3>), dim3(blocks_for_waves((tiles((long long)B * 96) + 2) / 3)), dim3(256), 0, st,
+                           P + OFF_C3W, dz3, a2, B, dz2);
+        hipLaunchKernelGGL((k_vf_conv_dw<32, 18, 8, 3, DenseStates, true>), dim3(blocks_for_waves((long long)chunks * 3)), dim3(256), 0, st, dz2, a1,
+                           (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw2);
+        hipLaunchKernelGGL((k_vf_conv_bwd_data<18, 8, 3>), dim3(blocks_for_waves((tiles((long long)B * 144) + 2) / 3)), dim3(256), 0, st,
+                           P + OFF_C2W, dz2, a1, B, dz1);
+        hipLaunchKernelGGL((k_vf_conv_dw<1, 20, 10, 1, SRC, true>), dim3(blocks_for_waves(chunks)), dim3(256), 0, st, dz1, (const float*)nullptr,
+                           S, ix, B, pw1);
+        hipLaunchKernelGGL(k_vf_conv_bias_part<true>, dim3(B), dim3(128), 0, st, dz1, dz2, dz3, B, cb);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw3, chunks, 9216LL, 9216, tmp + OFF_C3W);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(9216 / 16), dim3(256), 0, st, pw2, chunks, 9216LL, 9216, tmp + OFF_C2W);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(288 / 16), dim3(256), 0, st, pw1, chunks, 288LL, 288, tmp + OFF_C1W);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 96LL, 32, tmp + OFF_C1B);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 96LL, 32, tmp + OFF_C2B);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb + 64, B, 96LL, 32, tmp + OFF_C3B);
+        hipLaunchKernelGGL(k_vf_fisher_add, dim3((NPARAM + 255) / 256), dim3(256), 0, st, tmp, acc, (int)(r0 == 0), (int)(r0 + slab >= n),
+                           (double)n, fisher);
     }
     return (int)hipGetLastError();
 }
@@ -514,6 +626,26 @@ static int fit_validate(const float* params, const float* out_bounds, const type
 }  // namespace tmcts_vf
 
 extern "C" {
+
+long long tm_valuenet_fit_fisher_workspace(int slab) {
+    if (slab < 1 || slab > tmcts_vf::MAX_BATCH) return -1;
+    return tmcts_vf::layout(slab).total + tmcts_vf::FISHER_TMP + tmcts_vf::FISHER_ACC;
+}
+
+int tm_valuenet_fit_fisher(const float* params, const float* out_bounds, const int8_t* states, const float* value,
+                           const float* variance, const float* weight, const int64_t* idx, long long n, int slab, int weighted,
+                           float variance_clip, float* fisher, float* workspace, void* stream) {
+    return tmcts_vf::fit_fisher<tmcts_fit::DenseStates>(params, out_bounds, states, value, variance, weight, idx, n, slab, weighted,
+                                                        variance_clip, fisher, workspace, stream);
+}
+
+int tm_valuenet_fit_fisher_packed(const float* params, const float* out_bounds, const uint32_t* obs, const float* value,
+                                  const float* variance, const float* weight, const int64_t* idx, long long n, int slab, int weighted,
+                                  float variance_clip, float* fisher, float* workspace, void* stream) {
+    if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
+    return tmcts_vf::fit_fisher<tmcts_fit::PackedStates>(params, out_bounds, obs, value, variance, weight, idx, n, slab, weighted,
+                                                         variance_clip, fisher, workspace, stream);
+}
 
 long long tm_valuenet_fit_workspace(int batch) {
     if (batch < 1 || batch > tmcts_vf::MAX_BATCH) return -1;

@@ -10,7 +10,9 @@
 //   state (doubles): [0] step t, [1] beta1^t, [2] beta2^t, [3] lr / (1 - beta1^t), [4] sqrt(1 - beta2^t)
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <stdint.h>
 #include "../../include/tetris_mcts_hip.h"
+#include "fit_mma.h"      // block_sum, up4: the fixed-order sums of the fit's kernels
 
 namespace tmcts {
 
@@ -73,7 +75,54 @@ __global__ __launch_bounds__(256) void k_adam_step(float* __restrict__ p, const 
     v[i] = vi;
 }
 
+// ---- the penalty of elastic weight consolidation over the flat buffers (tm_ewc_penalty) ----
+// Per element, in float, in this order: d = p - anchor, t = (lam F) d, grad = grad + t.  A workgroup's share of the loss,
+// sum F d d in double (F and the float d converted first), goes to part[block] in block_sum's fixed order.
+constexpr int EWC_BLOCK = 256;
+
+__global__ __launch_bounds__(256) void k_ewc_penalty(const float* __restrict__ p, const float* __restrict__ anchor,
+                                                     const float* __restrict__ fisher, int n, float lam, float* __restrict__ grad,
+                                                     double* __restrict__ part) {
+    __shared__ double sm[256];
+    const int i = blockIdx.x * EWC_BLOCK + threadIdx.x;
+    double s = 0.0;
+    if (i < n) {
+        const float f = fisher[i], d = p[i] - anchor[i];
+        const float t = (lam * f) * d;
+        grad[i] = grad[i] + t;
+        s = ((double)f * (double)d) * (double)d;
+    }
+    s = tmcts_fit::block_sum(s, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// loss[0] = 0.5 lam (the sum of the S partials: thread t adds part[t], part[t + 256], ... in ascending order, then block_sum)
+__global__ __launch_bounds__(256) void k_ewc_loss(const double* __restrict__ part, int S, double lam, double* __restrict__ loss) {
+    __shared__ double sm[256];
+    double s = 0.0;
+    for (int k = threadIdx.x; k < S; k += 256) s += part[k];
+    s = tmcts_fit::block_sum(s, sm);
+    if (threadIdx.x == 0) loss[0] = (0.5 * lam) * s;
+}
+
 }  // namespace tmcts
+
+extern "C" long long tm_ewc_penalty_workspace(int n) {
+    if (n < 1) return -1;
+    const long long blocks = ((long long)n + tmcts::EWC_BLOCK - 1) / tmcts::EWC_BLOCK;
+    return tmcts_fit::up4(2 * blocks);      // one double a workgroup, in floats
+}
+
+extern "C" int tm_ewc_penalty(const float* p, const float* anchor, const float* fisher, int n, double lambda, float* grad, double* loss,
+                              float* workspace, void* stream) {
+    if (!p || !anchor || !fisher || !grad || !loss || !workspace || n < 1) return (int)hipErrorInvalidValue;
+    if (!(lambda >= 0.0) || !isfinite(lambda) || ((uintptr_t)workspace & 15) || ((uintptr_t)loss & 7)) return (int)hipErrorInvalidValue;
+    const int blocks = (int)(((long long)n + tmcts::EWC_BLOCK - 1) / tmcts::EWC_BLOCK);
+    double* part = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(tmcts::k_ewc_penalty, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, anchor, fisher, n, (float)lambda, grad, part);
+    hipLaunchKernelGGL(tmcts::k_ewc_loss, dim3(1), dim3(256), 0, (hipStream_t)stream, part, blocks, lambda, loss);
+    return (int)hipGetLastError();
+}
 
 extern "C" int tm_adam_step(float* p, const float* g, float* m, float* v, float* vmax, double* state, int n, double lr, double beta1,
                             double beta2, double eps, double weight_decay, int amsgrad, void* stream) {

@@ -122,6 +122,7 @@ class _HipHead:
 class Model_VV(_HipHead):
     """Inference-side mirror of the reference's Model_VV (load / inference / training(False))."""
     PARAM_ORDER, SCRATCH_ROW, PREPARE = PARAM_ORDER, SCRATCH_MFMA, "tm_valuenet_prepare"
+    fisher = ewc_anchor = None      # compute_fisher's, or a checkpoint's: what train_data(ewc_lambda=) penalises against
 
     def __init__(self, backend="hip", device="cuda", seed=None, fc1="fp32", **kwargs):
         if fc1 not in VALUENET_FC1:
@@ -162,12 +163,28 @@ class Model_VV(_HipHead):
             self.optimizer = Yogi(self.model.parameters(), lr=1e-3, eps=1e-3, weight_decay=1e-3)
         return self.optimizer
 
-    def train_data(self, data, **kwargs):
+    def train_data(self, data, ewc_lambda=None, **kwargs):
         """data: [states [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (numpy or tensors); fit_backend,
         validation_backend and state_format as train.train_data describes them (state_format="packed": data[0] holds the packed
-        observations, int32 [n,12] on the GPU, and is passed on as it is)."""
+        observations, int32 [n,12] on the GPU, and is passed on as it is).  ewc_lambda: None, or the lambda of elastic weight
+        consolidation against this model's Fisher and anchor (compute_fisher's or a checkpoint's; train.train_data's `ewc`,
+        fit_backend="hip"); a model that holds no Fisher logs one line and fits unpenalised, as on the first cycle."""
         from . import train as T
         dev = self.device
+        if ewc_lambda is not None:
+            import math
+            from sys import stderr
+            if isinstance(ewc_lambda, bool) or not isinstance(ewc_lambda, (int, float)) or not (math.isfinite(ewc_lambda) and ewc_lambda >= 0):
+                raise ValueError("Model_VV.train_data: ewc_lambda must be finite and >= 0, not %r" % (ewc_lambda,))
+            if kwargs.get("fit_backend", "torch") != "hip":
+                raise ValueError("Model_VV.train_data: ewc_lambda needs fit_backend='hip'")
+            if "ewc" in kwargs:
+                raise ValueError("Model_VV.train_data: give ewc_lambda or ewc, not both")
+            if self.fisher is None:
+                print("Model_VV.train_data: no Fisher to consolidate against (first cycle?): fitting without the penalty",
+                      file=stderr, flush=True)
+            else:
+                kwargs["ewc"] = dict(fisher=self.fisher, anchor=self.ewc_anchor, lam=float(ewc_lambda))
         packed = kwargs.get("state_format", "dense") == "packed"
         T.check_state_format(kwargs.get("state_format", "dense"), kwargs.get("fit_backend", "torch"),
                              kwargs.get("validation_backend", "torch"), kwargs.get("validation_fraction", 0.1), data)
@@ -194,6 +211,79 @@ class Model_VV(_HipHead):
         self.weights_changed()
         return res
 
+    def _flat_learnable(self):
+        """a fresh flat float32 copy of the ten learnable tensors in PARAM_ORDER: what tm_valuenet_fit_grad calls params"""
+        sd = self.model.state_dict()
+        return torch.cat([sd[k].detach().reshape(-1).float() for k in PARAM_ORDER[:10]]).contiguous()
+
+    @torch.no_grad()
+    def compute_fisher(self, data, weighted=False, state_format="dense", slab=1024):
+        """The empirical Fisher diagonal of the fit's loss over the rows of `data`, F[i] = (1/n) sum_b (d loss_b / d p_i)^2, by
+        ONE call of tm_valuenet_fit_fisher (csrc/valuenet_fit.hip; the reference's Model_VV.compute_fisher, model_vv.py:188-208,
+        one backward per row there).  data: [states, values, variances, weights] laid out as for train_data, device tensors (or
+        anything torch.as_tensor takes); with state_format="packed" data[0] holds the packed observations, int32 [n,12] on the
+        GPU.  weighted: the row's weight multiplies its loss, the weights taken AS GIVEN (train_data divides its weights by their
+        mean before it fits: hand over those to get the Fisher of the loss it fitted).  slab: rows per launch sequence; the
+        result does not depend on a slab >= n.  Sets self.fisher (flat float32 [478338] on the device, PARAM_ORDER[:10]) and
+        self.ewc_anchor (a copy of the flat learnable weights as they stand) and returns self.fisher.  The optimiser and the
+        weights are not touched."""
+        from . import train as T
+        dev = self.device
+        if dev.type != "cuda":
+            raise ValueError("Model_VV.compute_fisher runs the HIP Fisher pass: the model must be on the GPU, not %s" % (dev,))
+        if state_format not in ("dense", "packed"):
+            raise ValueError("state_format must be 'dense' or 'packed', not %r" % (state_format,))
+        if len(data) != 4:
+            raise ValueError("Model_VV.compute_fisher needs data = [states, values, variances, weights]")
+        if state_format == "packed":
+            fault = T._packed_states_fault(data[0])
+            if fault:
+                raise ValueError("state_format='packed' needs " + fault)
+            states, n, name = data[0].contiguous(), data[0].shape[0], "tm_valuenet_fit_fisher_packed"
+        else:
+            s = torch.as_tensor(data[0], device=dev)
+            n = s.shape[0]
+            if n < 1 or s.numel() != n * 200:
+                raise ValueError("Model_VV.compute_fisher needs states of 20 x 10 cells a row, got shape %s" % (tuple(s.shape),))
+            if not bool(((s == s.round()) & (s.abs() <= 127)).all()):
+                raise ValueError("Model_VV.compute_fisher reads the states as int8: they must be integers in [-127, 127]")
+            states, name = s.reshape(n, 200).to(torch.int8).contiguous(), "tm_valuenet_fit_fisher"
+        if n < 1:
+            raise ValueError("Model_VV.compute_fisher needs at least one row")
+        value, variance, weight = (torch.as_tensor(d, dtype=torch.float32, device=dev).reshape(-1).contiguous() for d in data[1:])
+        if any(t.numel() != n for t in (value, variance, weight)):
+            raise ValueError("Model_VV.compute_fisher needs one value, variance and weight a row")
+        slab = int(slab)
+        n_ws = _lib.lib().tm_valuenet_fit_fisher_workspace(slab)
+        if n_ws < 0:
+            raise ValueError("Model_VV.compute_fisher: a slab of %d rows is refused" % slab)
+        P = self._flat_learnable()
+        bounds = torch.cat([self.model.out_ubound.detach().reshape(2), self.model.out_lbound.detach().reshape(2)]).float().contiguous()
+        ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        fisher = torch.empty(P.numel(), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.lib(), name)(_p(P), _p(bounds), _p(states), _p(value), _p(variance), _p(weight), None, n, slab,
+                                                 int(bool(weighted)), float(variance_bound), _p(fisher), _p(ws), _stream()), name)
+        self.fisher, self.ewc_anchor = fisher, P
+        return self.fisher
+
+    def _ewc_dict(self, flat):
+        """a flat [478338] tensor as {parameter name: CPU tensor shaped like the parameter}"""
+        sd, out, off = self.model.state_dict(), OrderedDict(), 0
+        for k in PARAM_ORDER[:10]:
+            n = sd[k].numel()
+            out[k] = flat[off:off + n].detach().reshape(sd[k].shape).cpu().clone()
+            off += n
+        return out
+
+    def _ewc_flat(self, d, key):
+        sd = self.model.state_dict()
+        for k in PARAM_ORDER[:10]:
+            if k not in d or tuple(d[k].shape) != tuple(sd[k].shape):
+                raise ValueError("checkpoint key %r: %s has shape %s, the net's is %s"
+                                 % (key, k, tuple(d[k].shape) if k in d else None, tuple(sd[k].shape)))
+        return torch.cat([d[k].reshape(-1).float() for k in PARAM_ORDER[:10]]).to(self.device).contiguous()
+
     def load(self, filename=EXP_PATH + "model_checkpoint", verbose=True):
         if os.path.isfile(filename):
             if verbose:
@@ -207,6 +297,10 @@ class Model_VV(_HipHead):
                     from sys import stderr
                     print("WARNING: optimizer state of %s not loaded (%s): the optimiser restarts with fresh moments"
                           % (filename, e), file=stderr, flush=True)
+            # the Fisher and its anchor, when the checkpoint carries them (both or neither)
+            self.fisher = self.ewc_anchor = None
+            if "fisher" in ck and "ewc_anchor" in ck:
+                self.fisher, self.ewc_anchor = self._ewc_flat(ck["fisher"], "fisher"), self._ewc_flat(ck["ewc_anchor"], "ewc_anchor")
         elif verbose:
             print("Checkpoint not found, using default model", flush=True)
         self.weights_changed()
@@ -216,8 +310,10 @@ class Model_VV(_HipHead):
             print("Saving model...", flush=True)
         os.makedirs(os.path.dirname(filename) or ".", exist_ok=True)
         # the reference's Model.load indexes optimizer_state_dict['param_groups'] (model.py:166-170): always write a real one
-        torch.save({"model_state_dict": self.model.state_dict(), "optimizer_state_dict": self._optimizer().state_dict()},
-                   filename)
+        ck = {"model_state_dict": self.model.state_dict(), "optimizer_state_dict": self._optimizer().state_dict()}
+        if self.fisher is not None:      # (a model without a Fisher writes exactly those two keys)
+            ck["fisher"], ck["ewc_anchor"] = self._ewc_dict(self.fisher), self._ewc_dict(self.ewc_anchor)
+        torch.save(ck, filename)
 
     @torch.no_grad()
     def inference_device(self, states, v_out=None, var_out=None):

@@ -431,7 +431,7 @@ def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, ter
 
 def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
                  early_stopping_patience=10, fit_backend="torch", validation_backend="torch", gamma=1.0, bootstrap="recorded",
-                 bootstrap_rounds=1, on_round=None, **options):
+                 bootstrap_rounds=1, on_round=None, ewc_lambda=None, **options):
     """training_set(paths, gamma=gamma, **options) on the model's device, then model.train_data on it; returns what train_data
     returns plus `rounds`: one dict per round with iters, best_validation and graph_replay.
     max_iters and iters_per_val may be functions of the number of training rows (train.py computes its iterations from it).
@@ -445,7 +445,13 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
     within a round; the optimiser's state persists across rounds, as it does across online fits.  A prediction that is not
     finite raises RuntimeError before a target is computed from it (one .item() a round).
     on_round(r, data, v_rows), r = 0 .. R-1, is called before each round's train_data with the tensors in use (v_rows: None
-    with bootstrap="recorded")."""
+    with bootstrap="recorded").
+
+    ewc_lambda (None: off; needs fit_backend="hip"): elastic weight consolidation.  Every round's train_data gets it and
+    penalises against the Fisher and anchor the model holds (a loaded checkpoint's), if any.  After the last round
+    Model_VV.compute_fisher runs over the TRAINING rows (the held-out tail excluded) with that round's targets and the weights
+    as the fit used them, the new Fisher and anchor replace the model's, and rank 0 writes the checkpoint.  The result gains
+    ewc = dict(penalised: whether the fits were penalised, fisher_rows: the rows the new Fisher averages over)."""
     from .model import Model_VV
     if not isinstance(model, Model_VV):
         raise TypeError("fit_episodes fits a Model_VV: the reference has no episode target for a distribution (%s)"
@@ -460,6 +466,8 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
     if bootstrap == "recorded" and rounds > 1:
         raise ValueError("bootstrap='recorded' with %d rounds: nothing would change between them" % rounds)
     _check_discount(target_mode(options.get("td", False), options.get("lam"))[0], gamma, None)
+    if ewc_lambda is not None and fit_backend != "hip":
+        raise ValueError("ewc_lambda needs fit_backend='hip', not %r" % (fit_backend,))
     data, info = training_set(paths, device=model.device, gamma=gamma, **options)
     iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
     extra = {}
@@ -469,6 +477,9 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
         raise ValueError("%d iterations do not make %d rounds" % (iters, rounds))
     targets = {k: options[k] for k in ("td", "lam", "weighted", "weighted_mode", "terminal", "censored", "eps") if k in options}
     done = []
+    if ewc_lambda is not None:
+        extra["ewc_lambda"] = ewc_lambda
+    penalised = ewc_lambda is not None and model.fisher is not None
     for r in range(rounds):
         v_rows = None
         if bootstrap == "net":
@@ -485,6 +496,15 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
                                early_stopping_patience=early_stopping_patience, fit_backend=fit_backend,
                                validation_backend=validation_backend, **extra)
         done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
+    if ewc_lambda is not None:
+        # train_data fits with weighted=True on the weights divided by their mean over ALL rows: the same per-sample losses here
+        n_train = info["n_train"]
+        w = data[3] / data[3].mean()
+        model.compute_fisher([d[:n_train] for d in data[:3]] + [w[:n_train]], weighted=True)
+        from . import dist as tdist
+        if tdist.rank() == 0:
+            model.save(verbose=False)
+        res = dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
     return dict(res, rounds=done)
 
 

@@ -343,6 +343,32 @@ def check_state_format(state_format, fit_backend, validation_backend, validation
         raise ValueError("state_format='packed' needs " + fault)
 
 
+EWC_PARAMS = 478338      # the learnable floats of model.Net in model.PARAM_ORDER[:10]: the length of a Fisher and of its anchor
+
+
+def check_ewc(ewc, fit_backend):
+    """The refusals of train_data's `ewc`, a ValueError raised with the other early checks (before the optimiser is flattened).
+    ewc: None or dict(fisher=, anchor=, lam=); returns (fisher, anchor, lam) with contiguous tensors, or None."""
+    if ewc is None:
+        return None
+    if fit_backend != "hip":
+        raise ValueError("ewc adds its penalty to the flat gradient of the value net's HIP fit: it needs fit_backend='hip', not %r"
+                         % (fit_backend,))
+    if not isinstance(ewc, dict) or set(ewc) != {"fisher", "anchor", "lam"}:
+        raise ValueError("ewc is None or dict(fisher=, anchor=, lam=)")
+    for key in ("fisher", "anchor"):
+        t = ewc[key]
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == EWC_PARAMS):
+            raise ValueError("ewc: %s must be a float32 CUDA tensor of %d elements" % (key, EWC_PARAMS))
+    try:
+        lam = float(ewc["lam"])
+    except (TypeError, ValueError):
+        raise ValueError("ewc: lam must be a number, not %r" % (ewc["lam"],)) from None
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("ewc: lam must be finite and >= 0, not %r" % (ewc["lam"],))
+    return ewc["fisher"].reshape(-1).contiguous(), ewc["anchor"].reshape(-1).contiguous(), lam
+
+
 class _HipFitBase:
     """What the per-fit states of fit_backend="hip" and "hip_dist" share: the order of the checks (once per fit, everything that
     can refuse before the optimiser is flattened), the workspaces of the gradient step and of the validation pass, the index
@@ -357,9 +383,10 @@ class _HipFitBase:
     BACKEND = None
 
     def __init__(self, net, optimizer, train, batch, val=None, val_chunk=VALIDATION_CHUNK, val_slab=VALIDATION_SLAB,
-                 state_format="dense"):
+                 state_format="dense", ewc=None):
         from . import _lib
         self._lib = _lib
+        self.ewc = check_ewc(ewc, self.BACKEND)
         if state_format not in ("dense", "packed"):
             raise ValueError("state_format must be 'dense' or 'packed', not %r" % (state_format,))
         self.packed = state_format == "packed"
@@ -370,6 +397,8 @@ class _HipFitBase:
             val_slab = _validation_slab(vrows, val_chunk, val_slab)
             if self._workspace(val_slab, validation=True) < 0:
                 raise ValueError(V + ": a slab of %d rows is refused" % val_slab)
+        if self.ewc is not None and any(t.device != train[0].device for t in self.ewc[:2]):
+            raise ValueError(L + ": ewc's fisher and anchor must be on %s, where the data is" % (train[0].device,))
         F = optimizer.flatten()
         self._check_flat(net, optimizer, F, train[0].device, L)
         if batch < 1:
@@ -381,6 +410,9 @@ class _HipFitBase:
             raise ValueError(L + ": a batch of %d rows is refused" % batch)
         self.ws = torch.empty(n_ws, dtype=torch.float32, device=self.dev)
         self.loss = torch.zeros(2, dtype=torch.float32, device=self.dev)
+        if self.ewc is not None:      # the penalty's workspace and its loss (one double), once per fit
+            self.ewc_ws = torch.empty(_lib.lib().tm_ewc_penalty_workspace(F["n"]), dtype=torch.float32, device=self.dev)
+            self.ewc_loss = torch.zeros(1, dtype=torch.float64, device=self.dev)
         self._idx_checked = False
         self.val_rows = 0
         if val is not None:      # the int8 copy of the held-out states (once per fit), the slab's workspace and the chunks' rows
@@ -429,6 +461,16 @@ class _HipFitBase:
             self._idx_checked = True
         self._grad(idx.contiguous(), int(bool(weighted)), torch.cuda.current_stream(self.dev).cuda_stream)
         return self.loss[0]
+
+    def penalty(self):
+        """ONE call of tm_ewc_penalty on the current stream: lam F (p - anchor) is added to the optimiser's flat gradient as it
+        stands; returns the penalty 0.5 lam sum F (p - anchor)^2 (a 0-d float64 device tensor).  Needs a fit built with `ewc`."""
+        fisher, anchor, lam = self.ewc
+        F = self.F
+        self._lib.check(self._lib.lib().tm_ewc_penalty(
+            F["p"].data_ptr(), anchor.data_ptr(), fisher.data_ptr(), F["n"], lam, F["g"].data_ptr(), self.ewc_loss.data_ptr(),
+            self.ewc_ws.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream), "tm_ewc_penalty")
+        return self.ewc_loss[0]
 
 
 class HipFit(_HipFitBase):
@@ -618,7 +660,7 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
                sample_replacement=True, oversampling=False, weighted=True, early_stopping=True, early_stopping_patience=10,
                early_stopping_threshold=1.0, shuffle=False, max_iters=100000, grad_clip=0.0, save=None, load=None,
                generator=None, log=True, data_parallel=True, group=None, loss_fn=None, fit_backend="torch",
-               validation_backend="torch", state_format="dense"):
+               validation_backend="torch", state_format="dense", ewc=None):
     """data = [states f32 [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (device tensors); with `loss_fn`
     (net, batch, weighted) -> (mean, std) any list of arrays whose LAST one holds the sample weights (Model.train_data is
     generic in the reference too, model/model.py:176-249: the model class supplies `_loss`).
@@ -653,7 +695,15 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     rendered copy exists at any point, and the fit computes the bits of the dense one on the rendered rows.  The shuffle, the
     split, the index draws and the graph capture treat the keys as they treat dense rows.  It needs fit_backend "hip" or
     "hip_dist", and validation_backend "hip" unless no rows are held out; anything else is a ValueError raised before the model,
-    the optimiser or a sampling stream is touched (check_state_format)."""
+    the optimiser or a sampling stream is touched (check_state_format).
+
+    `ewc`: None, or dict(fisher=, anchor=, lam=) - elastic weight consolidation: the objective gains 0.5 lam sum F (p - anchor)^2
+    over the 478 338 learnable floats (fisher, anchor: float32 CUDA tensors of that length, Model_VV.compute_fisher's; lam finite
+    and >= 0).  ONE call of tm_ewc_penalty (csrc/yogi.hip) adds lam F (p - anchor) to the flat gradient after the gradient step
+    and after the data-parallel all-reduce (every rank adds the same penalty once) and before the gradient norm, which is then
+    the penalised objective's; the iteration stays a fixed sequence of launches and is replayed from the graph as before.  At
+    each validation one more line reports the mean penalty since the last.  It needs fit_backend="hip"; anything else, and a
+    fisher, anchor or lam that is not as described, is a ValueError raised before the optimiser is flattened."""
     import torch.distributed as tdist
     check_state_format(state_format, fit_backend, validation_backend, validation_fraction, data)
     if fit_backend not in ("torch", "hip", "hip_dist"):
@@ -663,6 +713,7 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     if validation_backend == "hip" and fit_backend == "torch":
         raise ValueError("validation_backend='hip' reads the flat parameter buffer of a HIP fit: it needs fit_backend='hip' or "
                          "'hip_dist' (a custom loss_fn, CPU tensors and the torch fit validate with validation_backend='torch')")
+    check_ewc(ewc, fit_backend)
     if fit_backend == "hip_dist":
         if loss_fn is not None and not getattr(loss_fn, "is_model_dist_loss", False):
             raise ValueError("fit_backend='hip_dist' computes Model_Dist.loss: a custom loss_fn needs fit_backend='torch'")
@@ -700,12 +751,13 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     net.train()
     # the one-kernel optimiser step (Yogi on the GPU): parameters and gradients are views of flat buffers from here on
     hip_val = val if validation_backend == "hip" else None
-    hip = (HipFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format) if fit_backend == "hip" else
+    hip = (HipFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format, ewc=ewc) if fit_backend == "hip" else
            HipDistFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format)
            if fit_backend == "hip_dist" else None)
     if hip is not None and hip.rows != n - n_val:      # every draw below is an index into [0, n - n_val): the rows the kernels hold
         raise ValueError("fit_backend=%r: %d training rows, but the index draws cover %d" % (fit_backend, hip.rows, n - n_val))
     flat_g = optimizer.flat_grad() if hasattr(optimizer, "flat_grad") else None
+    ewc_avg = torch.zeros((), dtype=torch.float64, device=data[0].device) if ewc is not None else None
 
     def one_iteration():
         if oversampling:    # model.py:194-195: draw proportionally to the visit weights
@@ -735,6 +787,8 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
                 for g in grads:
                     g.copy_(flat[off:off + g.numel()].view_as(g))
                     off += g.numel()
+        if ewc is not None:      # after the all-reduce: every rank adds the same penalty once
+            ewc_avg.add_(hip.penalty())
         # 2-norm over all parameter gradients (model.py:87-95), reported in the log line the dashboards parse
         if flat_g is not None:
             g_norm_avg.add_(torch.linalg.vector_norm(flat_g))
@@ -801,6 +855,11 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
                 print("Iteration:{:7d}  training loss:{:6.4f}  validation loss:{:6.4f}±{:6.4f}  gradient norm:{:6.3f}    {}"
                       .format(it + 1, float(loss_avg) / iters_per_val, vmean, vstd, float(g_norm_avg) / iters_per_val, mark),
                       file=stderr, flush=True)
+            if ewc is not None:
+                if log:
+                    print("EWC penalty (mean over the last %d iterations):%.6g" % (iters_per_val, float(ewc_avg) / iters_per_val),
+                          file=stderr, flush=True)
+                ewc_avg.zero_()
             loss_avg.zero_()
             g_norm_avg.zero_()
             if early_stopping and fails >= early_stopping_patience:

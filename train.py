@@ -7,7 +7,14 @@ pytorch_model/model_checkpoint, which the next play.py loads.
 The reference's script does not run as committed (`backend`, `eligibility_trace` and `eligibility_trace_lambda` are undefined and
 it reads row 3 of a 3-row child_stats), so what is kept is its intent: its flags, its file choice, its three target rules, its
 validation split and its iteration count.  `--td_lambda` stands for its eligibility trace: without it `--td` fits the recorded
-root values, with it the lambda-return.  --ewc and --save_loss are refused with a message.
+root values, with it the lambda-return.  --save_loss is refused with a message.
+
+--ewc --ewc_lambda L is elastic weight consolidation (the reference sketches it: model_vv.py:170-208, train.py:321-322): the fit is
+penalised by 0.5 L sum F (p - p*)^2 against the Fisher diagonal F and the weights p* that the loaded checkpoint carries (none on the
+first cycle, or with --new: nothing is penalised), and after the fit the Fisher of the fitted net over the training rows is computed
+by the HIP Fisher pass (csrc/valuenet_fit.hip: tm_valuenet_fit_fisher) and written into pytorch_model/model_checkpoint with the
+weights as the next cycle's anchor.  --ewc_lambda has no default: the Fisher's magnitude follows the loss's scale, and the
+reference's default of 1 never met a Fisher that was not zero.  The value net only, with --fit_backend hip.
 
 Beyond the reference: --target_gamma discounts the targets per move (0.999 is the search's discount; the default 1.0 is the
 reference's undiscounted rule), and --bootstrap net takes the values inside the lambda-return from the net being fitted, refreshed
@@ -34,6 +41,7 @@ def build_parser():
     add('--early_stopping_patience', default=10, type=int, help='Early stopping patience (default:10)')
     add('--epochs', default=10, type=int, help='Training epochs (default:10)')
     add('--ewc', default=False, help='Elastic weight consolidation (default:False)', action='store_true')
+    add('--ewc_lambda', default=None, type=float, help='Elastic weight consolidation lambda (no default: give it with --ewc)')
     add('--last_nfiles', default=1, type=int, help='Use last n files in training only (default:1, -1 for all)')
     add('--min_iters', default=-1, type=int, help='Min training iterations (default:-1, negative for unlimited)')
     add('--max_iters', default=-1, type=int, help='Max training iterations (default:-1, negative for unlimited)')
@@ -77,9 +85,18 @@ def build_parser():
 
 def check_args(args):
     """the refusals, before anything is imported or read"""
-    if args.ewc:
-        sys.exit('--ewc needs a Fisher pass over the training data (the reference\'s Model.compute_fisher), which this engine does '
-                 'not have: no elastic weight consolidation')
+    if args.ewc and args.head == 'dist':
+        sys.exit('--ewc: the Fisher pass exists for the value net only (--head value), not for --head dist')
+    if args.ewc and args.ewc_lambda is None:
+        sys.exit('--ewc needs --ewc_lambda: there is no default, because the magnitude of the Fisher follows the scale of the loss, '
+                 'and the reference\'s default of 1 never met a Fisher that was not zero')
+    if args.ewc_lambda is not None and not args.ewc:
+        sys.exit('--ewc_lambda is the weight of --ewc: it needs --ewc')
+    if args.ewc_lambda is not None and not (args.ewc_lambda >= 0.0 and args.ewc_lambda != float('inf')):
+        sys.exit('--ewc_lambda is finite and at least 0')
+    if args.ewc and args.fit_backend != 'hip':
+        sys.exit('--ewc adds its penalty to the gradient of the HIP fit and computes its Fisher with the HIP kernels: it needs '
+                 '--fit_backend hip')
     if args.save_loss:
         sys.exit('--save_loss writes the reference\'s HDF5 loss table (util/Data.py LossSaver: PyTables), which this engine does '
                  'not reimplement; the fit logs its losses to stderr')
@@ -183,7 +200,7 @@ def main(argv=None):
                        terminal=args.terminal, censored=args.censored, last_nfiles=args.last_nfiles, validation=args.validation,
                        val_mode=args.val_mode, val_episodes=args.val_episodes, val_set_size=args.val_set_size,
                        val_set_size_max=args.val_set_size_max, gamma=args.target_gamma, bootstrap=args.bootstrap,
-                       bootstrap_rounds=args.bootstrap_rounds)
+                       bootstrap_rounds=args.bootstrap_rounds, ewc_lambda=args.ewc_lambda if args.ewc else None)
     print('iters:%d/%d' % (sum(r['iters'] for r in res['rounds']), plan['iters'])
           + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
     model.save()
