@@ -457,6 +457,46 @@ int tm_episode_dist_targets(const void *rows, int n_rows, const int32_t *order, 
                             double vmin, double vmax, int mode, double lambda, int horizon, int weight_mode, float eps,
                             float *target, int target_stride, float *weight, int32_t *fault, void *stream);
 
+/* Node records (node_records.hip): the tuples the collections harvest into replay_obs / replay_stat (online != 0: the packed
+ * observation, value, variance and visits of every freed observation with at least min_visits_to_store visits), moved into one
+ * dense ring of rows that are a file's rows, and such rows turned into the arrays of a packed fit.  The reference writes its
+ * nodes at every collection (Agent.save_nodes, agents/agent.py:246-289); the policy, the child statistics and the action of its
+ * rows are not kept by the harvest and are not part of this row.  A node row, TM_NODE_ROW_BYTES, little-endian:
+ *     0 obs u4[12] (the packed observation, ENGINE_SPEC.md section 7) | 48 value f4 | 52 variance f4 | 56 visit f4 |
+ *    60 slot i4 (the game index)
+ * The first 60 bytes are the harvest's tuple, bit for bit.
+ * counters: device int32[4] = head (the ring rows in use), lost (rows that did not fit the ring), drains (calls), one spare; the
+ * caller clears them and, after it has copied the ring out, head.  offsets: device int32[n_games + 1] of scratch, no initial
+ * contents required (on return offsets[g] is game g's first ring row, saturated at ring_cap).
+ * tm_nodes_drain: with c[g] = min(replay_count[g], replay_cap) (a negative count is taken as 0), game g's tuples 0 .. c[g]-1 go
+ * to the ring rows head + sum_{h<g} c[h] + i - game-major, harvest order within a game, the order of TreeStore.replay() - and
+ * replay_count[g] = 0.  Rows at or beyond ring_cap are not written and are counted in lost; head advances by what was written.
+ * It belongs on the stream of the search, between two moves: it must not run beside tm_sim_step, whose collectors append to the
+ * same buffers.
+ * tm_nodes_sweep appends in the same way the observations still in the pools (the reference's save_occupied; once, at the end of
+ * a run): per game in ascending index every slot o >= gs[TM_GS_LOW_OBS] whose statistics word passes the collection's own test,
+ * (int)stat.x >= max(min_visits_to_store, 1) with bit 31 (a finished game) clear; the tuple is okey[o], stat.y, stat.z,
+ * (float)(int)stat.x.  It reads the store and changes nothing in it.
+ * tm_node_targets: rows (n_rows node rows, 16-byte aligned) -> obs [n][12] (4-byte aligned), value[n] and variance[n] (the bits
+ * copied), weight[n] by tm_episode_targets' four weight_mode rules with the row's visit in place of the seven visits' sum -
+ * 0: 1; 1: 1.0f / (variance + eps); 2: visit; 3: visit / (variance + eps), IEEE fp32.  A row whose value or variance is not
+ * finite or whose visit is below 1 gets weight 0 and sets *fault = 1 (a device int32 the caller cleared; a plain store).
+ * All three enqueue on stream (drain two kernels, sweep three, targets one) and make no other HIP call: no allocation, no
+ * synchronisation, nothing read back, no atomics, deterministic; the scan over the games is one workgroup whose threads own runs
+ * of games, for any n_games >= 1.  Nothing is written outside the ring's first ring_cap rows, counters, offsets and replay_count
+ * (drain), or outside the four outputs and *fault (targets).  hipErrorInvalidValue, nothing launched, checked before the first
+ * HIP call (so these answer on a machine without a GPU): a NULL pointer (a NULL array of the store that the call reads included);
+ * ring_cap < 1, n_rows < 0 or above 2^29 - 1, a weight_mode outside 0..3; a ring or rows that is not 16-byte aligned, an obs
+ * that is not 4-byte aligned, a replay_obs / replay_stat (drain) or obs_stat / obs_key (sweep) of the store that is not 16-byte
+ * aligned (they are read as 16-byte pieces; torch allocations and tm_store_slice keep them so); a store with n_games < 1, with replay_cap < 1 (drain) or of TM_KIND_DIST (drain and sweep: its
+ * harvest is of another shape, replay_dist).  n_rows == 0 returns 0 and launches nothing.
+ * Held on an MI355X to numpy statements of these definitions and to TreeStore.replay() inside a search (tests/test_gpu_nodes.py). */
+#define TM_NODE_ROW_BYTES 64
+int tm_nodes_drain(tm_store *tree, void *ring, int ring_cap, int32_t *counters, int32_t *offsets, void *stream);
+int tm_nodes_sweep(const tm_store *tree, void *ring, int ring_cap, int32_t *counters, int32_t *offsets, void *stream);
+int tm_node_targets(const void *rows, int n_rows, int weight_mode, float eps, uint32_t *obs, float *value, float *variance,
+                    float *weight, int32_t *fault, void *stream);
+
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel
  * workgroup's games; the groups of TM_GS_GC_ACTIVE4): hipErrorInvalidValue otherwise. */

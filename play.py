@@ -3,7 +3,8 @@
 on the MI355X engine.  `python play.py --agent_type ValueSimLP --mcts_sims 500 --ngames 10` behaves like the
 reference (same per-game log lines, play.py:25-37,164); `--n_games N` plays N games concurrently on the GPU
 (new, optional).  `--save` writes the reference's self-play rows (util/Data.py State), recorded on the device, as numbered
-.npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5).  --save_tree, --gui and --interactive belong to
+.npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5).  `--save_nodes` writes the tree nodes the
+collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`.  --save_tree, --gui and --interactive belong to
 the reference's storage / UI layers and are refused with a clear message.
 """
 import argparse
@@ -65,7 +66,45 @@ def build_parser():
     add('--evaluator_pure', default=False, action='store_true', help='[new] with --valuenet_backend torch: the evaluator is a '
         'function of the state and the weights alone, so the search posts only the requests its backup will use (ValueSim and '
         'ValueSimC without leaf parallelism: together with --dense_requests)')
+    add('--save_nodes', default=False, action='store_true', help='[new] write the tree nodes the collections harvest - packed '
+        'observation, value, variance, visits of every freed observation with at least --min_visit visits - as <save_dir>nodes<cycle> '
+        '(ValueSim, ValueSimLP, ValueSimC; tetris_mcts_amd/nodes.py), what train.py --nodes fits')
+    add('--save_nodes_occupied', default=False, action='store_true', help='[new] with --save_nodes: at the end of the run also '
+        'write the observations still in the trees that pass the same test (the reference\'s save_occupied)')
+    add('--nodes_ring_rows', default=0, type=int, help='[new] with --save_nodes: rows of the recorder\'s ring on the device, 64 bytes '
+        'each and twice that in pinned host memory (0: the default, tetris_mcts_amd/nodes.py RING_ROWS); it should hold twice the '
+        'rows one move can harvest')
+    add('--nodes_flush_moves', default=0, type=int, help='[new] with --save_nodes: copy the ring to the host at least every this '
+        'many moves when it holds rows (0: the default, FLUSH_MOVES)')
     return p
+
+
+def check_save_nodes(args):
+    """the refusals of --save_nodes, before anything is imported"""
+    if args.save_nodes_occupied and not args.save_nodes:
+        sys.exit('--save_nodes_occupied adds the trees\' remaining observations to what --save_nodes writes: it needs --save_nodes')
+    if not args.save_nodes:
+        return
+    if not args.agent_type:
+        sys.exit('--save_nodes records what an agent\'s collections harvest: it needs --agent_type (ValueSim, ValueSimLP, ValueSimC)')
+    if args.agent_type in ('Vanilla', 'VanillaC'):
+        sys.exit('--save_nodes is not offered for %s: the harvest of the rollout kinds is untested (no test checks their '
+                 'tuples); use ValueSim, ValueSimLP or ValueSimC' % args.agent_type)
+    if args.agent_type == 'DistValueSim':
+        sys.exit('--save_nodes is not offered for DistValueSim: its harvest is of another row shape (a distribution per node, '
+                 'tm_store.replay_dist), which the 64-byte node row does not hold; use ValueSim, ValueSimLP or ValueSimC')
+    if args.agent_type not in ('ValueSim', 'ValueSimLP', 'ValueSimC'):
+        sys.exit('--save_nodes applies to ValueSim, ValueSimLP and ValueSimC only')
+    if args.online:
+        sys.exit('--save_nodes together with --online: the online fit drains the same harvest buffers the recorder drains; '
+                 'record with --save_nodes and fit with train.py --nodes, or fit with --online')
+    if args.valuenet_backend == 'torch' and args.dense_requests:
+        sys.exit('--save_nodes with --valuenet_backend torch --dense_requests has not been shown to work: record with the hip '
+                 'back ends or without --dense_requests')
+    if args.nodes_ring_rows < 0 or args.nodes_flush_moves < 0:
+        sys.exit('--nodes_ring_rows and --nodes_flush_moves are positive (0: the defaults)')
+    if args.min_visit < 1:
+        sys.exit('--min_visit is at least 1 with --save_nodes (an observation without a visit has no statistics)')
 
 
 class Scoreboard:
@@ -93,6 +132,7 @@ def main(argv=None):
     if args.save and not args.agent_type:
         sys.exit('--save records what an agent plays (its root statistics, value and policy beside the board): it needs '
                  '--agent_type (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
+    check_save_nodes(args)
     if not args.agent_type:
         sys.exit('--agent_type is required (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     if args.fit_backend == 'hip_dist' and args.agent_type != 'DistValueSim':
@@ -139,6 +179,11 @@ def main(argv=None):
         extra['dense_requests'] = True
     if args.evaluator_pure:
         extra['evaluator_pure'] = True
+    if args.save_nodes:
+        # the store harvests without a fit; --min_visit is the harvest's threshold (ValueSimC takes it as min_visit already)
+        extra['harvest'] = True
+        if args.agent_type != 'ValueSimC':
+            extra['min_visits_to_store'] = args.min_visit
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     agent.update_root(game)
@@ -146,6 +191,12 @@ def main(argv=None):
     if args.save:
         from tetris_mcts_amd.episodes import EpisodeRecorder
         rec = EpisodeRecorder(args.save_dir, args.save_file, args.cycle, G)
+    node_rec = None
+    if args.save_nodes:
+        from tetris_mcts_amd.nodes import NodeRecorder
+        from tetris_mcts_amd.nodes import FLUSH_MOVES, RING_ROWS
+        node_rec = NodeRecorder(args.save_dir, 'nodes', args.cycle, G, ring_rows=args.nodes_ring_rows or RING_ROWS,
+                                flush_moves=args.nodes_flush_moves or FLUSH_MOVES)
 
     board_file = open('board_output', 'wb') if args.print_board_to_file else None
     if args.realtime_status:
@@ -200,11 +251,17 @@ def main(argv=None):
                     break
             game.reset('ended')
             agent.update_root(game)
+        if node_rec is not None:
+            node_rec.drain(agent)       # between two moves: what this move's collections harvested goes into the ring
         if args.max_moves and moves >= args.max_moves:
             break
     print(flush=True)
     if rec is not None:
         rec.close()
+    if node_rec is not None:
+        node_rec.close(agent, occupied=args.save_nodes_occupied)
+        print('node rows written: %d in %d file(s), %d lost' % (node_rec.rows_written, len(node_rec.files), node_rec.lost),
+              flush=True)
     agent.close()
 
 

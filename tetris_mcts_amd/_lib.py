@@ -61,6 +61,9 @@ SYMBOLS = {
     "tm_episode_gather_states": [vp, i32, vp, i32, vp, vp, vp],
     "tm_episode_dist_targets": [vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, f64, f64, i32, f64, i32, i32, C.c_float, vp, i32, vp, vp,
                                 vp],
+    "tm_nodes_drain": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
+    "tm_nodes_sweep": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
+    "tm_node_targets": [vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp],
     "tm_export_game": [C.POINTER(TmStore), i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "tm_core_select_trace_obs": [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp],
     "tm_core_backup_trace_obs": [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f64, vp],

@@ -14,7 +14,7 @@ class ValueSim(OnlineFit, TreeAgent):
 
     def __init__(self, online=True, memory_size=500000, min_visits_to_store=10, gamma=0.999, memory_growth_rate=5000,
                  max_nodes=100000, model=None, evaluator=None, valuenet_backend="hip", fit_backend="torch",
-                 validation_backend="torch", valuenet_fc1="fp32", fit_states="dense", **kwargs):
+                 validation_backend="torch", valuenet_fc1="fp32", fit_states="dense", harvest=False, **kwargs):
         """`valuenet_backend`: the Model_VV backend of the model the agent builds when `model` is None ("hip", the default;
         "hip_bf16x3", the split-precision kernels; "torch"), `valuenet_fc1` its fc1 ("fp32", the default; "bf16x3": fc1 split
         as well, with "hip_bf16x3" only - Model_VV refuses any other pairing).  `fit_backend`: how the online fits take their gradients
@@ -23,7 +23,14 @@ class ValueSim(OnlineFit, TreeAgent):
         `fit_states`: what the fits are fed ("dense", the default: the harvested observations rendered to [n,1,20,10] floats;
         "packed": the 48-byte observations themselves, read by the kernels - it needs fit_backend="hip" and validation_backend="hip").
         `evaluator`: a callable, int8 device tensor [B, 200] -> (v[B], var[B]); B is every slot of every game, or, under TreeAgent's
-        `dense_requests`, the posted requests padded to a multiple of `dense_pad`."""
+        `dense_requests`, the posted requests padded to a multiple of `dense_pad`.
+        `harvest`: the store harvests at its collections (tm_store.online = 1, a `replay_cap`, `min_visits_to_store` as given)
+        WITHOUT any fit: nothing else about the agent changes, and whoever asked for it drains the tuples (nodes.NodeRecorder).
+        Not together with an online fit, which drains the same buffers."""
+        benchmark = kwargs.get("benchmark", False)
+        if harvest and online and not benchmark:
+            raise ValueError("harvest=True records the harvested tuples and online=True fits them: both drain the same buffers, "
+                             "give one of the two")
         if fit_backend not in ("torch", "hip"):
             raise ValueError("fit_backend must be 'torch' or 'hip', not %r ('hip_dist' is DistValueSim's)" % (fit_backend,))
         if validation_backend not in ("torch", "hip"):
@@ -33,13 +40,14 @@ class ValueSim(OnlineFit, TreeAgent):
         self.fit_backend, self.validation_backend = fit_backend, validation_backend
         self.check_fit_states(fit_states, "hip")
         kwargs.pop("min_visit", None)  # play.py:89 forwards it; the reference ValueSim ignores it too
-        benchmark = kwargs.get("benchmark", False)
+        harvesting = bool(harvest) or (online and not benchmark)
         # device-side harvest buffer per game (64 B per tuple); a GC at a 100 000-entry pool frees a few thousand
         # observations with enough visits, and whatever exceeds the buffer between two drains is dropped
-        kwargs.setdefault("replay_cap", min(int(max_nodes), 16384) if (online and not benchmark) else 0)
-        super().__init__(max_nodes=max_nodes, gamma=gamma, online=(online and not benchmark),
+        kwargs.setdefault("replay_cap", min(int(max_nodes), 16384) if harvesting else 0)
+        super().__init__(max_nodes=max_nodes, gamma=gamma, online=harvesting,
                          min_visits_to_store=min_visits_to_store, **kwargs)
         self.online = online
+        self.harvest = bool(harvest)
         self.n_trains = 0
         self._memory = None       # (packed observations, stats) carried over between trainings
         self.memory_size = memory_size

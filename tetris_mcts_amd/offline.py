@@ -39,6 +39,9 @@ Two options go beyond the reference's rules (tm_episode_targets_discounted); the
 The distributional head has the same route with categorical targets (the second half of this file): dist_targets_numpy is the
 specification, dist_targets_device the call (csrc/episode_dist_targets.hip: tm_episode_dist_targets), episode_dist_targets,
 predict_rows_dist and fit_episodes_dist what episode_targets, predict_rows and fit_episodes are to the value net.
+
+The harvested tree nodes (`play.py --save_nodes`, nodes.py) are a third training set, the one the online fit learns from: the
+last part of this file - node_targets (csrc/node_records.hip: tm_node_targets), node_training_set and fit_nodes.
 """
 import ctypes as C
 import glob
@@ -798,3 +801,113 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
             model.save(verbose=False)
         done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
     return dict(res, rounds=done)
+
+
+# ---- node records: the harvested tree nodes as a training set (csrc/node_records.hip: tm_node_targets) ---------------------------
+#
+# `play.py --save_nodes` leaves NODE_DTYPE rows (nodes.py): the tuples the online fit trains on - packed observation, the search's
+# value and variance, the visits.  A node has no return and no episode: the target is the search's own value (the value net's mode
+# 2), the held-out rows are a random draw, and the fit reads the packed observations as they are (state_format="packed").
+
+def node_targets(rows, weighted=False, weighted_mode=0, eps=EPS, device=None):
+    """obs (int32 [n,12]), value, variance, weight (float32 [n]) of node rows: tm_node_targets on the rows' device, on the current
+    stream (`rows`: a NODE_DTYPE table or a contiguous uint8 tensor [n,64]; device: where a table goes), or with device="cpu"
+    the numpy statement of the same definitions.  Raises RuntimeError on a set fault word (one .item())."""
+    from . import nodes as N
+    wmode = weight_mode(weighted, weighted_mode)
+    on = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cuda"))
+    if torch.is_tensor(rows):
+        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != N.ROW_BYTES or not rows.is_contiguous():
+            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % N.ROW_BYTES)
+        table = None
+    else:
+        table = np.ascontiguousarray(rows)
+        if table.dtype != N.NODE_DTYPE:
+            raise ValueError("rows: a table of NODE_DTYPE, not %s" % (table.dtype,))
+        rows = torch.from_numpy(table.view(np.uint8).reshape(len(table), N.ROW_BYTES))
+    n = rows.shape[0]
+    if on.type == "cpu":
+        table = rows.cpu().numpy().reshape(-1).view(N.NODE_DTYPE) if table is None else table
+        obs, value, variance, weight, fault = N.node_targets_numpy(table, wmode, eps)
+        obs, value, variance, weight = (torch.from_numpy(np.ascontiguousarray(x)) for x in (obs.view(np.int32), value, variance, weight))
+    else:
+        from . import _lib
+        rows = rows.to(on)
+        obs = torch.zeros(n, 12, dtype=torch.int32, device=on)
+        value, variance, weight = (torch.zeros(n, dtype=torch.float32, device=on) for _ in range(3))
+        fault = torch.zeros(1, dtype=torch.int32, device=on)
+        if n:
+            with torch.cuda.device(on):
+                _lib.check(_lib.lib().tm_node_targets(_ptr(rows), n, wmode, float(eps), _ptr(obs), _ptr(value), _ptr(variance),
+                                                      _ptr(weight), _ptr(fault),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tm_node_targets")
+        fault = int(fault.item())
+    if fault:
+        raise RuntimeError("node_targets: a row's value or variance is not finite, or its visit count is below 1: these are not "
+                           "rows a collection harvested")
+    return obs, value, variance, weight
+
+
+def node_training_set(paths, weighted=False, weighted_mode=0, last_nfiles=1, validation=False, val_set_size=0.05,
+                      val_set_size_max=-1, generator=None, device="cuda", eps=EPS):
+    """data = [observations int32 [n,12], values [n,1], variances [n,1], weights [n,1]] on `device`, the training rows first and
+    the held-out rows last - what Model_VV.train_data(state_format="packed") splits - and a dict with n, n_val, n_train,
+    validation_fraction (train_data's int(n * fraction) is n_val exactly), the stems and the files.  paths / last_nfiles:
+    choose_stems' rule over node shards.  The rows go to the device once; values and variances are the search's own.
+    validation: a random int(n * val_set_size) rows are held out (at most val_set_size_max if that is positive; `generator`: a
+    torch.Generator for the draw) - a node table has no episodes, so there is no episodic split."""
+    from . import nodes as N
+    stems = choose_stems(paths, last_nfiles)
+    files = [f for s in stems for f in _parts(s)]
+    table = N.load_rows(files)
+    dev = torch.device(device)
+    obs, value, variance, weight = node_targets(table, weighted=weighted, weighted_mode=weighted_mode, eps=eps, device=dev)
+    n_all = obs.shape[0]
+    if n_all == 0:
+        raise RuntimeError("no rows to train on: the node shards of %s are empty" % (stems,))
+    sel, n_val = _split(None, torch.ones(n_all, dtype=torch.bool, device=dev), validation, 0, 0, val_set_size, val_set_size_max,
+                        generator, dev)
+    n = int(sel.shape[0])
+    data = [obs[sel].contiguous()] + [x[sel].reshape(n, 1) for x in (value, variance, weight)]
+    return data, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
+                      files=files, n_rows=n_all)
+
+
+def fit_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
+              early_stopping_patience=10, fit_backend="hip", validation_backend="hip", ewc_lambda=None, **options):
+    """node_training_set(paths, **options) on the model's device, then model.train_data(..., state_format="packed") on it;
+    returns what train_data returns plus n_train and n_val.  max_iters and iters_per_val may be functions, as in fit_episodes.
+    The packed observations are read by the HIP kernels alone: fit_backend must be "hip", and validation_backend "hip" unless
+    nothing is held out (ValueError otherwise).  ewc_lambda: as in fit_episodes - the fit is penalised against the Fisher and
+    anchor the model holds, then Model_VV.compute_fisher(state_format="packed") runs over the training rows with the weights as
+    the fit used them and rank 0 writes the checkpoint."""
+    from .model import Model_VV
+    if not isinstance(model, Model_VV):
+        raise TypeError("fit_nodes fits a Model_VV: a node row holds a value and a variance, not a distribution (%s)"
+                        % type(model).__name__)
+    if fit_backend != "hip":
+        raise ValueError("fit_nodes hands the fit packed observations, which only the HIP gradient step reads: it needs "
+                         "fit_backend='hip', not %r" % (fit_backend,))
+    data, info = node_training_set(paths, device=model.device, **options)
+    if info["n_val"] and validation_backend != "hip":
+        raise ValueError("fit_nodes holds %d rows out, and the torch validation does not read packed observations: it needs "
+                         "validation_backend='hip' (or no validation), not %r" % (info["n_val"], validation_backend))
+    iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
+    extra = {}
+    if iters_per_val is not None:
+        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    if ewc_lambda is not None:
+        extra["ewc_lambda"] = ewc_lambda
+    penalised = ewc_lambda is not None and model.fisher is not None
+    res = model.train_data(data, batch_size=batch_size, max_iters=iters, validation_fraction=info["validation_fraction"],
+                           shuffle=False, early_stopping=early_stopping, early_stopping_patience=early_stopping_patience,
+                           fit_backend=fit_backend, validation_backend=validation_backend, state_format="packed", **extra)
+    if ewc_lambda is not None:
+        n_train = info["n_train"]
+        w = data[3] / data[3].mean()
+        model.compute_fisher([d[:n_train] for d in data[:3]] + [w[:n_train]], weighted=True, state_format="packed")
+        from . import dist as tdist
+        if tdist.rank() == 0:
+            model.save(verbose=False)
+        res = dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
+    return dict(res, n_train=info["n_train"], n_val=info["n_val"])

@@ -26,6 +26,11 @@ that builds its own model loads.  Without --td the target is the realised return
 --bootstrap net is the lambda-return of the head's own distributions over at most --td_horizon moves, refreshed before each of
 --bootstrap_rounds parts.  --fit_backend hip then means the head's gradient step (hip_dist).  The head records no distribution
 and its backup has no discount, so --td alone, --bootstrap recorded with --td and a --target_gamma other than 1 are refused.
+
+--nodes --td --data_paths D/nodes* fits the node shards of `play.py --save_nodes` instead of episodes (offline.fit_nodes,
+csrc/node_records.hip): the harvested tree nodes, the training set of the online fit.  A node has the search's value and
+variance and no return, so --nodes needs --td and takes no --td_lambda, --bootstrap net, --target_gamma, --val_mode 1, --head
+dist or --fit_backend torch; --weighted, --validation, --early_stopping, --last_nfiles and --ewc keep their meaning.
 """
 import argparse
 import sys
@@ -80,11 +85,36 @@ def build_parser():
     add('--vmax', default=5000.0, type=float, help='[new] --head dist: the upper end of the atoms\' range (default:5000)')
     add('--td_horizon', default=64, type=int, help='[new] --head dist with --td: the moves after a row that its target takes in '
         'at most (default:64)')
+    add('--nodes', default=False, action='store_true', help='[new] --data_paths are the node shards of play.py --save_nodes (the '
+        'harvested tree nodes, e.g. data/self1/nodes*): fit the search\'s value and variance of every node from its packed '
+        'observation; needs --td')
     return p
+
+
+def check_nodes(args):
+    """the refusals of --nodes"""
+    if not args.td:
+        sys.exit('--nodes needs --td: a node has no return, only the search\'s value')
+    if args.td_lambda is not None:
+        sys.exit('--nodes takes no --td_lambda: a node table has no moves to trace along')
+    if args.bootstrap != 'recorded':
+        sys.exit('--nodes takes no --bootstrap net: there is no lambda-return whose values the net could refresh')
+    if args.target_gamma != 1.0:
+        sys.exit('--nodes takes no --target_gamma other than 1: the search discounted the node\'s value already')
+    if args.val_mode == 1:
+        sys.exit('--nodes takes no --val_mode 1: a node table has no episodes (--val_mode 0 holds out random rows)')
+    if args.head == 'dist':
+        sys.exit('--nodes takes no --head dist: a node row holds a value and a variance, not a distribution')
+    if args.fit_backend != 'hip':
+        sys.exit('--nodes takes no --fit_backend torch: the packed observations are read by the HIP gradient step alone')
+    if args.validation and args.validation_backend not in (None, 'hip'):
+        sys.exit('--nodes with --validation needs --validation_backend hip: the torch validation does not read packed observations')
 
 
 def check_args(args):
     """the refusals, before anything is imported or read"""
+    if args.nodes:
+        check_nodes(args)
     if args.ewc and args.head == 'dist':
         sys.exit('--ewc: the Fisher pass exists for the value net only (--head value), not for --head dist')
     if args.ewc and args.ewc_lambda is None:
@@ -193,6 +223,18 @@ def main(argv=None):
     def max_iters(n_train):
         plan['iters'], plan['val'] = iterations(args, n_train)
         return plan['iters']
+    if args.nodes:
+        from tetris_mcts_amd.offline import fit_nodes
+        res = fit_nodes(model, args.data_paths, batch_size=args.batch_size, max_iters=max_iters, iters_per_val=lambda _: plan['val'],
+                        early_stopping=args.early_stopping, early_stopping_patience=args.early_stopping_patience,
+                        fit_backend=args.fit_backend, validation_backend=args.validation_backend,
+                        weighted=args.weighted, weighted_mode=args.weighted_mode, last_nfiles=args.last_nfiles,
+                        validation=args.validation, val_set_size=args.val_set_size, val_set_size_max=args.val_set_size_max,
+                        ewc_lambda=args.ewc_lambda if args.ewc else None)
+        print('iters:%d/%d' % (res['iters'], plan['iters'])
+              + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
+        model.save()
+        return
     res = fit_episodes(model, args.data_paths, batch_size=args.batch_size, max_iters=max_iters, iters_per_val=lambda _: plan['val'],
                        early_stopping=args.early_stopping, early_stopping_patience=args.early_stopping_patience,
                        fit_backend=args.fit_backend, validation_backend=args.validation_backend,
