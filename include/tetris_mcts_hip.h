@@ -309,6 +309,14 @@ int tm_gc_step(const tm_store *s, void *stream);
                                   more than 100 000 nodes take, tree.hip gc_marks_in_lds); set by tm_sim_step / tm_gc_step themselves when
                                   TM_GC_MARKS_IN_MEMORY=1 is in the environment (tests) */
 int tm_sim_step(const tm_store *s, int flags, void *stream);
+/* The tree kernel exists once per agent family, each without the others' code; tm_sim_step picks by the store's kind and cap alone.
+ * tm_sim_step_kernel is that choice (host only, no GPU needed): one of TM_SIM_KERNEL_*, or -1 where tm_sim_step returns
+ * hipErrorInvalidValue - an unknown kind, a negative cap, or a cap on a kind that can not carry one (TM_KIND_DIST among them). */
+#define TM_SIM_KERNEL_VALUE 0    /* k_sim_step<false>: the value kinds (TM_KIND_VALUESIM .. TM_KIND_CPPAGENT) */
+#define TM_SIM_KERNEL_ROLLOUT 1  /* k_sim_step<true>: TM_KIND_VANILLA, TM_KIND_VANILLA_C */
+#define TM_SIM_KERNEL_CAPPED 2   /* k_sim_step_capped: TM_KIND_VALUESIM / TM_KIND_CPPAGENT with eval_cap > 0 */
+#define TM_SIM_KERNEL_DIST 3     /* k_sim_step_dist: TM_KIND_DIST */
+int tm_sim_step_kernel(int kind, int eval_cap);
 int tm_eval_render(const tm_store *s, int8_t *out /* [G*eval_slots][200] */, void *stream);
 /* Dense requests for an evaluator the engine does not own (eval_requests.hip): instead of rendering every slot, hand the
  * evaluator the posted ones only and put its rows back.  The REQUESTS of *s are the slots j in [0, n_games * eval_slots) with

@@ -44,6 +44,7 @@ SYMBOLS = {
     "tm_tree_expand": [C.POINTER(TmStore), vp, vp, vp, vp],
     "tm_tree_remove_nodes": [C.POINTER(TmStore), vp, vp],
     "tm_sim_step": [C.POINTER(TmStore), i32, vp],
+    "tm_sim_step_kernel": [i32, i32],
     "tm_move_begin": [C.POINTER(TmStore), i32, vp],
     "tm_sims_remaining": [C.POINTER(TmStore), vp, vp],
     "tm_sims_owing": [C.POINTER(TmStore), vp, vp, vp],

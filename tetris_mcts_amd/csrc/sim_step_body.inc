@@ -1,5 +1,6 @@
-// The body of the tree kernel (included by tree.hip, once per kernel): k_sim_step<VANILLA> with CAPPED = false, and k_sim_step_capped
-// (VANILLA = false, CAPPED = true), the launches under a request cap (tm_store::eval_cap > 0).  Two kernels from one text rather than
+// The body of the tree kernel (included by tree.hip, once per kernel): k_sim_step<VANILLA> with CAPPED = false, k_sim_step_capped
+// (VANILLA = false, CAPPED = true), the launches under a request cap (tm_store::eval_cap > 0), and k_sim_step_dist (DIST = true:
+// TM_KIND_DIST, whose back and front halves are its own; the others hold none of them).  Kernels from one text rather than
 // one template of both or a shared function: k_sim_step<...> keeps its name (the committed counter passes are filed under it) and,
 // to the instruction, the machine code it has without the cap - a common inlined body did not (1 700 instructions more, 50 more
 // scalar spills), and any change to its 45 000 instructions moves a launch by about a microsecond.
@@ -11,6 +12,7 @@
     // The first workgroups of the grid are collectors: each looks after the garbage collections of a range of games, in
     // slices of S.gc_slice_cycles per launch (catch-up launches pass TM_SIM_GC_FULL: to completion), beside the
     // simulation workgroups - they are dispatched first and share the CUs with them (a k_sim_step wave needs 70 registers).
+    constexpr int FAM = VANILLA ? FAM_ANY : (DIST ? FAM_DIST : FAM_VALUE);      // (the store's kind is the host's to match, tm_sim_step)
     const int n_gc = gc_blocks(S);
     if ((int)blockIdx.x < n_gc) {
         // the dense request list: this launch appends under S.eval_parity; the other set of counters (the list the evaluator
@@ -71,7 +73,7 @@
         const int leaf = GSV(gsv, TM_GS_LEAF);
         const uint32_t self_o = P.rec()[(size_t)leaf * TM_REC_DW + TM_REC_OBS];
         const uint32_t self_sc = P.rec()[(size_t)leaf * TM_REC_DW + TM_REC_SCORE];
-        wave_front_finish<VANILLA, CAPPED>(S, P, L, g, lane, leaf, 0, self_o, self_sc, gsv, gc_req_word, flags);
+        wave_front_finish<VANILLA, CAPPED, FAM>(S, P, L, g, lane, leaf, 0, self_o, self_sc, gsv, gc_req_word, flags);
         return;
     }
     // The request cap.  eval_served is what the evaluator's LAST launch served, so the comparison is only right in the launch that
@@ -94,10 +96,9 @@
         }
         return;
     }
-    const bool dist = !VANILLA && S.kind == TM_KIND_DIST;
     const long long t0 = __builtin_readcyclecounter();
     if ((flags & TM_SIM_BACKUP) && (pend == 1 || (CAPPED && pend == TM_PENDING_POSTED))) {
-        if (dist) wave_dist_back(S, P, L, g, lane, gsv);
+        if (DIST) wave_dist_back(S, P, L, g, lane, gsv);
         else wave_sim_back(S, P, L, lane, gsv, flags);
         __threadfence_block();
     }
@@ -107,8 +108,8 @@
 #endif
     // the per-move quota (tm_move_begin): games that lost launches to a collection catch up in extra launches
     if ((flags & TM_SIM_FRONT) && GSV(gsv, TM_GS_SIM_STARTED) < GSV(gsv, TM_GS_SIM_TARGET)) {
-        if (dist) wave_dist_front<VANILLA>(S, P, L, g, lane, gsv, gc_req_word, flags);
-        else wave_sim_front<VANILLA, CAPPED>(S, P, L, VANILLA ? &mt_lds[w] : nullptr, g, lane, gsv, gc_req_word, flags);
+        if (DIST) wave_dist_front<VANILLA, FAM>(S, P, L, g, lane, gsv, gc_req_word, flags);
+        else wave_sim_front<VANILLA, CAPPED, FAM>(S, P, L, VANILLA ? &mt_lds[w] : nullptr, g, lane, gsv, gc_req_word, flags);
     }
     else if (lane < S.eval_slots) P.eval_obs()[lane] = 0;   // nothing started: no request (the evaluator skips empty slots)
 #ifdef TM_TIMELINE

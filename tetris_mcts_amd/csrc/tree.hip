@@ -307,9 +307,17 @@ constexpr int GC_IDLE = 11;        // (a step, not a phase: a speculative markin
 constexpr int GC_FOREIGN = 13;     // (a step, not a phase: a collection that launches with another number of collectors began - not touched)
 
 
+// The agent family a caller is compiled for.  The tree kernel exists once per family (k_sim_step<false> / k_sim_step_capped: the
+// value kinds; k_sim_step_dist: TM_KIND_DIST), chosen on the host (tm_sim_step_kernel), so that neither carries the other's code;
+// the rollout kinds' kernel and the kernels off the hot path decide by S.kind as they run (FAM_ANY).
+enum { FAM_ANY = 0, FAM_VALUE = 1, FAM_DIST = 2 };
+template <int FAM>
+__device__ __forceinline__ bool fam_is_dist(const tm_store& S) { return FAM == FAM_ANY ? S.kind == TM_KIND_DIST : FAM == FAM_DIST; }
+
 // `gsv`: the wave's snapshot of the game's control block (word i in lane i), valid when nothing in this launch has changed
 // the free-list words yet (the expansion's first attempt); has_gsv = false: read them from memory (sequential retries,
 // update_root).
+template <int FAM = FAM_ANY>
 __device__ __forceinline__ void wave_new_nodes(const tm_store& S, const GP& P, WaveLds& L, int g, int n, int lane,
                                       int& r_idx, int& r_obs, bool has_gsv = false, int gsv = 0, bool barrier = false) {
     const bool act = lane < n;
@@ -383,7 +391,7 @@ __device__ __forceinline__ void wave_new_nodes(const tm_store& S, const GP& P, W
     }
     table_insert_seq(P.ntab(), mask, need, n, lane, h, ins, idx, L.misc);
     // 3. observations of the new nodes (agents/agent.py:112-128)
-    const bool ident = S.kind == TM_KIND_DIST;      // no projection: a node's statistics are its own (observation index = node index)
+    const bool ident = fam_is_dist<FAM>(S);         // no projection: a node's statistics are its own (observation index = node index)
     uint32_t* ok = L.okeys[act ? lane : 0];
     uint64_t ho = 0;
     if (isnew && !ident) { pack_obs(my, ok); ho = hash_obs(ok); }
@@ -503,6 +511,7 @@ __device__ __forceinline__ void wave_new_nodes(const tm_store& S, const GP& P, W
 // (TM_GS_GC_PHASE = 1) and the caller suspends the simulation; once the collection is complete the expansion is simply
 // redone - the successors already inserted are transposition hits, the others pop from the rebuilt free list in order.
 // ---------------------------------------------------------------------------------------------------
+template <int FAM = FAM_ANY>
 __device__ __forceinline__ bool wave_expand(const tm_store& S, const GP& P, WaveLds& L, int g, int lane, int leaf,
                                    uint32_t self_sc /* float bits of the leaf's own score */, uint32_t& hdr_out, int gsv,
                                    int gc_req_word /* (launch << 4) | GC_REQ: what a collection request looks like */) {
@@ -523,7 +532,7 @@ __device__ __forceinline__ bool wave_expand(const tm_store& S, const GP& P, Wave
     wave_sync();
     int idx, o;
     const bool barrier = (gc_req_word & 15) == GC_REQ_SPEC;      // the launch began in GC_SPEC_MARK
-    wave_new_nodes(S, P, L, g, 7, lane, idx, o, true, gsv, barrier);
+    wave_new_nodes<FAM>(S, P, L, g, 7, lane, idx, o, true, gsv, barrier);
     if (idx < 0) {
         // slow path: sequential new_node with a GC at the exhausting pop (rare: once per ~50 moves)
         int out_idx = 0, out_o = 0;
@@ -536,7 +545,7 @@ __device__ __forceinline__ bool wave_expand(const tm_store& S, const GP& P, Wave
             if (lane < GAME_DW) { keep = L.slots[0][lane]; L.slots[0][lane] = L.slots[7][lane]; }
             wave_sync();
             int i1, o1;
-            wave_new_nodes(S, P, L, g, 1, lane, i1, o1, false, 0, barrier);
+            wave_new_nodes<FAM>(S, P, L, g, 1, lane, i1, o1, false, 0, barrier);
             if (i1 < 0) {
                 if (!P.gs()[TM_GS_GC_RETRY] && !P.gs()[TM_GS_POOL_FULL]) {
                     if (lane < GAME_DW) L.slots[0][lane] = keep;
@@ -836,7 +845,7 @@ __device__ __forceinline__ void wave_sim_back(const tm_store& S, const GP& P, Wa
 // ---------------------------------------------------------------------------------------------------
 // (CAPPED: the launch runs under a request cap, tm_store::eval_cap > 0 - k_sim_step_capped; everything about the cap is behind it,
 //  so that the code of the other launches is what it is without the cap)
-template <bool VANILLA, bool CAPPED = false>
+template <bool VANILLA, bool CAPPED = false, int FAM = FAM_ANY>
 __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P, WaveLds& L, int g, int lane, int leaf,
                                                   int leaf_end, uint32_t self_o, uint32_t self_sc, int gsv, int gc_req_word,
                                                   int eflags) {
@@ -849,13 +858,13 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
     uint32_t post_obs = 0;
     // single-leaf kinds under TM_SIM_EVAL_NEEDED: what the evaluator returned for this observation when it was a leaf before
     // (another node, same board and piece), requested here so that it arrives under the expansion
-    const bool use_cache = !VANILLA && !leaf_end && (eflags & TM_SIM_EVAL_NEEDED) && S.obs_eval && S.eval_epoch > 0 &&
+    const bool use_cache = !VANILLA && FAM != FAM_DIST && !leaf_end && (eflags & TM_SIM_EVAL_NEEDED) && S.obs_eval && S.eval_epoch > 0 &&
                            (kind == TM_KIND_VALUESIM || kind == TM_KIND_CPPAGENT);
     uint4 ce = make_uint4(0u, 0u, 0u, 0u);
     if (use_cache) ce = *reinterpret_cast<const uint4*>(S.obs_eval + ((size_t)g * P.n() + (size_t)self_o) * 4);
     if (!leaf_end) {
         uint32_t lh;
-        if (!wave_expand(S, P, L, g, lane, leaf, self_sc, lh, gsv, gc_req_word)) {
+        if (!wave_expand<FAM>(S, P, L, g, lane, leaf, self_sc, lh, gsv, gc_req_word)) {
             if (lane < S.eval_slots) P.eval_obs()[lane] = 0;
             if (lane == 0) P.gs()[TM_GS_PENDING] = 2;
             return;
@@ -863,7 +872,7 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
         if (VANILLA) {
             k_eval = 0;
             if (lane < S.eval_slots) P.eval_obs()[lane] = 0;
-        } else if (kind == TM_KIND_VALUESIM || kind == TM_KIND_CPPAGENT || kind == TM_KIND_DIST) {
+        } else if (FAM == FAM_DIST || kind == TM_KIND_VALUESIM || kind == TM_KIND_CPPAGENT || (FAM == FAM_ANY && kind == TM_KIND_DIST)) {
             // (TM_KIND_DIST: the request names the leaf NODE - identity projection)
             // filed under the same weights: the evaluator would return the same two floats
             const bool hit = use_cache && (int)ce.z == S.eval_epoch;
@@ -940,7 +949,7 @@ __device__ __forceinline__ void wave_front_finish(const tm_store& S, const GP& P
 // ---------------------------------------------------------------------------------------------------
 // the front half: select_trace_obs (core.h:167-224), then expansion and evaluation requests
 // ---------------------------------------------------------------------------------------------------
-template <bool VANILLA, bool CAPPED = false>
+template <bool VANILLA, bool CAPPED = false, int FAM = FAM_ANY>
 __device__ __forceinline__ void wave_sim_front(const tm_store& S, const GP& P, WaveLds& L, MtLds* M, int g, int lane, int gsv,
                                                int gc_req_word, int eflags) {
     const long long tc_start = __builtin_readcyclecounter();
@@ -1241,7 +1250,7 @@ __device__ __forceinline__ void wave_sim_front(const tm_store& S, const GP& P, W
         if (lane < 32) S.rng[(size_t)g * 32 + lane] = rng_keep;
         if (lane == 0) P.gs()[TM_GS_RNG_POS] = rng_pos;
     }
-    wave_front_finish<VANILLA, CAPPED>(S, P, L, g, lane, leaf, leaf_end | (overflow ? 1 : 0), self_o, self_sc, gsv, gc_req_word, eflags);
+    wave_front_finish<VANILLA, CAPPED, FAM>(S, P, L, g, lane, leaf, leaf_end | (overflow ? 1 : 0), self_o, self_sc, gsv, gc_req_word, eflags);
 }
 
 __device__ __forceinline__ bool bit_test_set(uint8_t* bm, uint32_t i) {
@@ -1359,7 +1368,7 @@ __device__ __forceinline__ void wave_dist_back(const tm_store& S, const GP& P, W
 // else policy_dist (:66-79): q = (mean + score - own score) + norm_quantile(n) * sqrt(variance / (visit + 1e-3)), first
 // argmax (np.argmax: the first NaN wins).  One 8-lane group per unique child (the record's pieces), one dependent pair of
 // loads per level (record -> children's statistics).
-template <bool VANILLA>
+template <bool VANILLA, int FAM = FAM_ANY>
 __device__ __forceinline__ void wave_dist_front(const tm_store& S, const GP& P, WaveLds& L, int g, int lane, int gsv, int gc_req_word, int eflags) {
     const long long tc_start = __builtin_readcyclecounter();
     if (lane < 32) L.misc[lane] = S.rng[(size_t)g * 32 + lane];
@@ -1464,7 +1473,7 @@ __device__ __forceinline__ void wave_dist_front(const tm_store& S, const GP& P, 
         if (lane < 32) S.rng[(size_t)g * 32 + lane] = rng_keep;
         if (lane == 0) P.gs()[TM_GS_RNG_POS] = rng_pos;
     }
-    wave_front_finish<VANILLA>(S, P, L, g, lane, leaf, leaf_end, cur.y, cur.z, gsv, gc_req_word, eflags);
+    wave_front_finish<VANILLA, false, FAM>(S, P, L, g, lane, leaf, leaf_end, cur.y, cur.z, gsv, gc_req_word, eflags);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2852,14 +2861,20 @@ __host__ inline size_t sim_lds_bytes(const tm_store& S, bool vanilla) {
     const size_t sim = WPB * sizeof(WaveLds) + (vanilla ? WPB * sizeof(MtLds) : 0), gc = gc_lds_bytes(S.max_nodes);
     return (sim > gc ? sim : gc);
 }
+// One kernel per agent family from the one text: <false> the value kinds, <true> the rollout kinds ...
 template <bool VANILLA>
 __global__ __launch_bounds__(64 * WPB, 5) void k_sim_step(tm_store S, int flags) {
-    constexpr bool CAPPED = false;
+    constexpr bool CAPPED = false, DIST = false;
 #include "sim_step_body.inc"
 }
-// the launches under a request cap (single-leaf kinds, never the rollout kinds)
+// ... the value kinds' launches under a request cap (single-leaf kinds, never the rollout kinds, never TM_KIND_DIST) ...
 __global__ __launch_bounds__(64 * WPB, 5) void k_sim_step_capped(tm_store S, int flags) {
-    constexpr bool VANILLA = false, CAPPED = true;
+    constexpr bool VANILLA = false, CAPPED = true, DIST = false;
+#include "sim_step_body.inc"
+}
+// ... and TM_KIND_DIST
+__global__ __launch_bounds__(64 * WPB, 5) void k_sim_step_dist(tm_store S, int flags) {
+    constexpr bool VANILLA = false, CAPPED = false, DIST = true;
 #include "sim_step_body.inc"
 }
 
@@ -3284,12 +3299,28 @@ int tm_tree_remove_nodes(const tm_store* s, const uint8_t* mask, void* stream) {
     hipLaunchKernelGGL(k_tree_gc, dim3(s->n_games), dim3(64 * WPB), 0, (hipStream_t)stream, *s, mask);
     return TM_LAUNCH_CHECK();
 }
+// Which tree kernel a store's launches run: a pure function of (kind, eval_cap).  -1: no kernel - an unknown kind, a negative cap,
+// or a cap on a kind that can not carry one (only the single-leaf kinds with the built-in value net can).
+int tm_sim_step_kernel(int kind, int eval_cap) {
+    if (kind < TM_KIND_VALUESIM || kind > TM_KIND_DIST || eval_cap < 0) return -1;
+    if (eval_cap > 0) return (kind == TM_KIND_VALUESIM || kind == TM_KIND_CPPAGENT) ? TM_SIM_KERNEL_CAPPED : -1;
+    if (kind == TM_KIND_VANILLA || kind == TM_KIND_VANILLA_C) return TM_SIM_KERNEL_ROLLOUT;
+    return kind == TM_KIND_DIST ? TM_SIM_KERNEL_DIST : TM_SIM_KERNEL_VALUE;
+}
+static void sim_step_launch(int kernel, const tm_store* s, dim3 grid, dim3 block, int flags, void* stream) {
+    const size_t lds = sim_lds_bytes(*s, kernel == TM_SIM_KERNEL_ROLLOUT);
+    if (kernel == TM_SIM_KERNEL_ROLLOUT) hipLaunchKernelGGL(k_sim_step<true>, grid, block, lds, (hipStream_t)stream, *s, flags);
+    else if (kernel == TM_SIM_KERNEL_CAPPED) hipLaunchKernelGGL(k_sim_step_capped, grid, block, lds, (hipStream_t)stream, *s, flags);
+    else if (kernel == TM_SIM_KERNEL_DIST) hipLaunchKernelGGL(k_sim_step_dist, grid, block, lds, (hipStream_t)stream, *s, flags);
+    else hipLaunchKernelGGL(k_sim_step<false>, grid, block, lds, (hipStream_t)stream, *s, flags);
+}
 int tm_sim_step(const tm_store* s, int flags, void* stream) {
     if (!s->eval_list || !s->eval_cnt) return (int)hipErrorInvalidValue;      // (a tm_store of an older header: no request list)
     if (s->game_list && (s->n_listed < 0 || s->n_listed > s->n_games)) return (int)hipErrorInvalidValue;
+    const int kernel = tm_sim_step_kernel(s->kind, s->eval_cap);
+    if (kernel < 0) return (int)hipErrorInvalidValue;
     // the request cap: single-leaf kinds with the built-in value net, launches that back up and start simulations in one
-    if (s->eval_cap != 0 && (s->eval_cap < 0 || !s->eval_served || s->eval_slots != 1 ||
-                             (s->kind != TM_KIND_VALUESIM && s->kind != TM_KIND_CPPAGENT) ||
+    if (s->eval_cap != 0 && (!s->eval_served || s->eval_slots != 1 ||
                              (flags & (TM_SIM_BACKUP | TM_SIM_FRONT)) != (TM_SIM_BACKUP | TM_SIM_FRONT)))
         return (int)hipErrorInvalidValue;
     // the launch number (bits 8.. of the kernel's flags): what orders a game's wave and its collector workgroup, which
@@ -3297,22 +3328,17 @@ int tm_sim_step(const tm_store* s, int flags, void* stream) {
     flags = (flags & 0xFF) | (int)(((tm_launch_seq.fetch_add(1) + 1u) & 0x7FFFFu) << 8) | gc_mem_marks_flag();
     const int n_waves = s->game_list ? s->n_listed : s->n_games;       // simulation waves; the collectors are those of all n_games
     const dim3 grid((n_waves + WPB - 1) / WPB + gc_blocks(*s)), block(64 * WPB);
-    if (s->kind == TM_KIND_VANILLA || s->kind == TM_KIND_VANILLA_C)
-        hipLaunchKernelGGL(k_sim_step<true>, grid, block, sim_lds_bytes(*s, true), (hipStream_t)stream, *s, flags);
-    else if (s->eval_cap > 0)
-        hipLaunchKernelGGL(k_sim_step_capped, grid, block, sim_lds_bytes(*s, false), (hipStream_t)stream, *s, flags);
-    else
-        hipLaunchKernelGGL(k_sim_step<false>, grid, block, sim_lds_bytes(*s, false), (hipStream_t)stream, *s, flags);
+    sim_step_launch(kernel, s, grid, block, flags, stream);
     return TM_LAUNCH_CHECK();
 }
 int tm_gc_step(const tm_store* s, void* stream) {
     // the collector workgroups alone, no time limit: one step of every collection under way
     const int flags = TM_SIM_GC_FULL | (int)(((tm_launch_seq.fetch_add(1) + 1u) & 0x7FFFFu) << 8) | gc_mem_marks_flag();
     const dim3 grid(gc_blocks(*s)), block(64 * WPB);
-    if (s->kind == TM_KIND_VANILLA || s->kind == TM_KIND_VANILLA_C)
-        hipLaunchKernelGGL(k_sim_step<true>, grid, block, sim_lds_bytes(*s, true), (hipStream_t)stream, *s, flags);
-    else
-        hipLaunchKernelGGL(k_sim_step<false>, grid, block, sim_lds_bytes(*s, false), (hipStream_t)stream, *s, flags);
+    // (the collectors are the same in every kernel: the family's own without a cap, whose code the move's launches have loaded)
+    const int kernel = tm_sim_step_kernel(s->kind, 0);
+    if (kernel < 0) return (int)hipErrorInvalidValue;
+    sim_step_launch(kernel, s, grid, block, flags, stream);
     return TM_LAUNCH_CHECK();
 }
 int tm_move_begin(const tm_store* s, int sims, void* stream) {
