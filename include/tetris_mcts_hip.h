@@ -505,6 +505,46 @@ int tm_nodes_sweep(const tm_store *tree, void *ring, int ring_cap, int32_t *coun
 int tm_node_targets(const void *rows, int n_rows, int weight_mode, float eps, uint32_t *obs, float *value, float *variance,
                     float *weight, int32_t *fault, void *stream);
 
+/* Game snapshots (games_snapshot.hip): the games of an environment copied out and, after a check on the device, back in, so
+ * that the games alive when a self-play run stops go on in the next one.  A game is its packed record (TM_GAME_DW dwords,
+ * ENGINE_SPEC.md section 2) and its four line statistics; trees are not carried (tm_update_root builds a root from any game).
+ * The engine trusts a packed game - piece and rot index its tables, a lock writes rows[y + i] - so bytes from outside pass
+ * tm_env_check first.  fault[g] is a set of TM_GAME_BAD_* bits, 0 for a well-formed game:
+ *   TM_GAME_BAD_PIECE       piece > 6
+ *   TM_GAME_BAD_ROT         rot > 3
+ *   TM_GAME_BAD_ROWS        a row with a bit above column 9, or a full row (0x3FF: a full row never survives a lock)
+ *   TM_GAME_BAD_PLACE       the placement of the falling piece.  A game that has NOT ended: x outside -3..9 or y outside -3..19
+ *                           (the only ranges in which a box can have a cell inside the well), or - evaluated only when piece <= 6
+ *                           and rot <= 3 - the engine's collides(rows, PIECE_MASK[piece][rot], x, y): no collision is what keeps
+ *                           every cell of the piece inside rows 0..19 and columns 0..9.  A game that HAS ended (flag bit 0): the
+ *                           piece is where the engine leaves it.  The only place that sets the bit is spawn(), which has just set
+ *                           (rot, x, y) = (0, 3, 0), and play() returns at once for an ended game, so anything but
+ *                           (rot, x, y) == (0, 3, 0) is a fault (the piece's box is then inside the well whatever the rows hold).
+ *   TM_GAME_BAD_FIELDS      drop_ctr >= app, a flag bit other than 0 and 1, combo < -1, or piece_count == 0
+ *   TM_GAME_BAD_LINE_STATS  a negative line_stats entry (only when line_stats is given)
+ * No value read from a game is used as an index, an address or a shift count before it has passed its test.
+ * tm_env_check(games [n][16], line_stats [n][4] or NULL, n, app): writes fault[n] and n_bad[0] = the number of games with a fault
+ *   (added in a fixed order; no atomics).
+ * tm_env_save: games and line_stats <- s->env_game, s->env_line_stats (s->n_games games), a stream-ordered copy.
+ * tm_env_load: tm_env_check with s->n_games and s->app, then a launch that reads n_bad ON THE DEVICE and copies every game and
+ *   line statistic into s->env_game / s->env_line_stats only if it is 0: with any fault not one byte of the store changes.  The
+ *   caller reads fault / n_bad back when it likes; the call itself does not synchronise.
+ * tm_episode_resume: tm_episode_init with move_idx[g] taken from the array (a negative entry counts as 0): the recorder goes on
+ *   in the middle of loaded games.  The value is only ever written into rows.
+ * All four enqueue on stream, allocate nothing, read nothing back and write nothing outside the arrays named.
+ * hipErrorInvalidValue, nothing launched, for a NULL pointer (tm_env_check's line_stats excepted), n < 1, app < 1, first_id < 0 or
+ * a buffer that is not 4-byte aligned: checked before the first HIP call, so these answer on a machine without a GPU. */
+#define TM_GAME_BAD_PIECE 1
+#define TM_GAME_BAD_ROT 2
+#define TM_GAME_BAD_ROWS 4
+#define TM_GAME_BAD_PLACE 8
+#define TM_GAME_BAD_FIELDS 16
+#define TM_GAME_BAD_LINE_STATS 32
+int tm_env_check(const uint32_t *games, const int32_t *line_stats, int n, int app, int32_t *fault, int32_t *n_bad, void *stream);
+int tm_env_save(const tm_store *s, uint32_t *games, int32_t *line_stats, void *stream);
+int tm_env_load(const tm_store *s, const uint32_t *games, const int32_t *line_stats, int32_t *fault, int32_t *n_bad, void *stream);
+int tm_episode_resume(int n_games, int first_id, const int32_t *move_idx, int32_t *slot_state, int32_t *counters, void *stream);
+
 /* The store of games [first, first+n) of *s (every array is per game contiguous: a slice is the same struct with
  * offset pointers).  Sub-batches of one process, shards of a multi-GPU job.  `first` is a multiple of four (a tree-kernel
  * workgroup's games; the groups of TM_GS_GC_ACTIVE4): hipErrorInvalidValue otherwise. */

@@ -4,13 +4,22 @@ on the MI355X engine.  `python play.py --agent_type ValueSimLP --mcts_sims 500 -
 reference (same per-game log lines, play.py:25-37,164); `--n_games N` plays N games concurrently on the GPU
 (new, optional).  `--save` writes the reference's self-play rows (util/Data.py State), recorded on the device, as numbered
 .npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5).  `--save_nodes` writes the tree nodes the
-collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`.  --save_tree, --gui and --interactive belong to
+collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`.  `--games_out` / `--games_in` carry the
+games of the batch from one run to the next (tetris_mcts_amd/games.py).  --save_tree, --gui and --interactive belong to
 the reference's storage / UI layers and are refused with a clear message.
 """
 import argparse
 import sys
 
 import numpy as np
+
+
+def games_every_moves(text):
+    """the value of --games_every: a number of moves, at least 1 (the default, 0, is not a value one can give)"""
+    k = int(text)
+    if k < 1:
+        sys.exit('--games_every %s: it is a number of moves, at least 1 (leave the flag out to write only at the end)' % text)
+    return k
 
 
 def build_parser():
@@ -41,7 +50,8 @@ def build_parser():
     add('--tetris_scoring', default=0, type=int, help='Scoring system used by Tetris (0: official guideline, 1: line clears)')
     # extensions (not in the reference)
     add('--n_games', default=1, type=int, help='[new] concurrent games on the GPU')
-    add('--seed', default=0, type=int, help='[new] environment seed (game g uses seed+g)')
+    add('--seed', default=0, type=int, help='[new] environment seed (game g uses seed+g); it does not touch games loaded with '
+        '--games_in: each of them carries its own seed')
     add('--max_moves', default=0, type=int, help='[new] stop after this many moves (0 = no limit)')
     add('--train_every', default=0, type=int, help='[new] online mode: look for harvested tuples every k moves (0: every move '
         'with one game - the reference trains at every collection, ValueSim.py:101-120 - every 10 moves with more)')
@@ -76,7 +86,24 @@ def build_parser():
         'rows one move can harvest')
     add('--nodes_flush_moves', default=0, type=int, help='[new] with --save_nodes: copy the ring to the host at least every this '
         'many moves when it holds rows (0: the default, FLUSH_MOVES)')
+    add('--games_out', default=None, type=str, help='[new] at the end of the run write the games as they stand - the packed games, '
+        'their line statistics and each slot\'s move count (tetris_mcts_amd/games.py) - to this file, for a later --games_in; a game '
+        'that has just ended is stored ended')
+    add('--games_in', default=None, type=str, help='[new] go on with the games of this file (written by --games_out with the same '
+        '--n_games, --app, --tetris_scoring and --tetris_randomizer) instead of new ones; every game is checked on the device before '
+        'any is loaded; --seed does not touch loaded games, each carries its seed; trees are not carried, the agent builds new roots')
+    add('--games_every', default=0, type=games_every_moves, help='[new] with --games_out: also write the file every this many moves (0: only at '
+        'the end)')
     return p
+
+
+def check_games(args):
+    """the refusals of --games_in / --games_out / --games_every, before anything is imported"""
+    import os
+    if args.games_every and not args.games_out:
+        sys.exit('--games_every says how often --games_out is written: it needs --games_out')
+    if args.games_in is not None and not os.path.isfile(args.games_in):
+        sys.exit('--games_in %s: there is no such file (a first run of a cycle starts without --games_in)' % args.games_in)
 
 
 def check_save_nodes(args):
@@ -133,6 +160,7 @@ def main(argv=None):
         sys.exit('--save records what an agent plays (its root statistics, value and policy beside the board): it needs '
                  '--agent_type (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     check_save_nodes(args)
+    check_games(args)
     if not args.agent_type:
         sys.exit('--agent_type is required (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     if args.fit_backend == 'hip_dist' and args.agent_type != 'DistValueSim':
@@ -186,11 +214,19 @@ def main(argv=None):
             extra['min_visits_to_store'] = args.min_visit
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
+    slot_moves = np.zeros(G, np.int32)        # the moves played so far in each slot's episode
+    if args.games_in is not None:
+        try:
+            slot_moves = game.load_games(args.games_in)
+        except ValueError as e:
+            sys.exit('--games_in: %s' % e)
     agent.update_root(game)
     rec = None
     if args.save:
         from tetris_mcts_amd.episodes import EpisodeRecorder
         rec = EpisodeRecorder(args.save_dir, args.save_file, args.cycle, G)
+        if args.games_in is not None:
+            rec.resume(slot_moves)
     node_rec = None
     if args.save_nodes:
         from tetris_mcts_amd.nodes import NodeRecorder
@@ -236,6 +272,8 @@ def main(argv=None):
             agent.train_if_collected(every=args.train_every or (1 if G == 1 else 10),
                                      min_tuples=args.train_min_tuples or (1 if G == 1 else 1024))
         ended = np.atleast_1d(game.end)
+        slot_moves += 1
+        slot_moves[ended] = 0
         if ended.any():
             scores, lines = np.atleast_1d(game.score), np.atleast_1d(game.line_clears)
             for g in np.nonzero(ended)[0]:
@@ -253,11 +291,15 @@ def main(argv=None):
             agent.update_root(game)
         if node_rec is not None:
             node_rec.drain(agent)       # between two moves: what this move's collections harvested goes into the ring
+        if args.games_every and moves % args.games_every == 0:
+            game.save_games(args.games_out, slot_moves)
         if args.max_moves and moves >= args.max_moves:
             break
     print(flush=True)
     if rec is not None:
         rec.close()
+    if args.games_out:
+        print('games written to %s' % game.save_games(args.games_out, slot_moves), flush=True)
     if node_rec is not None:
         node_rec.close(agent, occupied=args.save_nodes_occupied)
         print('node rows written: %d in %d file(s), %d lost' % (node_rec.rows_written, len(node_rec.files), node_rec.lost),

@@ -34,7 +34,11 @@ def stats(files):
     last = np.nonzero(np.append((key[1:] != key[:-1]).any(axis=1), True))[0] if d.length else np.zeros(0, np.int64)
     open_rows = [i for i in last.tolist() if (int(d.cycle[i]), int(d.episode[i])) not in ended]
     lines_so_far = [int(d.lines[i]) for i in open_rows]
-    return {
+    # an episode whose first recorded move is above 0 went on from an earlier run's games (play.py --games_in): its rows here are
+    # its later part, its row in the episode table counts ALL its moves and carries its final score and lines
+    first = np.nonzero(np.append(True, (key[1:] != key[:-1]).any(axis=1)))[0] if d.length else np.zeros(0, np.int64)
+    continued = [i for i in first.tolist() if int(d.move[i]) > 0]
+    out = {
         "files": len(d.files), "state_rows": int(d.length),
         "finished": dict(count=int(len(ep)), lines=_summary(ep["lines"]), score=_summary(ep["score"]),
                          moves=_summary(ep["moves"])),
@@ -44,6 +48,13 @@ def stats(files):
                      "(lines so far, before their last recorded action), and a mean over finished episodes only is biased low in a "
                      "fixed-length run" % len(open_rows),
     }
+    if continued:
+        n_fin = sum((int(d.cycle[i]), int(d.episode[i])) in ended for i in continued)
+        out["continued"] = dict(count=len(continued), finished=n_fin, moves_before=_summary([int(d.move[i]) for i in continued]),
+                                note="%d episodes were continued from an earlier run (their first recorded move is above 0); the %d "
+                                     "of them that finished are in `finished` with totals that are complete: all their moves, final "
+                                     "score and lines" % (len(continued), n_fin))
+    return out
 
 
 def main(argv=None):

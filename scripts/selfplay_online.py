@@ -34,7 +34,11 @@ ap.add_argument("--no-train", action="store_true", help="play only (with --load:
 ap.add_argument("--fit_backend", default="torch", choices=("torch", "hip", "hip_dist"), help="gradients of the fits: PyTorch autograd, the HIP kernels of csrc/valuenet_fit.hip (hip: the value net) or of csrc/distnet_fit.hip (hip_dist: --agent DistValueSim only)")
 ap.add_argument("--validation_backend", default="torch", choices=("torch", "hip"), help="validation of the fits: PyTorch, or the forward of the same HIP kernels (hip: needs --fit_backend hip or hip_dist)")
 ap.add_argument("--fit_states", default="dense", choices=("dense", "packed"), help="what the fits are fed: rendered float boards, or the packed observations themselves (packed: needs --fit_backend hip or hip_dist and --validation_backend hip)")
+ap.add_argument("--games_in", default=None, help="go on with the games of this file (tetris_mcts_amd/games.py; written by --games_out or by play.py --games_out with the same number of games) instead of new ones; the seed does not touch loaded games")
+ap.add_argument("--games_out", default=None, help="at the end write the games as they stand to this file, for a later --games_in")
 args = ap.parse_args()
+if args.games_in is not None and not os.path.isfile(args.games_in):
+    sys.exit("--games_in %s: there is no such file" % args.games_in)
 if args.fit_states == "packed" and not (args.fit_backend != "torch" and args.validation_backend == "hip"):
     sys.exit("--fit_states packed needs --fit_backend hip or hip_dist and --validation_backend hip")
 if args.validation_backend == "hip" and args.fit_backend == "torch":
@@ -62,6 +66,12 @@ else:
 if args.load:
     assert os.path.isfile(args.load), args.load
     model.load(args.load, verbose=False)
+loaded_moves = None
+if args.games_in is not None:
+    try:
+        loaded_moves = game.load_games(args.games_in)
+    except ValueError as e:
+        sys.exit("--games_in: %s" % e)
 agent = getattr(agents, args.agent)(sims=args.sims, env=Tetris, env_args=env_args, n_games=G, max_nodes=args.max_nodes,
                                     model=model, online=not args.no_train, replay_cap=0 if args.no_train else 16384, **extra)
 agent.update_root(game)
@@ -69,9 +79,9 @@ t0 = t_round = time.time()
 train_total = 0.0
 moves, rounds = 0, 0
 ep_lines, ep_scores, ep_len = [], [], []
-alive = np.zeros(G, np.int64)
+alive = np.zeros(G, np.int64) if loaded_moves is None else loaded_moves.astype(np.int64)
 lines_round, moves_round = 0, 0          # lines cleared / moves played by all games since the last round
-prev_lines = np.zeros(G, np.int64)
+prev_lines = np.asarray(game.line_clears, np.int64).copy()
 log = open(args.out, "w")
 while time.time() - t0 < args.minutes * 60:
     act = agent.play()
@@ -123,6 +133,8 @@ while time.time() - t0 < args.minutes * 60:
         if args.save and rounds % args.save_every == 0:
             model.save(filename=args.save, verbose=False)
 log.close()
+if args.games_out:
+    print("games written to", game.save_games(args.games_out, alive), flush=True)
 if args.save:
     model.save(filename=args.save, verbose=False)
     print("checkpoint written to", args.save, flush=True)

@@ -65,6 +65,10 @@ SYMBOLS = {
     "tm_nodes_drain": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
     "tm_nodes_sweep": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
     "tm_node_targets": [vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp],
+    "tm_env_check": [vp, vp, i32, i32, vp, vp, vp],
+    "tm_env_save": [C.POINTER(TmStore), vp, vp, vp],
+    "tm_env_load": [C.POINTER(TmStore), vp, vp, vp, vp, vp],
+    "tm_episode_resume": [i32, i32, vp, vp, vp, vp],
     "tm_export_game": [C.POINTER(TmStore), i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "tm_core_select_trace_obs": [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp],
     "tm_core_backup_trace_obs": [i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f64, vp],

@@ -122,6 +122,19 @@ class EpisodeRecorder:
         self._check(self.L.tm_episode_init(self.G, self.writer.next_id, self._p(self.slot_state), self._p(self.counters),
                                            self._stream()), "tm_episode_init")
 
+    def resume(self, move_idx):
+        """Games that go on from an earlier run (games.py): call once, before the first add(), with the moves played so far in
+        each slot's episode.  The rows then continue that run's move numbers slot by slot (tm_episode_resume); episode ids are
+        numbered as without it."""
+        if self._pos or self._flushes or self.closed:
+            raise RuntimeError("EpisodeRecorder.resume comes before the first add()")
+        m = np.ascontiguousarray(np.asarray(move_idx).reshape(-1), dtype=np.int32)
+        if m.shape != (self.G,):
+            raise ValueError("move_idx: %d entries for %d games" % (m.size, self.G))
+        self._move_idx = self.torch.from_numpy(m).to(self.device)
+        self._check(self.L.tm_episode_resume(self.G, self.writer.next_id, self._p(self._move_idx), self._p(self.slot_state),
+                                             self._p(self.counters), self._stream()), "tm_episode_resume")
+
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream().cuda_stream)
 

@@ -74,6 +74,16 @@ class Tetris:
         self._ls.copy_(other._ls)
         self._host = None
 
+    def save_games(self, path, moves):
+        """write the games and each slot's move count to `path` (games.py: the snapshot a later run goes on from)"""
+        from .games import save_games
+        return save_games(path, self, moves)
+
+    def load_games(self, path):
+        """load a snapshot, all games or none (every game is checked on the device first); returns the move counts"""
+        from .games import load_games
+        return load_games(path, self)
+
     def getState(self):
         _lib.check(self.L.tm_env_render(C.byref(self.s), _p(self._state), _stream()), "tm_env_render")
         a = self._state.cpu().numpy().reshape(self.n_games, 20, 10)
