@@ -505,6 +505,45 @@ int tm_nodes_sweep(const tm_store *tree, void *ring, int ring_cap, int32_t *coun
 int tm_node_targets(const void *rows, int n_rows, int weight_mode, float eps, uint32_t *obs, float *value, float *variance,
                     float *weight, int32_t *fault, void *stream);
 
+/* Node records of the distributional head (node_records.hip): what the collections of a TM_KIND_DIST store harvest (online != 0:
+ * the packed observation, the backed-up distribution and the visits of every freed node with at least min_visits_to_store visits
+ * whose seven children have all been visited - replay_obs, replay_dist, replay_stat = (0, 0, visit, 0)), moved into one dense ring
+ * of rows that are a file's rows, and such rows turned into the arrays of a packed fit of the head (tm_distnet_fit_grad_packed).
+ * A dist node row, TM_NODE_DIST_ROW_BYTES, little-endian:
+ *     0 .. 63   the node row exactly as tm_nodes_drain would form it from this harvest: obs u4[12] | 48, 52 replay_stat words 0
+ *               and 1, bit for bit (the harvest leaves 0) | 56 visit f4 | 60 slot i4 (the game index)
+ *    64 .. 319  dist f4[TM_DIST_ROW]: the row of replay_dist, bit for bit (atoms beyond the store's dist_bins are the zero
+ *               padding the harvest wrote)
+ * tm_nodes_drain_dist is tm_nodes_drain on these rows, with the same counters and offsets: with c[g] = min(replay_count[g],
+ * replay_cap) (a negative count is taken as 0), game g's tuples 0 .. c[g]-1 go to the ring rows head + sum_{h<g} c[h] + i -
+ * game-major, harvest order within a game, the order of TreeStore.replay_dist() - and replay_count[g] = 0.  Offsets saturate at
+ * ring_cap; rows at or beyond ring_cap are not written and are counted in lost; head advances by what was written; drains by
+ * one.  It belongs on the stream of the search, between two moves: it must not run beside tm_sim_step, whose collectors append
+ * to the same buffers.
+ * tm_node_dist_targets: rows (n_rows dist node rows, 16-byte aligned) -> obs [n][12], target[i * target_stride + k] = atom k of
+ * row i for k < atoms, the bits copied (the floats from atoms to target_stride are not touched), weight[i] = 1.0f (weight_mode
+ * 0) or the row's visit (weight_mode 2); modes 1 and 3 of tm_node_targets divide by a variance, which this row does not carry,
+ * and are refused.  A row is at fault when its visit is not finite or is below 1, when one of its first `atoms` floats is not
+ * finite or is negative, when none of them is above 0 (no sum is formed: the rule has no summation order), or when a float
+ * from atoms to 63 compares unequal to 0 (a file recorded with more atoms than the model has).  Such a row gets weight 0 and
+ * sets *fault = 1 (a device int32 the caller cleared; a plain store); its obs and target are copied all the same.
+ * Both enqueue on stream (drain two kernels - tm_nodes_drain's scan and a copy of twenty 16-byte pieces a row -, targets one) and
+ * make no other HIP call: no allocation, no synchronisation, nothing read back, no atomics, deterministic.  Nothing is written
+ * outside the ring's first ring_cap rows, counters, offsets and replay_count (drain), or outside obs, target[:, :atoms], weight
+ * and *fault (targets).  hipErrorInvalidValue, nothing launched, checked before the first HIP call (so these answer on a machine
+ * without a GPU): a NULL pointer (replay_obs, replay_stat, replay_count or replay_dist of the store included); ring_cap < 1; a
+ * ring, a replay_obs, a replay_stat or a replay_dist that is not 16-byte aligned; a store with n_games < 1, with replay_cap < 1
+ * or of a kind other than TM_KIND_DIST (tm_nodes_drain has the others); n_rows < 0 or above 2^29 - 1; atoms outside 1 ..
+ * TM_DIST_ROW; target_stride < atoms; a weight_mode other than 0 or 2; rows that are not 16-byte aligned; an obs, target or weight
+ * that is not 4-byte aligned.  n_rows == 0 returns 0 and launches nothing.  There is no sweep of the pools for this kind: its
+ * harvest is per node and needs the seven-children test.
+ * Held on an MI355X to numpy statements of these definitions and to TreeStore.replay_dist() inside a search
+ * (tests/test_gpu_dist_nodes.py). */
+#define TM_NODE_DIST_ROW_BYTES 320
+int tm_nodes_drain_dist(tm_store *tree, void *ring, int ring_cap, int32_t *counters, int32_t *offsets, void *stream);
+int tm_node_dist_targets(const void *rows, int n_rows, int atoms, int weight_mode, uint32_t *obs, float *target, int target_stride,
+                         float *weight, int32_t *fault, void *stream);
+
 /* Game snapshots (games_snapshot.hip): the games of an environment copied out and, after a check on the device, back in, so
  * that the games alive when a self-play run stops go on in the next one.  A game is its packed record (TM_GAME_DW dwords,
  * ENGINE_SPEC.md section 2) and its four line statistics; trees are not carried (tm_update_root builds a root from any game).

@@ -4,7 +4,8 @@ on the MI355X engine.  `python play.py --agent_type ValueSimLP --mcts_sims 500 -
 reference (same per-game log lines, play.py:25-37,164); `--n_games N` plays N games concurrently on the GPU
 (new, optional).  `--save` writes the reference's self-play rows (util/Data.py State), recorded on the device, as numbered
 .npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5).  `--save_nodes` writes the tree nodes the
-collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`.  `--games_out` / `--games_in` carry the
+collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`; `--save_dist_nodes` does so for
+DistValueSim, whose harvest carries a distribution per node (`train.py --dist_nodes`).  `--games_out` / `--games_in` carry the
 games of the batch from one run to the next (tetris_mcts_amd/games.py).  --save_tree, --gui and --interactive belong to
 the reference's storage / UI layers and are refused with a clear message.
 """
@@ -81,11 +82,15 @@ def build_parser():
         '(ValueSim, ValueSimLP, ValueSimC; tetris_mcts_amd/nodes.py), what train.py --nodes fits')
     add('--save_nodes_occupied', default=False, action='store_true', help='[new] with --save_nodes: at the end of the run also '
         'write the observations still in the trees that pass the same test (the reference\'s save_occupied)')
-    add('--nodes_ring_rows', default=0, type=int, help='[new] with --save_nodes: rows of the recorder\'s ring on the device, 64 bytes '
-        'each and twice that in pinned host memory (0: the default, tetris_mcts_amd/nodes.py RING_ROWS); it should hold twice the '
-        'rows one move can harvest')
-    add('--nodes_flush_moves', default=0, type=int, help='[new] with --save_nodes: copy the ring to the host at least every this '
-        'many moves when it holds rows (0: the default, FLUSH_MOVES)')
+    add('--save_dist_nodes', default=False, action='store_true', help='[new] DistValueSim: write the tree nodes its collections '
+        'harvest - packed observation, the node\'s backed-up distribution, visits of every freed node with at least --min_visit '
+        'visits whose seven children have all been visited - as <save_dir>distnodes<cycle> with a sidecar of the head\'s atoms and '
+        'range (tetris_mcts_amd/nodes.py), what train.py --dist_nodes fits')
+    add('--nodes_ring_rows', default=0, type=int, help='[new] with --save_nodes / --save_dist_nodes: rows of the recorder\'s ring on '
+        'the device, 64 / 320 bytes each and twice that in pinned host memory (0: the default, tetris_mcts_amd/nodes.py RING_ROWS / '
+        'DIST_RING_ROWS); it should hold twice the rows one move can harvest')
+    add('--nodes_flush_moves', default=0, type=int, help='[new] with --save_nodes / --save_dist_nodes: copy the ring to the host at '
+        'least every this many moves when it holds rows (0: the default, FLUSH_MOVES)')
     add('--games_out', default=None, type=str, help='[new] at the end of the run write the games as they stand - the packed games, '
         'their line statistics and each slot\'s move count (tetris_mcts_amd/games.py) - to this file, for a later --games_in; a game '
         'that has just ended is stored ended')
@@ -119,7 +124,8 @@ def check_save_nodes(args):
                  'tuples); use ValueSim, ValueSimLP or ValueSimC' % args.agent_type)
     if args.agent_type == 'DistValueSim':
         sys.exit('--save_nodes is not offered for DistValueSim: its harvest is of another row shape (a distribution per node, '
-                 'tm_store.replay_dist), which the 64-byte node row does not hold; use ValueSim, ValueSimLP or ValueSimC')
+                 'tm_store.replay_dist), which the 64-byte node row does not hold; use ValueSim, ValueSimLP or ValueSimC, or record '
+                 'DistValueSim\'s harvest in rows of its own with --save_dist_nodes')
     if args.agent_type not in ('ValueSim', 'ValueSimLP', 'ValueSimC'):
         sys.exit('--save_nodes applies to ValueSim, ValueSimLP and ValueSimC only')
     if args.online:
@@ -132,6 +138,30 @@ def check_save_nodes(args):
         sys.exit('--nodes_ring_rows and --nodes_flush_moves are positive (0: the defaults)')
     if args.min_visit < 1:
         sys.exit('--min_visit is at least 1 with --save_nodes (an observation without a visit has no statistics)')
+
+
+def check_save_dist_nodes(args):
+    """the refusals of --save_dist_nodes, before anything is imported"""
+    if not args.save_dist_nodes:
+        return
+    if args.agent_type != 'DistValueSim':
+        sys.exit('--save_dist_nodes records the harvest of the distributional head: it needs --agent_type DistValueSim, not %s '
+                 '(--save_nodes records the harvest of ValueSim, ValueSimLP and ValueSimC)' % args.agent_type)
+    if args.save_nodes:
+        sys.exit('--save_dist_nodes together with --save_nodes: --save_nodes is not offered for DistValueSim, give --save_dist_nodes alone')
+    if args.online:
+        sys.exit('--save_dist_nodes together with --online: the online fit drains the same harvest buffers the recorder drains; '
+                 'record with --save_dist_nodes and fit with train.py --dist_nodes, or fit with --online')
+    if args.save_nodes_occupied:
+        sys.exit('--save_dist_nodes takes no --save_nodes_occupied: there is no sweep of the pools for the distributional harvest '
+                 '(it is per node and needs the seven-children test over live nodes only)')
+    if args.valuenet_backend == 'torch' and args.dense_requests:
+        sys.exit('--save_dist_nodes with --valuenet_backend torch --dense_requests has not been shown to work: record with the hip '
+                 'back ends or without --dense_requests')
+    if args.nodes_ring_rows < 0 or args.nodes_flush_moves < 0:
+        sys.exit('--nodes_ring_rows and --nodes_flush_moves are positive (0: the defaults)')
+    if args.min_visit < 1:
+        sys.exit('--min_visit is at least 1 with --save_dist_nodes (a node without a visit has no distribution)')
 
 
 class Scoreboard:
@@ -159,6 +189,7 @@ def main(argv=None):
     if args.save and not args.agent_type:
         sys.exit('--save records what an agent plays (its root statistics, value and policy beside the board): it needs '
                  '--agent_type (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
+    check_save_dist_nodes(args)
     check_save_nodes(args)
     check_games(args)
     if not args.agent_type:
@@ -212,6 +243,9 @@ def main(argv=None):
         extra['harvest'] = True
         if args.agent_type != 'ValueSimC':
             extra['min_visits_to_store'] = args.min_visit
+    if args.save_dist_nodes:
+        extra['harvest'] = True
+        extra['min_visits_to_store'] = args.min_visit
     agent = getattr(_agent_module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, benchmark=args.benchmark,
                                              online=args.online, min_visit=args.min_visit, n_games=G, **extra)
     slot_moves = np.zeros(G, np.int32)        # the moves played so far in each slot's episode
@@ -233,6 +267,10 @@ def main(argv=None):
         from tetris_mcts_amd.nodes import FLUSH_MOVES, RING_ROWS
         node_rec = NodeRecorder(args.save_dir, 'nodes', args.cycle, G, ring_rows=args.nodes_ring_rows or RING_ROWS,
                                 flush_moves=args.nodes_flush_moves or FLUSH_MOVES)
+    if args.save_dist_nodes:
+        from tetris_mcts_amd.nodes import DIST_RING_ROWS, FLUSH_MOVES, DistNodeRecorder
+        node_rec = DistNodeRecorder(args.save_dir, 'distnodes', args.cycle, G, agent.atoms, *agent.vrange,
+                                    ring_rows=args.nodes_ring_rows or DIST_RING_ROWS, flush_moves=args.nodes_flush_moves or FLUSH_MOVES)
 
     board_file = open('board_output', 'wb') if args.print_board_to_file else None
     if args.realtime_status:

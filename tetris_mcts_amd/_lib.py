@@ -65,6 +65,8 @@ SYMBOLS = {
     "tm_nodes_drain": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
     "tm_nodes_sweep": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
     "tm_node_targets": [vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp],
+    "tm_nodes_drain_dist": [C.POINTER(TmStore), vp, i32, vp, vp, vp],
+    "tm_node_dist_targets": [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp],
     "tm_env_check": [vp, vp, i32, i32, vp, vp, vp],
     "tm_env_save": [C.POINTER(TmStore), vp, vp, vp],
     "tm_env_load": [C.POINTER(TmStore), vp, vp, vp, vp, vp],

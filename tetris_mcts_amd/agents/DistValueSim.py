@@ -27,7 +27,7 @@ class DistValueSim(OnlineFit, TreeAgent):
 
     def __init__(self, atoms=50, vmin=0, vmax=5000, max_nodes=100000, model=None, evaluator=None, online=False,
                  min_visits_to_store=50, memory_size=500000, memory_growth_rate=5000, valuenet_backend=None, fit_backend="torch",
-                 validation_backend="torch", fit_states="dense", **kwargs):
+                 validation_backend="torch", fit_states="dense", harvest=False, **kwargs):
         """fit_backend: how train_nodes takes the gradients of the head's fits - "torch" (autograd, torch.optim.Adam) or
         "hip_dist" (csrc/distnet_fit.hip and the fused Adam).  "hip" names the value net's step (csrc/valuenet_fit.hip: the
         Gaussian loss, not this head's) and is refused here.
@@ -42,7 +42,13 @@ class DistValueSim(OnlineFit, TreeAgent):
         online: the reference's online leg (DistValueSimOnline.py:116-170) - a collection stores the freed nodes with at
         least `min_visits_to_store` visits whose seven children have all been visited (its commented store_nodes, default 50)
         as (board, distribution, visits) tuples, train_nodes fits the head on them (memory_size / memory_growth_rate as
-        ValueSim's)."""
+        ValueSim's).
+        harvest: ValueSim's - the store harvests at its collections (tm_store.online = 1, the default `replay_cap`,
+        `min_visits_to_store` as given) WITHOUT any fit: nothing else about the agent changes, and whoever asked for it drains the
+        tuples (nodes.DistNodeRecorder).  Not together with an online fit, which drains the same buffers."""
+        if harvest and online and not kwargs.get("benchmark", False):
+            raise ValueError("harvest=True records the harvested tuples and online=True fits them: both drain the same buffers, "
+                             "give one of the two")
         if fit_backend not in ("torch", "hip_dist"):
             raise ValueError("DistValueSim: fit_backend must be 'torch' or 'hip_dist', not %r ('hip' is the value net's gradient "
                              "step)" % (fit_backend,))
@@ -58,9 +64,11 @@ class DistValueSim(OnlineFit, TreeAgent):
         self.evaluator = evaluator
         benchmark = kwargs.get("benchmark", False)
         self.online = bool(online) and not benchmark
-        kwargs.setdefault("replay_cap", min(int(max_nodes), 16384) if self.online else 0)
+        self.harvest = bool(harvest)
+        harvesting = self.harvest or self.online
+        kwargs.setdefault("replay_cap", min(int(max_nodes), 16384) if harvesting else 0)
         self.memory_size, self.memory_growth_rate, self.n_trains, self._memory = int(memory_size), int(memory_growth_rate), 0, None
-        super().__init__(max_nodes=max_nodes, online=self.online, min_visits_to_store=min_visits_to_store, **kwargs)
+        super().__init__(max_nodes=max_nodes, online=harvesting, min_visits_to_store=min_visits_to_store, **kwargs)
         if evaluator is None:
             from ..model_distributional import Model_Dist
             if model is None:

@@ -25,6 +25,10 @@
 //
 // k_node_targets: four lanes a row again: three copy the observation's pieces, the fourth copies the value and variance bits and
 // computes the weight (tm_episode_targets' four rules with the row's visit count).
+//
+// The harvest of a TM_KIND_DIST store (replay_dist beside replay_obs / replay_stat) has rows of its own, the node row followed by the
+// 64 floats of the distribution: tm_nodes_drain_dist = k_nr_scan + k_nr_copy_dist, tm_node_dist_targets = k_node_dist_targets (the
+// kernels' own comments, below the value net's).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/tetris_mcts_hip.h"
@@ -185,6 +189,96 @@ __global__ __launch_bounds__(NR_THREADS) void k_node_targets(const uint4* __rest
     weight[r] = w;
 }
 
+// ---- the distributional harvest (TM_KIND_DIST): rows of TM_NODE_DIST_ROW_BYTES = the node row + replay_dist's 64 floats ----------
+constexpr int NRD_ROW_Q = TM_NODE_DIST_ROW_BYTES / 16;      // 16-byte pieces a row: 3 observation, 1 statistics, 16 distribution
+constexpr int NRD_DIST_Q = TM_DIST_ROW / 4;
+static_assert(TM_NODE_DIST_ROW_BYTES == TM_NODE_ROW_BYTES + 4 * TM_DIST_ROW && NRD_ROW_Q == 20 && NRD_DIST_Q == 16,
+              "a dist row is the node row's four pieces and the distribution's sixteen");
+
+// k_nr_copy_dist: a workgroup per (game, split) over the game's PIECES, not its rows: piece p of the game (row p / 20, piece
+// p % 20) goes to ring piece base * 20 + p, so consecutive lanes store consecutive 16-byte pieces of the ring (a wave stores 1 KiB
+// contiguous bytes per step) and read runs of 3, 1 and 16 consecutive pieces of replay_obs, replay_stat and replay_dist, each run
+// following the previous row's in its array.  A game's pieces are dealt to its NR_SPLIT workgroups 256 at a time.
+__global__ __launch_bounds__(NR_THREADS) void k_nr_copy_dist(const uint4* __restrict__ replay_obs, const uint4* __restrict__ replay_stat,
+                                                             const uint4* __restrict__ replay_dist, int replay_cap, int ring_cap,
+                                                             const int32_t* __restrict__ offsets, uint4* __restrict__ ring) {
+    const int g = blockIdx.x / NR_SPLIT, split = blockIdx.x % NR_SPLIT;
+    const int base = offsets[g];
+    const int c = nr_clamp(offsets[g + 1] - base, 0, replay_cap);              // the rows of game g that fit (k_nr_scan saturates)
+    const uint4* obs = replay_obs + (size_t)g * replay_cap * 3;
+    const uint4* stat = replay_stat + (size_t)g * replay_cap;
+    const uint4* dist = replay_dist + (size_t)g * replay_cap * NRD_DIST_Q;
+    const long long pieces = (long long)c * NRD_ROW_Q;
+    for (long long p = (long long)split * NR_THREADS + threadIdx.x; p < pieces; p += (long long)NR_SPLIT * NR_THREADS) {
+        const long long i = p / NRD_ROW_Q;
+        const int piece = (int)(p - i * NRD_ROW_Q);
+        if ((long long)base + i >= ring_cap) break;
+        uint4 v;
+        if (piece < 3) {
+            v = obs[(size_t)i * 3 + piece];
+        } else if (piece == 3) {
+            v = stat[i];
+            v.w = (uint32_t)g;
+        } else {
+            v = dist[(size_t)i * NRD_DIST_Q + (piece - 4)];
+        }
+        ring[(size_t)base * NRD_ROW_Q + (size_t)p] = v;
+    }
+}
+
+__device__ __forceinline__ bool nr_finite(float x) { return fabsf(x) <= 3.402823466e38f; }
+
+// k_node_dist_targets: sixteen lanes a row (four rows a wave).  Lane l of a row loads distribution piece l (atoms 4l .. 4l+3),
+// copies the atoms below `atoms` and tests all four; lanes 0 .. 2 also copy the observation's pieces, lane 3 reads the statistics.
+// Two wave ballots carry the row's verdict to its lane 3 (any float at fault; any atom above 0), which writes the weight: no sum
+// is formed, so the verdict does not depend on an order.
+__global__ __launch_bounds__(NR_THREADS) void k_node_dist_targets(const uint4* __restrict__ rows, int n_rows, int atoms, int weight_mode,
+                                                                  uint32_t* __restrict__ obs, uint32_t* __restrict__ target,
+                                                                  int target_stride, float* __restrict__ weight,
+                                                                  int32_t* __restrict__ fault, int obs_aligned) {
+    const long long q = (long long)blockIdx.x * NR_THREADS + threadIdx.x;
+    const long long r = q >> 4;
+    const int l = (int)(q & 15), lane = threadIdx.x & 63;
+    const bool live = r < n_rows;
+    bool bad = false, pos = false;
+    uint4 head = make_uint4(0u, 0u, 0u, 0u);
+    if (live) {
+        const uint4* row = rows + (size_t)r * NRD_ROW_Q;
+        const uint4 d = row[4 + l];
+        if (l < 4) head = row[l];
+        const uint32_t w[4] = {d.x, d.y, d.z, d.w};
+        uint32_t* dst = target + (size_t)r * target_stride;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = 4 * l + j;
+            const float x = __uint_as_float(w[j]);
+            if (k < atoms) {
+                dst[k] = w[j];
+                bad |= !nr_finite(x) || x < 0.0f;
+                pos |= x > 0.0f;
+            } else {
+                bad |= x != 0.0f;           // (a NaN included) a file recorded with more atoms than the model has
+            }
+        }
+        if (l < 3) {
+            uint32_t* o = obs + (size_t)r * TM_OBS_DW + l * 4;
+            if (obs_aligned) {
+                *reinterpret_cast<uint4*>(o) = head;
+            } else {
+                o[0] = head.x; o[1] = head.y; o[2] = head.z; o[3] = head.w;
+            }
+        }
+    }
+    const int shift = lane & ~15;
+    const bool row_bad = ((__ballot(bad) >> shift) & 0xFFFFull) != 0, row_pos = ((__ballot(pos) >> shift) & 0xFFFFull) != 0;
+    if (live && l == 3) {
+        const float visit = __uint_as_float(head.z);
+        float w = (weight_mode == 2) ? visit : 1.0f;
+        if (row_bad || !row_pos || !nr_finite(visit) || !(visit >= 1.0f)) { w = 0.0f; fault[0] = 1; }
+        weight[r] = w;
+    }
+}
+
 }  // namespace tmcts
 
 using namespace tmcts;
@@ -247,6 +341,40 @@ int tm_node_targets(const void* rows, int n_rows, int weight_mode, float eps, ui
     hipLaunchKernelGGL(k_node_targets, dim3((unsigned)((pieces + NR_THREADS - 1) / NR_THREADS)), dim3(NR_THREADS), 0,
                        (hipStream_t)stream, reinterpret_cast<const uint4*>(rows), n_rows, weight_mode, eps, obs, value, variance,
                        weight, fault, nr_aligned16(obs) ? 1 : 0);
+    return (int)hipGetLastError();
+}
+
+int tm_nodes_drain_dist(tm_store* tree, void* ring, int ring_cap, int32_t* counters, int32_t* offsets, void* stream) {
+    if (!tree || !ring || !counters || !offsets || ring_cap < 1) return (int)hipErrorInvalidValue;
+    if (!nr_aligned16(ring)) return (int)hipErrorInvalidValue;
+    if (tree->kind != TM_KIND_DIST || tree->n_games < 1 || tree->replay_cap < 1) return (int)hipErrorInvalidValue;
+    if (!tree->replay_obs || !tree->replay_stat || !tree->replay_count || !tree->replay_dist) return (int)hipErrorInvalidValue;
+    if (!nr_aligned16(tree->replay_obs) || !nr_aligned16(tree->replay_stat) || !nr_aligned16(tree->replay_dist))
+        return (int)hipErrorInvalidValue;                                                    // read as uint4
+    if ((long long)tree->n_games * NR_SPLIT > 0x7FFFFFFFll) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_nr_scan<true>, dim3(1), dim3(NR_SCAN_THREADS), 0, (hipStream_t)stream, tree->n_games, tree->replay_cap,
+                       tree->replay_count, ring_cap, counters, offsets);
+    hipLaunchKernelGGL(k_nr_copy_dist, dim3(tree->n_games * NR_SPLIT), dim3(NR_THREADS), 0, (hipStream_t)stream,
+                       reinterpret_cast<const uint4*>(tree->replay_obs), reinterpret_cast<const uint4*>(tree->replay_stat),
+                       reinterpret_cast<const uint4*>(tree->replay_dist), tree->replay_cap, ring_cap, offsets,
+                       reinterpret_cast<uint4*>(ring));
+    return (int)hipGetLastError();
+}
+
+int tm_node_dist_targets(const void* rows, int n_rows, int atoms, int weight_mode, uint32_t* obs, float* target, int target_stride,
+                         float* weight, int32_t* fault, void* stream) {
+    if (n_rows < 0 || n_rows > 0x7FFFFFFF / 4 || atoms < 1 || atoms > TM_DIST_ROW || target_stride < atoms)
+        return (int)hipErrorInvalidValue;
+    if (weight_mode != 0 && weight_mode != 2) return (int)hipErrorInvalidValue;             // 1 and 3 divide by a variance the row lacks
+    if (!rows || !obs || !target || !weight || !fault) return (int)hipErrorInvalidValue;
+    if (!nr_aligned16(rows)) return (int)hipErrorInvalidValue;
+    if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(weight)) & 3) != 0)
+        return (int)hipErrorInvalidValue;
+    if (n_rows == 0) return 0;
+    const long long lanes = (long long)n_rows * NRD_DIST_Q;                                  // sixteen lanes a row: at most 2^25 workgroups
+    hipLaunchKernelGGL(k_node_dist_targets, dim3((unsigned)((lanes + NR_THREADS - 1) / NR_THREADS)), dim3(NR_THREADS), 0,
+                       (hipStream_t)stream, reinterpret_cast<const uint4*>(rows), n_rows, atoms, weight_mode, obs,
+                       reinterpret_cast<uint32_t*>(target), target_stride, weight, fault, nr_aligned16(obs) ? 1 : 0);
     return (int)hipGetLastError();
 }
 

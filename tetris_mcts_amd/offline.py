@@ -41,7 +41,9 @@ specification, dist_targets_device the call (csrc/episode_dist_targets.hip: tm_e
 predict_rows_dist and fit_episodes_dist what episode_targets, predict_rows and fit_episodes are to the value net.
 
 The harvested tree nodes (`play.py --save_nodes`, nodes.py) are a third training set, the one the online fit learns from: the
-last part of this file - node_targets (csrc/node_records.hip: tm_node_targets), node_training_set and fit_nodes.
+next part of this file - node_targets (csrc/node_records.hip: tm_node_targets), node_training_set and fit_nodes.  The
+distributional head's harvest (`play.py --save_dist_nodes`) is the fourth, with rows that carry the node's distribution: the last
+part - node_dist_targets (tm_node_dist_targets), dist_node_training_set and fit_dist_nodes.
 """
 import ctypes as C
 import glob
@@ -883,8 +885,8 @@ def fit_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None,
     the fit used them and rank 0 writes the checkpoint."""
     from .model import Model_VV
     if not isinstance(model, Model_VV):
-        raise TypeError("fit_nodes fits a Model_VV: a node row holds a value and a variance, not a distribution (%s)"
-                        % type(model).__name__)
+        raise TypeError("fit_nodes fits a Model_VV: a node row holds a value and a variance, not a distribution (%s); the "
+                        "distributional head's harvest has rows and a fit of its own, fit_dist_nodes" % type(model).__name__)
     if fit_backend != "hip":
         raise ValueError("fit_nodes hands the fit packed observations, which only the HIP gradient step reads: it needs "
                          "fit_backend='hip', not %r" % (fit_backend,))
@@ -911,3 +913,126 @@ def fit_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None,
             model.save(verbose=False)
         res = dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
     return dict(res, n_train=info["n_train"], n_val=info["n_val"])
+
+
+# ---- dist node records: the harvested nodes of the distributional head (csrc/node_records.hip: tm_node_dist_targets) -------------
+#
+# `play.py --agent_type DistValueSim --save_dist_nodes` leaves NODE_DIST_DTYPE rows (nodes.py): the tuples the head's online fit
+# trains on - packed observation, the node's backed-up distribution, the visits.  The target is that distribution as recorded -
+# nothing is rebuilt from the head's own predictions -, the held-out rows are a random draw, and the fit reads the packed
+# observations as they are (Model_Dist.train_data(fit_backend="hip_dist", state_format="packed")).
+
+def dist_weight_mode(weighted, weighted_mode):
+    """weight_mode of tm_node_dist_targets: 0 without `weighted`, 2 (the visits) with weighted_mode 1; a dist row carries no
+    variance, so the value net's modes 0 (inverse of variance) and 2 (both) are a ValueError"""
+    if not weighted:
+        return 0
+    if weighted_mode != 1:
+        raise ValueError("weighted_mode must be 1 (number of visits) for dist node rows, not %r: they record no variance to "
+                         "divide by" % (weighted_mode,))
+    return 2
+
+
+def node_dist_targets(rows, atoms, weighted=False, weighted_mode=1, device=None):
+    """obs (int32 [n,12]), target (float32 [n,atoms]), weight (float32 [n]) of dist node rows: tm_node_dist_targets on the rows'
+    device, on the current stream (`rows`: a NODE_DIST_DTYPE table or a contiguous uint8 tensor [n,320]; device: where a table
+    goes), or with device="cpu" the numpy statement of the same definitions.  Raises RuntimeError on a set fault word (one .item())."""
+    from . import nodes as N
+    wmode = dist_weight_mode(weighted, weighted_mode)
+    atoms = int(atoms)
+    if not 1 <= atoms <= 64:
+        raise ValueError("atoms: 1 .. 64, not %r" % (atoms,))
+    on = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cuda"))
+    if torch.is_tensor(rows):
+        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != N.DIST_ROW_BYTES or not rows.is_contiguous():
+            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % N.DIST_ROW_BYTES)
+        table = None
+    else:
+        table = np.ascontiguousarray(rows)
+        if table.dtype != N.NODE_DIST_DTYPE:
+            raise ValueError("rows: a table of NODE_DIST_DTYPE, not %s" % (table.dtype,))
+        rows = torch.from_numpy(table.view(np.uint8).reshape(len(table), N.DIST_ROW_BYTES))
+    n = rows.shape[0]
+    if on.type == "cpu":
+        table = rows.cpu().numpy().reshape(-1).view(N.NODE_DIST_DTYPE) if table is None else table
+        obs, target, weight, fault = N.node_dist_targets_numpy(table, atoms, wmode)
+        obs, target, weight = (torch.from_numpy(np.ascontiguousarray(x)) for x in (obs.view(np.int32), target, weight))
+    else:
+        from . import _lib
+        rows = rows.to(on)
+        obs = torch.zeros(n, 12, dtype=torch.int32, device=on)
+        target = torch.zeros(n, atoms, dtype=torch.float32, device=on)
+        weight = torch.zeros(n, dtype=torch.float32, device=on)
+        fault = torch.zeros(1, dtype=torch.int32, device=on)
+        if n:
+            with torch.cuda.device(on):
+                _lib.check(_lib.lib().tm_node_dist_targets(_ptr(rows), n, atoms, wmode, _ptr(obs), _ptr(target), atoms, _ptr(weight),
+                                                           _ptr(fault), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                           "tm_node_dist_targets")
+        fault = int(fault.item())
+    if fault:
+        raise RuntimeError("node_dist_targets: a row's visit count is not finite or below 1, one of its %d atoms is not finite or "
+                           "negative, none of them is above 0, or a float beyond them is not 0 (a file recorded with more atoms): "
+                           "these are not rows a collection of this head harvested" % atoms)
+    return obs, target, weight
+
+
+def dist_node_training_set(paths, weighted=False, weighted_mode=1, last_nfiles=1, validation=False, val_set_size=0.05,
+                           val_set_size_max=-1, generator=None, device="cuda"):
+    """data = [observations int32 [n,12], targets [n,atoms], weights [n,1]] on `device`, the training rows first and the held-out
+    rows last - what Model_Dist.train_data(state_format="packed") splits - and a dict with n, n_val, n_train, validation_fraction
+    (train_data's int(n * fraction) is n_val exactly), the stems, the files and atoms, vmin, vmax from the stems' sidecars (which
+    must agree: ValueError).  paths / last_nfiles: choose_stems' rule over dist node shards.  The rows go to the device once; the
+    targets are the recorded distributions.  validation: node_training_set's random hold-out."""
+    from . import nodes as N
+    stems = choose_stems(paths, last_nfiles)
+    files = [f for s in stems for f in _parts(s)]
+    atoms, vmin, vmax = N.load_head(stems)
+    table = _concat([np.load(f) for f in files], N.NODE_DIST_DTYPE)
+    dev = torch.device(device)
+    obs, target, weight = node_dist_targets(table, atoms, weighted=weighted, weighted_mode=weighted_mode, device=dev)
+    n_all = obs.shape[0]
+    if n_all == 0:
+        raise RuntimeError("no rows to train on: the dist node shards of %s are empty" % (stems,))
+    sel, n_val = _split(None, torch.ones(n_all, dtype=torch.bool, device=dev), validation, 0, 0, val_set_size, val_set_size_max,
+                        generator, dev)
+    n = int(sel.shape[0])
+    data = [obs[sel].contiguous(), target[sel].contiguous(), weight[sel].reshape(n, 1)]
+    return data, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
+                      files=files, n_rows=n_all, atoms=atoms, vmin=vmin, vmax=vmax)
+
+
+def fit_dist_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
+                   early_stopping_patience=10, fit_backend="hip_dist", validation_backend="hip", **options):
+    """dist_node_training_set(paths, **options) on the model's device, then model.train_data(..., fit_backend="hip_dist",
+    state_format="packed") on it and, on rank 0, model.save(); returns what train_data returns plus n_train, n_val and the
+    sidecar's atoms, vmin, vmax.  model: a Model_Dist (TypeError otherwise) with the file's atoms (ValueError otherwise).
+    max_iters and iters_per_val may be functions, as in fit_episodes.  The packed observations are read by the HIP kernels
+    alone: fit_backend must be "hip_dist", and validation_backend "hip" unless nothing is held out (ValueError otherwise)."""
+    from .model_distributional import Model_Dist
+    if not isinstance(model, Model_Dist):
+        raise TypeError("fit_dist_nodes fits a Model_Dist: a dist node row holds a distribution, not a value and a variance (%s); "
+                        "the value net's harvest is fit_nodes'" % type(model).__name__)
+    if fit_backend != "hip_dist":
+        raise ValueError("fit_dist_nodes hands the fit packed observations, which only the head's HIP gradient step reads: it "
+                         "needs fit_backend='hip_dist', not %r" % (fit_backend,))
+    from . import nodes as N
+    stems = choose_stems(paths, options.get("last_nfiles", 1))
+    atoms = N.load_head(stems)[0]          # (before a row is read: the targets below are cut at the file's atoms)
+    if atoms != int(model.atoms):
+        raise ValueError("the shards of %s were recorded by a head of %d atoms, the model has %d" % (stems, atoms, int(model.atoms)))
+    data, info = dist_node_training_set(paths, device=model.device, **options)
+    if info["n_val"] and validation_backend != "hip":
+        raise ValueError("fit_dist_nodes holds %d rows out, and the torch validation does not read packed observations: it needs "
+                         "validation_backend='hip' (or no validation), not %r" % (info["n_val"], validation_backend))
+    iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
+    extra = {}
+    if iters_per_val is not None:
+        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    res = model.train_data(data, fit_backend="hip_dist", state_format="packed", shuffle=False, batch_size=batch_size, max_iters=iters,
+                           validation_fraction=info["validation_fraction"], early_stopping=early_stopping,
+                           early_stopping_patience=early_stopping_patience, validation_backend=validation_backend, **extra)
+    from . import dist as tdist
+    if tdist.rank() == 0:                  # replicas are identical: one checkpoint file, written by rank 0
+        model.save(verbose=False)
+    return dict(res, n_train=info["n_train"], n_val=info["n_val"], atoms=info["atoms"], vmin=info["vmin"], vmax=info["vmax"])

@@ -31,6 +31,12 @@ and its backup has no discount, so --td alone, --bootstrap recorded with --td an
 csrc/node_records.hip): the harvested tree nodes, the training set of the online fit.  A node has the search's value and
 variance and no return, so --nodes needs --td and takes no --td_lambda, --bootstrap net, --target_gamma, --val_mode 1, --head
 dist or --fit_backend torch; --weighted, --validation, --early_stopping, --last_nfiles and --ewc keep their meaning.
+
+--dist_nodes --data_paths D/distnodes* fits the distributional head to the dist node shards of `play.py --agent_type DistValueSim
+--save_dist_nodes` (offline.fit_dist_nodes): the target of a node is the distribution the search backed up into it, as recorded, so
+nothing is bootstrapped from the head's own predictions.  Atoms and range come from the shards' sidecar; an --atoms, --vmin or
+--vmax that says otherwise is refused.  It writes pytorch_model/model_checkpoint_dist.  It takes no --nodes, --td_lambda,
+--bootstrap net, --target_gamma, --val_mode 1, --ewc or --fit_backend torch, and --weighted only with --weighted_mode 1 (visits).
 """
 import argparse
 import sys
@@ -88,7 +94,41 @@ def build_parser():
     add('--nodes', default=False, action='store_true', help='[new] --data_paths are the node shards of play.py --save_nodes (the '
         'harvested tree nodes, e.g. data/self1/nodes*): fit the search\'s value and variance of every node from its packed '
         'observation; needs --td')
+    add('--dist_nodes', default=False, action='store_true', help='[new] --data_paths are the dist node shards of play.py '
+        '--agent_type DistValueSim --save_dist_nodes (e.g. data/self1/distnodes*): fit the distributional head to the recorded '
+        'distribution of every node from its packed observation; atoms and range come from the shards\' sidecar')
     return p
+
+
+def _given(argv, flag):
+    """whether the command line names `flag` itself (`--flag value` or `--flag=value`)"""
+    return any(a == flag or a.startswith(flag + '=') for a in argv)
+
+
+def check_dist_nodes(args, argv):
+    """the refusals of --dist_nodes that need no file"""
+    if args.nodes:
+        sys.exit('--dist_nodes together with --nodes: --nodes fits the value net to 64-byte node rows, --dist_nodes the '
+                 'distributional head to rows with a distribution; give one of the two')
+    if args.td_lambda is not None:
+        sys.exit('--dist_nodes takes no --td_lambda: a node table has no moves to trace along')
+    if args.bootstrap != 'recorded':
+        sys.exit('--dist_nodes takes no --bootstrap net: the target is the recorded distribution, nothing is bootstrapped')
+    if args.target_gamma != 1.0:
+        sys.exit('--dist_nodes takes no --target_gamma other than 1: the distributional backup does not discount')
+    if args.val_mode == 1:
+        sys.exit('--dist_nodes takes no --val_mode 1: a node table has no episodes (--val_mode 0 holds out random rows)')
+    if args.ewc:
+        sys.exit('--dist_nodes takes no --ewc: the Fisher pass exists for the value net only')
+    if args.fit_backend != 'hip':
+        sys.exit('--dist_nodes takes no --fit_backend torch: the packed observations are read by the HIP gradient step alone')
+    if args.validation and args.validation_backend not in (None, 'hip'):
+        sys.exit('--dist_nodes with --validation needs --validation_backend hip: the torch validation does not read packed '
+                 'observations')
+    if args.weighted and args.weighted_mode != 1:
+        sys.exit('--dist_nodes with --weighted needs --weighted_mode 1 (number of visits), not %d: a dist node row records no '
+                 'variance' % args.weighted_mode)
+    args.head_given = {k: getattr(args, k) for k in ('atoms', 'vmin', 'vmax') if _given(argv, '--' + k)}
 
 
 def check_nodes(args):
@@ -104,15 +144,18 @@ def check_nodes(args):
     if args.val_mode == 1:
         sys.exit('--nodes takes no --val_mode 1: a node table has no episodes (--val_mode 0 holds out random rows)')
     if args.head == 'dist':
-        sys.exit('--nodes takes no --head dist: a node row holds a value and a variance, not a distribution')
+        sys.exit('--nodes takes no --head dist: a node row holds a value and a variance, not a distribution (the distributional '
+                 'head\'s harvest, play.py --save_dist_nodes, is fitted with --dist_nodes)')
     if args.fit_backend != 'hip':
         sys.exit('--nodes takes no --fit_backend torch: the packed observations are read by the HIP gradient step alone')
     if args.validation and args.validation_backend not in (None, 'hip'):
         sys.exit('--nodes with --validation needs --validation_backend hip: the torch validation does not read packed observations')
 
 
-def check_args(args):
+def check_args(args, argv=()):
     """the refusals, before anything is imported or read"""
+    if args.dist_nodes:
+        check_dist_nodes(args, argv)
     if args.nodes:
         check_nodes(args)
     if args.ewc and args.head == 'dist':
@@ -133,9 +176,9 @@ def check_args(args):
     if args.td_lambda is not None and not args.td:
         sys.exit('--td_lambda is the trace of --td: it needs --td')
     if args.head == 'dist':
-        if args.td and args.td_lambda is None:
+        if args.td and args.td_lambda is None and not args.dist_nodes:
             sys.exit('--head dist with --td needs --td_lambda: the rows record no distribution to fit')
-        if args.td and args.bootstrap != 'net':
+        if args.td and args.bootstrap != 'net' and not args.dist_nodes:
             sys.exit('--head dist with --td needs --bootstrap net: the distributions inside the target are the head\'s own')
         if args.target_gamma != 1.0:
             sys.exit('--head dist takes no --target_gamma other than 1: the distributional backup does not discount')
@@ -208,9 +251,39 @@ def main_dist(args):
     model.save()
 
 
+def main_dist_nodes(args):
+    """--dist_nodes: the head of the shards' sidecar fitted to the recorded distributions (offline.fit_dist_nodes)"""
+    from tetris_mcts_amd.model_distributional import Model_Dist
+    from tetris_mcts_amd.nodes import load_head
+    from tetris_mcts_amd.offline import choose_stems, fit_dist_nodes
+    head = dict(zip(('atoms', 'vmin', 'vmax'), load_head(choose_stems(args.data_paths, args.last_nfiles))))
+    for k, v in args.head_given.items():
+        if v != head[k]:
+            sys.exit('--%s %s, but the shards were recorded by a head with %s %s (their sidecar, .head.npy): leave --%s out, '
+                     'or give the files of that head' % (k, v, k, head[k], k))
+    model = Model_Dist(atoms=head['atoms'], backend='hip')
+    if not args.new:
+        model.load()
+    plan = {}
+
+    def max_iters(n_train):
+        plan['iters'], plan['val'] = iterations(args, n_train)
+        return plan['iters']
+    res = fit_dist_nodes(model, args.data_paths, batch_size=args.batch_size, max_iters=max_iters, iters_per_val=lambda _: plan['val'],
+                         early_stopping=args.early_stopping, early_stopping_patience=args.early_stopping_patience,
+                         fit_backend='hip_dist', validation_backend=args.validation_backend, weighted=args.weighted,
+                         weighted_mode=args.weighted_mode, last_nfiles=args.last_nfiles, validation=args.validation,
+                         val_set_size=args.val_set_size, val_set_size_max=args.val_set_size_max)
+    print('iters:%d/%d' % (res['iters'], plan['iters'])
+          + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
+    model.save()
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    check_args(args)
+    check_args(args, sys.argv[1:] if argv is None else argv)
+    if args.dist_nodes:
+        return main_dist_nodes(args)
     if args.head == 'dist':
         return main_dist(args)
     from tetris_mcts_amd.model import Model_VV
