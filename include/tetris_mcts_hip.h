@@ -260,6 +260,13 @@ int tm_pool_init(const tm_store *s, void *stream);
 /* re-initialise the trees of the games with mask[g] != 0 (pool exhausted beyond what GC can reclaim; the reference has
  * undefined behaviour there, agent.cpp:227-231); clears TM_ERR_POOL; the caller re-roots with tm_update_root */
 int tm_pool_reset(const tm_store *s, const uint8_t *mask, void *stream);
+/* the trees of ALL games as tm_pool_init leaves them in a newly built (zero-filled) store: pools, tables, free lists, low-water
+ * marks, the whole control block (counters and error flags included), the rand() stream re-seeded (seed 1), replay_count, and
+ * trace, leaf, the evaluation slots, eval_list / eval_cnt / eval_served, obs_eval, the collector scratch and, for TM_KIND_DIST,
+ * node_dist / eval_dist.  NOT touched: env_game / env_line_stats, mt_state (the caller's Vanilla random states), replay_obs /
+ * replay_stat / replay_dist (unread beyond replay_count), the tables of constants.  Between two moves only; the caller re-roots
+ * with tm_update_root and tells its search handles (tm_search_fresh).  hipErrorInvalidValue for a store without its buffers. */
+int tm_pool_fresh(const tm_store *s, void *stream);
 /* host helper: fills host_table[n] = (float)norm_quantile((double)i) with this machine's libm */
 void tm_fill_norm_quantile(float *host_table, int n);
 void tm_fill_norm_quantile_f64(double *host_table, int n);      /* the same values in double (TM_KIND_DIST: nq_table_d) */
@@ -377,6 +384,33 @@ int tm_episode_init(int n_games, int first_id, int32_t *slot_state, int32_t *cou
 int tm_episode_record(const tm_store *env, const tm_store *tree, const float *stats, const int32_t *action, int cycle,
                       int32_t *slot_state, void *rows, void *stream);
 int tm_episode_advance(const tm_store *env, int cycle, int32_t *slot_state, int32_t *counters, void *done, int cap, void *stream);
+
+/* Position rows (episodes.hip): the game a State row was recorded from, so that the move can be searched again under other
+ * weights (reanalyse.py).  A position row, TM_POSITION_ROW_BYTES, little-endian:
+ *     0 episode i4 | 4 cycle i4 | 8 slot i4 | 12 move i4: the four values of the State row of that game and move |
+ *    16 game u4[16]: the packed game (ENGINE_SPEC.md section 2) as it stood when the row was recorded, before the action |
+ *    80 line_stats i4[4]
+ * tm_episode_record_positions, right after tm_episode_record and before tm_episode_advance, on the same env, slot_state and
+ * cycle, writes exactly G rows (rows: [G][96], 4-byte aligned) in slot order: for a game that has ended episode = -1 and every
+ * other byte 0, as its State row.  It reads slot_state and writes nothing but rows.
+ * tm_episode_rerecord: n <= G old State rows on the device, env the environment into which their positions were loaded (slot i =
+ * row i), tree the store searched from those roots and stats its tm_root_stats buffer -> n new State rows (rows: [n][368]).
+ * episode, cycle, slot, move and the action's dword (its pad bytes included) are the old row's; combo, lines, score, line_stats and
+ * board are recomputed from the loaded game by tm_episode_record's own rule; value, variance, child_stats and policy are
+ * tm_episode_record's from tree and stats.  THE GUARD: the recomputed columns must be the old row's bit for bit, and the loaded
+ * game must not have ended (such a game has no row).  fault: device int32 [2], set to (INT32_MAX, 0) by the caller; a row that
+ * fails does atomicMin(fault[0], 4 * row + group) with group the first of TM_REREC_* that differs, and atomicAdd(fault[1], 1);
+ * the caller then discards rows (they are written all the same).  Integer atomics only: the result does not depend on their order.
+ * Both enqueue one kernel on stream, allocate nothing and read nothing back.  hipErrorInvalidValue, nothing launched, for a NULL
+ * pointer, n_games < 1, n outside [0, G], a tree of another n_games, a misaligned buffer: checked before the first HIP call. */
+#define TM_POSITION_ROW_BYTES 96
+#define TM_REREC_SCALARS 0     /* combo, lines, score */
+#define TM_REREC_LINE_STATS 1
+#define TM_REREC_BOARD 2
+#define TM_REREC_ENDED 3       /* the loaded game has ended */
+int tm_episode_record_positions(const tm_store *env, const int32_t *slot_state, int cycle, void *rows, void *stream);
+int tm_episode_rerecord(const tm_store *env, const tm_store *tree, const float *stats, const void *old_rows, int n, void *rows,
+                        int32_t *fault, void *stream);
 
 /* Training targets from recorded episodes (episode_targets.hip; the reference's train.py:81-131).  rows: n_rows State rows on the
  * device in ANY order (file order - move-major, slot-minor - is the normal case; they are read in place, 4-byte aligned).
@@ -625,6 +659,10 @@ int tm_search_set_valuenet(tm_search *h, int backend, int fc1);
  * under other weights (tm_search_set_epoch) run without.  tm_search_stats: out[2], the catch-up launches, counts the launches
  * the deferred games needed as well, out[11] the moves that ran under a cap. */
 int tm_search_set_request_cap(tm_search *h, int cap);
+/* after tm_pool_fresh on the handle's store: the handle forgets what it keeps from the moves before (its sub-batches' list
+ * parity and cap rotation, the request counts the automatic cap decides from), as a handle just created; the epoch, the value
+ * net's mode, the request cap's mode and the counters of tm_search_stats stay.  A host call, no HIP call. */
+int tm_search_fresh(tm_search *h);
 #define TM_REQUEST_CAP_T 1.32   /* 1 + (cost of the value net's second round) / (cost of a full step): DESIGN.md section 3.6 */
 #define TM_REQUEST_CAP_LOW 0.95 /* below this many times cap no launch of the next move reaches the cap, and the capped tree kernel
                                    costs a microsecond a launch over the other one: DESIGN.md section 3.6 */

@@ -3,7 +3,8 @@
 on the MI355X engine.  `python play.py --agent_type ValueSimLP --mcts_sims 500 --ngames 10` behaves like the
 reference (same per-game log lines, play.py:25-37,164); `--n_games N` plays N games concurrently on the GPU
 (new, optional).  `--save` writes the reference's self-play rows (util/Data.py State), recorded on the device, as numbered
-.npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5).  `--save_nodes` writes the tree nodes the
+.npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5); `--save_positions` adds the packed game of every
+row, which reanalyse.py searches again under other weights.  `--save_nodes` writes the tree nodes the
 collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`; `--save_dist_nodes` does so for
 DistValueSim, whose harvest carries a distribution per node (`train.py --dist_nodes`).  `--games_out` / `--games_in` carry the
 games of the batch from one run to the next (tetris_mcts_amd/games.py).  --save_tree, --gui and --interactive belong to
@@ -97,6 +98,9 @@ def build_parser():
     add('--games_in', default=None, type=str, help='[new] go on with the games of this file (written by --games_out with the same '
         '--n_games, --app, --tetris_scoring and --tetris_randomizer) instead of new ones; every game is checked on the device before '
         'any is loaded; --seed does not touch loaded games, each carries its seed; trees are not carried, the agent builds new roots')
+    add('--save_positions', default=False, action='store_true', help='[new] with --save: beside every row also write the packed game '
+        'it was recorded from, as <save_dir>positions<cycle> (tetris_mcts_amd/episodes.py POSITION_DTYPE): what reanalyse.py '
+        'searches again under other weights')
     add('--games_every', default=0, type=games_every_moves, help='[new] with --games_out: also write the file every this many moves (0: only at '
         'the end)')
     return p
@@ -189,6 +193,8 @@ def main(argv=None):
     if args.save and not args.agent_type:
         sys.exit('--save records what an agent plays (its root statistics, value and policy beside the board): it needs '
                  '--agent_type (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
+    if args.save_positions and not args.save:
+        sys.exit('--save_positions writes the game beside every row that --save writes: it needs --save')
     check_save_dist_nodes(args)
     check_save_nodes(args)
     check_games(args)
@@ -259,6 +265,8 @@ def main(argv=None):
     if args.save:
         from tetris_mcts_amd.episodes import EpisodeRecorder
         rec = EpisodeRecorder(args.save_dir, args.save_file, args.cycle, G)
+        if args.save_positions:
+            rec.record_positions()
         if args.games_in is not None:
             rec.resume(slot_moves)
     node_rec = None

@@ -34,6 +34,7 @@ class TmStore(C.Structure):
 SYMBOLS = {
     "tm_pool_init": [C.POINTER(TmStore), vp],
     "tm_pool_reset": [C.POINTER(TmStore), vp, vp],
+    "tm_pool_fresh": [C.POINTER(TmStore), vp],
     "tm_env_init": [C.POINTER(TmStore), vp, vp],
     "tm_env_step": [C.POINTER(TmStore), vp, vp],
     "tm_env_reset": [C.POINTER(TmStore), vp, vp],
@@ -57,6 +58,8 @@ SYMBOLS = {
     "tm_episode_init": [i32, i32, vp, vp, vp],
     "tm_episode_record": [C.POINTER(TmStore), C.POINTER(TmStore), vp, vp, i32, vp, vp, vp],
     "tm_episode_advance": [C.POINTER(TmStore), i32, vp, vp, vp, i32, vp],
+    "tm_episode_record_positions": [C.POINTER(TmStore), vp, i32, vp, vp],
+    "tm_episode_rerecord": [C.POINTER(TmStore), C.POINTER(TmStore), vp, vp, i32, vp, vp, vp],
     "tm_episode_targets": [vp, i32, vp, vp, i32, vp, vp, vp, i32, f64, i32, C.c_float, vp, vp, vp, vp, vp],
     "tm_episode_targets_discounted": [vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, f64, f64, i32, C.c_float, vp, vp, vp, vp, vp],
     "tm_episode_gather_states": [vp, i32, vp, i32, vp, vp, vp],
@@ -116,6 +119,7 @@ SYMBOLS = {
     "tm_search_set_epoch": [vp, i32],
     "tm_search_set_valuenet": [vp, i32, i32],
     "tm_search_set_request_cap": [vp, i32],
+    "tm_search_fresh": [vp],
     "tm_valuenet_resident_states": [],
     "tm_fused_tile_rows": [i32, i32],
     "tm_valuenet_forward_requests_grid": [vp, vp, i32, i32, C.POINTER(TmStore), vp, vp, i32],

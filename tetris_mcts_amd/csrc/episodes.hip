@@ -11,6 +11,10 @@
 // k_episode_advance: ONE workgroup walks the slots in chunks of 256 in ascending order; a wave ballot and the waves' counts in
 // LDS give a finishing slot its rank among the slots that finish in this call.  The order is the loop's: no atomics, no
 // workgroup waits for another one.
+//
+// k_episode_record_positions writes, beside every State row, the packed game the row was made from (a position row), and
+// k_episode_rerecord makes State rows again from such positions after another search (reanalyse.py): both are described where
+// they stand.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/tetris_mcts_hip.h"
@@ -23,6 +27,9 @@ constexpr int EP_ROW_DW = TM_EPISODE_ROW_BYTES / 4, EP_DONE_DW = TM_EPISODE_DONE
 // dword offsets of the row's fields (include/tetris_mcts_hip.h, the table at tm_episode_record)
 constexpr int EP_LS = 7, EP_VALUE = 11, EP_STATS = 13, EP_POLICY = 34, EP_BOARD = 41, EP_ACTION = 91;
 static_assert(EP_ROW_DW == 92 && EP_DONE_DW == 10 && EP_BOARD + 50 == EP_ACTION, "the row of the header's table");
+// the position row (the table at tm_episode_record_positions)
+constexpr int POS_ROW_DW = TM_POSITION_ROW_BYTES / 4, POS_GAME = 4, POS_LS = POS_GAME + GAME_DW;
+static_assert(POS_ROW_DW == 24 && POS_LS + 4 == POS_ROW_DW, "the position row of the header's table");
 
 struct RecordArgs {
     const uint32_t* env_game;        // [G][16]
@@ -105,6 +112,84 @@ __global__ __launch_bounds__(EP_THREADS) void k_episode_record(RecordArgs A, con
     row[lane] = row_dword(A, g, lane, gm, s_key[wave], ss, st, act);
     if (lane < EP_ROW_DW - 64) row[64 + lane] = row_dword(A, g, 64 + lane, gm, s_key[wave], ss, st, act);
     if (lane == 0) ss[2] = 1;
+}
+
+// Position rows (TM_POSITION_ROW_BYTES): a thread per dword of the G x 24 the call writes, so a wave stores 256 contiguous bytes.
+// Dwords 0..3 the State row's identity, 4..19 the packed game, 20..23 its line statistics; an ended game: -1, then zeros.
+__global__ __launch_bounds__(EP_THREADS) void k_episode_record_positions(const uint32_t* __restrict__ env_game,
+                                                                         const int32_t* __restrict__ env_line_stats, int n_games,
+                                                                         int cycle, const int32_t* __restrict__ slot_state,
+                                                                         uint32_t* __restrict__ rows) {
+    const long long i = (long long)blockIdx.x * EP_THREADS + threadIdx.x;
+    if (i >= (long long)n_games * POS_ROW_DW) return;
+    const int g = (int)(i / POS_ROW_DW), d = (int)(i % POS_ROW_DW);
+    const uint32_t* gm = env_game + (size_t)g * GAME_DW;
+    uint32_t out;
+    if (((gm[11] >> 8) & 1u) != 0) out = d == 0 ? 0xFFFFFFFFu : 0u;
+    else if (d >= POS_LS) out = (uint32_t)env_line_stats[(size_t)g * 4 + d - POS_LS];
+    else if (d >= POS_GAME) out = gm[d - POS_GAME];
+    else if (d == 0) out = (uint32_t)slot_state[(size_t)g * EP_SLOT_DW];
+    else if (d == 1) out = (uint32_t)cycle;
+    else if (d == 2) out = (uint32_t)g;
+    else out = (uint32_t)slot_state[(size_t)g * EP_SLOT_DW + 1];
+    rows[i] = out;
+}
+
+// Re-recording (tm_episode_rerecord): k_episode_record's wave per row over the first n games of an environment into which the
+// rows' positions were loaded.  Dwords 0..3 and the action's dword are the old row's; every other dword is row_dword's, from the
+// loaded game, the searched tree and its statistics buffer.  The dwords row_dword takes from the game alone must be the old
+// row's: where they are not (or the loaded game has ended: such a game has no row) the row's first differing column group goes
+// into fault[0] by atomicMin as 4 x row + group, and fault[1] counts the row.
+__device__ __forceinline__ int guard_group(int d) {
+    if (d >= 4 && d < EP_LS) return TM_REREC_SCALARS;
+    if (d >= EP_LS && d < EP_VALUE) return TM_REREC_LINE_STATS;
+    if (d >= EP_BOARD && d < EP_ACTION) return TM_REREC_BOARD;
+    return -1;
+}
+
+__global__ __launch_bounds__(EP_THREADS) void k_episode_rerecord(RecordArgs A, const float* __restrict__ stats,
+                                                                 const uint32_t* __restrict__ old_rows, int n,
+                                                                 uint32_t* __restrict__ rows, int32_t* __restrict__ fault) {
+    __shared__ uint32_t s_gm[EP_WAVES][GAME_DW];
+    __shared__ uint32_t s_key[EP_WAVES][OBS_DW];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * EP_WAVES + wave;
+    const bool have = g < n;
+    if (have && lane < GAME_DW) {
+        uint32_t w = A.env_game[(size_t)g * GAME_DW + lane];
+        if (lane == 10 && ((w & 0xFFu) >= 7u || ((w >> 8) & 0xFFu) >= 4u)) w &= ~0xFFFFu;    // (as k_episode_record)
+        s_gm[wave][lane] = w;
+    }
+    __syncthreads();
+    if (have && lane == 0) pack_obs(s_gm[wave], s_key[wave]);
+    __syncthreads();
+    if (!have) return;
+    const uint32_t* gm = s_gm[wave];
+    const uint32_t* old = old_rows + (size_t)g * EP_ROW_DW;
+    uint32_t* row = rows + (size_t)g * EP_ROW_DW;
+    const float* st = stats + (size_t)g * 21;
+    const int32_t none[2] = {0, 0};       // (episode and move are the old row's: row_dword is not asked for them)
+    int group = ((gm[11] >> 8) & 1u) != 0 ? TM_REREC_ENDED : 4;       // this lane's first differing group, 4: none
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const int d = 64 * pass + lane;
+        if (d >= EP_ROW_DW) break;
+        const uint32_t was = old[d];
+        const bool copied = d < 4 || d == EP_ACTION;
+        const uint32_t now = copied ? was : row_dword(A, g, d, gm, s_key[wave], none, st, 0);
+        const int gg = guard_group(d);
+        if (gg >= 0 && now != was && gg < group) group = gg;
+        row[d] = now;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int other = __shfl_xor(group, o, 64);
+        group = other < group ? other : group;
+    }
+    if (lane == 0 && group < 4) {
+        atomicMin(&fault[0], 4 * g + group);
+        atomicAdd(&fault[1], 1);
+    }
 }
 
 __global__ __launch_bounds__(EP_THREADS) void k_episode_advance(const uint32_t* __restrict__ env_game,
@@ -190,6 +275,40 @@ int tm_episode_record(const tm_store* env, const tm_store* tree, const float* st
     A.cycle = cycle;
     hipLaunchKernelGGL(k_episode_record, dim3((A.n_games + EP_WAVES - 1) / EP_WAVES), dim3(EP_THREADS), 0, (hipStream_t)stream, A,
                        stats, action, slot_state, reinterpret_cast<uint32_t*>(rows));
+    return (int)hipGetLastError();
+}
+
+int tm_episode_record_positions(const tm_store* env, const int32_t* slot_state, int cycle, void* rows, void* stream) {
+    if (!env || !slot_state || !rows) return (int)hipErrorInvalidValue;
+    if (env->n_games < 1 || !env->env_game || !env->env_line_stats) return (int)hipErrorInvalidValue;
+    if ((reinterpret_cast<uintptr_t>(rows) & 3) != 0) return (int)hipErrorInvalidValue;
+    const long long dwords = (long long)env->n_games * POS_ROW_DW;
+    hipLaunchKernelGGL(k_episode_record_positions, dim3((unsigned)((dwords + EP_THREADS - 1) / EP_THREADS)), dim3(EP_THREADS), 0,
+                       (hipStream_t)stream, (const uint32_t*)env->env_game, (const int32_t*)env->env_line_stats, env->n_games, cycle,
+                       slot_state, reinterpret_cast<uint32_t*>(rows));
+    return (int)hipGetLastError();
+}
+
+int tm_episode_rerecord(const tm_store* env, const tm_store* tree, const float* stats, const void* old_rows, int n, void* rows,
+                        int32_t* fault, void* stream) {
+    if (!env || !tree || !stats || !old_rows || !rows || !fault) return (int)hipErrorInvalidValue;
+    if (env->n_games < 1 || !env->env_game || !env->env_line_stats || n < 0 || n > env->n_games) return (int)hipErrorInvalidValue;
+    if (tree->n_games != env->n_games || tree->max_nodes < 1 || !tree->gs || !tree->node_rec || !tree->obs_stat)
+        return (int)hipErrorInvalidValue;
+    if (((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(old_rows) | reinterpret_cast<uintptr_t>(fault)) & 3) != 0)
+        return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    RecordArgs A;
+    A.env_game = env->env_game;
+    A.env_line_stats = env->env_line_stats;
+    A.gs = tree->gs;
+    A.node_rec = tree->node_rec;
+    A.obs_stat = tree->obs_stat;
+    A.n_games = env->n_games;
+    A.max_nodes = tree->max_nodes;
+    A.cycle = 0;
+    hipLaunchKernelGGL(k_episode_rerecord, dim3((n + EP_WAVES - 1) / EP_WAVES), dim3(EP_THREADS), 0, (hipStream_t)stream, A, stats,
+                       reinterpret_cast<const uint32_t*>(old_rows), n, reinterpret_cast<uint32_t*>(rows), fault);
     return (int)hipGetLastError();
 }
 

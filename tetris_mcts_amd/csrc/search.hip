@@ -382,6 +382,18 @@ int tm_search_set_request_cap(tm_search* h, int cap) {
     return 0;
 }
 
+// After tm_pool_fresh: what the handle remembers of the moves before - the parity and the rotation its sub-batches' launches have
+// reached, the request counts the automatic cap decides from - goes back to what tm_search_create leaves.  The mode settings
+// (epoch, value net, request cap) and the counters of tm_search_stats stay.
+int tm_search_fresh(tm_search* h) {
+    if (!h) return (int)hipErrorInvalidValue;
+    h->full.eval_parity = 0;
+    for (auto& t : h->sub) { t.eval_parity = 0; t.eval_cap = 0; t.eval_rot = 0; }
+    h->prev_requests = -1.0;
+    h->posted_before = -1;
+    return 0;
+}
+
 // out[0..11] = runs, tree-kernel launches, catch-up launches, timed samples, sum of tree-kernel ms, sum of value-net ms,
 // sub-batches, collector-only launches, sum of the regular launch loops' ms (HIP events around sims x (value net, tree
 // kernel) of sub-batch 0's stream), simulations in those loops, simulation waves of the catch-up launches (each runs over the

@@ -3056,35 +3056,33 @@ __global__ void k_root_stats(tm_store S, float* stats, int32_t* action) {
     action[g] = (!cpp && first_nan >= 0) ? first_nan : best;
 }
 
+// one thread of a game: the control block, the low-water marks, the rand() stream and the harvest count of a new store
+__device__ __forceinline__ void pool_init_control(const tm_store& S, const GP& P, int g) {
+    const int N = S.max_nodes;
+    for (int i = 0; i < TM_GS_DW; ++i) P.gs()[i] = 0;
+    P.gs()[TM_GS_NFREE_NODE] = N - 1;
+    P.gs()[TM_GS_NFREE_OBS] = N - 1;
+    P.gs()[TM_GS_LOW_NODE] = N;
+    P.gs()[TM_GS_LOW_OBS] = N;
+    uint32_t r[32];
+    int pos;
+    srand_state(r, pos, 1u);   // the reference never calls srand(): glibc's default seed
+    for (int i = 0; i < 32; ++i) S.rng[(size_t)g * 32 + i] = r[i];
+    P.gs()[TM_GS_RNG_POS] = pos;
+    if (S.replay_count) S.replay_count[g] = 0;
+}
+
 __global__ void k_pool_init(tm_store S) {
     int g = blockIdx.x;
     GP P = game_ptrs(S, g);
     const int N = S.max_nodes;
     for (int i = threadIdx.x; i < N - 1; i += blockDim.x) { P.fnode()[i] = i + 1; P.fobs()[i] = i + 1; }
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < TM_GS_DW; ++i) P.gs()[i] = 0;
-        P.gs()[TM_GS_NFREE_NODE] = N - 1;
-        P.gs()[TM_GS_NFREE_OBS] = N - 1;
-        P.gs()[TM_GS_LOW_NODE] = N;
-        P.gs()[TM_GS_LOW_OBS] = N;
-        uint32_t r[32];
-        int pos;
-        srand_state(r, pos, 1u);   // the reference never calls srand(): glibc's default seed
-        for (int i = 0; i < 32; ++i) S.rng[(size_t)g * 32 + i] = r[i];
-        P.gs()[TM_GS_RNG_POS] = pos;
-        if (S.replay_count) S.replay_count[g] = 0;
-    }
+    if (threadIdx.x == 0) pool_init_control(S, P, g);
 }
 
-// Re-initialise the trees of the games selected by mask (pool exhausted beyond what GC can reclaim: the reference has
-// undefined behaviour there, agent.cpp:227-231).  Episode counter, rand() stream and statistics counters survive.
-__global__ void k_pool_reset(tm_store S, const uint8_t* mask) {
-    const int g = blockIdx.x;
-    if (!mask[g]) return;
-    GP P = game_ptrs(S, g);
+// one game's pools and tables zeroed and its free lists filled, by the threads t0, t0 + stride, ... of the game's workgroups
+__device__ __forceinline__ void pool_clear(const tm_store& S, const GP& P, size_t t0, size_t stride) {
     const int N = S.max_nodes;
-    // (a selected game's 40 MB are cleared by gridDim.y workgroups: one took 0.4 ms, a move's worth of 22 games under the trained net)
-    const size_t t0 = (size_t)blockIdx.y * blockDim.x + threadIdx.x, stride = (size_t)gridDim.y * blockDim.x;
     const uint4 z = make_uint4(0, 0, 0, 0);
     uint4* rec = reinterpret_cast<uint4*>(P.rec());
     for (size_t i = t0; i < (size_t)N * TM_REC_DW / 4; i += stride) rec[i] = z;
@@ -3098,6 +3096,18 @@ __global__ void k_pool_reset(tm_store S, const uint8_t* mask) {
     for (size_t i = t0; i < (size_t)N * OBS_DW / 4; i += stride) ok[i] = z;
     for (size_t i = t0; i < (size_t)S.table_cap; i += stride) { P.ntab()[i] = 0; P.otab()[i] = 0; }
     for (size_t i = t0; i < (size_t)N - 1; i += stride) { P.fnode()[i] = (int)i + 1; P.fobs()[i] = (int)i + 1; }
+}
+
+// Re-initialise the trees of the games selected by mask (pool exhausted beyond what GC can reclaim: the reference has
+// undefined behaviour there, agent.cpp:227-231).  Episode counter, rand() stream and statistics counters survive.
+__global__ void k_pool_reset(tm_store S, const uint8_t* mask) {
+    const int g = blockIdx.x;
+    if (!mask[g]) return;
+    GP P = game_ptrs(S, g);
+    const int N = S.max_nodes;
+    // (a selected game's 40 MB are cleared by gridDim.y workgroups: one took 0.4 ms, a move's worth of 22 games under the trained net)
+    const size_t t0 = (size_t)blockIdx.y * blockDim.x + threadIdx.x, stride = (size_t)gridDim.y * blockDim.x;
+    pool_clear(S, P, t0, stride);
     if (t0 == 0) {
         P.gs()[TM_GS_ROOT] = 0;
         P.gs()[TM_GS_NFREE_NODE] = N - 1;
@@ -3115,6 +3125,44 @@ __global__ void k_pool_reset(tm_store S, const uint8_t* mask) {
         P.gs()[TM_GS_SIM_STARTED] = P.gs()[TM_GS_SIM_TARGET];
         P.gs()[TM_GS_ERR] &= ~TM_ERR_POOL;
         P.gs()[TM_GS_N_POOL_RESET] += 1;
+    }
+}
+
+// The trees of ALL games as a newly built store has them (tm_pool_fresh): k_pool_reset's clear and k_pool_init's control block,
+// rand() stream and harvest count, and - what tm_pool_init leaves to the caller's zero fill - every per-game buffer a simulation,
+// the launch loop, the request lists or the per-observation evaluation cache reads.  gridDim.y workgroups a game, as k_pool_reset.
+__global__ void k_pool_fresh(tm_store S) {
+    const int g = blockIdx.x;
+    GP P = game_ptrs(S, g);
+    const size_t N = (size_t)S.max_nodes;
+    const size_t t0 = (size_t)blockIdx.y * blockDim.x + threadIdx.x, stride = (size_t)gridDim.y * blockDim.x;
+    pool_clear(S, P, t0, stride);
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    if (S.obs_eval) {
+        uint4* oe = reinterpret_cast<uint4*>(S.obs_eval + (size_t)g * N * 4);
+        for (size_t i = t0; i < N; i += stride) oe[i] = z;
+    }
+    if (S.kind == TM_KIND_DIST) {
+        uint4* nd = reinterpret_cast<uint4*>(S.node_dist + (size_t)g * N * TM_DIST_ROW);
+        for (size_t i = t0; i < N * TM_DIST_ROW / 4; i += stride) nd[i] = z;
+        for (size_t i = t0; i < (size_t)TM_DIST_ROW; i += stride) S.eval_dist[(size_t)g * TM_DIST_ROW + i] = 0.0f;
+    }
+    const size_t bm = ((N + 7) / 8 + 15) & ~(size_t)15;          // bytes of one bitmap (tm_store::gc_mark)
+    uint4* mk = reinterpret_cast<uint4*>(S.gc_mark + (size_t)g * 2 * bm);
+    for (size_t i = t0; i < 2 * bm / 16; i += stride) mk[i] = z;
+    for (size_t i = t0; i < N; i += stride) S.gc_queue[(size_t)g * N + i] = 0;
+    for (size_t i = t0; i < (size_t)TM_GC_PART_DW; i += stride) S.gc_part[(size_t)g * TM_GC_PART_DW + i] = 0;
+    for (size_t i = t0; i < (size_t)S.max_trace * 4; i += stride) P.trace()[i] = 0u;
+    for (size_t i = t0; i < (size_t)TM_LEAF_DW; i += stride) P.leaf()[i] = 0;
+    for (size_t i = t0; i < (size_t)S.eval_slots; i += stride) {
+        P.eval_obs()[i] = 0; P.eval_v()[i] = 0.0f; P.eval_var()[i] = 0.0f;
+        S.eval_list[((size_t)g * S.eval_slots + i) * 2] = 0; S.eval_list[((size_t)g * S.eval_slots + i) * 2 + 1] = 0;
+    }
+    if (t0 == 0) {
+        P.fnode()[N - 1] = 0; P.fobs()[N - 1] = 0;
+        S.eval_cnt[(size_t)g * 2] = 0; S.eval_cnt[(size_t)g * 2 + 1] = 0;
+        if (S.eval_served) S.eval_served[g] = 0;
+        pool_init_control(S, P, g);
     }
 }
 
@@ -3257,6 +3305,16 @@ int tm_pool_init(const tm_store* s, void* stream) {
 }
 int tm_pool_reset(const tm_store* s, const uint8_t* mask, void* stream) {
     hipLaunchKernelGGL(k_pool_reset, dim3(s->n_games, 16), dim3(256), 0, (hipStream_t)stream, *s, mask);
+    return TM_LAUNCH_CHECK();
+}
+int tm_pool_fresh(const tm_store* s, void* stream) {
+    if (!s || s->n_games < 1 || s->max_nodes < 2 || s->eval_slots < 1) return (int)hipErrorInvalidValue;
+    if (!s->node_rec || !s->node_child || !s->node_game || !s->obs_stat || !s->obs_key || !s->node_tab || !s->obs_tab ||
+        !s->free_node || !s->free_obs || !s->gs || !s->rng || !s->trace || !s->leaf || !s->eval_obs || !s->eval_v || !s->eval_var ||
+        !s->gc_mark || !s->gc_queue || !s->gc_part || !s->eval_list || !s->eval_cnt)
+        return (int)hipErrorInvalidValue;
+    if (s->kind == TM_KIND_DIST && (!s->node_dist || !s->eval_dist)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pool_fresh, dim3(s->n_games, 16), dim3(256), 0, (hipStream_t)stream, *s);
     return TM_LAUNCH_CHECK();
 }
 int tm_env_init(const tm_store* s, const uint32_t* seeds, void* stream) {

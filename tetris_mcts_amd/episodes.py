@@ -11,6 +11,12 @@ name; `.r<rank>` is appended under torch.distributed with more than one rank, an
     <stem>.part00000.npy, .part00001.npy, ...             STATE_DTYPE rows, move-major, slot-minor
     <stem>.episodes.part00000.npy, ...                    EPISODE_DTYPE rows: the episodes that ended, with their FINAL score
 Opening over existing parts continues their numbering and the episode ids (the reference's mode='a').
+
+After record_positions() (play.py --save_positions) the device writes, beside every State row, a POSITION row of 96 bytes
+(tm_episode_record_positions): the row's identity, the packed game the row was made from and its line statistics - what a later
+re-analysis (reanalyse.py) loads into an environment and searches again.  They go into
+    <dir>positions<rest>.part00000.npy, ...               POSITION_DTYPE rows; <rest>: the stem's file name after "data"
+(positions_stem), with the part number, the row count and the row order of the State shard the same flush wrote.
 """
 import ctypes as C
 import glob
@@ -20,6 +26,7 @@ import re
 import numpy as np
 
 ROW_BYTES, DONE_BYTES, SLOT_DW = 368, 40, 4       # TM_EPISODE_ROW_BYTES, TM_EPISODE_DONE_BYTES, TM_EPISODE_SLOT_DW
+POSITION_BYTES = 96                               # TM_POSITION_ROW_BYTES
 N_ACTIONS = 7
 
 # the reference's State columns (util/Data.py:14-26) plus slot and move; the order is the device row's, readers go by name
@@ -35,6 +42,13 @@ EPISODE_DTYPE = np.dtype({
     "formats": ["<i4", "<i4", "<i4", "<i4", "<i4", "<i4", ("<i4", (4,))],
     "offsets": [0, 4, 8, 12, 16, 20, 24],
     "itemsize": DONE_BYTES})
+# the game a State row was recorded from (include/tetris_mcts_hip.h, the table at tm_episode_record_positions)
+POSITION_DTYPE = np.dtype({
+    "names": ["episode", "cycle", "slot", "move", "game", "line_stats"],
+    "formats": ["<i4", "<i4", "<i4", "<i4", ("<u4", (16,)), ("<i4", (4,))],
+    "offsets": [0, 4, 8, 12, 16, 80],
+    "itemsize": POSITION_BYTES})
+IDENTITY = ("episode", "cycle", "slot", "move")
 
 _PART = re.compile(r"\.part(\d{5})\.npy$")
 
@@ -43,6 +57,21 @@ def _parts(stem, episodes=False):
     """the existing part files of a stem in the order of their numbers"""
     found = glob.glob(glob.escape(stem) + (".episodes" if episodes else "") + ".part[0-9][0-9][0-9][0-9][0-9].npy")
     return sorted(found, key=lambda f: int(_PART.search(f).group(1)))
+
+
+def positions_stem(stem):
+    """The stem of the position shards that go with the State shards of `stem`: "positions" in place of a file name's leading
+    "data" (D/data3.r1 -> D/positions3.r1), "positions." before any other file name - never a name that `D/data*` matches."""
+    d, base = os.path.split(str(stem))
+    return os.path.join(d, "positions" + base[4:] if base.startswith("data") else "positions." + base)
+
+
+def positions_file(state_file):
+    """the position shard of a State shard: the same part of positions_stem"""
+    m = _PART.search(str(state_file))
+    if not m:
+        raise ValueError("%s is not a part of a stem" % state_file)
+    return positions_stem(str(state_file)[:m.start()]) + m.group(0)
 
 
 class ShardWriter:
@@ -67,16 +96,26 @@ class ShardWriter:
                 ids.append(int(last["episode"].max()))
         self.next_id = 1 + max(ids, default=-1)
 
-    def write(self, rows, episodes, n_done, cap):
+    def write(self, rows, episodes, n_done, cap, positions=None):
+        """positions: None, or the flush's POSITION_DTYPE rows, one per row of `rows` in the same order: the rows the State rows'
+        mask keeps are written as the same part of positions_stem(stem) (returned as a third name)"""
         n_done = int(n_done)
         if n_done > int(cap) or n_done > len(episodes):
             raise RuntimeError("episode log overflow: %d episodes ended since the last flush, the buffer holds %d - their rows "
                                "are lost; flush more often (ring_moves)" % (n_done, min(int(cap), len(episodes))))
+        if positions is not None and len(positions) != len(rows):
+            raise ValueError("%d position rows for %d State rows" % (len(positions), len(rows)))
+        keep = rows["episode"] != -1
+        if positions is not None:
+            positions = np.ascontiguousarray(positions).view(np.uint8).reshape(len(rows), POSITION_BYTES)[keep].view(POSITION_DTYPE).reshape(-1)
         # (whole rows as bytes: the pad bytes stay what the device wrote)
-        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(len(rows), ROW_BYTES)[rows["episode"] != -1].view(STATE_DTYPE).reshape(-1)
+        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(len(rows), ROW_BYTES)[keep].view(STATE_DTYPE).reshape(-1)
         names = ("%s.part%05d.npy" % (self.stem, self.part), "%s.episodes.part%05d.npy" % (self.stem, self.part))
         np.save(names[0], rows)
         np.save(names[1], np.ascontiguousarray(episodes[:n_done]))
+        if positions is not None:
+            names += ("%s.part%05d.npy" % (positions_stem(self.stem), self.part),)
+            np.save(names[2], positions)
         self.part += 1
         return names
 
@@ -116,11 +155,24 @@ class EpisodeRecorder:
         self._off_done = self.cap * ROW_BYTES
         self._off_cnt = self._off_done + self.cap * DONE_BYTES
         self._host = [torch.zeros(self._off_cnt + 8, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.positions = False               # record_positions()
         self._pending = [None, None]         # per pinned buffer: (event, moves held)
         self._flushes, self._pos, self.closed = 0, 0, False
         self.files = []
         self._check(self.L.tm_episode_init(self.G, self.writer.next_id, self._p(self.slot_state), self._p(self.counters),
                                            self._stream()), "tm_episode_init")
+
+    def record_positions(self):
+        """Also write a position row beside every State row (play.py --save_positions): call once, before the first add().  A
+        ring of ring_moves x G x 96 bytes beside the State ring and a pair of pinned buffers of its own, copied by the same
+        flush and waited for by the same event."""
+        if self._pos or self._flushes or self.closed:
+            raise RuntimeError("EpisodeRecorder.record_positions comes before the first add()")
+        if not self.positions:
+            torch = self.torch
+            self.pos_ring = torch.zeros(self.cap * POSITION_BYTES, dtype=torch.uint8, device=self.device)
+            self._host_pos = [torch.zeros(self.cap * POSITION_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self.positions = True
 
     def resume(self, move_idx):
         """Games that go on from an earlier run (games.py): call once, before the first add(), with the moves played so far in
@@ -164,6 +216,10 @@ class EpisodeRecorder:
         self._check(self.L.tm_episode_record(C.byref(game.s), C.byref(store.s), self._p(store.stats_buf), self._p(act), self.cycle,
                                              self._p(self.slot_state), self._p(self.ring, self._pos * self.G * ROW_BYTES),
                                              self._stream()), "tm_episode_record")
+        if self.positions:
+            self._check(self.L.tm_episode_record_positions(C.byref(game.s), self._p(self.slot_state), self.cycle,
+                                                           self._p(self.pos_ring, self._pos * self.G * POSITION_BYTES),
+                                                           self._stream()), "tm_episode_record_positions")
         self._pos += 1
 
     def advance(self, game):
@@ -180,6 +236,9 @@ class EpisodeRecorder:
         host[:n].copy_(self.ring[:n], non_blocking=True)
         host[self._off_done:self._off_cnt].copy_(self.done, non_blocking=True)
         host[self._off_cnt:].copy_(self.counters.view(self.torch.uint8), non_blocking=True)
+        if self.positions:
+            m = self._pos * self.G * POSITION_BYTES
+            self._host_pos[k][:m].copy_(self.pos_ring[:m], non_blocking=True)
         self.counters[1:].zero_()            # the done buffer starts over (stream-ordered, after the copy)
         ev = self.torch.cuda.Event()
         ev.record()
@@ -197,7 +256,11 @@ class EpisodeRecorder:
         rows = buf[:moves * self.G * ROW_BYTES].view(STATE_DTYPE)
         episodes = buf[self._off_done:self._off_cnt].view(EPISODE_DTYPE)
         n_done = int(buf[self._off_cnt:].view(np.int32)[1])
-        self.files.append(self.writer.write(rows, episodes, n_done, self.cap))
+        positions = self._host_pos[k].numpy()[:moves * self.G * POSITION_BYTES].view(POSITION_DTYPE) if self.positions else None
+        if positions is None:
+            self.files.append(self.writer.write(rows, episodes, n_done, self.cap))
+        else:
+            self.files.append(self.writer.write(rows, episodes, n_done, self.cap, positions))
 
     def close(self):
         """flush the partial ring and write every copy that is still held"""
@@ -271,3 +334,40 @@ class EpisodeLoader:
 
     def getCombo(self, index):
         return self.combo[self.bound_index(index)]
+
+
+class PositionLoader:
+    """State shards and the position shards recorded beside them, paired part by part in the order of the files.
+    stems_or_files: State shards or stems, as EpisodeLoader takes them.  `.files` / `.position_files` the pairs, `.rows`
+    (STATE_DTYPE) and `.positions` (POSITION_DTYPE) the tables, row i of one with row i of the other, `.counts` the rows per file.
+    ValueError, naming the file and the row, for a position shard that is missing or of another length and for a row whose
+    identity (episode, cycle, slot, move) differs."""
+
+    def __init__(self, stems_or_files):
+        self.files = _expand(stems_or_files)
+        self.position_files = [positions_file(f) for f in self.files]
+        rows, positions = [], []
+        for f, pf in zip(self.files, self.position_files):
+            if not os.path.isfile(pf):
+                raise ValueError("%s: there is no position shard %s beside it (record with play.py --save --save_positions)" % (f, pf))
+            r, p = np.load(f), np.load(pf)
+            if r.dtype != STATE_DTYPE:
+                raise ValueError("a shard of another layout: %s: %s" % (f, r.dtype))
+            if p.dtype != POSITION_DTYPE:
+                raise ValueError("a position shard of another layout: %s: %s" % (pf, p.dtype))
+            if len(p) != len(r):
+                raise ValueError("%s holds %d rows, %s holds %d: row %d has no %s" % (
+                    pf, len(p), f, len(r), min(len(p), len(r)), "position" if len(p) < len(r) else "State row"))
+            bad = np.zeros(len(r), bool)
+            for c in IDENTITY:
+                bad |= r[c] != p[c]
+            if bad.any():
+                i = int(np.nonzero(bad)[0][0])
+                raise ValueError("%s: row %d is (episode, cycle, slot, move) = %s, row %d of %s is %s: the two files do not belong "
+                                 "together" % (pf, i, tuple(int(p[c][i]) for c in IDENTITY), i, f, tuple(int(r[c][i]) for c in IDENTITY)))
+            rows.append(r)
+            positions.append(p)
+        self.counts = [len(r) for r in rows]
+        self.rows = _concat(rows, STATE_DTYPE)
+        self.positions = _concat(positions, POSITION_DTYPE)
+        self.length = len(self.rows)

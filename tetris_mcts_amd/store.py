@@ -293,6 +293,15 @@ class TreeStore:
         m = mask.to(torch.uint8).contiguous()
         _lib.check(self.L.tm_pool_reset(C.byref(self.s), _p(m), _stream()), "tm_pool_reset")
 
+    def pool_fresh(self):
+        """The trees of ALL games as a newly built store has them (tm_pool_fresh): cleared pools, tables and control blocks, the
+        rand() streams re-seeded, the harvest counts cleared - and the search handles and the request list's parity as a new
+        agent's.  Between two moves; the caller re-roots (agent.update_root)."""
+        _lib.check(self.L.tm_pool_fresh(C.byref(self.s), _stream()), "tm_pool_fresh")
+        self.s.eval_parity = 0
+        for h in self._search.values():
+            _lib.check(self.L.tm_search_fresh(h), "tm_search_fresh")
+
     def errors(self):
         return self.t["gs"][:, GS["ERR"]]
 
