@@ -412,6 +412,26 @@ int tm_episode_record_positions(const tm_store *env, const int32_t *slot_state, 
 int tm_episode_rerecord(const tm_store *env, const tm_store *tree, const float *stats, const void *old_rows, int n, void *rows,
                         int32_t *fault, void *stream);
 
+/* Root-distribution rows (episodes.hip): the distribution the search of a TM_KIND_DIST tree backed up into the root, beside the
+ * State row of that game and move - what the distributional head is fitted to (train.py --head dist --td --bootstrap search) and
+ * what a re-analysis of DistValueSim's moves makes again (reanalyse.py --root_dists).  A root-distribution row,
+ * TM_ROOT_DIST_ROW_BYTES, little-endian:
+ *     0 episode i4 | 4 cycle i4 | 8 slot i4 | 12 move i4: the four values of the State row of that game and move |
+ *    16 dist f4[TM_DIST_ROW]: node_dist[g][root][0 .. 63] with root = gs[g][TM_GS_ROOT] (DistValueSim.get_value's node): the atoms
+ *       b < dist_bins as their bits, never converted; the atoms b >= dist_bins written as 0
+ * tm_episode_record_root_dists, right after tm_episode_record or tm_episode_rerecord on the same tree: state_rows are the n State
+ * rows (stride TM_EPISODE_ROW_BYTES) that call has just written on the device for the slots 0 .. n-1 of tree, rows: [n][272].  The
+ * identity is copied from the State rows, so the two tables cannot drift apart and neither env nor slot_state is read; a State row
+ * with episode == -1 (a game that has ended) gives episode = -1 and every other byte 0, as its State and position rows.  A root
+ * index outside [0, max_nodes) is never made an address: the row's dist is zeros.
+ * It enqueues one kernel on stream (plain stores, no atomics), allocates nothing, synchronises with nothing, reads nothing back and
+ * writes nothing outside rows; n == 0 returns 0 and launches nothing.  hipErrorInvalidValue, nothing launched, for a NULL pointer,
+ * n < 0 or n > tree->n_games, a tree whose kind is not TM_KIND_DIST or whose node_dist / gs is NULL, max_nodes < 1, dist_bins
+ * outside 1 .. TM_DIST_ROW, a state_rows / rows that is not 4-byte aligned: checked before the first HIP call, so these answer on a
+ * machine without a GPU. */
+#define TM_ROOT_DIST_ROW_BYTES 272
+int tm_episode_record_root_dists(const tm_store *tree, const void *state_rows, int n, void *rows, void *stream);
+
 /* Training targets from recorded episodes (episode_targets.hip; the reference's train.py:81-131).  rows: n_rows State rows on the
  * device in ANY order (file order - move-major, slot-minor - is the normal case; they are read in place, 4-byte aligned).
  * order: int32 [n_rows]; seg: int32 [n_seg + 1]: segment e is the sorted positions seg[e] .. seg[e+1]-1, and rows[order[j]] over
@@ -481,7 +501,8 @@ int tm_episode_targets_discounted(const void *rows, int n_rows, const int32_t *o
  *       padding is never read), P of the tail = e_0.  Per atom in fp64 in ascending k (the weight by repeated multiplication; a
  *       term in gather form, out[b] = p[b-n] (1 - f) + p[b-n-1] f, the top atom = the fp64 sum p[K-1] + p[K-2] + .. down to atom
  *       max(K-1-n, 0), added in that order, + p[K-2-n] f), divided once and rounded to fp32 once.  lambda == 0 copies P_i.
- * There is no discount (the distributional backup has none) and no mode 2 (no distribution is recorded).
+ * There is no discount (the distributional backup has none) and no mode 2: with the root-distribution rows of
+ * tm_episode_record_root_dists as p_rows, mode 1 at lambda = 0 copies the recorded distribution, which is that mode.
  * Outputs by sorted position j: target[j * target_stride + b] for b < atoms ONLY, weight[j] by tm_episode_targets' four
  * weight_mode rules from the row's visits and variance.  *fault (a device int32 the caller cleared): bit 0 - an order[j] outside
  * [0, n_rows) (never made an address: a zero target row, weight 0, left out of its episode's series) or a seg entry outside

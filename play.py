@@ -4,7 +4,8 @@ on the MI355X engine.  `python play.py --agent_type ValueSimLP --mcts_sims 500 -
 reference (same per-game log lines, play.py:25-37,164); `--n_games N` plays N games concurrently on the GPU
 (new, optional).  `--save` writes the reference's self-play rows (util/Data.py State), recorded on the device, as numbered
 .npy shards (tetris_mcts_amd/episodes.py; the container is numpy's, not HDF5); `--save_positions` adds the packed game of every
-row, which reanalyse.py searches again under other weights.  `--save_nodes` writes the tree nodes the
+row, which reanalyse.py searches again under other weights; `--save_root_dists` adds, for DistValueSim, the distribution the search
+backed up into the root (what `train.py --head dist --td --bootstrap search` fits).  `--save_nodes` writes the tree nodes the
 collections harvest (tetris_mcts_amd/nodes.py), the training set of `train.py --nodes`; `--save_dist_nodes` does so for
 DistValueSim, whose harvest carries a distribution per node (`train.py --dist_nodes`).  `--games_out` / `--games_in` carry the
 games of the batch from one run to the next (tetris_mcts_amd/games.py).  --save_tree, --gui and --interactive belong to
@@ -101,6 +102,10 @@ def build_parser():
     add('--save_positions', default=False, action='store_true', help='[new] with --save: beside every row also write the packed game '
         'it was recorded from, as <save_dir>positions<cycle> (tetris_mcts_amd/episodes.py POSITION_DTYPE): what reanalyse.py '
         'searches again under other weights')
+    add('--save_root_dists', default=False, action='store_true', help='[new] DistValueSim with --save: beside every row also write '
+        'the distribution the search backed up into the root, as <save_dir>rootdist<cycle> with a sidecar of the head\'s atoms and '
+        'range (tetris_mcts_amd/episodes.py ROOT_DIST_DTYPE): what train.py --head dist --td --bootstrap search fits and '
+        'reanalyse.py --agent_type DistValueSim --root_dists makes again under other weights')
     add('--games_every', default=0, type=games_every_moves, help='[new] with --games_out: also write the file every this many moves (0: only at '
         'the end)')
     return p
@@ -168,6 +173,21 @@ def check_save_dist_nodes(args):
         sys.exit('--min_visit is at least 1 with --save_dist_nodes (a node without a visit has no distribution)')
 
 
+def check_save_root_dists(args):
+    """the refusals of --save_root_dists, before anything is imported"""
+    if not args.save_root_dists:
+        return
+    if not args.save:
+        sys.exit('--save_root_dists writes the root\'s distribution beside every row that --save writes: it needs --save')
+    if args.agent_type != 'DistValueSim':
+        sys.exit('--save_root_dists records the distribution a distributional search backs up into its root: it needs --agent_type '
+                 'DistValueSim, not %s (the trees of the other agents keep a value and a variance, which --save records already)'
+                 % args.agent_type)
+    if args.valuenet_backend == 'torch' and args.dense_requests:
+        sys.exit('--save_root_dists with --valuenet_backend torch --dense_requests has not been shown to work: record with the hip '
+                 'back ends or without --dense_requests')
+
+
 class Scoreboard:
     """Running min/max/mean/std of finished episodes, printed like the reference's ScoreTracker (play.py:25-37)."""
 
@@ -195,6 +215,7 @@ def main(argv=None):
                  '--agent_type (ValueSim, ValueSimLP, ValueSimC, Vanilla, VanillaC, DistValueSim)')
     if args.save_positions and not args.save:
         sys.exit('--save_positions writes the game beside every row that --save writes: it needs --save')
+    check_save_root_dists(args)
     check_save_dist_nodes(args)
     check_save_nodes(args)
     check_games(args)
@@ -267,6 +288,11 @@ def main(argv=None):
         rec = EpisodeRecorder(args.save_dir, args.save_file, args.cycle, G)
         if args.save_positions:
             rec.record_positions()
+        if args.save_root_dists:
+            try:
+                rec.record_root_dists(agent.atoms, *agent.vrange)
+            except ValueError as e:
+                sys.exit('--save_root_dists: %s' % e)
         if args.games_in is not None:
             rec.resume(slot_moves)
     node_rec = None

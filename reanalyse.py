@@ -11,8 +11,15 @@ and policy from the new search.  The .episodes tables are copied, so `train.py -
 reads a recording.  A re-analysed row is a function of its position, the agent kind, --mcts_sims, --max_nodes, the back end and the
 weights, not of the slot, the batch, --n_games or the order of the input (tetris_mcts_amd/reanalyse.py).
 
-ValueSim, ValueSimLP and ValueSimC on the hip back ends, one process.  Vanilla, VanillaC (no net) and DistValueSim (its rows record
-no distribution) are refused.
+    python reanalyse.py --data_paths D/data3 --out_dir R/ --agent_type DistValueSim --root_dists --mcts_sims 200
+
+does the same for the moves of `play.py --agent_type DistValueSim --save --save_positions --save_root_dists`: the root-distribution
+shards beside the data (D/rootdist3.partNNNNN.npy and their sidecar, which gives the agent its atoms and range) are paired with the
+rows, and R/rootdist3.partNNNNN.npy and the sidecar are written beside R/data3..., so that `train.py --head dist --td --bootstrap
+search --data_paths R/data*` reads the result as a recording.  The contract is claimed for the 368 + 272 bytes of such a row.
+
+ValueSim, ValueSimLP and ValueSimC, and DistValueSim with --root_dists, on the hip back ends, one process.  Vanilla and VanillaC (no
+net) are refused, and so is DistValueSim without --root_dists: a State row alone records no distribution.
 """
 import argparse
 import os
@@ -24,12 +31,15 @@ def build_parser():
     add = p.add_argument
     add('--data_paths', default=[], nargs='*', help='State shards, their stems or glob patterns (play.py --save --save_positions)')
     add('--out_dir', default=None, type=str, help='Directory of the re-analysed shards (not the input\'s)')
-    add('--agent_type', default=None, type=str, help='ValueSim, ValueSimLP or ValueSimC')
+    add('--agent_type', default=None, type=str, help='ValueSim, ValueSimLP or ValueSimC; DistValueSim with --root_dists')
+    add('--root_dists', default=False, action='store_true', help='DistValueSim: also read the root-distribution shards recorded '
+        'beside the data (play.py --save_root_dists) and write the re-analysed ones and their sidecar beside the output')
     add('--mcts_sims', default=50, type=int, help='Simulations per position')
     add('--n_games', default=4096, type=int, help='Positions searched at a time')
     add('--max_nodes', default=0, type=int, help='Nodes per tree (0: 8 x mcts_sims + 1024, more than a tree that starts empty '
         'can grow to)')
-    add('--valuenet_backend', default='hip', choices=('hip', 'hip_bf16x3'), help='Value net: fp32 matrix cores or split-precision bf16')
+    add('--valuenet_backend', default='hip', choices=('hip', 'hip_bf16x3'), help='Value net (DistValueSim: the distributional head): fp32 '
+        'matrix cores or split-precision bf16')
     add('--last_nfiles', default=0, type=int, help='Only the stems written last, as train.py counts them (0: all)')
     add('--app', default=1, type=int, help='Actions-per-drop of the recording')
     add('--tetris_randomizer', default=0, type=int, help='Queue randomizer of the recording')
@@ -45,10 +55,14 @@ def check(args):
     if args.agent_type in ('Vanilla', 'VanillaC'):
         sys.exit('re-analysis is not offered for %s: its leaves are rollouts, there is no net whose weights could have changed; '
                  'use ValueSim, ValueSimLP or ValueSimC' % args.agent_type)
-    if args.agent_type == 'DistValueSim':
-        sys.exit('re-analysis is not offered for DistValueSim: its rows record no distribution, so a re-searched row has nothing '
-                 'the distributional fit reads; use ValueSim, ValueSimLP or ValueSimC')
-    if args.agent_type not in AGENTS:
+    if args.agent_type == 'DistValueSim' and not args.root_dists:
+        sys.exit('re-analysis of DistValueSim needs --root_dists: a State row alone records no distribution, so a re-searched row '
+                 'would have nothing the distributional fit reads; record with play.py --save --save_positions --save_root_dists and '
+                 'give --root_dists, or use ValueSim, ValueSimLP or ValueSimC')
+    if args.root_dists and args.agent_type != 'DistValueSim':
+        sys.exit('--root_dists re-analyses the root distributions of a distributional search: it needs --agent_type DistValueSim, '
+                 'not %s (the trees of the other agents keep no distribution)' % args.agent_type)
+    if args.agent_type not in AGENTS + ('DistValueSim',):
         sys.exit('--agent_type is required: ValueSim, ValueSimLP or ValueSimC')
     if not args.data_paths:
         sys.exit('--data_paths is required: the State shards of play.py --save --save_positions, their stems or glob patterns')
@@ -60,7 +74,7 @@ def check(args):
     if ws.isdigit() and int(ws) > 1:
         sys.exit('re-analysis runs in one process: WORLD_SIZE is %s (shards of ranked stems are read as any other stem)' % ws)
     # the files the run would read, by the package's own rules (numpy alone is imported: no torch, no HIP library, no device)
-    from tetris_mcts_amd.episodes import positions_file
+    from tetris_mcts_amd.episodes import positions_file, rootdist_file, rootdist_stem
     from tetris_mcts_amd.reanalyse import choose_inputs
     files = choose_inputs(args.data_paths, args.last_nfiles)
     if not files:
@@ -73,6 +87,18 @@ def check(args):
         if not os.path.isfile(positions_file(f)):
             sys.exit('%s: there are no positions beside the data (no %s): record with play.py --save --save_positions'
                      % (f, positions_file(f)))
+    args.head = None
+    if args.root_dists:
+        from tetris_mcts_amd.episodes import _PART
+        from tetris_mcts_amd.nodes import load_head
+        for f in files:
+            if not os.path.isfile(rootdist_file(f)):
+                sys.exit('%s: there are no root distributions beside the data (no %s): record with play.py --agent_type DistValueSim '
+                         '--save --save_positions --save_root_dists' % (f, rootdist_file(f)))
+        try:
+            args.head = load_head(dict.fromkeys(rootdist_stem(_PART.sub('', f)) for f in files))
+        except ValueError as e:
+            sys.exit('--root_dists: %s' % e)
 
 
 def main(argv=None):
@@ -88,9 +114,12 @@ def main(argv=None):
     G = args.n_games
     game = Tetris(*env_args, seed=0, n_games=G)
     module = import_module('agents.' + args.agent_type)
+    extra = {}
+    if args.head is not None:              # the head that recorded the distributions: its atoms and range
+        extra = dict(atoms=args.head[0], vmin=args.head[1], vmax=args.head[2])
     agent = getattr(module, args.agent_type)(sims=args.mcts_sims, env=Tetris, env_args=env_args, online=False, n_games=G,
                                              max_nodes=args.max_nodes or default_max_nodes(args.mcts_sims),
-                                             valuenet_backend=args.valuenet_backend)
+                                             valuenet_backend=args.valuenet_backend, **extra)
     try:
         written = reanalyse_files(args.data_paths, args.out_dir, agent, game, last_nfiles=args.last_nfiles, log=lambda m: print(m, flush=True))
     except ValueError as e:

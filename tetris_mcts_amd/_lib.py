@@ -60,6 +60,7 @@ SYMBOLS = {
     "tm_episode_advance": [C.POINTER(TmStore), i32, vp, vp, vp, i32, vp],
     "tm_episode_record_positions": [C.POINTER(TmStore), vp, i32, vp, vp],
     "tm_episode_rerecord": [C.POINTER(TmStore), C.POINTER(TmStore), vp, vp, i32, vp, vp, vp],
+    "tm_episode_record_root_dists": [C.POINTER(TmStore), vp, i32, vp, vp],
     "tm_episode_targets": [vp, i32, vp, vp, i32, vp, vp, vp, i32, f64, i32, C.c_float, vp, vp, vp, vp, vp],
     "tm_episode_targets_discounted": [vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, f64, f64, i32, C.c_float, vp, vp, vp, vp, vp],
     "tm_episode_gather_states": [vp, i32, vp, i32, vp, vp, vp],

@@ -14,7 +14,8 @@
 //
 // k_episode_record_positions writes, beside every State row, the packed game the row was made from (a position row), and
 // k_episode_rerecord makes State rows again from such positions after another search (reanalyse.py): both are described where
-// they stand.
+// they stand.  k_episode_record_root_dists writes, beside the State rows of a TM_KIND_DIST tree, the root's backed-up distribution
+// (a root-distribution row): what the distributional head is fitted to.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/tetris_mcts_hip.h"
@@ -30,6 +31,9 @@ static_assert(EP_ROW_DW == 92 && EP_DONE_DW == 10 && EP_BOARD + 50 == EP_ACTION,
 // the position row (the table at tm_episode_record_positions)
 constexpr int POS_ROW_DW = TM_POSITION_ROW_BYTES / 4, POS_GAME = 4, POS_LS = POS_GAME + GAME_DW;
 static_assert(POS_ROW_DW == 24 && POS_LS + 4 == POS_ROW_DW, "the position row of the header's table");
+// the root-distribution row (the table at tm_episode_record_root_dists)
+constexpr int RD_ROW_DW = TM_ROOT_DIST_ROW_BYTES / 4, RD_DIST = 4;
+static_assert(RD_ROW_DW == 68 && RD_DIST + TM_DIST_ROW == RD_ROW_DW, "the root-distribution row of the header's table");
 
 struct RecordArgs {
     const uint32_t* env_game;        // [G][16]
@@ -132,6 +136,29 @@ __global__ __launch_bounds__(EP_THREADS) void k_episode_record_positions(const u
     else if (d == 1) out = (uint32_t)cycle;
     else if (d == 2) out = (uint32_t)g;
     else out = (uint32_t)slot_state[(size_t)g * EP_SLOT_DW + 1];
+    rows[i] = out;
+}
+
+// Root-distribution rows (TM_ROOT_DIST_ROW_BYTES): a thread per dword of the n x 68 the call writes, so a wave stores 256 contiguous
+// bytes (and, 68 being no multiple of 64, always parts of two rows).  Dwords 0..3 are the State row's identity, copied from the
+// row tm_episode_record / tm_episode_rerecord has just written for that slot; 4..67 the bits of node_dist[g][gs[ROOT]][0..63], atoms
+// at or beyond dist_bins as 0.  A State row with episode -1: -1, then zeros.  A root outside the pool: zeros for the distribution.
+__global__ __launch_bounds__(EP_THREADS) void k_episode_record_root_dists(const uint32_t* __restrict__ state_rows,
+                                                                          const int32_t* __restrict__ gs,
+                                                                          const uint32_t* __restrict__ node_dist, int n, int max_nodes,
+                                                                          int dist_bins, uint32_t* __restrict__ rows) {
+    const long long i = (long long)blockIdx.x * EP_THREADS + threadIdx.x;
+    if (i >= (long long)n * RD_ROW_DW) return;
+    const int g = (int)(i / RD_ROW_DW), d = (int)(i % RD_ROW_DW);
+    const uint32_t* st = state_rows + (size_t)g * EP_ROW_DW;
+    uint32_t out;
+    if (st[0] == 0xFFFFFFFFu) out = d == 0 ? 0xFFFFFFFFu : 0u;
+    else if (d < RD_DIST) out = st[d];
+    else if (d - RD_DIST >= dist_bins) out = 0u;
+    else {
+        const uint32_t root = (uint32_t)gs[(size_t)g * TM_GS_DW + TM_GS_ROOT];
+        out = root < (uint32_t)max_nodes ? node_dist[((size_t)g * max_nodes + root) * TM_DIST_ROW + d - RD_DIST] : 0u;
+    }
     rows[i] = out;
 }
 
@@ -309,6 +336,21 @@ int tm_episode_rerecord(const tm_store* env, const tm_store* tree, const float* 
     A.cycle = 0;
     hipLaunchKernelGGL(k_episode_rerecord, dim3((n + EP_WAVES - 1) / EP_WAVES), dim3(EP_THREADS), 0, (hipStream_t)stream, A, stats,
                        reinterpret_cast<const uint32_t*>(old_rows), n, reinterpret_cast<uint32_t*>(rows), fault);
+    return (int)hipGetLastError();
+}
+
+int tm_episode_record_root_dists(const tm_store* tree, const void* state_rows, int n, void* rows, void* stream) {
+    if (!tree || !state_rows || !rows) return (int)hipErrorInvalidValue;
+    if (tree->kind != TM_KIND_DIST || !tree->node_dist || !tree->gs) return (int)hipErrorInvalidValue;
+    if (n < 0 || n > tree->n_games || tree->max_nodes < 1 || tree->dist_bins < 1 || tree->dist_bins > TM_DIST_ROW)
+        return (int)hipErrorInvalidValue;
+    if (((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(state_rows)) & 3) != 0) return (int)hipErrorInvalidValue;
+    if (n == 0) return 0;
+    const long long dwords = (long long)n * RD_ROW_DW;
+    hipLaunchKernelGGL(k_episode_record_root_dists, dim3((unsigned)((dwords + EP_THREADS - 1) / EP_THREADS)), dim3(EP_THREADS), 0,
+                       (hipStream_t)stream, reinterpret_cast<const uint32_t*>(state_rows), (const int32_t*)tree->gs,
+                       reinterpret_cast<const uint32_t*>(tree->node_dist), n, tree->max_nodes, tree->dist_bins,
+                       reinterpret_cast<uint32_t*>(rows));
     return (int)hipGetLastError();
 }
 

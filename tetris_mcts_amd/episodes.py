@@ -17,6 +17,12 @@ After record_positions() (play.py --save_positions) the device writes, beside ev
 re-analysis (reanalyse.py) loads into an environment and searches again.  They go into
     <dir>positions<rest>.part00000.npy, ...               POSITION_DTYPE rows; <rest>: the stem's file name after "data"
 (positions_stem), with the part number, the row count and the row order of the State shard the same flush wrote.
+
+After record_root_dists() (play.py --agent_type DistValueSim --save_root_dists) the device also writes a ROOT-DISTRIBUTION row of
+272 bytes (tm_episode_record_root_dists): the row's identity and the 64 floats of the distribution the search backed up into the
+root - what the distributional head is fitted to (train.py --head dist --td --bootstrap search).  They go into
+    <dir>rootdist<rest>.part00000.npy, ...                ROOT_DIST_DTYPE rows, paired with the State shard as the positions are
+    <dir>rootdist<rest>.head.npy                          float64 [3] = atoms, vmin, vmax of the head (nodes.py's sidecar)
 """
 import ctypes as C
 import glob
@@ -27,6 +33,7 @@ import numpy as np
 
 ROW_BYTES, DONE_BYTES, SLOT_DW = 368, 40, 4       # TM_EPISODE_ROW_BYTES, TM_EPISODE_DONE_BYTES, TM_EPISODE_SLOT_DW
 POSITION_BYTES = 96                               # TM_POSITION_ROW_BYTES
+ROOT_DIST_BYTES, DIST_ROW = 272, 64               # TM_ROOT_DIST_ROW_BYTES, TM_DIST_ROW
 N_ACTIONS = 7
 
 # the reference's State columns (util/Data.py:14-26) plus slot and move; the order is the device row's, readers go by name
@@ -48,6 +55,12 @@ POSITION_DTYPE = np.dtype({
     "formats": ["<i4", "<i4", "<i4", "<i4", ("<u4", (16,)), ("<i4", (4,))],
     "offsets": [0, 4, 8, 12, 16, 80],
     "itemsize": POSITION_BYTES})
+# the distribution the search backed up into the root a State row was recorded at (the table at tm_episode_record_root_dists)
+ROOT_DIST_DTYPE = np.dtype({
+    "names": ["episode", "cycle", "slot", "move", "dist"],
+    "formats": ["<i4", "<i4", "<i4", "<i4", ("<f4", (DIST_ROW,))],
+    "offsets": [0, 4, 8, 12, 16],
+    "itemsize": ROOT_DIST_BYTES})
 IDENTITY = ("episode", "cycle", "slot", "move")
 
 _PART = re.compile(r"\.part(\d{5})\.npy$")
@@ -74,6 +87,45 @@ def positions_file(state_file):
     return positions_stem(str(state_file)[:m.start()]) + m.group(0)
 
 
+def rootdist_stem(stem):
+    """The stem of the root-distribution shards that go with the State shards of `stem`, by positions_stem's rule: "rootdist" in
+    place of a leading "data" (D/data3.r1 -> D/rootdist3.r1), "rootdist." before any other file name - never a name that
+    `D/data*`, `D/dist*` or `D/positions*` matches."""
+    d, base = os.path.split(str(stem))
+    return os.path.join(d, "rootdist" + base[4:] if base.startswith("data") else "rootdist." + base)
+
+
+def rootdist_file(state_file):
+    """the root-distribution shard of a State shard: the same part of rootdist_stem"""
+    m = _PART.search(str(state_file))
+    if not m:
+        raise ValueError("%s is not a part of a stem" % state_file)
+    return rootdist_stem(str(state_file)[:m.start()]) + m.group(0)
+
+
+def write_root_dist_head(stem, atoms, vmin, vmax):
+    """The sidecar of the root-distribution shards of the State stem `stem`, <rootdist_stem>.head.npy (float64 [3]: atoms, vmin,
+    vmax; nodes.py's): written if it is not there, a ValueError if one is there that says otherwise.  Returns its name."""
+    from .nodes import _head_array, head_file
+    head, name = _head_array(atoms, vmin, vmax), head_file(rootdist_stem(stem))
+    if os.path.exists(name):
+        have = np.load(name)
+        if have.dtype != np.float64 or have.shape != (3,) or have.tobytes() != head.tobytes():
+            raise ValueError("%s records a head of (atoms, vmin, vmax) = %s, this run's is %s: another head's distributions go to "
+                             "another stem (--save_dir or --cycle)" % (name, have.tolist(), head.tolist()))
+    else:
+        d = os.path.dirname(name)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        np.save(name, head)
+    return name
+
+
+def _keep_raw(table, keep, dtype):
+    """the rows `keep` of a table as whole rows of bytes: the pad bytes stay what the device wrote"""
+    return np.ascontiguousarray(table).view(np.uint8).reshape(len(table), dtype.itemsize)[keep].view(dtype).reshape(-1)
+
+
 class ShardWriter:
     """The host half of the recorder: numbered shards of a stem.  `write(rows, episodes, n_done, cap)` takes a flush as the
     device left it - STATE_DTYPE rows with episode == -1 where a game had ended, the `done` buffer of `cap` EPISODE_DTYPE rows
@@ -96,26 +148,33 @@ class ShardWriter:
                 ids.append(int(last["episode"].max()))
         self.next_id = 1 + max(ids, default=-1)
 
-    def write(self, rows, episodes, n_done, cap, positions=None):
+    def write(self, rows, episodes, n_done, cap, positions=None, root_dists=None):
         """positions: None, or the flush's POSITION_DTYPE rows, one per row of `rows` in the same order: the rows the State rows'
-        mask keeps are written as the same part of positions_stem(stem) (returned as a third name)"""
+        mask keeps are written as the same part of positions_stem(stem) (returned as a third name).  root_dists: None, or the
+        flush's ROOT_DIST_DTYPE rows in the same way: the same part of rootdist_stem(stem) (returned as the last name)."""
         n_done = int(n_done)
         if n_done > int(cap) or n_done > len(episodes):
             raise RuntimeError("episode log overflow: %d episodes ended since the last flush, the buffer holds %d - their rows "
                                "are lost; flush more often (ring_moves)" % (n_done, min(int(cap), len(episodes))))
         if positions is not None and len(positions) != len(rows):
             raise ValueError("%d position rows for %d State rows" % (len(positions), len(rows)))
-        keep = rows["episode"] != -1
+        if root_dists is not None and len(root_dists) != len(rows):
+            raise ValueError("%d root-distribution rows for %d State rows" % (len(root_dists), len(rows)))
+        keep = rows["episode"] != -1             # the one mask: what it drops is dropped from every table
         if positions is not None:
-            positions = np.ascontiguousarray(positions).view(np.uint8).reshape(len(rows), POSITION_BYTES)[keep].view(POSITION_DTYPE).reshape(-1)
-        # (whole rows as bytes: the pad bytes stay what the device wrote)
-        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(len(rows), ROW_BYTES)[keep].view(STATE_DTYPE).reshape(-1)
+            positions = _keep_raw(positions, keep, POSITION_DTYPE)
+        if root_dists is not None:
+            root_dists = _keep_raw(root_dists, keep, ROOT_DIST_DTYPE)
+        rows = _keep_raw(rows, keep, STATE_DTYPE)
         names = ("%s.part%05d.npy" % (self.stem, self.part), "%s.episodes.part%05d.npy" % (self.stem, self.part))
         np.save(names[0], rows)
         np.save(names[1], np.ascontiguousarray(episodes[:n_done]))
         if positions is not None:
             names += ("%s.part%05d.npy" % (positions_stem(self.stem), self.part),)
             np.save(names[2], positions)
+        if root_dists is not None:
+            names += ("%s.part%05d.npy" % (rootdist_stem(self.stem), self.part),)
+            np.save(names[-1], root_dists)
         self.part += 1
         return names
 
@@ -156,6 +215,7 @@ class EpisodeRecorder:
         self._off_cnt = self._off_done + self.cap * DONE_BYTES
         self._host = [torch.zeros(self._off_cnt + 8, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.positions = False               # record_positions()
+        self.root_dists = False              # record_root_dists()
         self._pending = [None, None]         # per pinned buffer: (event, moves held)
         self._flushes, self._pos, self.closed = 0, 0, False
         self.files = []
@@ -173,6 +233,20 @@ class EpisodeRecorder:
             self.pos_ring = torch.zeros(self.cap * POSITION_BYTES, dtype=torch.uint8, device=self.device)
             self._host_pos = [torch.zeros(self.cap * POSITION_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
             self.positions = True
+
+    def record_root_dists(self, atoms, vmin, vmax):
+        """Also write a root-distribution row beside every State row (play.py --save_root_dists; an agent whose store is
+        KIND_DIST): call once, before the first add(), with the head's atoms and range, which go into the stem's sidecar.  A
+        third ring of ring_moves x G x 272 bytes and a pair of pinned buffers of its own, copied by the same flush and waited for
+        by the same event."""
+        if self._pos or self._flushes or self.closed:
+            raise RuntimeError("EpisodeRecorder.record_root_dists comes before the first add()")
+        if not self.root_dists:
+            write_root_dist_head(self.writer.stem, atoms, vmin, vmax)
+            torch = self.torch
+            self.dist_ring = torch.zeros(self.cap * ROOT_DIST_BYTES, dtype=torch.uint8, device=self.device)
+            self._host_dist = [torch.zeros(self.cap * ROOT_DIST_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self.root_dists = True
 
     def resume(self, move_idx):
         """Games that go on from an earlier run (games.py): call once, before the first add(), with the moves played so far in
@@ -204,6 +278,11 @@ class EpisodeRecorder:
         torch = self.torch
         if store.n_games != self.G or game.n_games != self.G:
             raise ValueError("the recorder was made for %d games" % self.G)
+        if self.root_dists:
+            from .store import KIND_DIST
+            if store.s.kind != KIND_DIST or store.t.get("node_dist") is None:
+                raise TypeError("record_root_dists records the root's distribution of a distributional tree (DistValueSim): this "
+                                "agent's store is of kind %d and keeps none" % store.s.kind)
         if self._pos == self.ring_moves:
             self._flush()
         act = store.action_buf
@@ -220,6 +299,10 @@ class EpisodeRecorder:
             self._check(self.L.tm_episode_record_positions(C.byref(game.s), self._p(self.slot_state), self.cycle,
                                                            self._p(self.pos_ring, self._pos * self.G * POSITION_BYTES),
                                                            self._stream()), "tm_episode_record_positions")
+        if self.root_dists:
+            self._check(self.L.tm_episode_record_root_dists(C.byref(store.s), self._p(self.ring, self._pos * self.G * ROW_BYTES), self.G,
+                                                            self._p(self.dist_ring, self._pos * self.G * ROOT_DIST_BYTES),
+                                                            self._stream()), "tm_episode_record_root_dists")
         self._pos += 1
 
     def advance(self, game):
@@ -239,6 +322,9 @@ class EpisodeRecorder:
         if self.positions:
             m = self._pos * self.G * POSITION_BYTES
             self._host_pos[k][:m].copy_(self.pos_ring[:m], non_blocking=True)
+        if self.root_dists:
+            m = self._pos * self.G * ROOT_DIST_BYTES
+            self._host_dist[k][:m].copy_(self.dist_ring[:m], non_blocking=True)
         self.counters[1:].zero_()            # the done buffer starts over (stream-ordered, after the copy)
         ev = self.torch.cuda.Event()
         ev.record()
@@ -257,7 +343,10 @@ class EpisodeRecorder:
         episodes = buf[self._off_done:self._off_cnt].view(EPISODE_DTYPE)
         n_done = int(buf[self._off_cnt:].view(np.int32)[1])
         positions = self._host_pos[k].numpy()[:moves * self.G * POSITION_BYTES].view(POSITION_DTYPE) if self.positions else None
-        if positions is None:
+        if self.root_dists:
+            dists = self._host_dist[k].numpy()[:moves * self.G * ROOT_DIST_BYTES].view(ROOT_DIST_DTYPE)
+            self.files.append(self.writer.write(rows, episodes, n_done, self.cap, positions, dists))
+        elif positions is None:
             self.files.append(self.writer.write(rows, episodes, n_done, self.cap))
         else:
             self.files.append(self.writer.write(rows, episodes, n_done, self.cap, positions))
@@ -371,3 +460,89 @@ class PositionLoader:
         self.rows = _concat(rows, STATE_DTYPE)
         self.positions = _concat(positions, POSITION_DTYPE)
         self.length = len(self.rows)
+
+
+def _check_paired(f, r, of, o, what):
+    """ValueError, naming the file and the row, unless table `o` (of file `of`) has the rows of the State table `r` (of `f`)"""
+    if len(o) != len(r):
+        raise ValueError("%s holds %d rows, %s holds %d: row %d has no %s" % (
+            of, len(o), f, len(r), min(len(o), len(r)), what if len(o) < len(r) else "State row"))
+    bad = np.zeros(len(r), bool)
+    for c in IDENTITY:
+        bad |= r[c] != o[c]
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise ValueError("%s: row %d is (episode, cycle, slot, move) = %s, row %d of %s is %s: the two files do not belong "
+                         "together" % (of, i, tuple(int(o[c][i]) for c in IDENTITY), i, f, tuple(int(r[c][i]) for c in IDENTITY)))
+
+
+class RootDistLoader:
+    """State shards and the root-distribution shards recorded beside them (play.py --save_root_dists, reanalyse.py --root_dists),
+    paired part by part in the order of the files.  stems_or_files: State shards or stems, as EpisodeLoader takes them.  `.files` /
+    `.dist_files` the pairs, `.rows` (STATE_DTYPE) and `.dists` (ROOT_DIST_DTYPE) the tables, row i of one with row i of the other,
+    `.counts` the rows per file, `.atoms`, `.vmin`, `.vmax` the head of the stems' sidecars (which must agree).  positions: True -
+    the position shards are paired too (`.position_files`, `.positions`), as PositionLoader pairs them; None - where every State
+    shard has one; False - not.  ValueError, naming the file and the row, for a shard that is missing or of another length and for a
+    row whose identity (episode, cycle, slot, move) differs; for a stem without a sidecar and for sidecars that disagree."""
+
+    def __init__(self, stems_or_files, positions=None):
+        from .nodes import load_head
+        self.files = _expand(stems_or_files)
+        self.dist_files = [rootdist_file(f) for f in self.files]
+        pfiles = [positions_file(f) for f in self.files]
+        if positions is None:
+            positions = bool(self.files) and all(os.path.isfile(pf) for pf in pfiles)
+        self.position_files = pfiles if positions else None
+        rows, dists, poss = [], [], []
+        for f, df, pf in zip(self.files, self.dist_files, pfiles):
+            if not os.path.isfile(df):
+                raise ValueError("%s: there is no root-distribution shard %s beside it (record with play.py --agent_type DistValueSim "
+                                 "--save --save_root_dists)" % (f, df))
+            r, o = np.load(f), np.load(df)
+            if r.dtype != STATE_DTYPE:
+                raise ValueError("a shard of another layout: %s: %s" % (f, r.dtype))
+            if o.dtype != ROOT_DIST_DTYPE:
+                raise ValueError("a root-distribution shard of another layout: %s: %s" % (df, o.dtype))
+            _check_paired(f, r, df, o, "root distribution")
+            if positions:
+                if not os.path.isfile(pf):
+                    raise ValueError("%s: there is no position shard %s beside it (record with play.py --save --save_positions)" % (f, pf))
+                p = np.load(pf)
+                if p.dtype != POSITION_DTYPE:
+                    raise ValueError("a position shard of another layout: %s: %s" % (pf, p.dtype))
+                _check_paired(f, r, pf, p, "position")
+                poss.append(p)
+            rows.append(r)
+            dists.append(o)
+        self.counts = [len(r) for r in rows]
+        self.rows = _concat(rows, STATE_DTYPE)
+        self.dists = _concat(dists, ROOT_DIST_DTYPE)
+        if positions:
+            self.positions = _concat(poss, POSITION_DTYPE)
+        self.length = len(self.rows)
+        self.atoms, self.vmin, self.vmax = load_head(dict.fromkeys(rootdist_stem(_PART.sub("", f)) for f in self.files))
+
+
+def record_root_dists_numpy(state_rows, roots, node_dist, atoms):
+    """tm_episode_record_root_dists as a numpy statement: ROOT_DIST_DTYPE [n].  state_rows: STATE_DTYPE [n], the rows just written
+    for the slots 0 .. n-1; roots: int [>= n], gs[g][ROOT]; node_dist: float32 [G, max_nodes, 64]; atoms: the store's dist_bins.
+    The identity is the State row's; dist the BITS of node_dist[g, roots[g], :atoms], zeros from `atoms` on; a State row with
+    episode -1 gives -1 and zeros; a root outside [0, max_nodes) gives a dist of zeros."""
+    n, atoms = len(state_rows), int(atoms)
+    if not 1 <= atoms <= DIST_ROW:
+        raise ValueError("atoms: 1 .. 64, not %r" % (atoms,))
+    nd = np.ascontiguousarray(node_dist, dtype=np.float32).view(np.uint32)
+    if nd.ndim != 3 or nd.shape[2] != DIST_ROW or nd.shape[0] < n:
+        raise ValueError("node_dist: float32 [>= %d, max_nodes, 64], not %s" % (n, nd.shape))
+    out = np.zeros(n, ROOT_DIST_DTYPE)
+    bits = out["dist"].view(np.uint32)                         # (bits, not values: a NaN's payload stays)
+    roots = np.asarray(roots).reshape(-1)[:n].astype(np.int64)
+    for g in range(n):
+        if state_rows["episode"][g] == -1:
+            out["episode"][g] = -1
+            continue
+        for c in IDENTITY:
+            out[c][g] = state_rows[c][g]
+        if 0 <= roots[g] < nd.shape[1]:
+            bits[g, :atoms] = nd[g, roots[g], :atoms]
+    return out

@@ -522,8 +522,9 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
 # ended (terminal="final"), one tail element: its final score with all mass in atom 0, the search's v_dummy.
 #     mode 0  not --td                 target_i = S_{s_end - s_i}(e_0)                                       (Monte Carlo)
 #     mode 1  --td --td_lambda L       target_i = sum_{k<=m} L^k S_{s_{i+k} - s_i}(P_{i+k}) / sum_{k<=m} L^k,  m = min(horizon, what follows i)
-# P comes from `p_rows`, float32 [n_rows, >= K] by TABLE row: the head's own output (predict_rows_dist).  There is no mode 2 (no
-# distribution is recorded) and no discount (the distributional backup has none).  Two interpolating shifts composed are not the
+# P comes from `p_rows`, float32 [n_rows, >= K] by TABLE row: the head's own output (predict_rows_dist), or the root distributions
+# recorded beside the rows (recorded_root_dists: play.py --save_root_dists, reanalyse.py --root_dists).  There is no mode 2: at
+# lambda = 0 mode 1 copies p_rows, which for recorded distributions is the value net's mode 2.  There is no discount (the distributional backup has none).  Two interpolating shifts composed are not the
 # shift by the sum, so nothing is carried from one target to the next: every term is one exact shift over a bounded horizon.
 
 def dist_target_mode(td, lam):
@@ -728,11 +729,42 @@ def predict_rows_dist(model, rows, chunk=65536):
     return out
 
 
+def recorded_root_dists(stems, atoms, vmin, vmax, n_rows=None):
+    """float32 [n_rows, 64] by TABLE row (load_stems' order): the root distributions recorded beside the State shards of `stems`
+    (episodes.RootDistLoader pairs them row by row).  ValueError, before anything is computed from them, for a stem without
+    root-distribution shards or sidecar, a sidecar that is not (atoms, vmin, vmax) and a recorded atom that is not finite or is
+    negative."""
+    from .episodes import RootDistLoader, rootdist_stem
+    from .nodes import head_file
+    for s in stems:
+        if not _parts(rootdist_stem(s)):
+            raise ValueError("%s has no root-distribution shards (%s.partNNNNN.npy): bootstrap='search' fits what play.py --agent_type "
+                             "DistValueSim --save --save_root_dists or reanalyse.py --root_dists recorded" % (s, rootdist_stem(s)))
+    from .nodes import load_head
+    loaders = [RootDistLoader([s], positions=False) for s in stems]        # (stem by stem: the table's order is load_stems')
+    head, want = load_head([rootdist_stem(s) for s in stems]), (int(atoms), float(vmin), float(vmax))
+    if head != want:
+        raise ValueError("the root distributions of %s were recorded by a head of (atoms, vmin, vmax) = %s (%s), the model and the "
+                         "range given are %s" % (list(stems), head, head_file(rootdist_stem(stems[0])), want))
+    files = [f for L in loaders for f in L.dist_files]
+    counts = [c for L in loaders for c in L.counts]
+    d = np.concatenate([np.ascontiguousarray(L.dists["dist"], dtype=np.float32).reshape(L.length, 64) for L in loaders])
+    if n_rows is not None and len(d) != n_rows:
+        raise ValueError("%d root distributions for %d State rows" % (len(d), n_rows))
+    bad = ~(np.isfinite(d[:, :want[0]]) & (d[:, :want[0]] >= 0)).all(axis=1)
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        j = int(np.searchsorted(np.cumsum(counts), i, side="right"))
+        raise ValueError("%s: row %d holds an atom that is not finite or is negative: not a recorded distribution"
+                         % (files[j], i - int(sum(counts[:j]))))
+    return d
+
+
 def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
                       early_stopping_patience=10, fit_backend=None, validation_backend="torch", td=False, lam=None, horizon=64,
                       vmin=0.0, vmax=5000.0, rounds=1, on_round=None, weighted=False, weighted_mode=0, terminal="final",
                       censored="drop", last_nfiles=1, validation=False, val_mode=0, val_episodes=0, val_set_size=0.05,
-                      val_set_size_max=-1, generator=None, eps=EPS):
+                      val_set_size_max=-1, generator=None, eps=EPS, bootstrap="net"):
     """fit_episodes for the distributional head: the recorded episodes of `paths` (choose_stems) -> categorical targets over the
     model's atoms on [vmin, vmax) (episode_dist_targets on the model's device) -> Model_Dist.train_data -> the checkpoint
     (Model_Dist.save, after every round).  Returns what train_data returns plus `rounds`, as fit_episodes does.
@@ -742,6 +774,11 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
     included, are recomputed and written into the same data[1] tensor, as fit_episodes(bootstrap="net") does.  The split
     (training_set's), the boards and the weights are computed once.  A prediction that is not finite raises RuntimeError before a
     target is computed from it, and so does a set fault word.
+    bootstrap="search" (with td): the distributions inside the target are the ones the SEARCH backed up into the roots, recorded
+    beside the rows (recorded_root_dists; the `rootdist` shards beside the chosen stems), loaded once; nothing is predicted and
+    rounds must be 1.  lam=None then means lambda = 0: the target is the recorded distribution itself, bit for bit - the
+    counterpart of the value net's mode 2.  A stem without such shards, a sidecar that is not the model's atoms and [vmin, vmax),
+    and a recorded atom that is not finite or is negative are a ValueError before any target is computed.
     fit_backend: None - "hip_dist" on a GPU, "torch" on the host.  max_iters / iters_per_val may be functions, as in fit_episodes.
     on_round(r, data, p_rows), r = 0 .. rounds-1, is called before each round's train_data with the tensors in use (p_rows: None
     in mode 0)."""
@@ -749,10 +786,20 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
     if not isinstance(model, Model_Dist):
         raise TypeError("fit_episodes_dist fits a Model_Dist: the value net's episode targets are fit_episodes' (%s)"
                         % type(model).__name__)
+    if bootstrap not in ("net", "search"):
+        raise ValueError("bootstrap is 'net' (the head's own distributions) or 'search' (the recorded root distributions), not %r"
+                         % (bootstrap,))
+    if bootstrap == "search":
+        if not td:
+            raise ValueError("bootstrap='search' puts the recorded root distributions inside the td target: it needs td=True")
+        if lam is None:
+            lam = 0.0                          # the recorded distribution itself
     mode, lam_ = dist_target_mode(td, lam)
     rounds = int(rounds)
     if rounds < 1:
         raise ValueError("rounds: at least 1, not %r" % (rounds,))
+    if bootstrap == "search" and rounds > 1:
+        raise ValueError("%d rounds with bootstrap='search': recorded distributions do not change between them" % rounds)
     if mode == 0 and rounds > 1:
         raise ValueError("%d rounds without td: the Monte Carlo targets do not change between them" % rounds)
     dev = torch.device(model.device)
@@ -761,6 +808,9 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
         fit_backend = "hip_dist" if dev.type == "cuda" else "torch"
     stems = choose_stems(paths, last_nfiles)
     table, stem_rows, episodes, episode_stems = load_stems(stems)
+    recorded = None
+    if bootstrap == "search":
+        recorded = torch.from_numpy(recorded_root_dists(stems, model.atoms, vmin, vmax, len(table))).to(dev)
     rows = rows_tensor(table, dev)
     index = episode_index(rows, stem_rows, episodes, episode_stems)
     sel, n_val = _split(index, _kept(index, mode, censored, dev), validation, val_mode, val_episodes, val_set_size, val_set_size_max,
@@ -781,7 +831,9 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
     data, done = None, []
     for r in range(rounds):
         p_rows = None
-        if mode == 1:
+        if recorded is not None:
+            p_rows = recorded
+        elif mode == 1:
             model.training(False)
             p_rows = predict_rows_dist(model, rows)
             if not bool(torch.isfinite(p_rows[:, :model.atoms]).all().item()):

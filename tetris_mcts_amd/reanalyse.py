@@ -12,6 +12,11 @@ THE CONTRACT: a re-analysed row is a function of its position, the agent kind, t
 weights - not of the slot, the batch, the batch size or the order of the input: every game's tree, counters and rand() stream
 start as a new store's, and the hip value nets are a function of the state alone.
 
+DistValueSim (an agent whose store is KIND_DIST; reanalyse.py --agent_type DistValueSim --root_dists): the root-distribution rows
+recorded beside the State rows (episodes.ROOT_DIST_DTYPE, play.py --save_root_dists) are made again too - tm_episode_record_root_dists
+on the rows tm_episode_rerecord has just written - and the contract is claimed for all 368 + 272 bytes: the HIP head is a function
+of the state alone, and a dist tree that starts empty grows by the same seven nodes a simulation.
+
 `rerecord_numpy` is the numpy statement of tm_episode_rerecord's definitions: what the kernel is held to.
 """
 import ctypes as C
@@ -21,10 +26,11 @@ import shutil
 
 import numpy as np
 
-from .episodes import (_PART, IDENTITY, POSITION_DTYPE, ROW_BYTES, STATE_DTYPE, PositionLoader, _expand, _parts)
+from .episodes import (_PART, IDENTITY, POSITION_DTYPE, ROOT_DIST_BYTES, ROOT_DIST_DTYPE, ROW_BYTES, STATE_DTYPE, PositionLoader,
+                       RootDistLoader, _expand, _parts, rootdist_file, write_root_dist_head)
 from .games import PIECE_CELLS, describe_fault, unpack_fields
 
-AGENTS = ("ValueSim", "ValueSimLP", "ValueSimC")
+AGENTS = ("ValueSim", "ValueSimLP", "ValueSimC", "DistValueSim")
 GROUPS = ("combo, lines or score", "line_stats", "board", "the game of the position has ended")     # TM_REREC_*
 NO_FAULT = 0x7FFFFFFF
 
@@ -44,7 +50,7 @@ def choose_inputs(paths, last_nfiles=0):
     found = []
     for p in map(str, paths):
         found += sorted(glob.glob(p)) or [p]
-    found = [f for f in found if not os.path.basename(f).startswith("positions")]
+    found = [f for f in found if not os.path.basename(f).startswith(("positions", "rootdist"))]
     files = _expand(found)
     stems = list(dict.fromkeys(_PART.sub("", f) for f in files))
     if last_nfiles and last_nfiles > 0:
@@ -110,7 +116,9 @@ def _p(t, offset=0):
 class Reanalyser:
     """The device half for one agent and one environment of the same n_games: submit(rows, positions) loads, searches and
     re-records a batch of at most n_games rows and enqueues the copy of the new rows and of the guard's words to a pinned buffer;
-    collect() waits for that copy and returns the rows (ValueError if the guard fired).  One batch at a time: the load report and
+    collect() waits for that copy and returns the rows (ValueError if the guard fired).  An agent whose store is KIND_DIST
+    (`.dist`): the root-distribution rows are written after the State rows and copied before the same event, and collect()
+    returns (rows, dists).  One batch at a time: the load report and
     the search itself (tm_search_run reads its catch-up counts back) synchronise with the host anyway, so there is nothing a
     second buffer could overlap but the 368 bytes a row of the copy."""
 
@@ -135,6 +143,11 @@ class Reanalyser:
         self.fault = torch.zeros(2, dtype=torch.int32, device=dev)
         self._fault0 = torch.tensor([NO_FAULT, 0], dtype=torch.int32, device=dev)
         self._host = torch.zeros(G * ROW_BYTES + 8, dtype=torch.uint8).pin_memory()
+        from .store import KIND_DIST
+        self.dist = agent.store.s.kind == KIND_DIST
+        if self.dist:
+            self.d_new_dists = torch.zeros(G * ROOT_DIST_BYTES, dtype=torch.uint8, device=dev)
+            self._host_dists = torch.zeros(G * ROOT_DIST_BYTES, dtype=torch.uint8).pin_memory()
         self._pending = None               # (event, n, what) of the batch submitted and not yet collected
         # the games of the slots a short batch does not use: new ones, kept from the environment's first reset
         game.reset()
@@ -199,6 +212,10 @@ class Reanalyser:
         self.fault.copy_(self._fault0)
         self._check(self.L.tm_episode_rerecord(C.byref(game.s), C.byref(agent.store.s), _p(stats), _p(self.d_old), n,
                                                _p(self.d_new), _p(self.fault), self._stream()), "tm_episode_rerecord")
+        if self.dist:
+            self._check(self.L.tm_episode_record_root_dists(C.byref(agent.store.s), _p(self.d_new), n, _p(self.d_new_dists),
+                                                            self._stream()), "tm_episode_record_root_dists")
+            self._host_dists[:n * ROOT_DIST_BYTES].copy_(self.d_new_dists[:n * ROOT_DIST_BYTES], non_blocking=True)
         buf = self._host
         buf[:n * ROW_BYTES].copy_(self.d_new[:n * ROW_BYTES], non_blocking=True)
         buf[G * ROW_BYTES:].copy_(self.fault.view(torch.uint8), non_blocking=True)
@@ -216,28 +233,43 @@ class Reanalyser:
             raise ValueError("%s: %d of %d rows do not belong to their positions, nothing is written for it; the first is row %d, "
                              "which differs in %s (a position file of another recording, or an edited one)"
                              % (what, count, n, first >> 2, GROUPS[first & 3]))
-        return buf[:n * ROW_BYTES].copy().view(STATE_DTYPE)          # (copied as bytes: the pad bytes stay)
+        rows = buf[:n * ROW_BYTES].copy().view(STATE_DTYPE)          # (copied as bytes: the pad bytes stay)
+        if self.dist:
+            return rows, self._host_dists.numpy()[:n * ROOT_DIST_BYTES].copy().view(ROOT_DIST_DTYPE)
+        return rows
 
 
 def reanalyse_rows(agent, game, rows, positions):
     """The State rows `rows` (STATE_DTYPE [n]) searched again from `positions` (POSITION_DTYPE [n], row i with row i) by `agent`
-    (a ValueSim, ValueSimLP or ValueSimC on a hip back end, agent.sims simulations a position) in batches of game.n_games:
-    STATE_DTYPE [n] in the order given.  ValueError for a malformed game and for a row that is not its position's."""
+    (a ValueSim, ValueSimLP, ValueSimC or DistValueSim on a hip back end, agent.sims simulations a position) in batches of
+    game.n_games: STATE_DTYPE [n] in the order given; for an agent whose store is KIND_DIST (DistValueSim) the pair (rows, dists),
+    dists ROOT_DIST_DTYPE [n], row i with row i.  ValueError for a malformed game and for a row that is not its position's."""
     R = Reanalyser(agent, game)
-    G, out = game.n_games, []
+    G, out, dists = game.n_games, [], []
     for a in range(0, len(rows), G):
         R.submit(rows[a:a + G], positions[a:a + G], what="rows %d..%d" % (a, min(a + G, len(rows)) - 1))
-        out.append(R.collect())
+        got = R.collect()
+        if R.dist:
+            got, d = got
+            dists.append(d)
+        out.append(got)
     raw = [r.view(np.uint8).reshape(len(r), ROW_BYTES) for r in out] + [np.zeros((0, ROW_BYTES), np.uint8)]
-    return np.concatenate(raw).view(STATE_DTYPE).reshape(-1)
+    new = np.concatenate(raw).view(STATE_DTYPE).reshape(-1)
+    if not R.dist:
+        return new
+    raw = [d.view(np.uint8).reshape(len(d), ROOT_DIST_BYTES) for d in dists] + [np.zeros((0, ROOT_DIST_BYTES), np.uint8)]
+    return new, np.concatenate(raw).view(ROOT_DIST_DTYPE).reshape(-1)
 
 
 def reanalyse_files(paths, out_dir, agent, game, last_nfiles=0, log=None):
     """reanalyse.py's loop: the State shards of `paths` (choose_inputs) with the position shards beside them -> shards of the same
     names, row counts and row order in out_dir, and copies of their .episodes tables.  Batches of game.n_games positions in file
     order, whatever the files' boundaries; a shard is written as soon as its last row has come back.  Returns the files written.
-    ValueError, with nothing written for the batch at fault or after it, for what PositionLoader, the load check and the guard
-    refuse."""
+    An agent whose store is KIND_DIST (DistValueSim): the input must have root-distribution shards and their sidecar beside it,
+    recorded by a head of the agent's atoms and range (RootDistLoader), and the re-analysed ones - rootdist<rest>.partNNNNN.npy
+    and the sidecar - are written beside the State shards, each right after its State shard.
+    ValueError, with nothing written of either table for the batch at fault or after it, for what PositionLoader, the load check
+    and the guard refuse."""
     files = choose_inputs(paths, last_nfiles)
     if not files:
         raise ValueError("no State shards match %s" % (list(paths),))
@@ -247,9 +279,18 @@ def reanalyse_files(paths, out_dir, agent, game, last_nfiles=0, log=None):
     names = [os.path.basename(f) for f in files]
     if len(set(names)) != len(names):
         raise ValueError("two inputs of the same file name would be written to the same output: %s" % sorted(names))
-    data = PositionLoader(files)
-    os.makedirs(out_dir, exist_ok=True)
     R = Reanalyser(agent, game)
+    if R.dist:
+        data = RootDistLoader(files, positions=True)
+        head, mine = (data.atoms, data.vmin, data.vmax), (int(agent.atoms), float(agent.vrange[0]), float(agent.vrange[1]))
+        if head != mine:
+            raise ValueError("the root distributions of %s were recorded by a head of (atoms, vmin, vmax) = %s, the agent's is %s"
+                             % (files[0], head, mine))
+        out_dists = np.zeros(data.length, ROOT_DIST_DTYPE)
+        raw_dists = out_dists.view(np.uint8).reshape(data.length, ROOT_DIST_BYTES)
+    else:
+        data = PositionLoader(files)
+    os.makedirs(out_dir, exist_ok=True)
     G, total = game.n_games, data.length
     ends = np.cumsum(data.counts)
     out = np.zeros(total, STATE_DTYPE)
@@ -267,6 +308,9 @@ def reanalyse_files(paths, out_dir, agent, game, last_nfiles=0, log=None):
             lo = ends[j] - data.counts[j]
             target = os.path.join(out_dir, names[j])
             np.save(target, out[lo:ends[j]])
+            if R.dist:
+                write_root_dist_head(_PART.sub("", target), *mine)
+                np.save(rootdist_file(target), out_dists[lo:ends[j]])
             ep = _PART.sub(lambda m: ".episodes" + m.group(0), files[j])
             if os.path.exists(ep):
                 shutil.copyfile(ep, os.path.join(out_dir, os.path.basename(ep)))
@@ -277,7 +321,11 @@ def reanalyse_files(paths, out_dir, agent, game, last_nfiles=0, log=None):
     for a in range(0, total, G):
         b = min(a + G, total)
         R.submit(data.rows[a:b], data.positions[a:b], what=name_rows(a, b))
-        raw[a:b] = R.collect().view(np.uint8).reshape(b - a, ROW_BYTES)
+        got = R.collect()
+        if R.dist:
+            got, d = got
+            raw_dists[a:b] = d.view(np.uint8).reshape(b - a, ROOT_DIST_BYTES)
+        raw[a:b] = got.view(np.uint8).reshape(b - a, ROW_BYTES)
         write_complete(b)
     write_complete(total)                            # (shards without a row at the end, or no row at all)
     return written

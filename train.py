@@ -24,8 +24,15 @@ before each of --bootstrap_rounds parts of the fit, instead of the values the pl
 atoms on [--vmin, --vmax), csrc/episode_dist_targets.hip) and writes pytorch_model/model_checkpoint_dist, which a DistValueSim
 that builds its own model loads.  Without --td the target is the realised return as a distribution; --td --td_lambda L
 --bootstrap net is the lambda-return of the head's own distributions over at most --td_horizon moves, refreshed before each of
---bootstrap_rounds parts.  --fit_backend hip then means the head's gradient step (hip_dist).  The head records no distribution
-and its backup has no discount, so --td alone, --bootstrap recorded with --td and a --target_gamma other than 1 are refused.
+--bootstrap_rounds parts.  --fit_backend hip then means the head's gradient step (hip_dist).  A State row records no distribution
+and the head's backup has no discount, so --td alone, --bootstrap recorded with --td and a --target_gamma other than 1 are refused.
+
+--head dist --td [--td_lambda L] --bootstrap search takes the distributions inside the target from the `rootdist` shards beside the
+data (`play.py --agent_type DistValueSim --save --save_root_dists`, or `reanalyse.py --agent_type DistValueSim --root_dists`): what
+the SEARCH backed up into each move's root, not the bare head's opinion.  Without --td_lambda the target is the recorded
+distribution itself (lambda = 0, the counterpart of the value net's --td alone).  Atoms and range come from the shards' sidecar; an
+--atoms, --vmin or --vmax that says otherwise is refused.  Nothing is predicted, so it takes no --bootstrap_rounds above 1; it is
+refused with --head value, --nodes and --dist_nodes and without --td.
 
 --nodes --td --data_paths D/nodes* fits the node shards of `play.py --save_nodes` instead of episodes (offline.fit_nodes,
 csrc/node_records.hip): the harvested tree nodes, the training set of the online fit.  A node has the search's value and
@@ -76,8 +83,10 @@ def build_parser():
         'out (drop) or end at their last row (keep, the reference\'s rule)')
     add('--target_gamma', default=1.0, type=float, help='[new] the discount per move of the targets, in (0, 1]: 0.999 is the '
         'search\'s discount (the value it adds to discounted score differences); default 1.0, the reference\'s undiscounted rule')
-    add('--bootstrap', default='recorded', choices=('recorded', 'net'), help='[new] with --td --td_lambda: the values inside the '
-        'lambda-return are the recorded root values (recorded) or the fitted net\'s own, refreshed every round (net)')
+    add('--bootstrap', default='recorded', choices=('recorded', 'net', 'search'), help='[new] with --td --td_lambda: the values inside '
+        'the lambda-return are the recorded root values (recorded) or the fitted net\'s own, refreshed every round (net); --head dist '
+        'with --td: search takes the root distributions recorded beside the rows (play.py --save_root_dists, reanalyse.py '
+        '--root_dists), and without --td_lambda fits them as they are')
     add('--bootstrap_rounds', default=1, type=int, help='[new] with --bootstrap net: the iterations are split into this many '
         'parts and the targets recomputed from the net before each (default:1)')
     add('--fit_backend', default='hip', choices=('torch', 'hip'), help='[new] gradients through PyTorch autograd (torch) or the '
@@ -131,6 +140,22 @@ def check_dist_nodes(args, argv):
     args.head_given = {k: getattr(args, k) for k in ('atoms', 'vmin', 'vmax') if _given(argv, '--' + k)}
 
 
+def check_search(args, argv):
+    """the refusals of --bootstrap search that need no file"""
+    if args.head != 'dist':
+        sys.exit('--bootstrap search takes the root distributions recorded beside the rows: it needs --head dist (the value net\'s '
+                 'recorded values are --bootstrap recorded)')
+    if args.nodes or args.dist_nodes:
+        sys.exit('--bootstrap search takes no --nodes or --dist_nodes: it reads the episodes\' rows and the root distributions beside '
+                 'them, a node table has neither')
+    if not args.td:
+        sys.exit('--bootstrap search puts the recorded root distributions inside the target of --td: it needs --td (with '
+                 '--td_lambda L the lambda-return over them, without it the recorded distribution itself)')
+    if args.bootstrap_rounds > 1:
+        sys.exit('--bootstrap search takes no --bootstrap_rounds above 1: recorded distributions do not change between rounds')
+    args.head_given = {k: getattr(args, k) for k in ('atoms', 'vmin', 'vmax') if _given(argv, '--' + k)}
+
+
 def check_nodes(args):
     """the refusals of --nodes"""
     if not args.td:
@@ -154,6 +179,8 @@ def check_nodes(args):
 
 def check_args(args, argv=()):
     """the refusals, before anything is imported or read"""
+    if args.bootstrap == 'search':
+        check_search(args, argv)
     if args.dist_nodes:
         check_dist_nodes(args, argv)
     if args.nodes:
@@ -176,10 +203,12 @@ def check_args(args, argv=()):
     if args.td_lambda is not None and not args.td:
         sys.exit('--td_lambda is the trace of --td: it needs --td')
     if args.head == 'dist':
-        if args.td and args.td_lambda is None and not args.dist_nodes:
-            sys.exit('--head dist with --td needs --td_lambda: the rows record no distribution to fit')
-        if args.td and args.bootstrap != 'net' and not args.dist_nodes:
-            sys.exit('--head dist with --td needs --bootstrap net: the distributions inside the target are the head\'s own')
+        if args.td and args.td_lambda is None and not args.dist_nodes and args.bootstrap != 'search':
+            sys.exit('--head dist with --td needs --td_lambda: the rows record no distribution to fit (the root distributions of '
+                     'play.py --save_root_dists are fitted with --bootstrap search)')
+        if args.td and args.bootstrap not in ('net', 'search') and not args.dist_nodes:
+            sys.exit('--head dist with --td needs --bootstrap net (the distributions inside the target are the head\'s own) or '
+                     '--bootstrap search (they are the recorded root distributions of play.py --save_root_dists)')
         if args.target_gamma != 1.0:
             sys.exit('--head dist takes no --target_gamma other than 1: the distributional backup does not discount')
         if args.td_horizon < 0:
@@ -230,6 +259,19 @@ def main_dist(args):
     """--head dist: the same files, split and iteration count; categorical targets (offline.fit_episodes_dist)"""
     from tetris_mcts_amd.model_distributional import Model_Dist
     from tetris_mcts_amd.offline import fit_episodes_dist
+    if args.bootstrap == 'search':
+        from tetris_mcts_amd.episodes import rootdist_stem
+        from tetris_mcts_amd.nodes import load_head
+        from tetris_mcts_amd.offline import choose_stems
+        try:
+            head = dict(zip(('atoms', 'vmin', 'vmax'), load_head([rootdist_stem(s) for s in choose_stems(args.data_paths, args.last_nfiles)])))
+        except ValueError as e:
+            sys.exit('--bootstrap search: %s (record with play.py --agent_type DistValueSim --save --save_root_dists)' % e)
+        for k, v in args.head_given.items():
+            if v != head[k]:
+                sys.exit('--%s %s, but the root distributions were recorded by a head with %s %s (their sidecar, .head.npy): leave '
+                         '--%s out, or give the files of that head' % (k, v, k, head[k], k))
+        args.atoms, args.vmin, args.vmax = head['atoms'], head['vmin'], head['vmax']
     model = Model_Dist(atoms=args.atoms, backend='hip')
     if not args.new:
         model.load()
@@ -245,7 +287,7 @@ def main_dist(args):
                             rounds=args.bootstrap_rounds, weighted=args.weighted, weighted_mode=args.weighted_mode,
                             terminal=args.terminal, censored=args.censored, last_nfiles=args.last_nfiles, validation=args.validation,
                             val_mode=args.val_mode, val_episodes=args.val_episodes, val_set_size=args.val_set_size,
-                            val_set_size_max=args.val_set_size_max)
+                            val_set_size_max=args.val_set_size_max, bootstrap='search' if args.bootstrap == 'search' else 'net')
     print('iters:%d/%d' % (sum(r['iters'] for r in res['rounds']), plan['iters'])
           + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
     model.save()
