@@ -9,6 +9,8 @@ scripts/episode_recording_timing.py): every figure is the median of --runs fresh
       with --save --save_root_dists, with --save alone and, with --parent DIR (a built checkout of the parent commit), with --save
       there; the margin is the spread max - min of the baseline's runs.  Every run plays its 200 moves: the 64-move ring is flushed
       at moves 64, 128 and 192, inside the moves timed (after the first 20); the script refuses a run that played fewer.
+      With --records (and --parent) the variants are two, this tree and the parent, both with --save --save_positions
+      --save_root_dists: the recorder's host path against the parent's.
   (b) re-analysis under DistValueSim at 4096 x 100: a child records 10 moves (positions and root distributions) with a DistValueSim
       whose pool is re-analysis' default (reanalyse.default_max_nodes), then re-analyses two batches of 4096 of the recorded
       positions with it: ms per batch between HIP events, split into upload + load + check, tm_pool_fresh, new roots + search + root
@@ -38,11 +40,14 @@ def play_args(sims):
             "--ngames", "100000000"]
 
 
-def part_a(runs, parent, sims, timeout):
+def part_a(runs, parent, sims, timeout, records=False):
     one = _script("episode_recording_timing").one
     variants = [("save_root_dists", HERE, ["--save", "--save_root_dists"]), ("save", HERE, ["--save"])]
     if parent:
         variants.append(("parent_save", os.path.abspath(parent), ["--save"]))
+    if records:
+        variants = [(name, repo, ["--save", "--save_positions", "--save_root_dists"])
+                    for name, repo in (("records", HERE), ("parent_records", os.path.abspath(parent)))]
     res = {name: [] for name, _, _ in variants}
     for i in range(runs):
         for name, repo, flags in variants:
@@ -56,11 +61,12 @@ def part_a(runs, parent, sims, timeout):
                 shutil.rmtree(tmp, ignore_errors=True)
             res[name].append(r)
             print(name, i, json.dumps(r), flush=True)
-    base = "parent_save" if parent else "save"
+    base = variants[-1][0] if parent else "save"
     med = {name: statistics.median(r["ms_per_move"] for r in rs) for name, rs in res.items()}
-    return dict(command="play.py " + " ".join(play_args(sims)), skip_moves=20, runs=res, median_ms_per_move=med, baseline=base,
+    return dict(command="play.py " + " ".join(play_args(sims)), flags={name: flags for name, _, flags in variants}, skip_moves=20,
+                runs=res, median_ms_per_move=med, baseline=base,
                 margin_ms=max(r["ms_per_move"] for r in res[base]) - min(r["ms_per_move"] for r in res[base]),
-                save_root_dists_minus_baseline_ms=med["save_root_dists"] - med[base], save_minus_baseline_ms=med["save"] - med[base])
+                **{name + "_minus_baseline_ms": med[name] - med[base] for name in med if name != base or not parent})
 
 
 def child_b(sims, n_games, moves):
@@ -134,16 +140,20 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--sims", type=int, default=1000, help="simulations a move in (a): 1000 is DistValueSim's benchmark batch")
     ap.add_argument("--only", choices=("a", "b"), default=None)
+    ap.add_argument("--records", action="store_true", help="(a) as a comparison of the recorder itself: this tree and --parent, both "
+                    "with --save --save_positions --save_root_dists (profiles/records_refactor_timing.json)")
     ap.add_argument("--timeout", type=int, default=600)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.child_b:
         return child_b(a.child_b, 4096, 10)
+    if a.records and not a.parent:
+        ap.error("--records compares with the parent's recorder: it needs --parent")
     out = {}
     if a.only != "a":
         out["reanalysis"] = part_b(a.runs, a.timeout)
     if a.only != "b":
-        out["recording"] = part_a(a.runs, a.parent, a.sims, a.timeout)
+        out["recording"] = part_a(a.runs, a.parent, a.sims, a.timeout, a.records)
     print(json.dumps(out))
     if a.out:
         with open(a.out, "w") as f:

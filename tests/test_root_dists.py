@@ -105,6 +105,37 @@ def test_the_writer_drops_ended_rows_of_all_three_tables_with_one_mask(tmp_path)
     assert len(glob.glob(D + "rootdist*")) == 2
 
 
+def test_one_flush_with_both_companions_keeps_the_same_rows_in_all_three_tables(tmp_path):
+    """2 slots x 3 moves, the smallest flush in which a dropped row sits between kept ones: ended rows first, in the middle, last"""
+    from tetris_mcts_amd.episodes import (EPISODE_DTYPE, IDENTITY, POSITION_DTYPE, ROOT_DIST_DTYPE, STATE_DTYPE, RootDistLoader,
+                                          ShardWriter, write_root_dist_head)
+    D = str(tmp_path) + "/"
+    tables = _flush(6)
+    for t in tables:
+        t["slot"], t["move"] = np.arange(6) % 2, np.arange(6) // 2            # move-major, slot-minor
+    ended, keep = (0, 3, 5), [1, 2, 4]
+    for t in tables:
+        t[list(ended)] = np.zeros((), t.dtype)
+        t["episode"][list(ended)] = -1
+    rows, pos, dist = tables
+    w = ShardWriter(D, "data", 3)
+    names = w.write(rows, np.zeros(6, EPISODE_DTYPE), 0, 6, positions=pos, root_dists=dist)
+    assert names == (D + "data3.part00000.npy", D + "data3.episodes.part00000.npy", D + "positions3.part00000.npy",
+                     D + "rootdist3.part00000.npy"), "State, episodes, positions, rootdist"
+    got = [np.load(names[i]) for i in (0, 2, 3)]
+    assert [g.dtype for g in got] == [STATE_DTYPE, POSITION_DTYPE, ROOT_DIST_DTYPE]
+    assert [len(g) for g in got] == [3, 3, 3], "the three tables have the same length"
+    for g, t in zip(got, tables):
+        assert _raw(g) == _raw(t, keep), "the kept rows' bytes"
+        for c in IDENTITY:
+            assert g[c].tolist() == got[0][c].tolist() == rows[c][keep].tolist(), c
+    write_root_dist_head(D + "data3", 50, 0, 5000)
+    L = RootDistLoader(D + "data3", positions=None)
+    assert (L.files, L.position_files, L.dist_files) == ([names[0]], [names[2]], [names[3]])
+    assert L.counts == [3] and L.length == 3
+    assert (_raw(L.rows), _raw(L.positions), _raw(L.dists)) == (_raw(rows, keep), _raw(pos, keep), _raw(dist, keep))
+
+
 def test_the_sidecar_is_written_once_and_must_agree(tmp_path):
     from tetris_mcts_amd.episodes import write_root_dist_head
     from tetris_mcts_amd.nodes import load_head

@@ -28,6 +28,7 @@ import ctypes as C
 import glob
 import os
 import re
+from typing import NamedTuple
 
 import numpy as np
 
@@ -72,53 +73,85 @@ def _parts(stem, episodes=False):
     return sorted(found, key=lambda f: int(_PART.search(f).group(1)))
 
 
-def positions_stem(stem):
-    """The stem of the position shards that go with the State shards of `stem`: "positions" in place of a file name's leading
-    "data" (D/data3.r1 -> D/positions3.r1), "positions." before any other file name - never a name that `D/data*` matches."""
+class Companion(NamedTuple):
+    """A table recorded beside the State rows, row for row: what the writer, the recorder and the loaders know of it."""
+    key: str             # the keyword of ShardWriter.write and of the loaders
+    prefix: str          # the file name's, in place of "data"
+    dtype: np.dtype
+    phrase: str          # in messages
+    hint: str            # how such shards come about
+
+    @property
+    def adj(self):
+        return self.phrase.replace(" ", "-")
+
+
+POSITIONS = Companion("positions", "positions", POSITION_DTYPE, "position", "record with play.py --save --save_positions")
+ROOT_DISTS = Companion("root_dists", "rootdist", ROOT_DIST_DTYPE, "root distribution",
+                       "record with play.py --agent_type DistValueSim --save --save_root_dists")
+COMPANIONS = (POSITIONS, ROOT_DISTS)     # the order of the writer's names, of the flush's copies and of the attributes
+
+
+def companion_stem(table, stem):
+    """The stem of a companion's shards that go with the State shards of `stem`: the prefix in place of a file name's leading "data"
+    (D/data3.r1 -> D/positions3.r1, D/rootdist3.r1), the prefix and "." before any other file name - never a name that `D/data*`,
+    `D/dist*` or another companion's prefix matches."""
     d, base = os.path.split(str(stem))
-    return os.path.join(d, "positions" + base[4:] if base.startswith("data") else "positions." + base)
+    return os.path.join(d, table.prefix + base[4:] if base.startswith("data") else table.prefix + "." + base)
+
+
+def companion_file(table, state_file):
+    """a companion's shard of a State shard: the same part of companion_stem"""
+    m = _PART.search(str(state_file))
+    if not m:
+        raise ValueError("%s is not a part of a stem" % state_file)
+    return companion_stem(table, str(state_file)[:m.start()]) + m.group(0)
+
+
+def positions_stem(stem):
+    """the stem of the position shards that go with the State shards of `stem` (companion_stem)"""
+    return companion_stem(POSITIONS, stem)
 
 
 def positions_file(state_file):
     """the position shard of a State shard: the same part of positions_stem"""
-    m = _PART.search(str(state_file))
-    if not m:
-        raise ValueError("%s is not a part of a stem" % state_file)
-    return positions_stem(str(state_file)[:m.start()]) + m.group(0)
+    return companion_file(POSITIONS, state_file)
 
 
 def rootdist_stem(stem):
-    """The stem of the root-distribution shards that go with the State shards of `stem`, by positions_stem's rule: "rootdist" in
-    place of a leading "data" (D/data3.r1 -> D/rootdist3.r1), "rootdist." before any other file name - never a name that
-    `D/data*`, `D/dist*` or `D/positions*` matches."""
-    d, base = os.path.split(str(stem))
-    return os.path.join(d, "rootdist" + base[4:] if base.startswith("data") else "rootdist." + base)
+    """the stem of the root-distribution shards that go with the State shards of `stem` (companion_stem)"""
+    return companion_stem(ROOT_DISTS, stem)
 
 
 def rootdist_file(state_file):
     """the root-distribution shard of a State shard: the same part of rootdist_stem"""
-    m = _PART.search(str(state_file))
-    if not m:
-        raise ValueError("%s is not a part of a stem" % state_file)
-    return rootdist_stem(str(state_file)[:m.start()]) + m.group(0)
+    return companion_file(ROOT_DISTS, state_file)
 
 
 def write_root_dist_head(stem, atoms, vmin, vmax):
     """The sidecar of the root-distribution shards of the State stem `stem`, <rootdist_stem>.head.npy (float64 [3]: atoms, vmin,
-    vmax; nodes.py's): written if it is not there, a ValueError if one is there that says otherwise.  Returns its name."""
-    from .nodes import _head_array, head_file
-    head, name = _head_array(atoms, vmin, vmax), head_file(rootdist_stem(stem))
-    if os.path.exists(name):
-        have = np.load(name)
-        if have.dtype != np.float64 or have.shape != (3,) or have.tobytes() != head.tobytes():
-            raise ValueError("%s records a head of (atoms, vmin, vmax) = %s, this run's is %s: another head's distributions go to "
-                             "another stem (--save_dir or --cycle)" % (name, have.tolist(), head.tolist()))
-    else:
-        d = os.path.dirname(name)
-        if d:
-            os.makedirs(d, exist_ok=True)
-        np.save(name, head)
-    return name
+    vmax; nodes.write_head): written if it is not there, a ValueError if one is there that says otherwise.  Returns its name."""
+    from .nodes import write_head
+    return write_head(rootdist_stem(stem), atoms, vmin, vmax, "distributions go")[0]
+
+
+def _stem(save_dir, save_file, cycle, rank=None):
+    """save_dir + save_file + str(cycle), `.r<rank>` after it for a rank; the stem's directory is made"""
+    stem = "%s%s%s" % (save_dir, save_file, cycle)
+    if rank is not None:
+        stem += ".r%d" % rank
+    d = os.path.dirname(stem)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    return stem
+
+
+def _rank():
+    """this process's rank under torch.distributed with more than one rank, else None"""
+    import torch
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        return torch.distributed.get_rank()
+    return None
 
 
 def _keep_raw(table, keep, dtype):
@@ -132,12 +165,7 @@ class ShardWriter:
     of which the first n_done are valid - drops the -1 rows and writes the next part of both tables."""
 
     def __init__(self, save_dir, save_file, cycle, rank=None):
-        self.stem = "%s%s%s" % (save_dir, save_file, cycle)
-        if rank is not None:
-            self.stem += ".r%d" % rank
-        d = os.path.dirname(self.stem)
-        if d:
-            os.makedirs(d, exist_ok=True)
+        self.stem = _stem(save_dir, save_file, cycle, rank)
         have, have_ep = _parts(self.stem), _parts(self.stem, episodes=True)
         self.part = 1 + max([int(_PART.search(f).group(1)) for f in have + have_ep], default=-1)
         # the ids already given: the episodes that ended, and the ones under way in the last rows written
@@ -156,25 +184,19 @@ class ShardWriter:
         if n_done > int(cap) or n_done > len(episodes):
             raise RuntimeError("episode log overflow: %d episodes ended since the last flush, the buffer holds %d - their rows "
                                "are lost; flush more often (ring_moves)" % (n_done, min(int(cap), len(episodes))))
-        if positions is not None and len(positions) != len(rows):
-            raise ValueError("%d position rows for %d State rows" % (len(positions), len(rows)))
-        if root_dists is not None and len(root_dists) != len(rows):
-            raise ValueError("%d root-distribution rows for %d State rows" % (len(root_dists), len(rows)))
+        beside = [(t, table) for t, table in zip(COMPANIONS, (positions, root_dists)) if table is not None]
+        for t, table in beside:
+            if len(table) != len(rows):
+                raise ValueError("%d %s rows for %d State rows" % (len(table), t.adj, len(rows)))
         keep = rows["episode"] != -1             # the one mask: what it drops is dropped from every table
-        if positions is not None:
-            positions = _keep_raw(positions, keep, POSITION_DTYPE)
-        if root_dists is not None:
-            root_dists = _keep_raw(root_dists, keep, ROOT_DIST_DTYPE)
+        beside = [(t, _keep_raw(table, keep, t.dtype)) for t, table in beside]
         rows = _keep_raw(rows, keep, STATE_DTYPE)
         names = ("%s.part%05d.npy" % (self.stem, self.part), "%s.episodes.part%05d.npy" % (self.stem, self.part))
         np.save(names[0], rows)
         np.save(names[1], np.ascontiguousarray(episodes[:n_done]))
-        if positions is not None:
-            names += ("%s.part%05d.npy" % (positions_stem(self.stem), self.part),)
-            np.save(names[2], positions)
-        if root_dists is not None:
-            names += ("%s.part%05d.npy" % (rootdist_stem(self.stem), self.part),)
-            np.save(names[-1], root_dists)
+        for t, table in beside:
+            names += ("%s.part%05d.npy" % (companion_stem(t, self.stem), self.part),)
+            np.save(names[-1], table)
         self.part += 1
         return names
 
@@ -199,10 +221,7 @@ class EpisodeRecorder:
         self.torch, self._check = torch, _lib.check
         self.cycle, self.G, self.ring_moves = int(cycle), int(n_games), int(ring_moves)
         self.device = torch.device(device)
-        rank = None
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            rank = torch.distributed.get_rank()
-        self.writer = ShardWriter(save_dir, save_file, cycle, rank)
+        self.writer = ShardWriter(save_dir, save_file, cycle, _rank())
         self.cap = self.ring_moves * self.G
         dev = self.device
         self.ring = torch.zeros(self.cap * ROW_BYTES, dtype=torch.uint8, device=dev)
@@ -216,44 +235,47 @@ class EpisodeRecorder:
         self._host = [torch.zeros(self._off_cnt + 8, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.positions = False               # record_positions()
         self.root_dists = False              # record_root_dists()
+        self._beside = {}                    # per companion recorded, by its keyword: (ring, the two pinned buffers)
         self._pending = [None, None]         # per pinned buffer: (event, moves held)
         self._flushes, self._pos, self.closed = 0, 0, False
         self.files = []
         self._check(self.L.tm_episode_init(self.G, self.writer.next_id, self._p(self.slot_state), self._p(self.counters),
                                            self._stream()), "tm_episode_init")
 
-    def record_positions(self):
-        """Also write a position row beside every State row (play.py --save_positions): call once, before the first add().  A
-        ring of ring_moves x G x 96 bytes beside the State ring and a pair of pinned buffers of its own, copied by the same
-        flush and waited for by the same event."""
+    def _before_add(self, caller):
         if self._pos or self._flushes or self.closed:
-            raise RuntimeError("EpisodeRecorder.record_positions comes before the first add()")
-        if not self.positions:
-            torch = self.torch
-            self.pos_ring = torch.zeros(self.cap * POSITION_BYTES, dtype=torch.uint8, device=self.device)
-            self._host_pos = [torch.zeros(self.cap * POSITION_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            self.positions = True
+            raise RuntimeError("EpisodeRecorder.%s comes before the first add()" % caller)
+
+    def _record_beside(self, table, caller, head=None):
+        """A companion's ring of ring_moves x G rows beside the State ring and a pair of pinned buffers of its own, copied by the
+        same flush and waited for by the same event; returns the ring.  A second call allocates nothing.  head: the (atoms, vmin,
+        vmax) of the stem's sidecar, written first, so that a stem of another head leaves no ring behind."""
+        self._before_add(caller)
+        if table.key not in self._beside:
+            if head is not None:
+                write_root_dist_head(self.writer.stem, *head)
+            torch, n = self.torch, self.cap * table.dtype.itemsize
+            self._beside[table.key] = (torch.zeros(n, dtype=torch.uint8, device=self.device),
+                                       [torch.zeros(n, dtype=torch.uint8).pin_memory() for _ in range(2)])
+        return self._beside[table.key][0]
+
+    def record_positions(self):
+        """Also write a position row of 96 bytes beside every State row (play.py --save_positions): call once, before the first
+        add()."""
+        self.pos_ring = self._record_beside(POSITIONS, "record_positions")
+        self.positions = True
 
     def record_root_dists(self, atoms, vmin, vmax):
-        """Also write a root-distribution row beside every State row (play.py --save_root_dists; an agent whose store is
-        KIND_DIST): call once, before the first add(), with the head's atoms and range, which go into the stem's sidecar.  A
-        third ring of ring_moves x G x 272 bytes and a pair of pinned buffers of its own, copied by the same flush and waited for
-        by the same event."""
-        if self._pos or self._flushes or self.closed:
-            raise RuntimeError("EpisodeRecorder.record_root_dists comes before the first add()")
-        if not self.root_dists:
-            write_root_dist_head(self.writer.stem, atoms, vmin, vmax)
-            torch = self.torch
-            self.dist_ring = torch.zeros(self.cap * ROOT_DIST_BYTES, dtype=torch.uint8, device=self.device)
-            self._host_dist = [torch.zeros(self.cap * ROOT_DIST_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
-            self.root_dists = True
+        """Also write a root-distribution row of 272 bytes beside every State row (play.py --save_root_dists; an agent whose store
+        is KIND_DIST): call once, before the first add(), with the head's atoms and range, which go into the stem's sidecar."""
+        self.dist_ring = self._record_beside(ROOT_DISTS, "record_root_dists", (atoms, vmin, vmax))
+        self.root_dists = True
 
     def resume(self, move_idx):
         """Games that go on from an earlier run (games.py): call once, before the first add(), with the moves played so far in
         each slot's episode.  The rows then continue that run's move numbers slot by slot (tm_episode_resume); episode ids are
         numbered as without it."""
-        if self._pos or self._flushes or self.closed:
-            raise RuntimeError("EpisodeRecorder.resume comes before the first add()")
+        self._before_add("resume")
         m = np.ascontiguousarray(np.asarray(move_idx).reshape(-1), dtype=np.int32)
         if m.shape != (self.G,):
             raise ValueError("move_idx: %d entries for %d games" % (m.size, self.G))
@@ -312,6 +334,10 @@ class EpisodeRecorder:
         if self._pos == self.ring_moves:
             self._flush()
 
+    def _recorded_beside(self):
+        """(companion, (ring, pinned buffers)) of the companions recorded, in COMPANIONS' order whatever the order of the calls"""
+        return [(t, self._beside[t.key]) for t in COMPANIONS if t.key in self._beside]
+
     def _flush(self):
         k = self._flushes % 2
         self._drain(k)                       # the buffer's earlier contents become files first
@@ -319,12 +345,9 @@ class EpisodeRecorder:
         host[:n].copy_(self.ring[:n], non_blocking=True)
         host[self._off_done:self._off_cnt].copy_(self.done, non_blocking=True)
         host[self._off_cnt:].copy_(self.counters.view(self.torch.uint8), non_blocking=True)
-        if self.positions:
-            m = self._pos * self.G * POSITION_BYTES
-            self._host_pos[k][:m].copy_(self.pos_ring[:m], non_blocking=True)
-        if self.root_dists:
-            m = self._pos * self.G * ROOT_DIST_BYTES
-            self._host_dist[k][:m].copy_(self.dist_ring[:m], non_blocking=True)
+        for t, (ring, hosts) in self._recorded_beside():
+            m = self._pos * self.G * t.dtype.itemsize
+            hosts[k][:m].copy_(ring[:m], non_blocking=True)
         self.counters[1:].zero_()            # the done buffer starts over (stream-ordered, after the copy)
         ev = self.torch.cuda.Event()
         ev.record()
@@ -342,14 +365,8 @@ class EpisodeRecorder:
         rows = buf[:moves * self.G * ROW_BYTES].view(STATE_DTYPE)
         episodes = buf[self._off_done:self._off_cnt].view(EPISODE_DTYPE)
         n_done = int(buf[self._off_cnt:].view(np.int32)[1])
-        positions = self._host_pos[k].numpy()[:moves * self.G * POSITION_BYTES].view(POSITION_DTYPE) if self.positions else None
-        if self.root_dists:
-            dists = self._host_dist[k].numpy()[:moves * self.G * ROOT_DIST_BYTES].view(ROOT_DIST_DTYPE)
-            self.files.append(self.writer.write(rows, episodes, n_done, self.cap, positions, dists))
-        elif positions is None:
-            self.files.append(self.writer.write(rows, episodes, n_done, self.cap))
-        else:
-            self.files.append(self.writer.write(rows, episodes, n_done, self.cap, positions))
+        beside = {t.key: hosts[k].numpy()[:moves * self.G * t.dtype.itemsize].view(t.dtype) for t, (_, hosts) in self._recorded_beside()}
+        self.files.append(self.writer.write(rows, episodes, n_done, self.cap, **beside))
 
     def close(self):
         """flush the partial ring and write every copy that is still held"""
@@ -425,43 +442,6 @@ class EpisodeLoader:
         return self.combo[self.bound_index(index)]
 
 
-class PositionLoader:
-    """State shards and the position shards recorded beside them, paired part by part in the order of the files.
-    stems_or_files: State shards or stems, as EpisodeLoader takes them.  `.files` / `.position_files` the pairs, `.rows`
-    (STATE_DTYPE) and `.positions` (POSITION_DTYPE) the tables, row i of one with row i of the other, `.counts` the rows per file.
-    ValueError, naming the file and the row, for a position shard that is missing or of another length and for a row whose
-    identity (episode, cycle, slot, move) differs."""
-
-    def __init__(self, stems_or_files):
-        self.files = _expand(stems_or_files)
-        self.position_files = [positions_file(f) for f in self.files]
-        rows, positions = [], []
-        for f, pf in zip(self.files, self.position_files):
-            if not os.path.isfile(pf):
-                raise ValueError("%s: there is no position shard %s beside it (record with play.py --save --save_positions)" % (f, pf))
-            r, p = np.load(f), np.load(pf)
-            if r.dtype != STATE_DTYPE:
-                raise ValueError("a shard of another layout: %s: %s" % (f, r.dtype))
-            if p.dtype != POSITION_DTYPE:
-                raise ValueError("a position shard of another layout: %s: %s" % (pf, p.dtype))
-            if len(p) != len(r):
-                raise ValueError("%s holds %d rows, %s holds %d: row %d has no %s" % (
-                    pf, len(p), f, len(r), min(len(p), len(r)), "position" if len(p) < len(r) else "State row"))
-            bad = np.zeros(len(r), bool)
-            for c in IDENTITY:
-                bad |= r[c] != p[c]
-            if bad.any():
-                i = int(np.nonzero(bad)[0][0])
-                raise ValueError("%s: row %d is (episode, cycle, slot, move) = %s, row %d of %s is %s: the two files do not belong "
-                                 "together" % (pf, i, tuple(int(p[c][i]) for c in IDENTITY), i, f, tuple(int(r[c][i]) for c in IDENTITY)))
-            rows.append(r)
-            positions.append(p)
-        self.counts = [len(r) for r in rows]
-        self.rows = _concat(rows, STATE_DTYPE)
-        self.positions = _concat(positions, POSITION_DTYPE)
-        self.length = len(self.rows)
-
-
 def _check_paired(f, r, of, o, what):
     """ValueError, naming the file and the row, unless table `o` (of file `of`) has the rows of the State table `r` (of `f`)"""
     if len(o) != len(r):
@@ -476,6 +456,47 @@ def _check_paired(f, r, of, o, what):
                          "together" % (of, i, tuple(int(o[c][i]) for c in IDENTITY), i, f, tuple(int(r[c][i]) for c in IDENTITY)))
 
 
+def _load_paired(files, tables):
+    """The State shards `files` and, beside each, the shard of every companion of `tables` (at least one), paired part by part.
+    Checked file by file and, within a file, companion by companion in the order of `tables`: the companion's shard is there, the
+    State shard's layout, the companion's layout, its length and identity columns (_check_paired).  Returns the State table, the
+    rows per file and {keyword: (the companion's files, its table)}."""
+    names = {t.key: [companion_file(t, f) for f in files] for t in tables}
+    rows, beside = [], {t.key: [] for t in tables}
+    for i, f in enumerate(files):
+        r = None
+        for t in tables:
+            of = names[t.key][i]
+            if not os.path.isfile(of):
+                raise ValueError("%s: there is no %s shard %s beside it (%s)" % (f, t.adj, of, t.hint))
+            first = r is None
+            if first:
+                r = np.load(f)
+            o = np.load(of)                  # (both are read before either layout is judged)
+            if first and r.dtype != STATE_DTYPE:
+                raise ValueError("a shard of another layout: %s: %s" % (f, r.dtype))
+            if o.dtype != t.dtype:
+                raise ValueError("a %s shard of another layout: %s: %s" % (t.adj, of, o.dtype))
+            _check_paired(f, r, of, o, t.phrase)
+            beside[t.key].append(o)
+        rows.append(r)
+    return _concat(rows, STATE_DTYPE), [len(r) for r in rows], {t.key: (names[t.key], _concat(beside[t.key], t.dtype)) for t in tables}
+
+
+class PositionLoader:
+    """State shards and the position shards recorded beside them, paired part by part in the order of the files.
+    stems_or_files: State shards or stems, as EpisodeLoader takes them.  `.files` / `.position_files` the pairs, `.rows`
+    (STATE_DTYPE) and `.positions` (POSITION_DTYPE) the tables, row i of one with row i of the other, `.counts` the rows per file.
+    ValueError, naming the file and the row, for a position shard that is missing or of another length and for a row whose
+    identity (episode, cycle, slot, move) differs."""
+
+    def __init__(self, stems_or_files):
+        self.files = _expand(stems_or_files)
+        self.rows, self.counts, beside = _load_paired(self.files, [POSITIONS])
+        self.position_files, self.positions = beside["positions"]
+        self.length = len(self.rows)
+
+
 class RootDistLoader:
     """State shards and the root-distribution shards recorded beside them (play.py --save_root_dists, reanalyse.py --root_dists),
     paired part by part in the order of the files.  stems_or_files: State shards or stems, as EpisodeLoader takes them.  `.files` /
@@ -488,37 +509,13 @@ class RootDistLoader:
     def __init__(self, stems_or_files, positions=None):
         from .nodes import load_head
         self.files = _expand(stems_or_files)
-        self.dist_files = [rootdist_file(f) for f in self.files]
-        pfiles = [positions_file(f) for f in self.files]
         if positions is None:
-            positions = bool(self.files) and all(os.path.isfile(pf) for pf in pfiles)
-        self.position_files = pfiles if positions else None
-        rows, dists, poss = [], [], []
-        for f, df, pf in zip(self.files, self.dist_files, pfiles):
-            if not os.path.isfile(df):
-                raise ValueError("%s: there is no root-distribution shard %s beside it (record with play.py --agent_type DistValueSim "
-                                 "--save --save_root_dists)" % (f, df))
-            r, o = np.load(f), np.load(df)
-            if r.dtype != STATE_DTYPE:
-                raise ValueError("a shard of another layout: %s: %s" % (f, r.dtype))
-            if o.dtype != ROOT_DIST_DTYPE:
-                raise ValueError("a root-distribution shard of another layout: %s: %s" % (df, o.dtype))
-            _check_paired(f, r, df, o, "root distribution")
-            if positions:
-                if not os.path.isfile(pf):
-                    raise ValueError("%s: there is no position shard %s beside it (record with play.py --save --save_positions)" % (f, pf))
-                p = np.load(pf)
-                if p.dtype != POSITION_DTYPE:
-                    raise ValueError("a position shard of another layout: %s: %s" % (pf, p.dtype))
-                _check_paired(f, r, pf, p, "position")
-                poss.append(p)
-            rows.append(r)
-            dists.append(o)
-        self.counts = [len(r) for r in rows]
-        self.rows = _concat(rows, STATE_DTYPE)
-        self.dists = _concat(dists, ROOT_DIST_DTYPE)
+            positions = bool(self.files) and all(os.path.isfile(positions_file(f)) for f in self.files)
+        self.rows, self.counts, beside = _load_paired(self.files, [ROOT_DISTS, POSITIONS] if positions else [ROOT_DISTS])
+        self.dist_files, self.dists = beside["root_dists"]
+        self.position_files = None
         if positions:
-            self.positions = _concat(poss, POSITION_DTYPE)
+            self.position_files, self.positions = beside["positions"]
         self.length = len(self.rows)
         self.atoms, self.vmin, self.vmax = load_head(dict.fromkeys(rootdist_stem(_PART.sub("", f)) for f in self.files))
 

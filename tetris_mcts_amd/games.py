@@ -93,10 +93,9 @@ def describe_fault(bits):
 
 def _ranked(path):
     """`.r<rank>` on the path under torch.distributed with more than one rank, as ShardWriter names its stems"""
-    import torch
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        return "%s.r%d" % (path, torch.distributed.get_rank())
-    return str(path)
+    from .episodes import _rank
+    rank = _rank()
+    return str(path) if rank is None else "%s.r%d" % (path, rank)
 
 
 def _meta(game):

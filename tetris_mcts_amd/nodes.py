@@ -27,7 +27,7 @@ import sys
 
 import numpy as np
 
-from .episodes import _PART, _concat, _expand, _parts
+from .episodes import _PART, _concat, _expand, _parts, _rank, _stem
 
 ROW_BYTES = 64                 # TM_NODE_ROW_BYTES
 NODE_DTYPE = np.dtype({
@@ -59,12 +59,7 @@ class NodeShardWriter:
     DTYPE, DTYPE_NAME = NODE_DTYPE, "NODE_DTYPE"
 
     def __init__(self, save_dir, save_file, cycle, rank=None):
-        self.stem = "%s%s%s" % (save_dir, save_file, cycle)
-        if rank is not None:
-            self.stem += ".r%d" % rank
-        d = os.path.dirname(self.stem)
-        if d:
-            os.makedirs(d, exist_ok=True)
+        self.stem = _stem(save_dir, save_file, cycle, rank)
         self.part = 1 + max([int(_PART.search(f).group(1)) for f in _parts(self.stem)], default=-1)
 
     def write(self, rows):
@@ -90,6 +85,23 @@ def _head_array(atoms, vmin, vmax):
     return head
 
 
+def write_head(stem, atoms, vmin, vmax, goes="harvest goes"):
+    """The sidecar of `stem`, <stem>.head.npy (float64 [3]: atoms, vmin, vmax): written if it is not there, a ValueError if one is
+    there that says otherwise (goes: what another head's then does, in the message's words).  Returns its name and the array."""
+    head, name = _head_array(atoms, vmin, vmax), head_file(stem)
+    if os.path.exists(name):
+        have = np.load(name)
+        if have.dtype != np.float64 or have.shape != (3,) or have.tobytes() != head.tobytes():
+            raise ValueError("%s records a head of (atoms, vmin, vmax) = %s, this run's is %s: another head's %s to another stem "
+                             "(--save_dir or --cycle)" % (name, have.tolist(), head.tolist(), goes))
+    else:
+        d = os.path.dirname(name)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        np.save(name, head)
+    return name, head
+
+
 class DistNodeShardWriter(NodeShardWriter):
     """NodeShardWriter for NODE_DIST_DTYPE rows.  Creating it writes the stem's sidecar, <stem>.head.npy (float64 [3]: atoms, vmin,
     vmax); over a stem that has one already, a sidecar that differs is a ValueError: one stem holds the harvest of one head."""
@@ -97,15 +109,7 @@ class DistNodeShardWriter(NodeShardWriter):
 
     def __init__(self, save_dir, save_file, cycle, atoms, vmin, vmax, rank=None):
         super().__init__(save_dir, save_file, cycle, rank)
-        self.head = _head_array(atoms, vmin, vmax)
-        name = head_file(self.stem)
-        if os.path.exists(name):
-            have = np.load(name)
-            if have.dtype != np.float64 or have.shape != (3,) or have.tobytes() != self.head.tobytes():
-                raise ValueError("%s records a head of (atoms, vmin, vmax) = %s, this run's is %s: another head's harvest goes "
-                                 "to another stem (--save_dir or --cycle)" % (name, have.tolist(), self.head.tolist()))
-        else:
-            np.save(name, self.head)
+        self.head = write_head(self.stem, atoms, vmin, vmax)[1]
 
 
 def report_loss(lost, dropped, ring_rows, replay_cap, out=None):
@@ -156,10 +160,7 @@ class NodeRecorder:
         self.torch, self._check = torch, _lib.check
         self.cycle, self.G, self.ring_rows, self.flush_moves = int(cycle), int(n_games), int(ring_rows), int(flush_moves)
         self.device = torch.device(device)
-        rank = None
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            rank = torch.distributed.get_rank()
-        self.writer = self._writer(save_dir, save_file, cycle, rank)
+        self.writer = self._writer(save_dir, save_file, cycle, _rank())
         dev = self.device
         self._ring_bytes = self.ring_rows * self.ROW
         self.ring = torch.zeros(self._ring_bytes, dtype=torch.uint8, device=dev)
@@ -298,34 +299,33 @@ class DistNodeRecorder(NodeRecorder):
         super().close(agent)
 
 
-def load_rows(files):
-    """the NODE_DTYPE rows of the shards one after the other; a shard of another layout (an episode shard) is a ValueError"""
-    return _concat([np.load(f) for f in files], NODE_DTYPE)
+def load_rows(files, dtype=NODE_DTYPE):
+    """the rows of the shards one after the other, NODE_DTYPE or the `dtype` given; a shard of another layout (an episode shard)
+    is a ValueError"""
+    return _concat([np.load(f) for f in files], dtype)
 
 
 class NodeLoader:
     """Node shards as one table: `rows`, `length`, and every column (obs, value, variance, visit, slot) a concatenated attribute.
     paths: node shards or stems."""
+    DTYPE = NODE_DTYPE
 
     def __init__(self, paths):
         self.files = _expand(paths)
-        self.rows = load_rows(self.files)
-        for c in NODE_DTYPE.names:
+        self.rows = load_rows(self.files, self.DTYPE)
+        for c in self.DTYPE.names:
             setattr(self, c, np.ascontiguousarray(self.rows[c]))
         self.length = len(self.rows)
 
 
-class DistNodeLoader:
+class DistNodeLoader(NodeLoader):
     """Dist node shards as one table: `rows`, `length`, every column (obs, value, variance, visit, slot, dist) a concatenated
     attribute, and `atoms`, `vmin`, `vmax` from the stems' sidecars.  paths: dist node shards or stems.  A shard of another layout
     and stems whose sidecars disagree (or a stem without one) are a ValueError."""
+    DTYPE = NODE_DIST_DTYPE
 
     def __init__(self, paths):
-        self.files = _expand(paths)
-        self.rows = _concat([np.load(f) for f in self.files], NODE_DIST_DTYPE)
-        for c in NODE_DIST_DTYPE.names:
-            setattr(self, c, np.ascontiguousarray(self.rows[c]))
-        self.length = len(self.rows)
+        super().__init__(paths)
         self.atoms, self.vmin, self.vmax = load_head(dict.fromkeys(_PART.sub("", f) for f in self.files))
 
 

@@ -65,16 +65,22 @@ the sorted positions seg[e] .. seg[e+1]-1; ended bool [n_seg]: the episode table
 row's score (0 where censored); stem, cycle, episode int32 [n_seg]: the episode's key.  Tensors on the rows' device."""
 
 
+def _row_bytes(rows, dtype, name):
+    """Rows as a contiguous uint8 tensor [n, dtype.itemsize] - such a tensor already, or a numpy table of `dtype` (`name` in the
+    message), which is then returned beside it (else None).  ValueError for anything else."""
+    if torch.is_tensor(rows):
+        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != dtype.itemsize or not rows.is_contiguous():
+            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % dtype.itemsize)
+        return rows, None
+    table = np.ascontiguousarray(rows)
+    if table.dtype != dtype:
+        raise ValueError("rows: a table of %s, not %s" % (name, table.dtype))
+    return torch.from_numpy(table.view(np.uint8).reshape(len(table), dtype.itemsize)), table
+
+
 def rows_tensor(rows, device=None):
     """State rows as a uint8 tensor [n, 368]: a numpy STATE_DTYPE table (one copy, to `device`) or such a tensor already."""
-    if torch.is_tensor(rows):
-        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != ROW_BYTES or not rows.is_contiguous():
-            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % ROW_BYTES)
-        return rows if device is None else rows.to(device)
-    rows = np.asarray(rows)
-    if rows.dtype != STATE_DTYPE:
-        raise ValueError("rows: a table of STATE_DTYPE, not %s" % (rows.dtype,))
-    t = torch.from_numpy(np.ascontiguousarray(rows).view(np.uint8).reshape(len(rows), ROW_BYTES))
+    t = _row_bytes(rows, STATE_DTYPE, "STATE_DTYPE")[0]
     return t if device is None else t.to(device)
 
 
@@ -309,9 +315,8 @@ def episode_targets(rows, index, td=False, lam=None, weighted=False, weighted_mo
     wmode = weight_mode(weighted, weighted_mode)
     rows = rows_tensor(rows)
     on = rows.device if device is None else torch.device(device)
-    n, n_seg = index.order.shape[0], index.ended.shape[0]
     tail_kind = (index.ended if terminal == "final" else torch.zeros_like(index.ended)).to(torch.uint8)
-    tail_value = torch.zeros(n_seg, dtype=torch.float32, device=tail_kind.device)
+    tail_value = torch.zeros(index.ended.shape[0], dtype=torch.float32, device=tail_kind.device)
     if on.type == "cpu":
         table = rows.cpu().numpy().reshape(-1).view(STATE_DTYPE)
         value, variance, weight, fault = targets_numpy(table, index.order.cpu().numpy(), index.seg.cpu().numpy(), tail_kind.cpu().numpy(),
@@ -326,11 +331,7 @@ def episode_targets(rows, index, td=False, lam=None, weighted=False, weighted_mo
         fault = int(fault.item())
     if fault:
         raise RuntimeError("episode_targets: the index names rows outside the %d given" % rows.shape[0])
-    keep = torch.ones(n, dtype=torch.bool, device=value.device)
-    if mode == 0 and censored == "drop" and n_seg:
-        length = (index.seg[1:] - index.seg[:-1]).to(torch.int64)
-        keep = torch.repeat_interleave(index.ended, length, output_size=n).to(value.device)
-    return value, variance, weight, keep
+    return value, variance, weight, _kept(index, mode, censored, value.device)
 
 
 def choose_stems(paths, last_nfiles=1):
@@ -434,6 +435,37 @@ def training_set(paths, td=False, lam=None, weighted=False, weighted_mode=0, ter
                       rows=rows, index=index, sel=sel)
 
 
+def _iterations(max_iters, iters_per_val, n_train):
+    """(iters, the iters_per_val keyword of train_data if one was given): either may be a function - max_iters of the number of
+    training rows, iters_per_val of the iterations"""
+    iters = int(max_iters(n_train)) if callable(max_iters) else int(max_iters)
+    extra = {}
+    if iters_per_val is not None:
+        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    return iters, extra
+
+
+def _round_iters(iters, r, rounds):
+    """the iterations of round r of `rounds`: iters // rounds each, the remainder to the last"""
+    return iters // rounds + (iters % rounds if r == rounds - 1 else 0)
+
+
+def _save_on_rank0(model):
+    from . import dist as tdist
+    if tdist.rank() == 0:                  # replicas are identical: one checkpoint file, written by rank 0
+        model.save(verbose=False)
+
+
+def _consolidate(model, data, n_train, res, penalised, **fisher):
+    """The end of a fit with ewc_lambda: Model_VV.compute_fisher (fisher: its state_format) over the training rows of `data` with
+    the weights as the fit used them - train_data fits with weighted=True on the weights divided by their mean over ALL rows:
+    the same per-sample losses here -, the checkpoint, and `res` with the ewc dict."""
+    w = data[3] / data[3].mean()
+    model.compute_fisher([d[:n_train] for d in data[:3]] + [w[:n_train]], weighted=True, **fisher)
+    _save_on_rank0(model)
+    return dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
+
+
 def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
                  early_stopping_patience=10, fit_backend="torch", validation_backend="torch", gamma=1.0, bootstrap="recorded",
                  bootstrap_rounds=1, on_round=None, ewc_lambda=None, **options):
@@ -474,10 +506,7 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
     if ewc_lambda is not None and fit_backend != "hip":
         raise ValueError("ewc_lambda needs fit_backend='hip', not %r" % (fit_backend,))
     data, info = training_set(paths, device=model.device, gamma=gamma, **options)
-    iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
-    extra = {}
-    if iters_per_val is not None:
-        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    iters, extra = _iterations(max_iters, iters_per_val, info["n_train"])
     if rounds > 1 and iters < rounds:
         raise ValueError("%d iterations do not make %d rounds" % (iters, rounds))
     targets = {k: options[k] for k in ("td", "lam", "weighted", "weighted_mode", "terminal", "censored", "eps") if k in options}
@@ -496,20 +525,13 @@ def fit_episodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=No
             data[1].copy_(value[info["sel"]].reshape(-1, 1))
         if on_round is not None:
             on_round(r, data, v_rows)
-        res = model.train_data(data, batch_size=batch_size, max_iters=iters // rounds + (iters % rounds if r == rounds - 1 else 0),
+        res = model.train_data(data, batch_size=batch_size, max_iters=_round_iters(iters, r, rounds),
                                validation_fraction=info["validation_fraction"], shuffle=False, early_stopping=early_stopping,
                                early_stopping_patience=early_stopping_patience, fit_backend=fit_backend,
                                validation_backend=validation_backend, **extra)
         done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
     if ewc_lambda is not None:
-        # train_data fits with weighted=True on the weights divided by their mean over ALL rows: the same per-sample losses here
-        n_train = info["n_train"]
-        w = data[3] / data[3].mean()
-        model.compute_fisher([d[:n_train] for d in data[:3]] + [w[:n_train]], weighted=True)
-        from . import dist as tdist
-        if tdist.rank() == 0:
-            model.save(verbose=False)
-        res = dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
+        res = _consolidate(model, data, info["n_train"], res, penalised)
     return dict(res, rounds=done)
 
 
@@ -820,10 +842,7 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
         raise RuntimeError("no rows to train on: every episode of %s is censored (censored='keep' takes them as they are)" % (stems,))
     states = torch.zeros(n, 1, 22, 10, dtype=torch.float32, device=dev)
     states[:, :, 2:, :] = gather_states(rows, index.order[sel])              # the head's 22 rows: two empty ones on top
-    iters = int(max_iters(n - n_val)) if callable(max_iters) else int(max_iters)
-    extra = {}
-    if iters_per_val is not None:
-        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    iters, extra = _iterations(max_iters, iters_per_val, n - n_val)
     if rounds > 1 and iters < rounds:
         raise ValueError("%d iterations do not make %d rounds" % (iters, rounds))
     options = dict(td=td, lam=lam, horizon=horizon, atoms=model.atoms, vmin=vmin, vmax=vmax, weighted=weighted,
@@ -846,13 +865,10 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
                 data[1].copy_(target[sel])
         if on_round is not None:
             on_round(r, data, p_rows)
-        res = model.train_data(data, fit_backend=fit_backend, batch_size=batch_size,
-                               max_iters=iters // rounds + (iters % rounds if r == rounds - 1 else 0),
+        res = model.train_data(data, fit_backend=fit_backend, batch_size=batch_size, max_iters=_round_iters(iters, r, rounds),
                                validation_fraction=validation_fraction(n, n_val), shuffle=False, early_stopping=early_stopping,
                                early_stopping_patience=early_stopping_patience, validation_backend=validation_backend, **extra)
-        from . import dist as tdist
-        if tdist.rank() == 0:                  # replicas are identical: one checkpoint file, written by rank 0
-            model.save(verbose=False)
+        _save_on_rank0(model)
         done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
     return dict(res, rounds=done)
 
@@ -863,30 +879,30 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
 # value and variance, the visits.  A node has no return and no episode: the target is the search's own value (the value net's mode
 # 2), the held-out rows are a random draw, and the fit reads the packed observations as they are (state_format="packed").
 
+def _node_rows(rows, dtype, name, device):
+    """What the two target functions of node rows take in: the rows as a uint8 tensor [n, ROW] (_row_bytes) on the device `on`
+    the targets are computed on - `device`; None: the tensor's own, "cuda" for a table - and, where that is the host, the table
+    of `dtype` the numpy statement reads (else None).  Returns rows, table, on."""
+    on = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cuda"))
+    rows, table = _row_bytes(rows, dtype, name)
+    if on.type != "cpu":
+        return rows.to(on), None, on
+    return rows, rows.cpu().numpy().reshape(-1).view(dtype) if table is None else table, on
+
+
 def node_targets(rows, weighted=False, weighted_mode=0, eps=EPS, device=None):
     """obs (int32 [n,12]), value, variance, weight (float32 [n]) of node rows: tm_node_targets on the rows' device, on the current
     stream (`rows`: a NODE_DTYPE table or a contiguous uint8 tensor [n,64]; device: where a table goes), or with device="cpu"
     the numpy statement of the same definitions.  Raises RuntimeError on a set fault word (one .item())."""
     from . import nodes as N
     wmode = weight_mode(weighted, weighted_mode)
-    on = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cuda"))
-    if torch.is_tensor(rows):
-        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != N.ROW_BYTES or not rows.is_contiguous():
-            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % N.ROW_BYTES)
-        table = None
-    else:
-        table = np.ascontiguousarray(rows)
-        if table.dtype != N.NODE_DTYPE:
-            raise ValueError("rows: a table of NODE_DTYPE, not %s" % (table.dtype,))
-        rows = torch.from_numpy(table.view(np.uint8).reshape(len(table), N.ROW_BYTES))
+    rows, table, on = _node_rows(rows, N.NODE_DTYPE, "NODE_DTYPE", device)
     n = rows.shape[0]
     if on.type == "cpu":
-        table = rows.cpu().numpy().reshape(-1).view(N.NODE_DTYPE) if table is None else table
         obs, value, variance, weight, fault = N.node_targets_numpy(table, wmode, eps)
         obs, value, variance, weight = (torch.from_numpy(np.ascontiguousarray(x)) for x in (obs.view(np.int32), value, variance, weight))
     else:
         from . import _lib
-        rows = rows.to(on)
         obs = torch.zeros(n, 12, dtype=torch.int32, device=on)
         value, variance, weight = (torch.zeros(n, dtype=torch.float32, device=on) for _ in range(3))
         fault = torch.zeros(1, dtype=torch.int32, device=on)
@@ -902,6 +918,24 @@ def node_targets(rows, weighted=False, weighted_mode=0, eps=EPS, device=None):
     return obs, value, variance, weight
 
 
+def _node_files(paths, last_nfiles):
+    """the stems choose_stems picks and their shards"""
+    stems = choose_stems(paths, last_nfiles)
+    return stems, [f for s in stems for f in _parts(s)]
+
+
+def _node_hold_out(n_all, what, stems, files, validation, val_set_size, val_set_size_max, generator, dev):
+    """The random hold-out of a node table of n_all rows (a node table has no episodes: _split's val_mode 0): the rows that train
+    followed by the ones held out, how many they are together, and the training set's dict.  RuntimeError for no row at all."""
+    if n_all == 0:
+        raise RuntimeError("no rows to train on: the %s shards of %s are empty" % (what, stems))
+    sel, n_val = _split(None, torch.ones(n_all, dtype=torch.bool, device=dev), validation, 0, 0, val_set_size, val_set_size_max,
+                        generator, dev)
+    n = int(sel.shape[0])
+    return sel, n, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
+                        files=files, n_rows=n_all)
+
+
 def node_training_set(paths, weighted=False, weighted_mode=0, last_nfiles=1, validation=False, val_set_size=0.05,
                       val_set_size_max=-1, generator=None, device="cuda", eps=EPS):
     """data = [observations int32 [n,12], values [n,1], variances [n,1], weights [n,1]] on `device`, the training rows first and
@@ -911,20 +945,13 @@ def node_training_set(paths, weighted=False, weighted_mode=0, last_nfiles=1, val
     validation: a random int(n * val_set_size) rows are held out (at most val_set_size_max if that is positive; `generator`: a
     torch.Generator for the draw) - a node table has no episodes, so there is no episodic split."""
     from . import nodes as N
-    stems = choose_stems(paths, last_nfiles)
-    files = [f for s in stems for f in _parts(s)]
+    stems, files = _node_files(paths, last_nfiles)
     table = N.load_rows(files)
     dev = torch.device(device)
     obs, value, variance, weight = node_targets(table, weighted=weighted, weighted_mode=weighted_mode, eps=eps, device=dev)
-    n_all = obs.shape[0]
-    if n_all == 0:
-        raise RuntimeError("no rows to train on: the node shards of %s are empty" % (stems,))
-    sel, n_val = _split(None, torch.ones(n_all, dtype=torch.bool, device=dev), validation, 0, 0, val_set_size, val_set_size_max,
-                        generator, dev)
-    n = int(sel.shape[0])
+    sel, n, info = _node_hold_out(obs.shape[0], "node", stems, files, validation, val_set_size, val_set_size_max, generator, dev)
     data = [obs[sel].contiguous()] + [x[sel].reshape(n, 1) for x in (value, variance, weight)]
-    return data, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
-                      files=files, n_rows=n_all)
+    return data, info
 
 
 def fit_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
@@ -946,10 +973,7 @@ def fit_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None,
     if info["n_val"] and validation_backend != "hip":
         raise ValueError("fit_nodes holds %d rows out, and the torch validation does not read packed observations: it needs "
                          "validation_backend='hip' (or no validation), not %r" % (info["n_val"], validation_backend))
-    iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
-    extra = {}
-    if iters_per_val is not None:
-        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    iters, extra = _iterations(max_iters, iters_per_val, info["n_train"])
     if ewc_lambda is not None:
         extra["ewc_lambda"] = ewc_lambda
     penalised = ewc_lambda is not None and model.fisher is not None
@@ -957,13 +981,7 @@ def fit_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None,
                            shuffle=False, early_stopping=early_stopping, early_stopping_patience=early_stopping_patience,
                            fit_backend=fit_backend, validation_backend=validation_backend, state_format="packed", **extra)
     if ewc_lambda is not None:
-        n_train = info["n_train"]
-        w = data[3] / data[3].mean()
-        model.compute_fisher([d[:n_train] for d in data[:3]] + [w[:n_train]], weighted=True, state_format="packed")
-        from . import dist as tdist
-        if tdist.rank() == 0:
-            model.save(verbose=False)
-        res = dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
+        res = _consolidate(model, data, info["n_train"], res, penalised, state_format="packed")
     return dict(res, n_train=info["n_train"], n_val=info["n_val"])
 
 
@@ -994,24 +1012,13 @@ def node_dist_targets(rows, atoms, weighted=False, weighted_mode=1, device=None)
     atoms = int(atoms)
     if not 1 <= atoms <= 64:
         raise ValueError("atoms: 1 .. 64, not %r" % (atoms,))
-    on = torch.device(device) if device is not None else (rows.device if torch.is_tensor(rows) else torch.device("cuda"))
-    if torch.is_tensor(rows):
-        if rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != N.DIST_ROW_BYTES or not rows.is_contiguous():
-            raise ValueError("rows: a contiguous uint8 tensor [n, %d]" % N.DIST_ROW_BYTES)
-        table = None
-    else:
-        table = np.ascontiguousarray(rows)
-        if table.dtype != N.NODE_DIST_DTYPE:
-            raise ValueError("rows: a table of NODE_DIST_DTYPE, not %s" % (table.dtype,))
-        rows = torch.from_numpy(table.view(np.uint8).reshape(len(table), N.DIST_ROW_BYTES))
+    rows, table, on = _node_rows(rows, N.NODE_DIST_DTYPE, "NODE_DIST_DTYPE", device)
     n = rows.shape[0]
     if on.type == "cpu":
-        table = rows.cpu().numpy().reshape(-1).view(N.NODE_DIST_DTYPE) if table is None else table
         obs, target, weight, fault = N.node_dist_targets_numpy(table, atoms, wmode)
         obs, target, weight = (torch.from_numpy(np.ascontiguousarray(x)) for x in (obs.view(np.int32), target, weight))
     else:
         from . import _lib
-        rows = rows.to(on)
         obs = torch.zeros(n, 12, dtype=torch.int32, device=on)
         target = torch.zeros(n, atoms, dtype=torch.float32, device=on)
         weight = torch.zeros(n, dtype=torch.float32, device=on)
@@ -1037,21 +1044,14 @@ def dist_node_training_set(paths, weighted=False, weighted_mode=1, last_nfiles=1
     must agree: ValueError).  paths / last_nfiles: choose_stems' rule over dist node shards.  The rows go to the device once; the
     targets are the recorded distributions.  validation: node_training_set's random hold-out."""
     from . import nodes as N
-    stems = choose_stems(paths, last_nfiles)
-    files = [f for s in stems for f in _parts(s)]
+    stems, files = _node_files(paths, last_nfiles)
     atoms, vmin, vmax = N.load_head(stems)
-    table = _concat([np.load(f) for f in files], N.NODE_DIST_DTYPE)
+    table = N.load_rows(files, N.NODE_DIST_DTYPE)
     dev = torch.device(device)
     obs, target, weight = node_dist_targets(table, atoms, weighted=weighted, weighted_mode=weighted_mode, device=dev)
-    n_all = obs.shape[0]
-    if n_all == 0:
-        raise RuntimeError("no rows to train on: the dist node shards of %s are empty" % (stems,))
-    sel, n_val = _split(None, torch.ones(n_all, dtype=torch.bool, device=dev), validation, 0, 0, val_set_size, val_set_size_max,
-                        generator, dev)
-    n = int(sel.shape[0])
+    sel, n, info = _node_hold_out(obs.shape[0], "dist node", stems, files, validation, val_set_size, val_set_size_max, generator, dev)
     data = [obs[sel].contiguous(), target[sel].contiguous(), weight[sel].reshape(n, 1)]
-    return data, dict(n=n, n_val=n_val, n_train=n - n_val, validation_fraction=validation_fraction(n, n_val), stems=stems,
-                      files=files, n_rows=n_all, atoms=atoms, vmin=vmin, vmax=vmax)
+    return data, dict(info, atoms=atoms, vmin=vmin, vmax=vmax)
 
 
 def fit_dist_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
@@ -1077,14 +1077,9 @@ def fit_dist_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=
     if info["n_val"] and validation_backend != "hip":
         raise ValueError("fit_dist_nodes holds %d rows out, and the torch validation does not read packed observations: it needs "
                          "validation_backend='hip' (or no validation), not %r" % (info["n_val"], validation_backend))
-    iters = int(max_iters(info["n_train"])) if callable(max_iters) else int(max_iters)
-    extra = {}
-    if iters_per_val is not None:
-        extra["iters_per_val"] = int(iters_per_val(iters)) if callable(iters_per_val) else int(iters_per_val)
+    iters, extra = _iterations(max_iters, iters_per_val, info["n_train"])
     res = model.train_data(data, fit_backend="hip_dist", state_format="packed", shuffle=False, batch_size=batch_size, max_iters=iters,
                            validation_fraction=info["validation_fraction"], early_stopping=early_stopping,
                            early_stopping_patience=early_stopping_patience, validation_backend=validation_backend, **extra)
-    from . import dist as tdist
-    if tdist.rank() == 0:                  # replicas are identical: one checkpoint file, written by rank 0
-        model.save(verbose=False)
+    _save_on_rank0(model)
     return dict(res, n_train=info["n_train"], n_val=info["n_val"], atoms=info["atoms"], vmin=info["vmin"], vmax=info["vmax"])
