@@ -883,6 +883,29 @@ int tm_distnet_fit_validate(const float *params, const int8_t *states, const flo
 int tm_distnet_fit_validate_packed(const float *params, const uint32_t *obs, const float *target, int target_stride,
                                    const float *weight, long long n, int chunk, int slab, int atoms, int weighted,
                                    double *rows_out, float *workspace, void *stream);
+/* The Fisher pass of the distributional head's fit (csrc/distnet_fit.hip): fisher[i] = (1/n) sum_b (d loss_b / d p_i)^2 over the rows
+ * idx[0 .. n) (idx NULL: rows 0 .. n-1; repeats allowed; every entry must be a valid row - the caller checks), loss_b the per-sample loss
+ * of tm_distnet_fit_grad, w_b sum_a (t log t - t log p) with w_b = 1 when weighted == 0, i over the P = TM_DISTNET_PARAMS(atoms) =
+ * 279232 + 129 atoms floats of params: the empirical Fisher diagonal at the targets the fit used.  The rows are taken `slab` at a time
+ * (1 .. 2^20): per slab the gradient step's forward, its output layer with the divisor 1 (not batch) and its data-gradient kernels as
+ * they are, and the squared forms of its weight-gradient kernels (the FC layers: the product of the squared operands; the convolutions:
+ * the square of each sample's sum over positions); the slab's sums go through the gradient step's second stages into a temporary and
+ * from there into a double accumulator, slab after slab in stream order; after the last slab fisher = (float)(accumulator / n).  No
+ * atomics: every sum is in a fixed order that follows from (n, slab, atoms) alone, and a slab >= n gives the bits of slab == n.  fisher
+ * is OVERWRITTEN, never read.  workspace: tm_distnet_fit_fisher_workspace(slab, atoms) floats = tm_distnet_fit_workspace(slab, atoms)
+ * + up4(P) (the temporary) + up4(2 P) (the accumulator), up4 rounding up to a multiple of four; 16-byte aligned, no initial contents
+ * required.  Everything is enqueued on `stream`: no allocation, no host synchronisation, nothing read back.  hipErrorInvalidValue, and
+ * nothing launched, for a NULL pointer (idx excepted), n < 1, slab < 1 or > 2^20, atoms outside 1..64, target_stride < atoms, or a
+ * misaligned workspace or params.  tm_distnet_fit_fisher_workspace is host arithmetic only (callable without a GPU): -1 when refused. */
+long long tm_distnet_fit_fisher_workspace(int slab, int atoms);
+int tm_distnet_fit_fisher(const float *params, const int8_t *states, const float *target, int target_stride, const float *weight,
+                          const int64_t *idx, long long n, int slab, int atoms, int weighted, float *fisher, float *workspace,
+                          void *stream);
+/* tm_distnet_fit_fisher on packed rows (obs uint32 [rows][12], 4-byte aligned): as tm_distnet_fit_grad_packed is to its twin - fisher
+ * bit-identical to the int8 call's on the rendered rows, any 48 bytes safe to read, a misaligned obs hipErrorInvalidValue. */
+int tm_distnet_fit_fisher_packed(const float *params, const uint32_t *obs, const float *target, int target_stride,
+                                 const float *weight, const int64_t *idx, long long n, int slab, int atoms, int weighted,
+                                 float *fisher, float *workspace, void *stream);
 /* value network forward (model/model_vv.py:13-52; Model_VV.inference 210-217): states int8 [n][200] -> v[n], var[n].
  * params: 478342 floats in PyTorch state_dict layouts (order as in oracle/valuenet_oracle.c).
  * It runs in one of three modes (backend, fc1), checked by tm_valuenet_check_mode (host arithmetic only: 0, or

@@ -100,6 +100,9 @@ SYMBOLS = {
     "tm_distnet_fit_validate_workspace": [i32, i32],     # (returns long long: restype set in lib())
     "tm_distnet_fit_validate": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
     "tm_distnet_fit_validate_packed": [vp, vp, vp, i32, vp, C.c_longlong, i32, i32, i32, i32, vp, vp, vp],
+    "tm_distnet_fit_fisher_workspace": [i32, i32],       # (returns long long: restype set in lib())
+    "tm_distnet_fit_fisher": [vp, vp, vp, i32, vp, vp, C.c_longlong, i32, i32, i32, vp, vp, vp],
+    "tm_distnet_fit_fisher_packed": [vp, vp, vp, i32, vp, vp, C.c_longlong, i32, i32, i32, vp, vp, vp],
     "tm_valuenet_check_mode": [i32, i32],
     "tm_valuenet_prepare": [vp, vp, i32, i32, vp],
     "tm_valuenet_forward": [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp],
@@ -152,6 +155,7 @@ def lib():
         L.tm_valuenet_fit_validate_workspace.restype = C.c_longlong
         L.tm_distnet_fit_validate_workspace.restype = C.c_longlong
         L.tm_valuenet_fit_fisher_workspace.restype = C.c_longlong
+        L.tm_distnet_fit_fisher_workspace.restype = C.c_longlong
         L.tm_ewc_penalty_workspace.restype = C.c_longlong
         L.tm_fill_norm_quantile.argtypes, L.tm_fill_norm_quantile.restype = [vp, i32], None
         L.tm_fill_norm_quantile_f64.argtypes, L.tm_fill_norm_quantile_f64.restype = [vp, i32], None

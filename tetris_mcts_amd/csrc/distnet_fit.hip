@@ -29,6 +29,10 @@
 //
 // The states come as int8 [rows][200] or as packed observations, uint32 [rows][12] (tm_distnet_fit_grad_packed,
 // tm_distnet_fit_validate_packed), through the template argument SRC of conv1's two kernels, as in valuenet_fit.hip.
+//
+// The Fisher pass (tm_distnet_fit_fisher) is the diagonal of the empirical Fisher matrix over n rows: the
+// gradient step's forward and data gradients with the divisor 1, the SQ forms of the weight-gradient kernels and a double
+// accumulator across slabs (fit_fisher below).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -155,15 +159,16 @@ __device__ __forceinline__ double wave_max(double v) {
 }
 
 // ---- output layer, log-softmax, loss and their gradients: one wave per sample, lane a = atom a, in double ----
-// per = w sum_a (t log t - t log p); dzv[b][a] = (w / B) (p_a sum_a t - t_a) (zero for a >= atoms);
+// per = w sum_a (t log t - t log p); dzv[b][a] = (w / div) (p_a sum_a t - t_a) (zero for a >= atoms), div = B in the gradient
+// step (the mean's gradient) and 1 in the Fisher pass (per-sample gradients);
 // dh[b][i] = (sum_a dzv[a] Wv[a][i]) times 1 where h > 0, 0.01 elsewhere.
 // GRAD = false (the validation pass): per alone, by the same statements; dzv and dh are not touched.
 template <bool GRAD>
 __global__ __launch_bounds__(256) void k_df_head(const float* __restrict__ Wv, const float* __restrict__ bv,
                                                  const float* __restrict__ h, const float* __restrict__ target, int tstride,
                                                  const float* __restrict__ weight, const int64_t* __restrict__ idx, int B,
-                                                 int atoms, int weighted, float* __restrict__ dzv, double* __restrict__ per,
-                                                 float* __restrict__ dh) {
+                                                 int atoms, int weighted, double div, float* __restrict__ dzv,
+                                                 double* __restrict__ per, float* __restrict__ dh) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;
     const bool on = lane < atoms;
@@ -190,7 +195,7 @@ __global__ __launch_bounds__(256) void k_df_head(const float* __restrict__ Wv, c
     const double loss = w * wave_sum(term);
     if (lane == 0) per[b] = loss;
     if (!GRAD) return;
-    const double dz = on ? (w / (double)B) * (p * T - t) : 0.0;
+    const double dz = on ? (w / div) * (p * T - t) : 0.0;
     dzv[(size_t)b * ROW + lane] = (float)dz;
     double g0 = 0.0, g1 = 0.0;
     for (int a = 0; a < atoms; ++a) {
@@ -203,19 +208,25 @@ __global__ __launch_bounds__(256) void k_df_head(const float* __restrict__ Wv, c
     dh[(size_t)b * HID + 64 + lane] = (float)(h1 > 0.0f ? g1 : 0.01 * g1);
 }
 
-// partial sums over HEAD_CHUNK samples of db_fc1 = sum dh and db_v = sum dzv
+// partial sums over HEAD_CHUNK samples of db_fc1 = sum dh and db_v = sum dzv; SQ (the Fisher pass): of dh^2 and dzv^2
+template <bool SQ>
 __global__ __launch_bounds__(192) void k_df_head_part(const float* __restrict__ dzv, const float* __restrict__ dh, int B,
                                                       float* __restrict__ part) {
     const int i = threadIdx.x, b0 = blockIdx.x * HEAD_CHUNK, b1 = min(B, b0 + HEAD_CHUNK);
     float s = 0.f;
-    for (int b = b0; b < b1; ++b) s += i < HID ? dh[(size_t)b * HID + i] : dzv[(size_t)b * ROW + (i - HID)];
+    for (int b = b0; b < b1; ++b) {
+        const float v = i < HID ? dh[(size_t)b * HID + i] : dzv[(size_t)b * ROW + (i - HID)];
+        s += SQ ? v * v : v;
+    }
     part[(size_t)blockIdx.x * HEAD_PART + i] = s;
 }
 
 // ---- FC weight gradient: part[s][m][n] = sum over the samples of split s of dA[b][m] act[b][n]; M = MS, N = NS, K = samples.
 // fc1: dA = dh (MS = 128), act = a2 (NS = 2048); fc_v: dA = dzv (MS = 64, zero beyond the atoms), act = h (NS = 128) ----
 // (chunks of 32 samples here and ONE chain a split in valuenet_fit.hip's k_vf_fc1_dw: one kernel for both would change that one's bits)
-template <int MS, int NS, int NT>
+// SQ (the Fisher pass): both operands are squared as they are loaded - the sum over the samples of the squared outer products
+// (dA[b][m] act[b][n])^2 is the matrix product of the squared operands.
+template <int MS, int NS, int NT, bool SQ = false>
 __global__ __launch_bounds__(256) void k_df_fc_dw(const float* __restrict__ dA, const float* __restrict__ act, int B,
                                                   float* __restrict__ part) {
     const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
@@ -243,6 +254,11 @@ __global__ __launch_bounds__(256) void k_df_fc_dw(const float* __restrict__ dA, 
                 av[r] = in ? acol[bb * MS] : 0.0f;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) bv[t][r] = in ? bcol[bb * NS + 32 * t] : 0.0f;
+                if constexpr (SQ) {
+                    av[r] = av[r] * av[r];
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) bv[t][r] = bv[t][r] * bv[t][r];
+                }
             }
             float4 b4[NT];
 #pragma unroll
@@ -328,7 +344,10 @@ __global__ __launch_bounds__(256) void k_df_conv_bwd_data(const float* __restric
 // CIN == 1: ain is the state of row idx[b] under two empty rows, read through SRC.  A lane's tap is fixed and the loop walks the
 // positions, so the strip is built per quad of positions (four positions lie in two rows at most) from the row the lane keeps
 // per sample.
-template <int CIN, int IW, int ISTR, int OW, int OP, int OSTR, int NT, typename SRC = DenseStates>
+// SQ (the Fisher pass): tot starts every sample from zero and holds that sample's gradient after its positions; its square is
+// added to a second set of accumulators, which is what is stored, so a partial is the sum over its samples of the squared
+// per-sample gradients.
+template <int CIN, int IW, int ISTR, int OW, int OP, int OSTR, int NT, typename SRC = DenseStates, bool SQ = false>
 __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dzo, const float* __restrict__ ain,
                                                     const typename SRC::elem* __restrict__ states,
                                                     const int64_t* __restrict__ idx, int B, float* __restrict__ part) {
@@ -350,7 +369,9 @@ __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dz
         nkx[t] = nn & 3;
     }
     f32x16 tot[NT], acc[NT];
+    [[maybe_unused]] f32x16 sq[SQ ? NT : 1];
     vf_zero<NT>(tot);
+    if constexpr (SQ) vf_zero<NT>(sq);
     for (int b = b0; b < b1; ++b) {
         const float* arow = dzo + (size_t)b * (32 * OSTR) + l31 * OSTR + 4 * half;
         const size_t ibase = (size_t)b * (CIN * ISTR);
@@ -397,6 +418,15 @@ __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dz
             }
             vf_add<NT>(tot, acc);
         }
+        if constexpr (SQ) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    sq[t][r] += tot[t][r] * tot[t][r];
+                    tot[t][r] = 0.0f;
+                }
+        }
     }
     float* dst = part + (size_t)chunk * (32 * KW);
 #pragma unroll
@@ -404,11 +434,16 @@ __global__ __launch_bounds__(256) void k_df_conv_dw(const float* __restrict__ dz
         if (nok[t]) {
             const int n = (ng * NT + t) * 32 + l31;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dst[drow(r, half) * KW + n] = tot[t][r];
+            for (int r = 0; r < 16; ++r) {
+                if constexpr (SQ) dst[drow(r, half) * KW + n] = sq[t][r];
+                else dst[drow(r, half) * KW + n] = tot[t][r];
+            }
         }
 }
 
-// per sample, the sums over positions of dz1 / dz2 per channel: cb[b][64] (conv1, conv2); dz1's padding holds zeros
+// per sample, the sums over positions of dz1 / dz2 per channel: cb[b][64] (conv1, conv2); dz1's padding holds zeros; SQ (the
+// Fisher pass): their squares
+template <bool SQ>
 __global__ __launch_bounds__(64) void k_df_conv_bias_part(const float* __restrict__ dz1, const float* __restrict__ dz2, int B,
                                                           float* __restrict__ cb) {
     const int b = blockIdx.x, i = threadIdx.x;
@@ -420,7 +455,7 @@ __global__ __launch_bounds__(64) void k_df_conv_bias_part(const float* __restric
         const float4 v = *reinterpret_cast<const float4*>(src + p);
         s += (v.x + v.y) + (v.z + v.w);
     }
-    cb[(size_t)b * 64 + i] = s;
+    cb[(size_t)b * 64 + i] = SQ ? s * s : s;
 }
 
 // the forward of B rows (states: SRC's rows, int8 [.][200] or packed [.][12]; row idx[b], or row b when idx is NULL) into a1, a2,
@@ -471,9 +506,9 @@ static int fit_grad(const float* params, const typename SRC::elem* states, const
     forward<SRC>(P, states, idx, B, a1, a2, h, st);
     // ---- output layer, loss, and the bias sums of the two FC layers ----
     hipLaunchKernelGGL(k_df_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P + OFF_FVW, P + OFF_FVB, h, target, target_stride, weight, idx,
-                       B, atoms, weighted, dzv, per, dh);
+                       B, atoms, weighted, (double)B, dzv, per, dh);
     hipLaunchKernelGGL(k_fit_loss<1>, dim3(1), dim3(256), 0, st, per, B, loss);
-    hipLaunchKernelGGL(k_df_head_part, dim3(L.hchunks), dim3(HEAD_PART), 0, st, dzv, dh, B, hp);
+    hipLaunchKernelGGL(k_df_head_part<false>, dim3(L.hchunks), dim3(HEAD_PART), 0, st, dzv, dh, B, hp);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(HID / 16), dim3(256), 0, st, hp, L.hchunks, (long long)HEAD_PART, HID, grad + OFF_F1B);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3((atoms + 15) / 16), dim3(256), 0, st, hp + HID, L.hchunks, (long long)HEAD_PART, atoms,
                        grad + OFF_FVB);
@@ -491,7 +526,7 @@ static int fit_grad(const float* params, const typename SRC::elem* states, const
                        dz2, a1, B, dz1);
     hipLaunchKernelGGL((k_df_conv_dw<1, 10, 0, 7, P1, S1, 1, SRC>), dim3(blocks_for_waves(L.chunks)), dim3(256), 0, st, dz1,
                        (const float*)nullptr, states, idx, B, pw1);
-    hipLaunchKernelGGL(k_df_conv_bias_part, dim3(B), dim3(64), 0, st, dz1, dz2, B, cb);
+    hipLaunchKernelGGL(k_df_conv_bias_part<false>, dim3(B), dim3(64), 0, st, dz1, dz2, B, cb);
     // ---- second stages of the convolutions' sums ----
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(16384 / 16), dim3(256), 0, st, pw2, L.chunks, 16384LL, 16384, grad + OFF_C2W);
     hipLaunchKernelGGL((k_fit_reduce<16>), dim3(512 / 16), dim3(256), 0, st, pw1, L.chunks, 512LL, 512, grad + OFF_C1W);
@@ -520,9 +555,81 @@ static int fit_validate(const float* params, const typename SRC::elem* states, c
         forward<SRC>(params, states + r0 * SRC::STRIDE, (const int64_t*)nullptr, B, a1, a2, h, st);
         hipLaunchKernelGGL(k_df_head<false>, dim3((B + 3) / 4), dim3(256), 0, st, params + OFF_FVW, params + OFF_FVB, h,
                            target + r0 * target_stride, target_stride, weight + r0, (const int64_t*)nullptr, B, atoms, weighted,
-                           (float*)nullptr, per, (float*)nullptr);
+                           1.0, (float*)nullptr, per, (float*)nullptr);
         hipLaunchKernelGGL(k_fit_val_moments<1>, dim3((B + chunk - 1) / chunk), dim3(256), 0, st, per, weight + r0, B, chunk, weighted,
                            rows_out + 3 * (r0 / chunk));
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- the Fisher pass: F[i] = (1/n) sum_b (d loss_b / d p_i)^2 over n rows, a slab at a time ----
+// A slab is the gradient step's forward, k_df_head with the divisor 1 (dzv and dh are then PER-SAMPLE gradients) and its data
+// gradients as they are, and the SQ forms of the weight-gradient kernels, whose partials hold sums over samples of squared
+// per-sample gradients; the unchanged second stages add them into a temporary [P], which k_df_fisher_add adds to a double
+// accumulator, slab after slab in stream order.  The workspace is the gradient step's of `slab` rows, then the temporary, then
+// the accumulator.
+__host__ inline int nparam(int atoms) { return OFF_FVW + atoms * HID + atoms; }
+
+// acc[i] = (first ? 0 : acc[i]) + tmp[i]; after the last slab fisher[i] = (float)(acc[i] / n)
+__global__ __launch_bounds__(256) void k_df_fisher_add(const float* __restrict__ tmp, double* __restrict__ acc, int np, int first,
+                                                       int last, double n, float* __restrict__ fisher) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= np) return;
+    const double a = (first ? 0.0 : acc[i]) + (double)tmp[i];
+    acc[i] = a;
+    if (last) fisher[i] = (float)(a / n);
+}
+
+template <typename SRC>
+static int fit_fisher(const float* params, const typename SRC::elem* states, const float* target, int target_stride,
+                      const float* weight, const int64_t* idx, long long n, int slab, int atoms, int weighted, float* fisher,
+                      float* workspace, void* stream_) {
+    if (!params || !states || !target || !weight || !fisher || !workspace) return (int)hipErrorInvalidValue;
+    if (n < 1 || slab < 1 || slab > MAX_BATCH || atoms < 1 || atoms > ROW || target_stride < atoms) return (int)hipErrorInvalidValue;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)params & 15)) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream_;
+    const Layout L = layout(slab);
+    const int NP = nparam(atoms), OFF_FVB = OFF_FVW + atoms * HID;
+    float* ws = workspace;
+    float *a1 = ws + L.a1, *dz1 = ws + L.dz1, *a2 = ws + L.a2, *dz2 = ws + L.dz2, *h = ws + L.h, *dh = ws + L.dh, *dzv = ws + L.dzv;
+    float *pf1 = ws + L.pf1, *pfv = ws + L.pfv, *pw2 = ws + L.pw2, *pw1 = ws + L.pw1, *cb = ws + L.cb, *hp = ws + L.hp;
+    float* tmp = ws + L.total;
+    double *per = reinterpret_cast<double*>(ws + L.per), *acc = reinterpret_cast<double*>(ws + L.total + up4(NP));
+    const float* P = params;
+    // slab by slab on the one stream: a slab's kernels have read the workspace before the next slab's overwrite it
+    for (long long r0 = 0; r0 < n; r0 += slab) {
+        const int B = (int)(n - r0 < slab ? n - r0 : slab);
+        const int s1 = (B + FC_KC - 1) / FC_KC, chunks = (B + SPW - 1) / SPW, hchunks = (B + HEAD_CHUNK - 1) / HEAD_CHUNK;
+        // rows idx[r0 + b]; without idx the rows r0 + b
+        const int64_t* ix = idx ? idx + r0 : nullptr;
+        const long long base = idx ? 0 : r0;
+        const typename SRC::elem* S = states + base * SRC::STRIDE;
+        forward<SRC>(P, S, ix, B, a1, a2, h, st);
+        hipLaunchKernelGGL(k_df_head<true>, dim3((B + 3) / 4), dim3(256), 0, st, P + OFF_FVW, P + OFF_FVB, h, target + base * target_stride,
+                           target_stride, weight + base, ix, B, atoms, weighted, 1.0, dzv, per, dh);
+        hipLaunchKernelGGL(k_df_head_part<true>, dim3(hchunks), dim3(HEAD_PART), 0, st, dzv, dh, B, hp);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(HID / 16), dim3(256), 0, st, hp, hchunks, (long long)HEAD_PART, HID, tmp + OFF_F1B);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3((atoms + 15) / 16), dim3(256), 0, st, hp + HID, hchunks, (long long)HEAD_PART, atoms,
+                           tmp + OFF_FVB);
+        hipLaunchKernelGGL((k_df_fc_dw<ROW, HID, 2, true>), dim3(blocks_for_waves((long long)s1 * 2 * 2)), dim3(256), 0, st, dzv, h, B, pfv);
+        hipLaunchKernelGGL((k_fit_reduce<4>), dim3((atoms * HID + 63) / 64), dim3(256), 0, st, pfv, s1, (long long)ROW * HID, atoms * HID,
+                           tmp + OFF_FVW);
+        hipLaunchKernelGGL((k_df_fc_dw<HID, A2, 2, true>), dim3(blocks_for_waves((long long)s1 * 4 * 32)), dim3(256), 0, st, dh, a2, B, pf1);
+        hipLaunchKernelGGL((k_fit_reduce<4>), dim3(HID * A2 / 64), dim3(256), 0, st, pf1, s1, (long long)HID * A2, HID * A2, tmp + OFF_F1W);
+        hipLaunchKernelGGL((k_fit_fc1_bwd_data<HID, A2, Leaky, 2>), dim3(blocks_for_waves(tiles(B) * 32)), dim3(256), 0, st, P + OFF_F1W, dh, a2, B, dz2);
+        hipLaunchKernelGGL((k_df_conv_dw<32, 7, S1, 4, P2, P2, 4, DenseStates, true>), dim3(blocks_for_waves((long long)chunks * 4)), dim3(256),
+                           0, st, dz2, a1, (const int8_t*)nullptr, (const int64_t*)nullptr, B, pw2);
+        hipLaunchKernelGGL((k_df_conv_bwd_data<2>), dim3(blocks_for_waves((tiles((long long)B * S1) + 1) / 2)), dim3(256), 0, st, P + OFF_C2W,
+                           dz2, a1, B, dz1);
+        hipLaunchKernelGGL((k_df_conv_dw<1, 10, 0, 7, P1, S1, 1, SRC, true>), dim3(blocks_for_waves(chunks)), dim3(256), 0, st, dz1,
+                           (const float*)nullptr, S, ix, B, pw1);
+        hipLaunchKernelGGL(k_df_conv_bias_part<true>, dim3(B), dim3(64), 0, st, dz1, dz2, B, cb);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(16384 / 16), dim3(256), 0, st, pw2, chunks, 16384LL, 16384, tmp + OFF_C2W);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(512 / 16), dim3(256), 0, st, pw1, chunks, 512LL, 512, tmp + OFF_C1W);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb, B, 64LL, 32, tmp + OFF_C1B);
+        hipLaunchKernelGGL((k_fit_reduce<16>), dim3(2), dim3(256), 0, st, cb + 32, B, 64LL, 32, tmp + OFF_C2B);
+        hipLaunchKernelGGL(k_df_fisher_add, dim3((NP + 255) / 256), dim3(256), 0, st, tmp, acc, NP, (int)(r0 == 0), (int)(r0 + slab >= n),
+                           (double)n, fisher);
     }
     return (int)hipGetLastError();
 }
@@ -549,6 +656,27 @@ int tm_distnet_fit_grad_packed(const float* params, const uint32_t* obs, const f
     if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
     return tmcts_df::fit_grad<tmcts_fit::PackedStates>(params, obs, target, target_stride, weight, idx, batch, atoms, weighted,
                                                        grad, loss, workspace, stream);
+}
+
+long long tm_distnet_fit_fisher_workspace(int slab, int atoms) {
+    if (slab < 1 || slab > tmcts_df::MAX_BATCH || atoms < 1 || atoms > tmcts_df::ROW) return -1;
+    const long long np = tmcts_df::nparam(atoms);
+    return tmcts_df::layout(slab).total + tmcts_fit::up4(np) + tmcts_fit::up4(2 * np);
+}
+
+int tm_distnet_fit_fisher(const float* params, const int8_t* states, const float* target, int target_stride, const float* weight,
+                          const int64_t* idx, long long n, int slab, int atoms, int weighted, float* fisher, float* workspace,
+                          void* stream) {
+    return tmcts_df::fit_fisher<tmcts_fit::DenseStates>(params, states, target, target_stride, weight, idx, n, slab, atoms, weighted,
+                                                        fisher, workspace, stream);
+}
+
+int tm_distnet_fit_fisher_packed(const float* params, const uint32_t* obs, const float* target, int target_stride,
+                                 const float* weight, const int64_t* idx, long long n, int slab, int atoms, int weighted,
+                                 float* fisher, float* workspace, void* stream) {
+    if ((uintptr_t)obs & 3) return (int)hipErrorInvalidValue;
+    return tmcts_df::fit_fisher<tmcts_fit::PackedStates>(params, obs, target, target_stride, weight, idx, n, slab, atoms, weighted,
+                                                         fisher, workspace, stream);
 }
 
 long long tm_distnet_fit_validate_workspace(int slab, int atoms) {

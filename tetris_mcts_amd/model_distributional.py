@@ -63,6 +63,7 @@ class Model_Dist(_HipHead):
     """inference(batch [B,1,22,10]) -> [dist [B, atoms]] (model_distributional.py:100-107); loss = the cross entropy
     against a target distribution, -value * (log p - log value) summed over atoms (model_distributional.py:86-98)."""
     PARAM_ORDER, SCRATCH_ROW, PREPARE = PARAM_ORDER, SCRATCH, "tm_distnet_prepare"
+    fisher = ewc_anchor = None      # compute_fisher's, or a checkpoint's: what train_data(ewc_lambda=) penalises against
 
     def __init__(self, atoms=50, device=None, seed=None, backend=None):
         if seed is not None:
@@ -149,7 +150,11 @@ class Model_Dist(_HipHead):
             atoms = int(state["seq.fc_v.weight"].shape[0])
             if atoms != self.atoms:
                 raise ValueError("%s holds a head of %d atoms, this Model_Dist has %d" % (filename, atoms, self.atoms))
+            fisher = anchor = None      # the Fisher and its anchor, when the checkpoint carries them (both or neither)
+            if "fisher" in ck and "ewc_anchor" in ck:
+                fisher, anchor = self._ewc_flat(ck["fisher"], "fisher"), self._ewc_flat(ck["ewc_anchor"], "ewc_anchor")
             self.model.load_state_dict(state)
+            self.fisher, self.ewc_anchor = fisher, anchor
             if ck.get("optimizer_state_dict"):
                 try:
                     (getattr(self, "optimizer", None) or self._optimizer()).load_state_dict(ck["optimizer_state_dict"])
@@ -168,7 +173,67 @@ class Model_Dist(_HipHead):
             print("Saving model...", flush=True)
         os.makedirs(os.path.dirname(filename) or ".", exist_ok=True)
         opt = getattr(self, "optimizer", None) or self._optimizer()
-        torch.save({"model_state_dict": self.model.state_dict(), "optimizer_state_dict": opt.state_dict()}, filename)
+        ck = {"model_state_dict": self.model.state_dict(), "optimizer_state_dict": opt.state_dict()}
+        if self.fisher is not None:      # (a model without a Fisher writes exactly those two keys)
+            ck["fisher"], ck["ewc_anchor"] = self._ewc_dict(self.fisher), self._ewc_dict(self.ewc_anchor)
+        torch.save(ck, filename)
+
+    def _ewc_dict(self, flat):
+        """a flat [TM_DISTNET_PARAMS(atoms)] tensor as {parameter name: CPU tensor shaped like the parameter}, in PARAM_ORDER"""
+        sd, out, off = self.model.state_dict(), OrderedDict(), 0
+        for k in PARAM_ORDER:
+            n = sd[k].numel()
+            out[k] = flat[off:off + n].detach().reshape(sd[k].shape).cpu().clone()
+            off += n
+        return out
+
+    def _ewc_flat(self, d, key):
+        sd = self.model.state_dict()
+        for k in PARAM_ORDER:
+            if k not in d or tuple(d[k].shape) != tuple(sd[k].shape):
+                raise ValueError("checkpoint key %r: %s has shape %s, the net's is %s"
+                                 % (key, k, tuple(d[k].shape) if k in d else None, tuple(sd[k].shape)))
+        return torch.cat([d[k].reshape(-1).float() for k in PARAM_ORDER]).to(self.device).contiguous()
+
+    @torch.no_grad()
+    def compute_fisher(self, data, weighted=False, state_format="dense", slab=1024):
+        """The empirical Fisher diagonal of the fit's loss over the rows of `data`, F[i] = (1/n) sum_b (d loss_b / d p_i)^2, by
+        ONE call of tm_distnet_fit_fisher (csrc/distnet_fit.hip).  data: [states, targets, weights] laid
+        out as for train_data(fit_backend="hip_dist") and checked by its rules (train.HipDistFit._check_rows): states [n,1,22,10]
+        with the two top rows empty, or with state_format="packed" the packed observations, int32 [n,12] on the GPU; targets
+        [n,atoms] finite and >= 0; one weight a row.  weighted: the row's weight multiplies its loss, the weights taken AS GIVEN
+        (train_data divides its weights by their mean before it fits: hand over those to get the Fisher of the loss it fitted).
+        slab: rows per launch sequence; the result does not depend on a slab >= n.  Sets self.fisher (flat float32
+        [279232 + 129 atoms] on the device, PARAM_ORDER) and self.ewc_anchor (a copy of the flat weights as they stand) and
+        returns self.fisher.  The optimiser and the weights are not touched."""
+        from . import train as T
+        dev = self.device
+        if dev.type != "cuda":
+            raise ValueError("Model_Dist.compute_fisher runs the HIP Fisher pass: the model must be on the GPU, not %s" % (dev,))
+        if state_format not in ("dense", "packed"):
+            raise ValueError("state_format must be 'dense' or 'packed', not %r" % (state_format,))
+        if len(data) != 3:
+            raise ValueError("Model_Dist.compute_fisher needs data = [states, targets, weights]")
+        packed = state_format == "packed"
+        data = [d if packed and i == 0 else torch.as_tensor(d, dtype=torch.float32, device=dev) for i, d in enumerate(data)]
+        rows = T.HipDistFit.__new__(T.HipDistFit)      # the rules and the kept copies of a hip_dist fit's rows, without a fit
+        rows.packed, rows.atoms = packed, self.atoms
+        n = rows._check_rows(data, "Model_Dist.compute_fisher", "data")
+        rows._keep(data, n, "")
+        slab = int(slab)
+        n_ws = _lib.lib().tm_distnet_fit_fisher_workspace(slab, self.atoms)
+        if n_ws < 0:
+            raise ValueError("Model_Dist.compute_fisher: a slab of %d rows is refused" % slab)
+        sd = self.model.state_dict()
+        P = torch.cat([sd[k].detach().reshape(-1).float() for k in PARAM_ORDER]).contiguous()      # (a fresh copy: the anchor)
+        ws = torch.empty(n_ws, dtype=torch.float32, device=dev)
+        fisher = torch.empty(P.numel(), dtype=torch.float32, device=dev)
+        name = "tm_distnet_fit_fisher" + ("_packed" if packed else "")
+        with torch.cuda.device(dev):
+            _lib.check(getattr(_lib.lib(), name)(_p(P), _p(rows.states), _p(rows.target), rows.target.stride(0), _p(rows.weight), None,
+                                                 n, slab, self.atoms, int(bool(weighted)), _p(fisher), _p(ws), _stream()), name)
+        self.fisher, self.ewc_anchor = fisher, P
+        return self.fisher
 
     def _fused_optimizer(self, commit=True):
         """the model's optimiser as a train.FusedAdam (one HIP kernel a step, a flat gradient buffer), the state of the Adam it
@@ -186,14 +251,31 @@ class Model_Dist(_HipHead):
             self.optimizer = new
         return new
 
-    def train_data(self, data, fit_backend="torch", **kwargs):
+    def train_data(self, data, fit_backend="torch", ewc_lambda=None, **kwargs):
         """data: [states [n,1,22,10], distributions [n,atoms], weights [n,1]]; Model.train_data (model/model.py:176-249) with
         this class's loss; data-parallel over the ranks as train.train_data describes.  fit_backend: "torch" (the default:
         autograd and the model's optimiser as it stands) or "hip_dist" (csrc/distnet_fit.hip's gradient step and the fused Adam;
         train.HipDistFit lists what it needs); "hip" names the value net's step and is refused.  validation_backend (in kwargs): "torch"
         or "hip" (csrc/distnet_fit.hip's validation pass; it needs fit_backend="hip_dist").  state_format (in kwargs): "dense" or
-        "packed" (data[0] holds the packed observations, int32 [n,12] on the GPU, and is passed on as it is; train.train_data)."""
+        "packed" (data[0] holds the packed observations, int32 [n,12] on the GPU, and is passed on as it is; train.train_data).
+        ewc_lambda: None, or the lambda of elastic weight consolidation against this model's Fisher and anchor (compute_fisher's or
+        a checkpoint's; train.train_data's `ewc_dist`, fit_backend="hip_dist"); a model that holds no Fisher logs one line and
+        fits unpenalised, as on the first cycle."""
         from . import train as T
+        if ewc_lambda is not None:
+            import math
+            from sys import stderr
+            if isinstance(ewc_lambda, bool) or not isinstance(ewc_lambda, (int, float)) or not (math.isfinite(ewc_lambda) and ewc_lambda >= 0):
+                raise ValueError("Model_Dist.train_data: ewc_lambda must be finite and >= 0, not %r" % (ewc_lambda,))
+            if fit_backend != "hip_dist":
+                raise ValueError("Model_Dist.train_data: ewc_lambda needs fit_backend='hip_dist'")
+            if "ewc_dist" in kwargs:
+                raise ValueError("Model_Dist.train_data: give ewc_lambda or ewc_dist, not both")
+            if self.fisher is None:
+                print("Model_Dist.train_data: no Fisher to consolidate against (first cycle?): fitting without the penalty",
+                      file=stderr, flush=True)
+            else:
+                kwargs["ewc_dist"] = dict(fisher=self.fisher, anchor=self.ewc_anchor, lam=float(ewc_lambda))
         if fit_backend not in ("torch", "hip_dist"):
             raise ValueError("Model_Dist.train_data: fit_backend must be 'torch' or 'hip_dist', not %r" % (fit_backend,))
         if kwargs.get("validation_backend", "torch") not in ("torch", "hip"):

@@ -457,11 +457,12 @@ def _save_on_rank0(model):
 
 
 def _consolidate(model, data, n_train, res, penalised, **fisher):
-    """The end of a fit with ewc_lambda: Model_VV.compute_fisher (fisher: its state_format) over the training rows of `data` with
-    the weights as the fit used them - train_data fits with weighted=True on the weights divided by their mean over ALL rows:
-    the same per-sample losses here -, the checkpoint, and `res` with the ewc dict."""
-    w = data[3] / data[3].mean()
-    model.compute_fisher([d[:n_train] for d in data[:3]] + [w[:n_train]], weighted=True, **fisher)
+    """The end of a fit with ewc_lambda: the model's compute_fisher (Model_VV's or Model_Dist's; fisher: its state_format) over
+    the training rows of `data`, whose last array holds the weights, with the weights as the fit used them - train_data fits with
+    weighted=True on the weights divided by their mean over ALL rows: the same per-sample losses here -, the checkpoint, and
+    `res` with the ewc dict."""
+    w = data[-1] / data[-1].mean()
+    model.compute_fisher([d[:n_train] for d in data[:-1]] + [w[:n_train]], weighted=True, **fisher)
     _save_on_rank0(model)
     return dict(res, ewc=dict(penalised=bool(penalised), fisher_rows=int(n_train)))
 
@@ -786,7 +787,7 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
                       early_stopping_patience=10, fit_backend=None, validation_backend="torch", td=False, lam=None, horizon=64,
                       vmin=0.0, vmax=5000.0, rounds=1, on_round=None, weighted=False, weighted_mode=0, terminal="final",
                       censored="drop", last_nfiles=1, validation=False, val_mode=0, val_episodes=0, val_set_size=0.05,
-                      val_set_size_max=-1, generator=None, eps=EPS, bootstrap="net"):
+                      val_set_size_max=-1, generator=None, eps=EPS, bootstrap="net", ewc_lambda=None):
     """fit_episodes for the distributional head: the recorded episodes of `paths` (choose_stems) -> categorical targets over the
     model's atoms on [vmin, vmax) (episode_dist_targets on the model's device) -> Model_Dist.train_data -> the checkpoint
     (Model_Dist.save, after every round).  Returns what train_data returns plus `rounds`, as fit_episodes does.
@@ -803,7 +804,12 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
     and a recorded atom that is not finite or is negative are a ValueError before any target is computed.
     fit_backend: None - "hip_dist" on a GPU, "torch" on the host.  max_iters / iters_per_val may be functions, as in fit_episodes.
     on_round(r, data, p_rows), r = 0 .. rounds-1, is called before each round's train_data with the tensors in use (p_rows: None
-    in mode 0)."""
+    in mode 0).
+    ewc_lambda (None: off; needs fit_backend="hip_dist"): elastic weight consolidation, as in fit_episodes.  Every round is
+    penalised against the Fisher and anchor the model holds (a loaded checkpoint's), if any.  After the last round
+    Model_Dist.compute_fisher runs over the TRAINING rows (the held-out tail excluded) with that round's targets and the weights
+    as the fit used them, the new Fisher and anchor replace the model's, and rank 0 writes the checkpoint once more.  The result
+    gains ewc = dict(penalised, fisher_rows)."""
     from .model_distributional import Model_Dist
     if not isinstance(model, Model_Dist):
         raise TypeError("fit_episodes_dist fits a Model_Dist: the value net's episode targets are fit_episodes' (%s)"
@@ -828,6 +834,8 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
     _check_dist(model.atoms, vmin, vmax, 0, horizon, None, 0)
     if fit_backend is None:
         fit_backend = "hip_dist" if dev.type == "cuda" else "torch"
+    if ewc_lambda is not None and fit_backend != "hip_dist":
+        raise ValueError("ewc_lambda needs fit_backend='hip_dist', not %r" % (fit_backend,))
     stems = choose_stems(paths, last_nfiles)
     table, stem_rows, episodes, episode_stems = load_stems(stems)
     recorded = None
@@ -848,6 +856,9 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
     options = dict(td=td, lam=lam, horizon=horizon, atoms=model.atoms, vmin=vmin, vmax=vmax, weighted=weighted,
                    weighted_mode=weighted_mode, terminal=terminal, censored=censored, eps=eps)
     data, done = None, []
+    if ewc_lambda is not None:
+        extra["ewc_lambda"] = ewc_lambda
+    penalised = ewc_lambda is not None and model.fisher is not None
     for r in range(rounds):
         p_rows = None
         if recorded is not None:
@@ -870,6 +881,8 @@ def fit_episodes_dist(model, paths, batch_size=32, max_iters=100000, iters_per_v
                                early_stopping_patience=early_stopping_patience, validation_backend=validation_backend, **extra)
         _save_on_rank0(model)
         done.append(dict(iters=res["iters"], best_validation=res["best_validation"], graph_replay=res["graph_replay"]))
+    if ewc_lambda is not None:
+        res = _consolidate(model, data, n - n_val, res, penalised)
     return dict(res, rounds=done)
 
 
@@ -1055,12 +1068,15 @@ def dist_node_training_set(paths, weighted=False, weighted_mode=1, last_nfiles=1
 
 
 def fit_dist_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=None, early_stopping=False,
-                   early_stopping_patience=10, fit_backend="hip_dist", validation_backend="hip", **options):
+                   early_stopping_patience=10, fit_backend="hip_dist", validation_backend="hip", ewc_lambda=None, **options):
     """dist_node_training_set(paths, **options) on the model's device, then model.train_data(..., fit_backend="hip_dist",
     state_format="packed") on it and, on rank 0, model.save(); returns what train_data returns plus n_train, n_val and the
     sidecar's atoms, vmin, vmax.  model: a Model_Dist (TypeError otherwise) with the file's atoms (ValueError otherwise).
     max_iters and iters_per_val may be functions, as in fit_episodes.  The packed observations are read by the HIP kernels
-    alone: fit_backend must be "hip_dist", and validation_backend "hip" unless nothing is held out (ValueError otherwise)."""
+    alone: fit_backend must be "hip_dist", and validation_backend "hip" unless nothing is held out (ValueError otherwise).
+    ewc_lambda: as in fit_episodes_dist - the fit is penalised against the Fisher and anchor the model holds, then
+    Model_Dist.compute_fisher(state_format="packed") runs over the training rows with the weights as the fit used them and rank 0
+    writes the checkpoint; the result gains ewc = dict(penalised, fisher_rows)."""
     from .model_distributional import Model_Dist
     if not isinstance(model, Model_Dist):
         raise TypeError("fit_dist_nodes fits a Model_Dist: a dist node row holds a distribution, not a value and a variance (%s); "
@@ -1078,8 +1094,14 @@ def fit_dist_nodes(model, paths, batch_size=32, max_iters=100000, iters_per_val=
         raise ValueError("fit_dist_nodes holds %d rows out, and the torch validation does not read packed observations: it needs "
                          "validation_backend='hip' (or no validation), not %r" % (info["n_val"], validation_backend))
     iters, extra = _iterations(max_iters, iters_per_val, info["n_train"])
+    if ewc_lambda is not None:
+        extra["ewc_lambda"] = ewc_lambda
+    penalised = ewc_lambda is not None and model.fisher is not None
     res = model.train_data(data, fit_backend="hip_dist", state_format="packed", shuffle=False, batch_size=batch_size, max_iters=iters,
                            validation_fraction=info["validation_fraction"], early_stopping=early_stopping,
                            early_stopping_patience=early_stopping_patience, validation_backend=validation_backend, **extra)
-    _save_on_rank0(model)
+    if ewc_lambda is not None:
+        res = _consolidate(model, data, info["n_train"], res, penalised, state_format="packed")
+    else:
+        _save_on_rank0(model)
     return dict(res, n_train=info["n_train"], n_val=info["n_val"], atoms=info["atoms"], vmin=info["vmin"], vmax=info["vmax"])

@@ -369,6 +369,34 @@ def check_ewc(ewc, fit_backend):
     return ewc["fisher"].reshape(-1).contiguous(), ewc["anchor"].reshape(-1).contiguous(), lam
 
 
+def check_ewc_dist(ewc_dist, fit_backend, net):
+    """check_ewc for the distributional head: the refusals of train_data's `ewc_dist`, raised with the other early checks.
+    ewc_dist: None or dict(fisher=, anchor=, lam=) with float32 CUDA tensors of the 279232 + 129 atoms flat parameters of `net`
+    (model_distributional.PARAM_ORDER); returns (fisher, anchor, lam) with contiguous tensors, or None."""
+    if ewc_dist is None:
+        return None
+    if fit_backend != "hip_dist":
+        raise ValueError("ewc_dist adds its penalty to the flat gradient of the distributional head's HIP fit: it needs "
+                         "fit_backend='hip_dist', not %r" % (fit_backend,))
+    atoms = getattr(getattr(getattr(net, "seq", None), "fc_v", None), "out_features", None)
+    if not isinstance(atoms, int):
+        raise ValueError("ewc_dist: fit_backend='hip_dist' computes model_distributional.Net, not %s" % type(net).__name__)
+    if not isinstance(ewc_dist, dict) or set(ewc_dist) != {"fisher", "anchor", "lam"}:
+        raise ValueError("ewc_dist is None or dict(fisher=, anchor=, lam=)")
+    n = HipDistFit.N_PARAMS_0 + 129 * atoms
+    for key in ("fisher", "anchor"):
+        t = ewc_dist[key]
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == n):
+            raise ValueError("ewc_dist: %s must be a float32 CUDA tensor of %d elements (%d atoms)" % (key, n, atoms))
+    try:
+        lam = float(ewc_dist["lam"])
+    except (TypeError, ValueError):
+        raise ValueError("ewc_dist: lam must be a number, not %r" % (ewc_dist["lam"],)) from None
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError("ewc_dist: lam must be finite and >= 0, not %r" % (ewc_dist["lam"],))
+    return ewc_dist["fisher"].reshape(-1).contiguous(), ewc_dist["anchor"].reshape(-1).contiguous(), lam
+
+
 class _HipFitBase:
     """What the per-fit states of fit_backend="hip" and "hip_dist" share: the order of the checks (once per fit, everything that
     can refuse before the optimiser is flattened), the workspaces of the gradient step and of the validation pass, the index
@@ -386,7 +414,7 @@ class _HipFitBase:
                  state_format="dense", ewc=None):
         from . import _lib
         self._lib = _lib
-        self.ewc = check_ewc(ewc, self.BACKEND)
+        self.ewc = self._check_ewc(net, ewc)
         if state_format not in ("dense", "packed"):
             raise ValueError("state_format must be 'dense' or 'packed', not %r" % (state_format,))
         self.packed = state_format == "packed"
@@ -420,6 +448,9 @@ class _HipFitBase:
             self._keep(val, vrows, "val_")
             self.val_ws = torch.empty(self._workspace(val_slab, validation=True), dtype=torch.float32, device=self.dev)
             self.val_out = torch.zeros((vrows + val_chunk - 1) // val_chunk, 3, dtype=torch.float64, device=self.dev)
+
+    def _check_ewc(self, net, ewc):
+        return check_ewc(ewc, self.BACKEND)
 
     def validate(self, weighted):
         """the held-out rows' [w, mean, std] per chunk (a list of lists of Python floats, what combine_chunk_rows takes), at the
@@ -579,6 +610,10 @@ class HipDistFit(_HipFitBase):
     BACKEND = "hip_dist"
     N_PARAMS_0 = 279232      # the flat parameters without fc_v's 129 an atom
 
+    def _check_ewc(self, net, ewc):
+        """`ewc` is train_data's ewc_dist here: the head's Fisher and anchor (check_ewc_dist)"""
+        return check_ewc_dist(ewc, self.BACKEND, net)
+
     def _check_rows(self, data, L, what):
         """the checks of one list of rows (`what`: "data", the training rows, or "validation data"); the number of rows"""
         if self.packed:      # (20 board rows a row: the kernels supply the two empty rows on top, which holds the dense rule by construction)
@@ -660,7 +695,7 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
                sample_replacement=True, oversampling=False, weighted=True, early_stopping=True, early_stopping_patience=10,
                early_stopping_threshold=1.0, shuffle=False, max_iters=100000, grad_clip=0.0, save=None, load=None,
                generator=None, log=True, data_parallel=True, group=None, loss_fn=None, fit_backend="torch",
-               validation_backend="torch", state_format="dense", ewc=None):
+               validation_backend="torch", state_format="dense", ewc=None, ewc_dist=None):
     """data = [states f32 [n,1,20,10], values [n,1], variances [n,1], weights [n,1]] (device tensors); with `loss_fn`
     (net, batch, weighted) -> (mean, std) any list of arrays whose LAST one holds the sample weights (Model.train_data is
     generic in the reference too, model/model.py:176-249: the model class supplies `_loss`).
@@ -703,7 +738,12 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     and after the data-parallel all-reduce (every rank adds the same penalty once) and before the gradient norm, which is then
     the penalised objective's; the iteration stays a fixed sequence of launches and is replayed from the graph as before.  At
     each validation one more line reports the mean penalty since the last.  It needs fit_backend="hip"; anything else, and a
-    fisher, anchor or lam that is not as described, is a ValueError raised before the optimiser is flattened."""
+    fisher, anchor or lam that is not as described, is a ValueError raised before the optimiser is flattened.
+
+    `ewc_dist`: the same for the distributional head - None, or dict(fisher=, anchor=, lam=) with float32 CUDA tensors of the
+    279 232 + 129 atoms flat parameters of the net (Model_Dist.compute_fisher's).  The same ONE call of tm_ewc_penalty
+    at the same place of the iteration, the same log line.  It needs fit_backend="hip_dist"; `ewc` and `ewc_dist` together are
+    refused, and `ewc` itself stays the value net's (with "hip_dist" it is refused as before)."""
     import torch.distributed as tdist
     check_state_format(state_format, fit_backend, validation_backend, validation_fraction, data)
     if fit_backend not in ("torch", "hip", "hip_dist"):
@@ -713,7 +753,10 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     if validation_backend == "hip" and fit_backend == "torch":
         raise ValueError("validation_backend='hip' reads the flat parameter buffer of a HIP fit: it needs fit_backend='hip' or "
                          "'hip_dist' (a custom loss_fn, CPU tensors and the torch fit validate with validation_backend='torch')")
+    if ewc is not None and ewc_dist is not None:
+        raise ValueError("ewc is the value net's penalty and ewc_dist the distributional head's: give one of the two, not both")
     check_ewc(ewc, fit_backend)
+    check_ewc_dist(ewc_dist, fit_backend, net)
     if fit_backend == "hip_dist":
         if loss_fn is not None and not getattr(loss_fn, "is_model_dist_loss", False):
             raise ValueError("fit_backend='hip_dist' computes Model_Dist.loss: a custom loss_fn needs fit_backend='torch'")
@@ -752,11 +795,12 @@ def train_data(net, optimizer, data, batch_size=128, iters_per_val=500, validati
     # the one-kernel optimiser step (Yogi on the GPU): parameters and gradients are views of flat buffers from here on
     hip_val = val if validation_backend == "hip" else None
     hip = (HipFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format, ewc=ewc) if fit_backend == "hip" else
-           HipDistFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format)
+           HipDistFit(net, optimizer, train, batch_size // world, val=hip_val, state_format=state_format, ewc=ewc_dist)
            if fit_backend == "hip_dist" else None)
     if hip is not None and hip.rows != n - n_val:      # every draw below is an index into [0, n - n_val): the rows the kernels hold
         raise ValueError("fit_backend=%r: %d training rows, but the index draws cover %d" % (fit_backend, hip.rows, n - n_val))
     flat_g = optimizer.flat_grad() if hasattr(optimizer, "flat_grad") else None
+    ewc = ewc if ewc is not None else ewc_dist      # (one of the two at the most: the penalty of the fit's own head)
     ewc_avg = torch.zeros((), dtype=torch.float64, device=data[0].device) if ewc is not None else None
 
     def one_iteration():

@@ -16,6 +16,11 @@ by the HIP Fisher pass (csrc/valuenet_fit.hip: tm_valuenet_fit_fisher) and writt
 weights as the next cycle's anchor.  --ewc_lambda has no default: the Fisher's magnitude follows the loss's scale, and the
 reference's default of 1 never met a Fisher that was not zero.  The value net only, with --fit_backend hip.
 
+--ewc_dist --ewc_lambda L is the same for the distributional head: with --head dist (--bootstrap search included) and with
+--dist_nodes the fit is penalised against the Fisher and anchor that pytorch_model/model_checkpoint_dist carries, and after the fit
+the head's Fisher over the training rows (csrc/distnet_fit.hip: tm_distnet_fit_fisher) is written into it with the weights.  It
+needs --fit_backend hip; --ewc stays the value net's flag and is refused with --head dist and --dist_nodes.
+
 Beyond the reference: --target_gamma discounts the targets per move (0.999 is the search's discount; the default 1.0 is the
 reference's undiscounted rule), and --bootstrap net takes the values inside the lambda-return from the net being fitted, refreshed
 before each of --bootstrap_rounds parts of the fit, instead of the values the playing net recorded.
@@ -43,7 +48,8 @@ dist or --fit_backend torch; --weighted, --validation, --early_stopping, --last_
 --save_dist_nodes` (offline.fit_dist_nodes): the target of a node is the distribution the search backed up into it, as recorded, so
 nothing is bootstrapped from the head's own predictions.  Atoms and range come from the shards' sidecar; an --atoms, --vmin or
 --vmax that says otherwise is refused.  It writes pytorch_model/model_checkpoint_dist.  It takes no --nodes, --td_lambda,
---bootstrap net, --target_gamma, --val_mode 1, --ewc or --fit_backend torch, and --weighted only with --weighted_mode 1 (visits).
+--bootstrap net, --target_gamma, --val_mode 1, --ewc (its consolidation is --ewc_dist) or --fit_backend torch, and --weighted only
+with --weighted_mode 1 (visits).
 """
 import argparse
 import sys
@@ -60,6 +66,8 @@ def build_parser():
     add('--epochs', default=10, type=int, help='Training epochs (default:10)')
     add('--ewc', default=False, help='Elastic weight consolidation (default:False)', action='store_true')
     add('--ewc_lambda', default=None, type=float, help='Elastic weight consolidation lambda (no default: give it with --ewc)')
+    add('--ewc_dist', default=False, action='store_true', help='[new] --head dist / --dist_nodes: elastic weight consolidation of the '
+        'distributional head, with --ewc_lambda (the head\'s Fisher and anchor travel in pytorch_model/model_checkpoint_dist)')
     add('--last_nfiles', default=1, type=int, help='Use last n files in training only (default:1, -1 for all)')
     add('--min_iters', default=-1, type=int, help='Min training iterations (default:-1, negative for unlimited)')
     add('--max_iters', default=-1, type=int, help='Max training iterations (default:-1, negative for unlimited)')
@@ -128,7 +136,8 @@ def check_dist_nodes(args, argv):
     if args.val_mode == 1:
         sys.exit('--dist_nodes takes no --val_mode 1: a node table has no episodes (--val_mode 0 holds out random rows)')
     if args.ewc:
-        sys.exit('--dist_nodes takes no --ewc: the Fisher pass exists for the value net only')
+        sys.exit('--dist_nodes takes no --ewc: the Fisher pass exists for the value net only behind that flag (the distributional '
+                 'head\'s consolidation is --ewc_dist)')
     if args.fit_backend != 'hip':
         sys.exit('--dist_nodes takes no --fit_backend torch: the packed observations are read by the HIP gradient step alone')
     if args.validation and args.validation_backend not in (None, 'hip'):
@@ -186,17 +195,27 @@ def check_args(args, argv=()):
     if args.nodes:
         check_nodes(args)
     if args.ewc and args.head == 'dist':
-        sys.exit('--ewc: the Fisher pass exists for the value net only (--head value), not for --head dist')
+        sys.exit('--ewc: the Fisher pass exists for the value net only (--head value) behind this flag, not for --head dist: the '
+                 'distributional head\'s consolidation is --ewc_dist')
+    if args.ewc_dist and not (args.head == 'dist' or args.dist_nodes):
+        sys.exit('--ewc_dist consolidates the distributional head: it needs --head dist or --dist_nodes (the value net\'s flag is '
+                 '--ewc)')
+    if args.ewc_dist and args.ewc_lambda is None:
+        sys.exit('--ewc_dist needs --ewc_lambda: there is no default, because the magnitude of the Fisher follows the scale of the '
+                 'loss, as for --ewc')
     if args.ewc and args.ewc_lambda is None:
         sys.exit('--ewc needs --ewc_lambda: there is no default, because the magnitude of the Fisher follows the scale of the loss, '
                  'and the reference\'s default of 1 never met a Fisher that was not zero')
-    if args.ewc_lambda is not None and not args.ewc:
+    if args.ewc_lambda is not None and not (args.ewc or args.ewc_dist):
         sys.exit('--ewc_lambda is the weight of --ewc: it needs --ewc')
     if args.ewc_lambda is not None and not (args.ewc_lambda >= 0.0 and args.ewc_lambda != float('inf')):
         sys.exit('--ewc_lambda is finite and at least 0')
     if args.ewc and args.fit_backend != 'hip':
         sys.exit('--ewc adds its penalty to the gradient of the HIP fit and computes its Fisher with the HIP kernels: it needs '
                  '--fit_backend hip')
+    if args.ewc_dist and args.fit_backend != 'hip':
+        sys.exit('--ewc_dist adds its penalty to the gradient of the head\'s HIP fit and computes its Fisher with the HIP kernels: it '
+                 'needs --fit_backend hip')
     if args.save_loss:
         sys.exit('--save_loss writes the reference\'s HDF5 loss table (util/Data.py LossSaver: PyTables), which this engine does '
                  'not reimplement; the fit logs its losses to stderr')
@@ -287,7 +306,8 @@ def main_dist(args):
                             rounds=args.bootstrap_rounds, weighted=args.weighted, weighted_mode=args.weighted_mode,
                             terminal=args.terminal, censored=args.censored, last_nfiles=args.last_nfiles, validation=args.validation,
                             val_mode=args.val_mode, val_episodes=args.val_episodes, val_set_size=args.val_set_size,
-                            val_set_size_max=args.val_set_size_max, bootstrap='search' if args.bootstrap == 'search' else 'net')
+                            val_set_size_max=args.val_set_size_max, bootstrap='search' if args.bootstrap == 'search' else 'net',
+                            ewc_lambda=args.ewc_lambda if args.ewc_dist else None)
     print('iters:%d/%d' % (sum(r['iters'] for r in res['rounds']), plan['iters'])
           + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
     model.save()
@@ -315,7 +335,8 @@ def main_dist_nodes(args):
                          early_stopping=args.early_stopping, early_stopping_patience=args.early_stopping_patience,
                          fit_backend='hip_dist', validation_backend=args.validation_backend, weighted=args.weighted,
                          weighted_mode=args.weighted_mode, last_nfiles=args.last_nfiles, validation=args.validation,
-                         val_set_size=args.val_set_size, val_set_size_max=args.val_set_size_max)
+                         val_set_size=args.val_set_size, val_set_size_max=args.val_set_size_max,
+                         ewc_lambda=args.ewc_lambda if args.ewc_dist else None)
     print('iters:%d/%d' % (res['iters'], plan['iters'])
           + (' best validation loss: %.5f' % res['best_validation'] if args.early_stopping else ''), flush=True)
     model.save()
